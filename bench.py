@@ -44,6 +44,13 @@ Extra objects in the line:
 Test hooks (used only by tests/): `--backend gloo --device cpu --ops <module>` runs the same
 launcher / sharding / reduction code on CPU tensors with a non-product operator module (the line is
 then marked "selftest"); `--dump-grads PATH` saves rank 0's reduced gradient bucket.
+
+`--dump-outputs DIR`: after the timed steps, rank 0 writes what the headline route's LAST timed step computed as
+float32 `DIR/<name>.npy` (dump_outputs: a seeded sample of pixels / Gaussians, at most DUMP_BYTES in all):
+  config 4   img_<rgb|feature|depth|normal> of the step's last view, grad_<parameter> of the reduced gradients
+             (--reduce rs_ag: param_<parameter>, the parameters after the step's Adam update);
+  config 5   img_<...> and fea_up (the MLP's 512-ch output) of the step's last view.
+Inputs are seeded: the same arguments give the same inputs, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -113,9 +120,14 @@ def parse(argv=None):
     ap.add_argument("--device", default="cuda", choices=("cuda", "cpu"))
     ap.add_argument("--ops", default=PRODUCT_OPS, help="operator module (tests only)")
     ap.add_argument("--dump-grads", default=None)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, seeded sample, "
+                         "at most 60 MiB in all)")
     ap.add_argument("--share-gpu", action="store_true",
                     help="test hook: every rank uses cuda:0 (a one-GPU box rehearsing N ranks; gloo backend)")
     a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.keep_gc:
         os.environ["GG_BENCH_KEEP_GC"] = "1"
     d4 = dict(points=1_000_000, height=1200, width=1600, feature_dim=32)
@@ -267,6 +279,42 @@ def freeze_gc():
         return
     gc.collect()
     gc.freeze()
+
+
+DUMP_BYTES = 60 << 20       # --dump-outputs: payload of all files together
+DUMP_ROWS = 65536           # pixels / Gaussians sampled per array, before DUMP_BYTES scales both counts down
+
+
+def dump_outputs(path, images, rows):
+    """--dump-outputs: `images` name -> one view's (H, W[, C]) tensor, `rows` name -> a tensor with one row per
+    Gaussian; written as float32 `path/img_<name>.npy` (K_pix, C) and `path/<name>.npy` (K_gauss, C).  Arrays with
+    more rows than the sample size keep a seeded, sorted subset — the same pixels for every image and the same
+    Gaussians for every per-Gaussian array, a function of the shapes only, so two runs dump the same elements.  The
+    sampled indices go beside them (pixel_index.npy / gaussian_index.npy, float64)."""
+    import numpy as np
+    import torch
+
+    groups = []      # (file prefix, index file, seed, arrays flattened to (rows, channels))
+    for arrays, lead, prefix, index_name, seed in ((images, 2, "img_", "pixel_index", 1),
+                                                   (rows, 1, "", "gaussian_index", 2)):
+        if arrays:
+            flat = {k: t.detach().reshape(t.shape[:lead].numel(), -1) for k, t in arrays.items()}
+            groups.append((prefix, index_name, seed, flat))
+    n_rows = [next(iter(g[3].values())).shape[0] for g in groups]
+    want = [min(n, DUMP_ROWS) for n in n_rows]
+    row_bytes = [8 + 4 * sum(t.shape[1] for t in g[3].values()) for g in groups]
+    scale = min(1.0, DUMP_BYTES / max(1, sum(k * b for k, b in zip(want, row_bytes))))
+    os.makedirs(path, exist_ok=True)
+    for (prefix, index_name, seed, flat), n, k in zip(groups, n_rows, want):
+        k = max(1, int(k * scale))
+        if k < n:
+            idx = torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:k].sort().values
+        else:
+            idx = torch.arange(n)
+        np.save(os.path.join(path, index_name + ".npy"), idx.double().numpy())
+        for name, t in flat.items():
+            sample = t.index_select(0, idx.to(t.device)).float().cpu().numpy()
+            np.save(os.path.join(path, prefix + name + ".npy"), sample)
 
 
 def read_kernel_times(lib):
@@ -479,11 +527,22 @@ def run_rank(args, rank: int, local_rank: int, world: int) -> int:
     if hasattr(ops, "clear_bin_cache"):
         ops.clear_bin_cache()
 
+    from gaussiangrasper_amd.pipeline import CHANNELS
+    last_images = {}     # --dump-outputs: detached aliases of the images of the view rendered last
+
     def make_step(fused: bool):
         if fused:
             render = lambda v: plugin_model(cameras[v])
         else:
             render = lambda v: render_view(scene, views[v], ops, fused=False)
+        if args.dump_outputs and rank == 0:
+            plain_render = render
+
+            def render(v):
+                out = plain_render(v)
+                last_images.clear()
+                last_images.update({k: out[k].detach() for k in CHANNELS if k in out})
+                return out
 
         def render_and_backward(v):
             backward_view(render(v), cot)
@@ -529,6 +588,14 @@ def run_rank(args, rank: int, local_rank: int, world: int) -> int:
         freeze_gc()
         t = timed(fn, args.steps)
         grads = bucket.gathered().detach().cpu().clone() if (args.dump_grads and rank == 0) else None
+        if args.dump_outputs and rank == 0 and fused == plugin_first:
+            names = ("means", "scales", "quats", "opacities", "colors_all", "feature")
+            if stepper is None:
+                per_gaussian = {"grad_" + k: sl.view_as(p) for k, sl, p in zip(names, bucket.slices, bucket.params)}
+            else:
+                per_gaussian = {"param_" + k: p for k, p in zip(names, bucket.params)}
+            dump_outputs(args.dump_outputs, last_images, per_gaussian)
+            last_images.clear()
         kern, t_prof = {}, None
         if lib is not None and not args.no_prof:               # all ranks take part (collectives)
             saved, pipe_streams_box[0] = pipe_streams_box[0], None   # per-kernel times: one stream, no overlap
@@ -646,6 +713,7 @@ def run_rank(args, rank: int, local_rank: int, world: int) -> int:
         a5 = argparse.Namespace(**vars(args))
         a5.config, a5.points, a5.height, a5.width, a5.feature_dim = 5, 5_000_000, 1080, 1920, 128
         a5.views_per_step, a5.steps, a5.warmup = 2, 5, 1
+        a5.dump_outputs = None                            # the dump is the headline's
         try:
             r5 = render_only_result(a5, rank, world, dev, ops, lib, barrier, max_over_ranks)
             result["config5"] = {k: r5[k] for k in ("metric", "value", "unit", "ms_per_view", "steps", "kernels",
@@ -718,12 +786,24 @@ def render_only_result(args, rank, world, dev, ops, lib, barrier, max_over_ranks
                 render(v)
         freeze_gc()
         barrier()
+        keep = bool(args.dump_outputs) and rank == 0
+        last = None
         t0 = time.perf_counter()
         for _ in range(args.steps):
             for v in my_views:
-                render(v)
+                if keep:
+                    last = render(v)
+                else:
+                    render(v)
         barrier()
         elapsed = max_over_ranks(time.perf_counter() - t0)
+        if last is not None:
+            from gaussiangrasper_amd.pipeline import CHANNELS
+            out, clip = last
+            images = {k: out[k] for k in CHANNELS if k in out}
+            images["fea_up"] = clip
+            dump_outputs(args.dump_outputs, images, {})
+            del out, clip, last, images
         kernels = {}
         if lib is not None and not args.no_prof:
             lib.gg_prof_reset()

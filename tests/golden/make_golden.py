@@ -3,7 +3,7 @@ build).  The reference holds no fixture for this path and its implementation (gs
 available offline (parity unpinned), so these vectors pin the oracle against
 regressions and give the GPU box (which has no /root/reference and needs none) known answers.
 
-    python tests/golden/make_golden.py          # rewrites tests/golden/*.npz
+    python tests/golden/make_golden.py          # rewrites tests/golden/*.npz and tests/golden/compat/*.npz
 """
 import os
 import sys
@@ -72,5 +72,27 @@ def main():
               "mean final_T = %.3f" % saved["final_Ts"].mean())
 
 
+def compat_project_case():
+    """The inputs of tests/test_compat_variant.py's CPU projection case (_project_case(): 4000 Gaussians spread
+    beyond the FOV clamp, 96x128, view 1 of 3, seeded cotangents), stored: the view matrix (small fp32 matmuls) and
+    torch's exp round differently in the last bits on different hosts, and that test holds two oracle builds to
+    1e-12 on gradients with cancellation in them.  In a subdirectory: not one of the fixtures above."""
+    n, h, w = 4000, 96, 128
+    sc = make_scene(n, config_index=12)
+    sc.means.mul_(2.5)
+    v = ring_cameras(3, h, w, fov_x_deg=60.0)[1]
+    rng = np.random.default_rng(3)
+    v_xy, v_depth, v_conic = (rng.standard_normal((n, 2)).astype(np.float32),
+                              rng.standard_normal(n).astype(np.float32),
+                              rng.standard_normal((n, 3)).astype(np.float32))
+    os.makedirs(os.path.join(HERE, "compat"), exist_ok=True)
+    np.savez_compressed(
+        os.path.join(HERE, "compat", "project_case_n4000_96x128.npz"), means=sc.means.numpy(),
+        scales=sc.scales.exp().numpy(), quats=sc.quats.numpy(), viewmat=v.viewmat.numpy(), projmat=v.projmat.numpy(),
+        intr=np.array([v.fx, v.fy, v.cx, v.cy], np.float64), hw=np.array([h, w]), v_xy=v_xy, v_depth=v_depth,
+        v_conic=v_conic)
+
+
 if __name__ == "__main__":
     main()
+    compat_project_case()

@@ -5,12 +5,13 @@ include/gg_constants.h.  Both the oracle and the HIP library are also built with
 other exactly as the default builds are held to each other, so a later session that has the gsplat
 source only flips constants."""
 import os
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
-from gaussiangrasper_amd.camera import ring_cameras
+from gaussiangrasper_amd.camera import ViewParams, ring_cameras
 from gaussiangrasper_amd.scene import make_scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -33,19 +34,33 @@ def _project_case(n=4000, h=96, w=128, fov=60.0):
     return sc, v, cot
 
 
-def _oracle_project_bwd(O, sc, v, cot, dtype=np.float32):
-    a = (sc.means.numpy(), sc.scales.exp().numpy(), 1.0, sc.quats.numpy(), v.viewmat[:3].numpy(),
+def _stored_project_case():
+    """_project_case()'s inputs as stored by tests/golden/make_golden.py (compat_project_case): the view matrix and
+    torch's exp differ in the last bits from host to host, and the comparison inside the FOV clamp below is exact to
+    1e-12 on gradients with cancellation in them.  -> (scene-like, view, cotangents, activated scales)"""
+    z = np.load(os.path.join(ROOT, "tests", "golden", "compat", "project_case_n4000_96x128.npz"))
+    fx, fy, cx, cy = (float(x) for x in z["intr"])
+    v = ViewParams(torch.from_numpy(z["viewmat"]), torch.from_numpy(z["projmat"]), fx, fy, cx, cy,
+                   int(z["hw"][0]), int(z["hw"][1]), torch.zeros(3))
+    sc = SimpleNamespace(means=torch.from_numpy(z["means"]), quats=torch.from_numpy(z["quats"]))
+    return sc, v, (z["v_xy"], z["v_depth"], z["v_conic"]), z["scales"]
+
+
+def _oracle_project_bwd(O, sc, v, cot, dtype=np.float32, scales=None):
+    """scales: the activated scales (default: exp of the scene's)"""
+    scales = sc.scales.exp().numpy() if scales is None else scales
+    a = (sc.means.numpy(), scales, 1.0, sc.quats.numpy(), v.viewmat[:3].numpy(),
          v.projmat.numpy(), v.fx, v.fy, v.cx, v.cy, v.height, v.width)
     fwd = O.project_fwd(*a, v.tile_bounds, dtype=dtype)
     return fwd, O.project_bwd(*a, fwd[2], fwd[3], *cot, dtype=dtype)
 
 
 def test_compat_oracle_differs_from_the_exact_vjp_only_where_documented(oracle):
-    sc, v, cot = _project_case()
-    fwd, exact = _oracle_project_bwd(oracle, sc, v, cot, np.float64)
+    sc, v, cot, scales = _stored_project_case()
+    fwd, exact = _oracle_project_bwd(oracle, sc, v, cot, np.float64, scales)
     oracle.use_variant("compat")
     try:
-        fwd_c, compat = _oracle_project_bwd(oracle, sc, v, cot, np.float64)
+        fwd_c, compat = _oracle_project_bwd(oracle, sc, v, cot, np.float64, scales)
     finally:
         oracle.use_variant("")
     for a, b in zip(fwd, fwd_c):

@@ -193,6 +193,14 @@ def test_oracle_split_dup_matches_the_reference_torch_code(oracle, overlap):
             untouched[n:n + samps * int(split.sum())] = False
             if name == "scales":
                 untouched[:n][split.numpy()] = False
+                # the dup rows of Gaussians also split carry the shrunk scale (exp / log as well): exactly the
+                # oracle's own shrunk row, and within the tolerance above of torch's
+                dup_ids = np.nonzero(dup.numpy())[0]
+                dup_rows = n + samps * int(split.sum()) + np.arange(len(dup_ids))
+                both = split.numpy()[dup_ids]
+                assert both.any() == overlap
+                assert np.array_equal(got[dup_rows[both]], got[dup_ids[both]]), name
+                untouched[dup_rows[both]] = False
             assert np.array_equal(got[untouched], w[untouched]), name
         else:
             assert np.array_equal(got, w), name

@@ -235,6 +235,35 @@ def test_bench_reduce_scatter_adam_all_gather_scheme_runs_on_two_gloo_ranks(tmp_
     assert lines[0]["config"]["grad_allreduce"].startswith("reduce-scatter")
 
 
+def test_bench_dump_outputs_are_the_last_steps_and_repeat_run_to_run(tmp_path):
+    """`--dump-outputs DIR`: the last timed step's images and reduced gradients as float32 .npy files (sampled
+    indices float64), under the size cap; two runs with the same arguments dump the same arrays; `--steps` is the
+    number of timed steps the line reports, with `ms_per_step`"""
+    import numpy as np
+    import bench
+    dumps = []
+    for name in ("a", "b"):
+        d = tmp_path / name
+        r = _run_bench(["--dump-outputs", str(d), "--steps", "3"], tmp_path, 1)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = _json_lines(r.stdout)[0]
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        dumps.append({f.name: np.load(f) for f in sorted(d.iterdir())})
+    a, b = dumps
+    want = {"img_" + k for k in ("rgb", "feature", "depth", "normal")}
+    want |= {"grad_" + k for k in ("means", "scales", "quats", "opacities", "colors_all", "feature")}
+    want = {k + ".npy" for k in want | {"pixel_index", "gaussian_index"}}
+    assert set(a) == want
+    assert sum(x.nbytes for x in a.values()) <= bench.DUMP_BYTES
+    for k, x in a.items():
+        assert x.dtype == (np.float64 if k.endswith("_index.npy") else np.float32), k
+        assert np.array_equal(x, b[k]), k
+    assert a["img_rgb.npy"].shape == (32 * 48, 3) and a["grad_colors_all.npy"].shape == (300, 75)
+    assert float(np.abs(a["grad_means.npy"]).max()) > 0 and float(np.abs(a["img_rgb.npy"]).max()) > 0
+    r = _run_bench(["--steps", "0"], tmp_path, 1)
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
 def test_bench_refuses_a_world_size_that_is_not_gpus(tmp_path):
     """no silent single-GPU fallback: WORLD_SIZE=1 with --gpus 2 is an error, not a 1-GPU run"""
     r = _run_bench([], tmp_path, 2, env_extra={"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
