@@ -1,0 +1,235 @@
+"""Scene update after a grasp: the first half of the reference's `update.sh` (nerfstudio/scripts/update.py, SURVEY.md
+§3.3) — select the Gaussians inside the convex hull of an object's point cloud and move them rigidly with the
+gripper's pose change — on one HIP kernel (`gg_hull_edit`, csrc/edit.hip) instead of a host round trip.
+
+    update.py                                  here
+    points_inside_convex_hull :293-328         filter_object_points -> hull_planes -> select_and_move (mask)
+    prepare_transform :342-355, main :141-158  rotvec_to_matrix, compose_transform, object_points_to_scene
+    transformed_gs :217-240                    select_and_move (in place) / edit_model
+    save_checkpoint :257-286                   python -m gaussiangrasper_amd.edit ... --out step-000000000.ckpt
+
+The fine-tune that follows is the existing training path.  Two deliberate differences from the reference
+(PARITY.md): the inside test is the hull's half-spaces with a tolerance instead of `Delaunay.find_simplex`, and the
+moved quaternions come from Shepperd's method, which takes the reference's formula where the trace is the largest
+diagonal term and never produces NaN.  scipy (Qhull) is needed only to build the hull from points; callers that
+have the planes pass them directly."""
+from __future__ import annotations
+
+import argparse
+import ctypes
+import json
+import os
+import sys
+from typing import Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+from torch import Tensor
+
+from . import _lib
+from .interop import MODEL_PREFIX
+from .ops import _ptr, _require_hip, _stream
+
+ArrayLike = Union[np.ndarray, Tensor, Sequence]
+
+
+# ------------------------------------------------------------------------------------------------
+# host side: the object's hull and the rigid transform (numpy, fp64)
+# ------------------------------------------------------------------------------------------------
+def filter_object_points(points: ArrayLike, outlier_factor: float = 1.0) -> np.ndarray:
+    """The reference's outlier filter (update.py:313-319): per axis Q1 = 0th and Q3 = 80th percentile, IQR = Q3 - Q1;
+    a row is dropped when any coordinate lies outside [Q1 - f IQR, Q3 + f IQR].  Q1 is the minimum, so the low side
+    never drops anything — kept as the reference has it."""
+    p = np.asarray(points, dtype=np.float64)
+    lo = np.percentile(p, 0, axis=0)
+    hi = np.percentile(p, 80, axis=0)
+    iqr = hi - lo
+    out = (p < lo - outlier_factor * iqr) | (p > hi + outlier_factor * iqr)
+    return p[~out.any(axis=1)]
+
+
+def hull_planes(points: ArrayLike) -> np.ndarray:
+    """(F, 4) float64 outward half-spaces (n0, n1, n2, d) of the convex hull of `points`, inside where n.x + d <= 0:
+    Qhull's `equations` through scipy.spatial.ConvexHull."""
+    try:
+        from scipy.spatial import ConvexHull
+    except ImportError as exc:
+        raise ImportError("hull_planes needs scipy (scipy.spatial.ConvexHull); without it, build the hull elsewhere "
+                          "and pass its (F, 4) half-spaces as planes= directly") from exc
+    eq = ConvexHull(np.asarray(points, dtype=np.float64)).equations
+    return np.ascontiguousarray(eq, dtype=np.float64)
+
+
+def rotvec_to_matrix(rotvec: ArrayLike) -> np.ndarray:
+    """3x3 rotation of an axis-angle vector (Rodrigues; what scipy's Rotation.from_rotvec(v).as_matrix() gives)."""
+    v = np.asarray(rotvec, dtype=np.float64).reshape(3)
+    theta = float(np.linalg.norm(v))
+    if theta == 0.0:
+        return np.eye(3)
+    k = v / theta
+    K = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+    return np.eye(3) + np.sin(theta) * K + (1.0 - np.cos(theta)) * (K @ K)
+
+
+def pose_to_matrix(pose: ArrayLike) -> np.ndarray:
+    """4x4 homogeneous matrix of a gripper pose x, y, z, rx, ry, rz (translation, rotation vector)."""
+    p = np.asarray(pose, dtype=np.float64).reshape(6)
+    T = np.eye(4)
+    T[:3, :3] = rotvec_to_matrix(p[3:])
+    T[:3, 3] = p[:3]
+    return T
+
+
+def compose_transform(matrix: ArrayLike, scale: float, pose_from: ArrayLike, pose_to: ArrayLike) -> np.ndarray:
+    """The scene-frame rigid motion of the grasped object (update.py main :151-155 with prepare_transform :342-355):
+    T = matrix @ T_to @ inv(T_from) @ inv(matrix) in fp64, its translation times `scale`.  Returns [R | t], (3, 4)
+    float32 — what select_and_move takes."""
+    M = np.asarray(matrix, dtype=np.float64)
+    T = M @ (pose_to_matrix(pose_to) @ np.linalg.inv(pose_to_matrix(pose_from))) @ np.linalg.inv(M)
+    T[:3, 3] *= float(scale)
+    return T[:3, :].astype(np.float32)
+
+
+def object_points_to_scene(points: ArrayLike, matrix: ArrayLike, scale: float) -> np.ndarray:
+    """Object points into the scene's frame (update.py:148-149): [x, 1] @ matrix[:3, :].T, times scale."""
+    p = np.asarray(points, dtype=np.float64)[:, :3]
+    M = np.asarray(matrix, dtype=np.float64)
+    return (np.concatenate((p, np.ones((p.shape[0], 1))), axis=1) @ M[:3, :].T) * float(scale)
+
+
+# ------------------------------------------------------------------------------------------------
+# device side: one launch of gg_hull_edit
+# ------------------------------------------------------------------------------------------------
+def _rigid_host(transform: Optional[ArrayLike]):
+    if transform is None:
+        return None
+    t = transform.detach().cpu().numpy() if isinstance(transform, Tensor) else np.asarray(transform)
+    if t.shape not in ((3, 4), (4, 4)):
+        raise ValueError(f"transform must be [R | t] (3, 4) or homogeneous (4, 4), got {t.shape}")
+    rt = np.ascontiguousarray(t[:3, :], dtype=np.float32).reshape(12)
+    return rt
+
+
+def select_and_move(means: Tensor, quats: Optional[Tensor], planes: ArrayLike,
+                    transform: Optional[ArrayLike] = None, tol: float = 0.0) -> Tuple[Tensor, Tensor]:
+    """Select the Gaussians whose mean is inside the hull (every plane n.x + d <= tol) and, with a transform, move
+    them in place: means' = R x + t, quats' = quaternion of R quat_to_rotmat(q) (Shepperd, w >= 0).  Rows not
+    selected are not written.  One launch; nothing waits on the host.
+
+    means (N, 3) and quats (N, 4): fp32, contiguous, on the HIP device (no CPU path); quats may be None without a
+    transform.  planes: (F >= 4, 4) half-spaces (hull_planes).  Returns (mask (N,) uint8, count () int64), both on
+    the device."""
+    dev = _require_hip(means) if quats is None else _require_hip(means, quats)
+    for name, t, w in (("means", means, 3), ("quats", quats, 4)):
+        if t is None:
+            continue
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.ndim != 2 or t.shape[1] != w:
+            raise ValueError(f"{name} must be a contiguous float32 (N, {w}) tensor, got {t.dtype} "
+                             f"{tuple(t.shape)}{'' if t.is_contiguous() else ' (not contiguous)'}")
+    n = means.shape[0]
+    if quats is not None and quats.shape[0] != n:
+        raise ValueError(f"means has {n} rows, quats {quats.shape[0]}")
+    rt = _rigid_host(transform)
+    if rt is not None and quats is None:
+        raise ValueError("a transform moves means and quats: pass quats")
+    pl = torch.as_tensor(planes.detach() if isinstance(planes, Tensor) else np.asarray(planes))
+    pl = pl.to(device=dev, dtype=torch.float64).contiguous()
+    if pl.ndim != 2 or pl.shape[1] != 4 or pl.shape[0] < 4:
+        raise ValueError(f"planes must be (F >= 4, 4) half-spaces (n0, n1, n2, d), got {tuple(pl.shape)}")
+    mask = torch.empty(n, dtype=torch.uint8, device=dev)
+    count = torch.empty((), dtype=torch.int64, device=dev)
+    rt_ptr = None if rt is None else rt.ctypes.data_as(ctypes.c_void_p)
+    _lib.check(_lib.load().gg_hull_edit(n, _ptr(means), _ptr(quats), pl.shape[0], _ptr(pl), float(tol), rt_ptr,
+                                        _ptr(mask), _ptr(count), _stream(dev)), "gg_hull_edit")
+    return mask, count
+
+
+@torch.no_grad()
+def edit_model(model, planes: ArrayLike, transform: Optional[ArrayLike], tol: float = 0.0) -> int:
+    """update.py transformed_gs (:217-240) on a model holding `means` / `quats` Parameters (the plugin's fused model,
+    stub.StubGaussianSplattingModel): the same Parameter objects are edited in place, so an optimizer keeps
+    referencing them and its Adam moments stay as they are (the reference keeps them too: it saves the original
+    checkpoint's `optimizers`).  The version counters are bumped after the raw-pointer write, so nothing keyed on
+    (data_ptr, _version) serves the unedited scene.  Returns the number of Gaussians selected; raises if none are
+    (the reference asserts the same)."""
+    means, quats = model.means, model.quats
+    mask, count = select_and_move(means.detach(), quats.detach(), planes, transform, tol)
+    torch.autograd.graph.increment_version(means)
+    torch.autograd.graph.increment_version(quats)
+    selected = int(count.item())
+    if selected == 0:
+        raise ValueError("no Gaussian lies inside the object's hull")
+    return selected
+
+
+# ------------------------------------------------------------------------------------------------
+# command line: update.sh steps 1-3 on a checkpoint
+# ------------------------------------------------------------------------------------------------
+def load_object_points(path: str) -> np.ndarray:
+    """(M, 3) object points from .npy or text (update.py:144-147: the first three columns)."""
+    pts = np.load(path) if path.endswith(".npy") else np.loadtxt(path)
+    pts = np.asarray(pts, dtype=np.float64)
+    if pts.ndim != 2 or pts.shape[1] < 3:
+        raise ValueError(f"{path}: expected (M, >=3) points, got {pts.shape}")
+    return pts[:, :3]
+
+
+def edit_checkpoint(ckpt: str, object_points: np.ndarray, matrix: ArrayLike, scale: float, pose_from: ArrayLike,
+                    pose_to: ArrayLike, out: str, tol: float = 0.0, outlier_factor: float = 1.0,
+                    device: str = "cuda") -> int:
+    """Load `ckpt`, move the Gaussians inside the object's hull, write `out` with `step` 0.  Only
+    `pipeline["_model.means"]` and `pipeline["_model.quats"]` change; every other entry, `optimizers` included, is
+    saved as loaded (update.py save_checkpoint :257-286).  Returns the selected count."""
+    blob = torch.load(ckpt, map_location="cpu", weights_only=True)
+    pipe = blob.get("pipeline") if isinstance(blob, dict) else None
+    keys = (MODEL_PREFIX + "means", MODEL_PREFIX + "quats")
+    if not isinstance(pipe, dict) or any(k not in pipe for k in keys):
+        raise KeyError(f"{ckpt}: not a splatting checkpoint (no pipeline entries {', '.join(keys)})")
+    pts = filter_object_points(object_points_to_scene(object_points, matrix, scale), outlier_factor)
+    planes = hull_planes(pts)
+    rt = compose_transform(matrix, scale, pose_from, pose_to)
+    m0, q0 = pipe[keys[0]], pipe[keys[1]]
+    means = m0.detach().to(device=device, dtype=torch.float32).contiguous()
+    quats = q0.detach().to(device=device, dtype=torch.float32).contiguous()
+    _, count = select_and_move(means, quats, planes, rt, tol)
+    selected = int(count.item())
+    if selected == 0:
+        raise ValueError("no Gaussian lies inside the object's hull")
+    new_pipe = dict(pipe)
+    new_pipe[keys[0]] = means.cpu().to(m0.dtype)
+    new_pipe[keys[1]] = quats.cpu().to(q0.dtype)
+    new_blob = dict(blob)
+    new_blob["pipeline"] = new_pipe
+    new_blob["step"] = 0
+    if os.path.dirname(out):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+    torch.save(new_blob, out)
+    return selected
+
+
+def main(argv: Optional[Sequence[str]] = None) -> int:
+    ap = argparse.ArgumentParser(prog="python -m gaussiangrasper_amd.edit",
+                                 description="Move the Gaussians inside an object's convex hull with the gripper's "
+                                             "pose change (update.sh steps 1-3) and write a checkpoint to fine-tune.")
+    ap.add_argument("--ckpt", required=True, help="input step-*.ckpt")
+    ap.add_argument("--object-points", required=True, help="object point cloud, .npy or text, first 3 columns")
+    ap.add_argument("--transform-json", required=True, help="JSON with transform_matrix (4x4) and scale")
+    ap.add_argument("--pose-from", type=float, nargs=6, required=True, metavar=("X", "Y", "Z", "RX", "RY", "RZ"))
+    ap.add_argument("--pose-to", type=float, nargs=6, required=True, metavar=("X", "Y", "Z", "RX", "RY", "RZ"))
+    ap.add_argument("--out", required=True, help="output checkpoint, e.g. .../step-000000000.ckpt")
+    ap.add_argument("--tol", type=float, default=0.0, help="a mean is inside when every n.x + d <= tol")
+    ap.add_argument("--outlier-factor", type=float, default=1.0)
+    a = ap.parse_args(argv)
+    with open(a.transform_json) as f:
+        tj = json.load(f)
+    try:
+        n = edit_checkpoint(a.ckpt, load_object_points(a.object_points), tj["transform_matrix"], float(tj["scale"]),
+                            a.pose_from, a.pose_to, a.out, a.tol, a.outlier_factor)
+    except (KeyError, ValueError) as exc:
+        raise SystemExit(f"error: {exc}") from exc
+    print(f"selected {n} Gaussians; wrote {a.out}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

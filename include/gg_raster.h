@@ -513,6 +513,25 @@ typedef struct {
 } gg_adam_group_t;
 int gg_adam_step(int num_groups, const gg_adam_group_t *groups, int zero_grad, gg_stream_t stream);
 
+/* ---- scene update after a grasp (reference nerfstudio/scripts/update.py:141-158, 217-240, 293-328) -----------
+ * One pass over num_points Gaussians: select every Gaussian whose mean lies inside a convex hull and, when rt is
+ * given, move the selected ones rigidly, in place.
+ *   planes: num_planes x (n0, n1, n2, d) fp64, outward normals (Qhull's `equations`); num_planes >= 4, no upper
+ *           limit.  Mean x is inside iff every plane has v = ((n0*x0 + n1*x1) + n2*x2) + d <= tol, evaluated in
+ *           fp64 in that order, x widened exactly from fp32; a NaN / inf mean is outside (!(v <= tol)).
+ *   rt:     HOST array of 12 floats, [R | t] row-major 3 x 4, or NULL (select only: means / quats untouched,
+ *           quats may be NULL).
+ *   For selected rows, with rt: means' = ((R_i0*x0 + R_i1*x1) + R_i2*x2) + t_i (fp32, in that order);
+ *           quats' = Shepperd(R . quat_to_rotmat(q)), where quat_to_rotmat is gg_quat_to_rotmat_fwd's bit for bit,
+ *           the product is fp32, and the quaternion comes from the branch of the largest of tr, m00, m11, m22 (the
+ *           tr branch is the reference's rotmat_to_quat expression by expression), sign set so that w >= 0, not
+ *           renormalised.  Rows not selected are never written.
+ *   mask:      (num_points) uint8, 1 = selected, fully written.
+ *   count_out: DEVICE int64, the number of selected rows (zeroed by the call, so num_points == 0 leaves 0).
+ * quats 16-byte aligned.  No workspace. */
+int gg_hull_edit(int num_points, float *means, float *quats, int num_planes, const double *planes, double tol,
+                 const float *rt, uint8_t *mask, int64_t *count_out, gg_stream_t stream);
+
 /* ---- in-library kernel timing (measurement only; off by default) --------------------------------
  * When enabled, every launch of the kernels below is bracketed by a hipEvent pair recorded on the
  * launch stream, so bench.py can report the average duration of exactly that kernel over its
