@@ -106,6 +106,7 @@ extern "C" const char *gg_prof_name(int id) {
         case GG_K_ACTIVATE_BWD: return "activate_bwd_kernel";
         case GG_K_COUNT: return "count_kernel";
         case GG_K_TAIL_SPLIT: return "tail_split_kernel";
+        case GG_K_QUERY: return "clip_query_kernel";
         default: break;
     }
     if (id >= GG_K_BLEND_FWD && id < GG_K_BLEND_FWD + 6) {

@@ -532,6 +532,25 @@ int gg_adam_step(int num_groups, const gg_adam_group_t *groups, int zero_grad, g
 int gg_hull_edit(int num_points, float *means, float *quats, int num_planes, const double *planes, double tol,
                  const float *rt, uint8_t *mask, int64_t *count_out, gg_stream_t stream);
 
+/* ---- language query of the feature field ------------------------------------------------------------
+ * fea_up followed by the CLIP comparison, with the 512-float fea_up output never written to memory:
+ *   y   = relu(x @ w1^T + b1) @ w2^T + b2 per row, as gg_mlp_fwd_fast computes it (in_dim 32 / 64 / 128, hidden 128,
+ *         out_dim a multiple of 16 and at most 3968, and 2 out_dim + 129 num_queries + 256 <= 8192: LDS);
+ *   s_k = (y . q_k) / max(|y|_2, 1e-12) for the num_queries rows q_k of `queries` (num_queries x out_dim, unit norm:
+ *         F.normalize(y) @ q^T); the first num_positives rows are positives, the rest canonical negatives;
+ *   r_p = 1 / (1 + exp(temperature (max_j s_nj - s_p))) = min_j softmax(temperature [s_p, s_nj])[0]  (LERF).
+ *   sims:      num_rows x num_queries, or NULL;  relevancy: num_rows x num_positives, or NULL (needs 1 <= num_positives
+ *              < num_queries).  At least one of the two.  y = 0 gives s = 0, r = 1/2; a NaN feature makes that row's
+ *              outputs NaN; num_rows = 0 does nothing.  Fixed summation orders, no atomics: identical run to run.
+ * x 16-byte aligned; `ws`: gg_clip_query_workspace() bytes (0 = shape not supported), 16-byte aligned, rewritten by
+ * every call (the packed weights of gg_mlp_fwd_fast). */
+#define GG_QUERY_MAX 8
+size_t gg_clip_query_workspace(int in_dim, int hidden_dim, int out_dim, int num_queries);
+int gg_clip_query(int64_t num_rows, int in_dim, int hidden_dim, int out_dim, const float *x, const float *w1,
+                  const float *b1, const float *w2, const float *b2, int num_queries, int num_positives,
+                  const float *queries, float temperature, float *sims, float *relevancy, void *ws, size_t ws_bytes,
+                  gg_stream_t stream);
+
 /* ---- in-library kernel timing (measurement only; off by default) --------------------------------
  * When enabled, every launch of the kernels below is bracketed by a hipEvent pair recorded on the
  * launch stream, so bench.py can report the average duration of exactly that kernel over its
@@ -560,6 +579,7 @@ int gg_hull_edit(int num_points, float *means, float *quats, int num_planes, con
 #define GG_K_COUNT 18         /* gg_count_intersects */
 #define GG_K_TAIL_SPLIT 19    /* gg_shade_tail_bwd_split */
 #define GG_K_VIEW_FWD 32      /* gg_view_fwd: activations + projection of a view in one kernel */
+#define GG_K_QUERY 33         /* gg_clip_query: weight packing + clip_query_kernel */
 #define GG_K_IDS 40           /* ids are below this */
 #define GG_PROF_NUM_KERNELS 32
 int gg_prof_enable(int on);
