@@ -103,6 +103,8 @@ SIGNATURES = {
     "gg_hull_edit": (_I, [_I, _P, _P, _I, _P, C.c_double, _P, _P, _P, _P]),
     "gg_clip_query_workspace": (_SZ, [_I, _I, _I, _I]),
     "gg_clip_query": (_I, [_I64, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _P, _F, _P, _P, _P, _SZ, _P]),
+    "gg_grasp_contacts_workspace": (_SZ, [_I, _I]),
+    "gg_grasp_contacts": (_I, [_I, _P, _P, _P, _I, _P] + [C.c_double] * 6 + [_P] * 8 + [_SZ, _P]),
     "gg_prof_enable": (_I, [_I]),
     "gg_prof_reset": (_I, []),
     "gg_prof_get": (_I, [_I, C.POINTER(C.c_int), C.POINTER(C.c_double)]),

@@ -107,6 +107,7 @@ extern "C" const char *gg_prof_name(int id) {
         case GG_K_COUNT: return "count_kernel";
         case GG_K_TAIL_SPLIT: return "tail_split_kernel";
         case GG_K_QUERY: return "clip_query_kernel";
+        case GG_K_GRASP: return "gg_grasp_contacts(all launches)";
         default: break;
     }
     if (id >= GG_K_BLEND_FWD && id < GG_K_BLEND_FWD + 6) {

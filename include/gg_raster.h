@@ -551,6 +551,43 @@ int gg_clip_query(int64_t num_rows, int in_dim, int hidden_dim, int out_dim, con
                   const float *queries, float temperature, float *sims, float *relevancy, void *ws, size_t ws_bytes,
                   gg_stream_t stream);
 
+/* ---- normal-guided grasp filtering (PARITY "Grasp filtering") --------------------------------------
+ * Every grasp candidate against every oriented point, exact in fp64, with a deterministic reduction.
+ *   grasps: num_grasps x 17 fp32, graspnetAPI GraspGroup rows [score, width, height, depth, R (9, row-major),
+ *           t (3), object_id]; gripper frame a = R[:,0] approach, b = R[:,1] closing (fingers at -b and +b),
+ *           c = R[:,2] height.
+ *   points, normals: num_points x 3 fp32 (normals any sign, any length); weights: num_points fp32.  A point takes
+ *           part iff p and n are finite and (double)w > min_weight.
+ * Per grasp g, in fp64 from the fp32 inputs, no contraction:
+ *   d_k = (double)p_k - (double)t_k;  u_j = (R[0][j] d_0 + R[1][j] d_1) + R[2][j] d_2;
+ *   region:       -depth_base <= u_0 <= depth, |u_2| <= height/2, |u_1| <= width/2;
+ *   finger boxes: the same u_0 / u_2 bounds, -width/2 - finger_width <= u_1 < -width/2 or
+ *                 width/2 < u_1 <= width/2 + finger_width;
+ *   contacts:     y_L = min u_1, y_R = max u_1 over the region, i_L / i_R the smallest indices reaching them;
+ *   patches:      left: region points with u_1 <= y_L + band, right: u_1 >= y_R - band; n oriented toward its finger
+ *                 (left: s = -1 if b.n > 0 else +1; right: s = -1 if b.n < 0 else +1, b.n = (b0 n0 + b1 n1) + b2 n2);
+ *                 N_L = sum_L w s n, N_R = sum_R w s n in fp64, normalised;
+ *   angles:       theta_L = atan2(|x cross b|, x . b) with x = -N_L/|N_L|, theta_R the same with x = N_R/|N_R|;
+ *   valid:        region not empty, y_L < y_R, |N_L| > 0 and |N_R| > 0;
+ *   feasible:     valid, max(theta_L, theta_R) <= atan(mu) and collision_weight <= max_collision (fp64).
+ * A grasp row with a non-finite entry, width <= 0, height <= 0 or depth < -depth_base is not valid (data, not an
+ * error).  Outputs, every grasp written:
+ *   contact_idx int32 [M][2] (i_L, i_R; -1 when the region is empty); normals_out fp32 [M][2][3] (unit, outward;
+ *   NaN when not valid); angles fp32 [M][2] (radians, NaN when not valid); region_count int32 [M];
+ *   region_weight / collision_weight fp32 [M] (sum of w over the region / over both finger boxes); feasible uint8 [M].
+ * depth_base, finger_width, band and mu finite and >= 0; min_weight and max_collision not NaN (+inf: no collision
+ * limit).  num_grasps == 0 does nothing; num_points == 0 marks every grasp not valid.  No atomics: per-chunk
+ * partials combined in a fixed order, identical run to run.  `ws`: gg_grasp_contacts_workspace() bytes, 256-byte
+ * aligned (0 bytes for num_grasps == 0; 0 is also returned for counts out of range). */
+#define GG_GRASP_MAX (1 << 20)
+#define GG_GRASP_MAX_POINTS (1 << 30)
+size_t gg_grasp_contacts_workspace(int num_points, int num_grasps);
+int gg_grasp_contacts(int num_points, const float *points, const float *normals, const float *weights, int num_grasps,
+                      const float *grasps, double depth_base, double finger_width, double band, double mu,
+                      double min_weight, double max_collision, int32_t *contact_idx, float *normals_out, float *angles,
+                      int32_t *region_count, float *region_weight, float *collision_weight, uint8_t *feasible,
+                      void *ws, size_t ws_bytes, gg_stream_t stream);
+
 /* ---- in-library kernel timing (measurement only; off by default) --------------------------------
  * When enabled, every launch of the kernels below is bracketed by a hipEvent pair recorded on the
  * launch stream, so bench.py can report the average duration of exactly that kernel over its
@@ -580,6 +617,7 @@ int gg_clip_query(int64_t num_rows, int in_dim, int hidden_dim, int out_dim, con
 #define GG_K_TAIL_SPLIT 19    /* gg_shade_tail_bwd_split */
 #define GG_K_VIEW_FWD 32      /* gg_view_fwd: activations + projection of a view in one kernel */
 #define GG_K_QUERY 33         /* gg_clip_query: weight packing + clip_query_kernel */
+#define GG_K_GRASP 34         /* gg_grasp_contacts: both passes and both per-grasp reductions */
 #define GG_K_IDS 40           /* ids are below this */
 #define GG_PROF_NUM_KERNELS 32
 int gg_prof_enable(int on);
