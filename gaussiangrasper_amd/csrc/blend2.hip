@@ -308,14 +308,7 @@ void blend2_fwd_kernel(
         STAMP(4);
     }
     STAMP(8);
-#ifndef GG_EPI_SKIP
-#define GG_EPI_SKIP 0   // diagnostic builds only (with GG_STAMPS): 1 no final_T / final_idx stores, 2 no image stores.
-                        // A backward after a GG_EPI_SKIP=1 forward reads an uninitialised final_idx image: it faulted
-                        // once (r02).  Since r03 the backward kernels hold final_idx to the tile's list range, and
-                        // tools/stamps.py asks the build (gg_debug_epi_skip) and runs no backward on such a forward.
-#endif
-    if (GG_EPI_SKIP == 1) { KEEP(T); KEEP(last); }
-    if (GG_EPI_SKIP != 1 && inside && write_final) {
+    if (inside && write_final) {
         const size_t p = (size_t)i * img_w + j;
         final_T[p] = T;
         final_idx[p] = last;
@@ -361,7 +354,6 @@ void blend2_fwd_kernel(
                 const int pq = 16 * q4 + pl;
                 const float Tp = __shfl(T, pq, 64);
                 const int pj = qx0 + (pq & 7), pi = qy0 + (pq >> 3);
-                if (GG_EPI_SKIP == 2) { KEEP(v.x + v.y + v.z + v.w + Tp); continue; }
                 if (pi < img_h && pj < img_w) {
                     typedef float f4v __attribute__((ext_vector_type(4)));
                     const f4v o = {__builtin_fmaf(Tp, bg4.x, v.x), __builtin_fmaf(Tp, bg4.y, v.y),
@@ -887,24 +879,9 @@ __global__ __launch_bounds__(64 * GG_WPB_OTHER) void blend2_bwd_narrow_kernel(
 // (split2h / pow2_scale / pow2_inv / H8: gg_common.h, "fp32 products on the fp16 matrix rate")
 #define GG_FAC_SCALE 32768.0f          // fac = alpha T in [3.9e-7, 0.99]: x 2^15 before the split
 #define GG_FAC_UNSCALE (1.0f / 32768.0f)
-#ifndef GG_F16_SWAPMAX
-#define GG_F16_SWAPMAX 1   // the slot's row maximum across its four lanes: v_permlane16/32_swap (0: ds_bpermute; measured +2 %)
-#endif
-#ifndef GG_F16_NLL
-#define GG_F16_NLL 0       // 1: without the lo x lo piece products (2^-24 each; measured -1.5 % of the kernel: not taken)
-#endif
 // quadrants without any cotangent of the first array (feat_any, below): its flush is skipped (measured: training
 // iteration -1.6 %, dense bench view +-0; skipping its colour rows and D k-steps as well measured +4 % on the dense
-// view: profiles/r03_featany_d_experiment.patch)
-#ifndef GG_FEATANY_FLUSH
-#define GG_FEATANY_FLUSH 1
-#endif
-#ifndef GG_MG_MOMENTS
-#define GG_MG_MOMENTS 1   // merged-flush builds: geometry sums as moments about the Gaussian's centre (0: the per-pixel form)
-#endif
-#ifndef GG_S16_F16
-#define GG_S16_F16 1    // 0: the 16-slot backward's products on v_mfma_f32_16x16x4_f32 (the build before)
-#endif
+// view)
 #ifndef GG_S16_WAVES
 #define GG_S16_WAVES 4    // waves per SIMD the 16-slot backward is compiled for (128 registers)
 #endif
@@ -914,9 +891,6 @@ __global__ __launch_bounds__(64 * GG_WPB_OTHER) void blend2_bwd_narrow_kernel(
 // instead of 16 v_mfma_f32_16x16x4_f32 (512 of the batch's 1 280) for 48 more vector instructions per batch.
 // Measured (tools/pairbench.py, interleaved variants, bench view): 0.7825 -> 0.7604 ms.  The B pieces split ONCE per wave
 // and held in 16 registers across the walk: 25 spilled registers at four waves per SIMD, 0.8898 ms — not kept.
-#ifndef GG_F2_F16
-#define GG_F2_F16 1   // 0: the fp32 second flush of round 3
-#endif
 
 // =============================================================================================
 // backward, wide (32-channel chunk): wave-autonomous, matrix pipe for D = <colour, v_out> AND for the colour
@@ -964,7 +938,7 @@ struct Seg2B {
 // (A build for four workgroups per CU that re-read the cotangents per batch instead of holding them — 128 VGPRs,
 // batches of 28 slots — spilled 81 registers in the walk and ran 1.50 ms against 1.00: removed in r03; the 16-slot
 // build below took the fourth wave instead.)
-// S16 (experiment for FOUR waves per SIMD, -DGG_BWD_S16=1): batches of 16 slots on v_mfma_f32_16x16x4_f32 — D
+// S16 (FOUR waves per SIMD): batches of 16 slots on 16 x 16 MFMAs, D and the flush on fp16 two-piece operands — D
 // accumulators 16 registers instead of 32, flush accumulators 8 instead of 16, slab 4 160 B instead of 8 320, the walk
 // re-reading its records.  k-step s of lane group q = lane >> 4 is channel 8 q + s, so a lane's B operand is still two
 // float4 loads of its Gaussian's colour row.  Needs 16-byte aligned colour rows and cotangent rows (the launcher
@@ -1042,14 +1016,13 @@ __global__ __launch_bounds__(64 * GG_WPB_WIDE_BWD) __attribute__((amdgpu_waves_p
                       ((reinterpret_cast<uintptr_t>(v_out) & 15) == 0);   // wave-uniform
     float voa_keep[2][S16 ? 1 : KS], vob_keep[S16 ? 1 : 32];
     float va16[S16 ? 4 : 1][S16 ? 8 : 1], vb16[S16 ? 16 : 1][S16 ? 2 : 1];   // S16: A operands of D, B operands of the flush
-    // F16: the same elements as two fp16 pieces each (packed pairs): D's A operands V_OUT[pixel 16 blk + (lane & 15)]
+    // S16: the same elements as two fp16 pieces each (packed pairs): D's A operands V_OUT[pixel 16 blk + (lane & 15)]
     // [channel 8 (lane >> 4) + 0..7] x s_w, the flush's B operands V_OUT[pixel 32 ks + 8 (lane >> 4) + 0..7][channel
     // 16 nb + (lane & 15)] x s_c.  s_w: one power of two for the quadrant's cotangents (all channels of both arrays),
     // s_c: one per channel of this lane; the raw values above are dead after the prologue.
-    constexpr bool F16 = S16 && (GG_S16_F16 != 0);
-    constexpr bool F2 = F16 && EX && (GG_F2_F16 != 0);
-    unsigned vah[F16 ? 4 : 1][F16 ? 4 : 1], val[F16 ? 4 : 1][F16 ? 4 : 1];
-    unsigned vbh[F16 ? 2 : 1][F16 ? 2 : 1][F16 ? 4 : 1], vbl[F16 ? 2 : 1][F16 ? 2 : 1][F16 ? 4 : 1];
+    constexpr bool F2 = S16 && EX;
+    unsigned vah[S16 ? 4 : 1][S16 ? 4 : 1], val[S16 ? 4 : 1][S16 ? 4 : 1];
+    unsigned vbh[S16 ? 2 : 1][S16 ? 2 : 1][S16 ? 4 : 1], vbl[S16 ? 2 : 1][S16 ? 2 : 1][S16 ? 4 : 1];
     float sw = 1.0f, inv_sw = 1.0f, inv_scf[2] = {1.0f, 1.0f};
     float Bsum = 0.0f;
     // A wave starts with a chain of dependent loads: tile range -> final_idx -> (wave maximum) -> list ids -> records.
@@ -1113,8 +1086,8 @@ __global__ __launch_bounds__(64 * GG_WPB_WIDE_BWD) __attribute__((amdgpu_waves_p
                 }
             }
 #pragma unroll
-            for (int ss = 0; ss < 8; ++ss) {   // B operands of the flush: pixel 4 (8 hh + ss) + q4, channel 16 nb + sl
-                const int pl = F16 ? 8 * q4 + ss : 4 * ss + q4;   // (F16: pixel 32 hh + 8 q4 + ss — the K = 32 layout)
+            for (int ss = 0; ss < 8; ++ss) {   // B operands of the flush: pixel 32 hh + 8 q4 + ss, channel 16 nb + sl
+                const int pl = 8 * q4 + ss;
 #pragma unroll
                 for (int nb = 0; nb < 2; ++nb) {
                     const int c = 16 * nb + sl;
@@ -1177,21 +1150,21 @@ __global__ __launch_bounds__(64 * GG_WPB_WIDE_BWD) __attribute__((amdgpu_waves_p
     // the prologue
     ra_p = reinterpret_cast<const float4 *>(rec + g_first)[0];
     rb_p = reinterpret_cast<const float4 *>(rec + g_first)[1];
-    // F16: s_w from the largest |cotangent| of the quadrant — every element of the first array's tile is in exactly one
+    // S16: s_w from the largest |cotangent| of the quadrant — every element of the first array's tile is in exactly one
     // lane's va16, every element of the second array's in one lane's t8
     float mloc = 0.0f;
     // feat_any (wave-uniform): does the quadrant's cotangent of THIS array have a non-zero (or NaN) element at all?  The
     // reference's training loss reaches the feature image at <= 2 600 sampled pixels of 1.9 M (gaussian_splatting.py:
     // 909-918): nine quadrants in ten have none, and for them a batch's flush of this array is skipped (its colour
-    // gradients are exactly zero; GG_FEATANY_* above)
+    // gradients are exactly zero; measured above the backward kernel)
     bool feat_any = true;
-    if (F16) {
+    if (S16) {
         bool nz = false;
 #pragma unroll
         for (int blk = 0; blk < 4; ++blk)
 #pragma unroll
             for (int t = 0; t < 8; ++t) {
-                const float v = va16[F16 ? blk : 0][F16 ? t : 0];
+                const float v = va16[S16 ? blk : 0][S16 ? t : 0];
                 mloc = fmaxf(mloc, fabsf(v));
                 nz = nz || (v != 0.0f);
             }
@@ -1202,7 +1175,7 @@ __global__ __launch_bounds__(64 * GG_WPB_WIDE_BWD) __attribute__((amdgpu_waves_p
         sw = pow2_scale(mloc);
         inv_sw = pow2_inv(sw);
     };
-    if (F16 && !EX) tile_scale();
+    if (S16 && !EX) tile_scale();
     if (EX) {
         float t8[8];
 #pragma unroll
@@ -1221,7 +1194,7 @@ __global__ __launch_bounds__(64 * GG_WPB_WIDE_BWD) __attribute__((amdgpu_waves_p
             t8[c] = (inside && c < seg2.nch2) ? t8[c] : 0.0f;
             if (c < seg2.nch2) Bsum = __builtin_fmaf(seg2.background[c], t8[c], Bsum);
         }
-        if (F16) {
+        if (S16) {
 #pragma unroll
             for (int c = 0; c < 8; ++c) mloc = fmaxf(mloc, fabsf(t8[c]));
             tile_scale();
@@ -1246,18 +1219,18 @@ __global__ __launch_bounds__(64 * GG_WPB_WIDE_BWD) __attribute__((amdgpu_waves_p
             __builtin_amdgcn_wave_barrier();
         }
     }
-    if (F16) {
+    if (S16) {
 #pragma unroll
         for (int blk = 0; blk < 4; ++blk)
 #pragma unroll
             for (int t = 0; t < 4; ++t)
-                split2h(va16[F16 ? blk : 0][F16 ? 2 * t : 0] * sw, va16[F16 ? blk : 0][F16 ? 2 * t + 1 : 0] * sw,
-                        vah[F16 ? blk : 0][F16 ? t : 0], val[F16 ? blk : 0][F16 ? t : 0]);
+                split2h(va16[S16 ? blk : 0][S16 ? 2 * t : 0] * sw, va16[S16 ? blk : 0][S16 ? 2 * t + 1 : 0] * sw,
+                        vah[S16 ? blk : 0][S16 ? t : 0], val[S16 ? blk : 0][S16 ? t : 0]);
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb) {
             float m = 0.0f;
 #pragma unroll
-            for (int t = 0; t < 16; ++t) m = fmaxf(m, fabsf(vb16[F16 ? t : 0][F16 ? nb : 0]));
+            for (int t = 0; t < 16; ++t) m = fmaxf(m, fabsf(vb16[S16 ? t : 0][S16 ? nb : 0]));
             m = fmaxf(m, __shfl_xor(m, 16, 64));
             m = fmaxf(m, __shfl_xor(m, 32, 64));
             const float sc = pow2_scale(m);
@@ -1266,8 +1239,8 @@ __global__ __launch_bounds__(64 * GG_WPB_WIDE_BWD) __attribute__((amdgpu_waves_p
             for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
                 for (int t = 0; t < 4; ++t)
-                    split2h(vb16[F16 ? 8 * ks + 2 * t : 0][F16 ? nb : 0] * sc, vb16[F16 ? 8 * ks + 2 * t + 1 : 0][F16 ? nb : 0] * sc,
-                            vbh[F16 ? ks : 0][F16 ? nb : 0][F16 ? t : 0], vbl[F16 ? ks : 0][F16 ? nb : 0][F16 ? t : 0]);
+                    split2h(vb16[S16 ? 8 * ks + 2 * t : 0][S16 ? nb : 0] * sc, vb16[S16 ? 8 * ks + 2 * t + 1 : 0][S16 ? nb : 0] * sc,
+                            vbh[S16 ? ks : 0][S16 ? nb : 0][S16 ? t : 0], vbl[S16 ? ks : 0][S16 ? nb : 0][S16 ? t : 0]);
         }
     }
     W = T_final * Bsum;
@@ -1330,7 +1303,7 @@ __global__ __launch_bounds__(64 * GG_WPB_WIDE_BWD) __attribute__((amdgpu_waves_p
         STAMP_BATCH();
         const int jl = S16 ? (lane & 15) : (lane & 31);
         const int cgid = (jl < n) ? __builtin_bit_cast(int, Q.b[base + jl].w) : -1;
-        if (S16) {   // D[64 pixels x 16 slots] as 4 x 10 v_mfma_f32_16x16x4_f32
+        if (S16) {   // D[64 pixels x 16 slots] as 4 x 4 v_mfma_f32_16x16x32_f16 (+ 4 x 2 v_mfma_f32_16x16x4_f32: EX)
             const int q4 = lane >> 4;
             const float *row = colors + (size_t)(cgid < 0 ? 0 : cgid) * C + ch_off + 8 * q4;
             float4 c0 = make_float4(0.f, 0.f, 0.f, 0.f), c1 = c0;
@@ -1350,74 +1323,48 @@ __global__ __launch_bounds__(64 * GG_WPB_WIDE_BWD) __attribute__((amdgpu_waves_p
                     va2[blk][1] = t2.y;
                 }
             }
+            // s_g: the power of two for this slot's colour row (both arrays; the four lanes of a slot hold it all)
+            float m = 0.0f;
+#pragma unroll
+            for (int t = 0; t < 8; ++t) m = fmaxf(m, fabsf(colb[t]));
+            m = fmaxf(m, fmaxf(fabsf(colb2[0]), fabsf(colb2[1])));
+            m = cgid < 0 ? 0.0f : m;
+            {   // (v_permlane16/32_swap; ds_bpermute measured +2 %)
+                auto r16 = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, m), __builtin_bit_cast(unsigned, m), false, false);
+                m = fmaxf(__builtin_bit_cast(float, (unsigned)r16[0]), __builtin_bit_cast(float, (unsigned)r16[1]));
+                auto r32 = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, m), __builtin_bit_cast(unsigned, m), false, false);
+                m = fmaxf(__builtin_bit_cast(float, (unsigned)r32[0]), __builtin_bit_cast(float, (unsigned)r32[1]));
+            }
+            const float sg = cgid < 0 ? 0.0f : pow2_scale(m);   // (null slot: every operand 0)
+            const float unscale = pow2_inv(cgid < 0 ? 1.0f : sg) * inv_sw;
+            unsigned ch_[4] = {0u, 0u, 0u, 0u}, cl_[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int t = 0; t < 4; ++t) split2h(colb[2 * t] * sg, colb[2 * t + 1] * sg, ch_[t], cl_[t]);
+            const h16x8 Bh = H8(ch_[0], ch_[1], ch_[2], ch_[3]), Bl = H8(cl_[0], cl_[1], cl_[2], cl_[3]);
+            const float b2[2] = {colb2[0] * sg, colb2[1] * sg};   // (zeros without a second array)
             f32x4 d[4];
-            if (F16) {
-                // s_g: the power of two for this slot's colour row (both arrays; the four lanes of a slot hold it all)
-                float m = 0.0f;
-#pragma unroll
-                for (int t = 0; t < 8; ++t) m = fmaxf(m, fabsf(colb[t]));
-                m = fmaxf(m, fmaxf(fabsf(colb2[0]), fabsf(colb2[1])));
-                m = cgid < 0 ? 0.0f : m;
-#if GG_F16_SWAPMAX
-                {
-                    auto r16 = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, m), __builtin_bit_cast(unsigned, m), false, false);
-                    m = fmaxf(__builtin_bit_cast(float, (unsigned)r16[0]), __builtin_bit_cast(float, (unsigned)r16[1]));
-                    auto r32 = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, m), __builtin_bit_cast(unsigned, m), false, false);
-                    m = fmaxf(__builtin_bit_cast(float, (unsigned)r32[0]), __builtin_bit_cast(float, (unsigned)r32[1]));
-                }
-#else
-                m = fmaxf(m, __shfl_xor(m, 16, 64));
-                m = fmaxf(m, __shfl_xor(m, 32, 64));
-#endif
-                const float sg = cgid < 0 ? 0.0f : pow2_scale(m);   // (null slot: every operand 0)
-                const float unscale = pow2_inv(cgid < 0 ? 1.0f : sg) * inv_sw;
-                unsigned ch_[4] = {0u, 0u, 0u, 0u}, cl_[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-                for (int t = 0; t < 4; ++t) split2h(colb[2 * t] * sg, colb[2 * t + 1] * sg, ch_[t], cl_[t]);
-                const h16x8 Bh = H8(ch_[0], ch_[1], ch_[2], ch_[3]), Bl = H8(cl_[0], cl_[1], cl_[2], cl_[3]);
-                const float b2[2] = {colb2[0] * sg, colb2[1] * sg};   // (zeros without a second array)
-#pragma unroll
-                for (int blk = 0; blk < 4; ++blk) {
-                    const int bb = F16 ? blk : 0;
-                    const h16x8 Ah = H8(vah[bb][0], vah[bb][F16 ? 1 : 0], vah[bb][F16 ? 2 : 0], vah[bb][F16 ? 3 : 0]);
-                    const h16x8 Al = H8(val[bb][0], val[bb][F16 ? 1 : 0], val[bb][F16 ? 2 : 0], val[bb][F16 ? 3 : 0]);
-                    d[blk] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-#if !GG_F16_NLL
-                    d[blk] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al, Bl, d[blk], 0, 0, 0);
-#endif
-                    d[blk] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al, Bh, d[blk], 0, 0, 0);
-                    d[blk] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah, Bl, d[blk], 0, 0, 0);
-                    d[blk] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah, Bh, d[blk], 0, 0, 0);
-                    if (EX) {
-#pragma unroll
-                        for (int t = 0; t < 2; ++t)   // the second array's channels: fp32 k-steps on operands carrying s_w, s_g
-                            d[blk] = __builtin_amdgcn_mfma_f32_16x16x4f32(va2[blk][t], b2[t], d[blk], 0, 0, 0);
-                    }
-                }
-#pragma unroll
-                for (int blk = 0; blk < 4; ++blk)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) fac_w[FIDX(jl, 16 * blk + 4 * q4 + r)] = d[blk][r] * unscale;
-            } else {
 #pragma unroll
             for (int blk = 0; blk < 4; ++blk) {
+                const int bb = S16 ? blk : 0;
+                const h16x8 Ah = H8(vah[bb][0], vah[bb][S16 ? 1 : 0], vah[bb][S16 ? 2 : 0], vah[bb][S16 ? 3 : 0]);
+                const h16x8 Al = H8(val[bb][0], val[bb][S16 ? 1 : 0], val[bb][S16 ? 2 : 0], val[bb][S16 ? 3 : 0]);
                 d[blk] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-                for (int t = 0; t < 8; ++t)
-                    d[blk] = __builtin_amdgcn_mfma_f32_16x16x4f32(va16[S16 ? blk : 0][S16 ? t : 0], cgid < 0 ? 0.0f : colb[t],
-                                                                  d[blk], 0, 0, 0);
+                // (lo x lo: 2^-24 each; leaving it out measured -1.5 % of the kernel, not taken)
+                d[blk] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al, Bl, d[blk], 0, 0, 0);
+                d[blk] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al, Bh, d[blk], 0, 0, 0);
+                d[blk] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah, Bl, d[blk], 0, 0, 0);
+                d[blk] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah, Bh, d[blk], 0, 0, 0);
                 if (EX) {
 #pragma unroll
-                    for (int t = 0; t < 2; ++t)
-                        d[blk] = __builtin_amdgcn_mfma_f32_16x16x4f32(va2[blk][t], cgid < 0 ? 0.0f : colb2[t], d[blk], 0, 0, 0);
+                    for (int t = 0; t < 2; ++t)   // the second array's channels: fp32 k-steps on operands carrying s_w, s_g
+                        d[blk] = __builtin_amdgcn_mfma_f32_16x16x4f32(va2[blk][t], b2[t], d[blk], 0, 0, 0);
                 }
             }
             // D[pixel 16 blk + 4 q4 + r][slot jl]
 #pragma unroll
             for (int blk = 0; blk < 4; ++blk)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) fac_w[FIDX(jl, 16 * blk + 4 * q4 + r)] = d[blk][r];
-            }
+                for (int r = 0; r < 4; ++r) fac_w[FIDX(jl, 16 * blk + 4 * q4 + r)] = d[blk][r] * unscale;
         }
         f32x16 d0, d1;
 #pragma unroll
@@ -1530,16 +1477,15 @@ __global__ __launch_bounds__(64 * GG_WPB_WIDE_BWD) __attribute__((amdgpu_waves_p
                 const float D = fac_w[FIDX(g + q, lane)];
                 // MG: a pair that does not pass takes alpha = 0 and exp = 0 through the SAME arithmetic instead of five
                 // selects: 1 / (1 - 0) = 1, so T and (D finite) W stay as they are and fac, v_sigma and the moments are zeros
-                constexpr bool SEL2 = MG && GG_MG_MOMENTS;
-                const float al = SEL2 ? (pass[q] ? alpha[q] : 0.0f) : alpha[q];
+                const float al = MG ? (pass[q] ? alpha[q] : 0.0f) : alpha[q];
                 const float ra_ = __builtin_amdgcn_rcpf(1.0f - al);
                 const float Tn = T * ra_;
-                const float fac = SEL2 ? al * Tn : (pass[q] ? alpha[q] * Tn : 0.0f);
-                const float v_alpha = SEL2 ? __builtin_fmaf(Tn, D, -(ra_ * W)) : (pass[q] ? (Tn * D - ra_ * W) : 0.0f);
-                W = SEL2 ? __builtin_fmaf(D, fac, W) : (pass[q] ? __builtin_fmaf(D, fac, W) : W);
-                T = SEL2 ? Tn : (pass[q] ? Tn : T);
+                const float fac = MG ? al * Tn : (pass[q] ? alpha[q] * Tn : 0.0f);
+                const float v_alpha = MG ? __builtin_fmaf(Tn, D, -(ra_ * W)) : (pass[q] ? (Tn * D - ra_ * W) : 0.0f);
+                W = MG ? __builtin_fmaf(D, fac, W) : (pass[q] ? __builtin_fmaf(D, fac, W) : W);
+                T = MG ? Tn : (pass[q] ? Tn : T);
                 const float dx = A.x - px, dy = A.y - py;
-                if (MG && GG_MG_MOMENTS) {
+                if (MG) {
                     // moments about the Gaussian's own centre: sum v_sigma {dx, dy, dx^2, dx dy, dy^2}; the conic enters
                     // AFTER the reduction, in the flush (v_x = a M0 + b M1, v_y = b M0 + c M1, conic gradients M2..4 / 2):
                     // 5 multiplies per pair instead of 14 operations.  (Not the experiment of 3.5c: no expansion about a
@@ -1593,13 +1539,13 @@ __global__ __launch_bounds__(64 * GG_WPB_WIDE_BWD) __attribute__((amdgpu_waves_p
         slotmask = __builtin_amdgcn_readfirstlane(slotmask);
         if (ABL >= 2 || slotmask == 0u) return;
         f32x4 a4f_keep = {0.0f, 0.0f, 0.0f, 0.0f};   // F2: the second array's flush, formed beside the first one's
-        if (S16) {   // FAC[16 slots x 64 pixels] * V_OUT[64 x 32 channels] as 2 x 16 v_mfma_f32_16x16x4_f32
+        if (S16) {   // FAC[16 slots x 64 pixels] * V_OUT[64 x 32 channels] as 2 x 2 x 4 v_mfma_f32_16x16x32_f16
             int sl = lane & 15, q4 = lane >> 4;
             asm volatile("" : "+v"(sl), "+v"(q4));
             f32x4 acc2[2] = {f32x4{0.0f, 0.0f, 0.0f, 0.0f}, f32x4{0.0f, 0.0f, 0.0f, 0.0f}};
-            const bool first_on = !(F16 && !feat_any && GG_FEATANY_FLUSH);   // (no cotangent of the first array in the
-            f32x4 &a4f = a4f_keep;                                            //  quadrant: its colour gradients are zeros)
-            if (F16 && (first_on || F2)) {   // A: FAC[slot sl][pixel 32 ks + 8 q4 + 0..7] x 2^15 in two pieces
+            // (!feat_any: no cotangent of the first array in the quadrant, its colour gradients are zeros)
+            f32x4 &a4f = a4f_keep;
+            if (feat_any || F2) {   // A: FAC[slot sl][pixel 32 ks + 8 q4 + 0..7] x 2^15 in two pieces
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
                     unsigned fh[4], fl[4];
@@ -1608,15 +1554,13 @@ __global__ __launch_bounds__(64 * GG_WPB_WIDE_BWD) __attribute__((amdgpu_waves_p
                         split2h(fac_w[FIDX(sl, 32 * ks + 8 * q4 + 2 * t)] * GG_FAC_SCALE,
                                 fac_w[FIDX(sl, 32 * ks + 8 * q4 + 2 * t + 1)] * GG_FAC_SCALE, fh[t], fl[t]);
                     const h16x8 Fh = H8(fh[0], fh[1], fh[2], fh[3]), Fl = H8(fl[0], fl[1], fl[2], fl[3]);
-                    if (first_on) {   // 2 x 2 x 4 v_mfma_f32_16x16x32_f16
+                    if (feat_any) {   // 2 x 2 x 4 v_mfma_f32_16x16x32_f16
 #pragma unroll
                     for (int nb = 0; nb < 2; ++nb) {
-                        const int kk = F16 ? ks : 0, nn = F16 ? nb : 0;
-                        const h16x8 Vh = H8(vbh[kk][nn][0], vbh[kk][nn][F16 ? 1 : 0], vbh[kk][nn][F16 ? 2 : 0], vbh[kk][nn][F16 ? 3 : 0]);
-                        const h16x8 Vl = H8(vbl[kk][nn][0], vbl[kk][nn][F16 ? 1 : 0], vbl[kk][nn][F16 ? 2 : 0], vbl[kk][nn][F16 ? 3 : 0]);
-#if !GG_F16_NLL
+                        const int kk = S16 ? ks : 0, nn = S16 ? nb : 0;
+                        const h16x8 Vh = H8(vbh[kk][nn][0], vbh[kk][nn][S16 ? 1 : 0], vbh[kk][nn][S16 ? 2 : 0], vbh[kk][nn][S16 ? 3 : 0]);
+                        const h16x8 Vl = H8(vbl[kk][nn][0], vbl[kk][nn][S16 ? 1 : 0], vbl[kk][nn][S16 ? 2 : 0], vbl[kk][nn][S16 ? 3 : 0]);
                         acc2[nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Fl, Vl, acc2[nb], 0, 0, 0);
-#endif
                         acc2[nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Fl, Vh, acc2[nb], 0, 0, 0);
                         acc2[nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Fh, Vl, acc2[nb], 0, 0, 0);
                         acc2[nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Fh, Vh, acc2[nb], 0, 0, 0);
@@ -1633,9 +1577,7 @@ __global__ __launch_bounds__(64 * GG_WPB_WIDE_BWD) __attribute__((amdgpu_waves_p
                                     vt[(32 * ks + 8 * q4 + 2 * t + 1) * 8 + (sl & 7)] * wm, wh[t], wl[t]);
                         const h16x8 Wh = H8(wh[0], wh[1], wh[2], wh[3]);
                         const h16x8 Wl = H8(wl[0], wl[1], wl[2], wl[3]);
-#if !GG_F16_NLL
                         a4f = __builtin_amdgcn_mfma_f32_16x16x32_f16(Fl, Wl, a4f, 0, 0, 0);
-#endif
                         a4f = __builtin_amdgcn_mfma_f32_16x16x32_f16(Fl, Wh, a4f, 0, 0, 0);
                         a4f = __builtin_amdgcn_mfma_f32_16x16x32_f16(Fh, Wl, a4f, 0, 0, 0);
                         a4f = __builtin_amdgcn_mfma_f32_16x16x32_f16(Fh, Wh, a4f, 0, 0, 0);
@@ -1645,18 +1587,9 @@ __global__ __launch_bounds__(64 * GG_WPB_WIDE_BWD) __attribute__((amdgpu_waves_p
                 for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) acc2[nb][r] *= inv_scf[nb];
-            } else if (F16) {
-                // (nothing to add for the first array, and the second flush takes its operands itself)
-            } else {
-#pragma unroll
-            for (int t = 0; t < 16; ++t) {
-                const float a = fac_w[FIDX(sl, 4 * t + q4)];
-                acc2[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, vb16[S16 ? t : 0][0], acc2[0], 0, 0, 0);
-                acc2[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, vb16[S16 ? t : 0][S16 ? 1 : 0], acc2[1], 0, 0, 0);
-            }
             }
             // lane holds channel 16 nb + sl of slots 4 q4 + r
-            if (!F16 || feat_any || !GG_FEATANY_FLUSH)
+            if (feat_any)
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
@@ -1741,8 +1674,8 @@ __global__ __launch_bounds__(64 * GG_WPB_WIDE_BWD) __attribute__((amdgpu_waves_p
                         const float ga = geo_w[slot * 8 + (gcol < 2 ? 0 : gcol)], gb = geo_w[slot * 8 + 1];
                         const float ca = gcol == 0 ? cq.x : (gcol == 1 ? cq.y : (gcol == 5 ? 1.0f : 0.5f));
                         const float cb = gcol == 0 ? cq.y : cq.z;
-                        const float gv = !GG_MG_MOMENTS ? geo_w[slot * 8 + gcol] : (gcol < 2 ? ca * ga + cb * gb : ca * ga);
-                        const float val = n16 < 8 ? (F16 ? a4[r] * inv_sw : a4[r]) : gv;
+                        const float gv = gcol < 2 ? ca * ga + cb * gb : ca * ga;
+                        const float val = n16 < 8 ? (S16 ? a4[r] * inv_sw : a4[r]) : gv;
                         const bool on = ((slotmask >> slot) & 1u) != 0u && lane_on;
                         if (on && val != 0.0f) {
                             const int sg = __builtin_bit_cast(int, Q.b[base + slot].w);
@@ -1758,7 +1691,7 @@ __global__ __launch_bounds__(64 * GG_WPB_WIDE_BWD) __attribute__((amdgpu_waves_p
                     const bool on = ((slotmask >> slot) & 1u) != 0u && n16 < seg2.nch2;
                     if (on && a4[r] != 0.0f) {
                         const int sg = __builtin_bit_cast(int, Q.b[base + slot].w);
-                        atomicAdd(seg2.v_colors + (size_t)sg * seg2.cs2 + n16, F16 ? a4[r] * inv_sw : a4[r]);
+                        atomicAdd(seg2.v_colors + (size_t)sg * seg2.cs2 + n16, S16 ? a4[r] * inv_sw : a4[r]);
                     }
                 }
             }
@@ -1847,12 +1780,6 @@ __global__ __launch_bounds__(64 * GG_WPB_WIDE_BWD) __attribute__((amdgpu_waves_p
 // =============================================================================================
 // launchers used by the C ABI in blend.hip
 // =============================================================================================
-#ifndef GG_BWD_S16
-#define GG_BWD_S16 1
-#endif
-#ifndef GG_BWD_MERGE
-#define GG_BWD_MERGE 1   // 16-float records: geometry and second-array gradients in one atomic request per Gaussian (MG)
-#endif
 #define B2_FWD_ARGS C, off, n, img_h, img_w, tiles_x, ntiles, ids, bins, rec, colors, background, \
                     out_img, final_Ts, final_idx, write_final
 void gg_launch_blend2_fwd(int width, int C, int off, int n, int img_h, int img_w, int tiles_x,
@@ -1968,9 +1895,9 @@ void gg_launch_blend2_bwd(int width, int C, int off, int n, int img_h, int img_w
         hipLaunchKernelGGL((blend2_bwd_narrow_kernel<3>), grid, block, 0, s, B2_BWDN_ARGS);
     else if (width == 8)
         hipLaunchKernelGGL((blend2_bwd_narrow_kernel<8>), grid, block, 0, s, B2_BWDN_ARGS);
-    else if (n == 32 && GG_BWD_S16 && C % 4 == 0 && off % 4 == 0 && (reinterpret_cast<uintptr_t>(colors) & 15) == 0 &&
+    else if (n == 32 && C % 4 == 0 && off % 4 == 0 && (reinterpret_cast<uintptr_t>(colors) & 15) == 0 &&
              (reinterpret_cast<uintptr_t>(v_out) & 15) == 0)   // the 16-slot build (four waves per SIMD)
-        hipLaunchKernelGGL((blend2_bwd_wide_kernel<true, 0, 32, false, false, GG_BWD_S16 != 0>), gridw, blockw, 0, s,
+        hipLaunchKernelGGL((blend2_bwd_wide_kernel<true, 0, 32, false, false, true>), gridw, blockw, 0, s,
                            B2_BWDW_ARGS);
     else if (n == 32)
         hipLaunchKernelGGL((blend2_bwd_wide_kernel<true>), gridw, blockw, 0, s, B2_BWDW_ARGS);
@@ -2022,18 +1949,19 @@ void gg_launch_blend2_bwd_pair(int C, int img_h, int img_w, int tiles_x, int nti
 #else
     const bool ablated = false;
 #endif
-    if (GG_BWD_S16 && !ablated && C % 4 == 0 && (reinterpret_cast<uintptr_t>(colors) & 15) == 0 &&
+    if (!ablated && C % 4 == 0 && (reinterpret_cast<uintptr_t>(colors) & 15) == 0 &&
         (reinterpret_cast<uintptr_t>(v_out) & 15) == 0) {   // the 16-slot build (four waves per SIMD)
         // one 16-float record per Gaussian on a 64-byte boundary, geometry 0..5 | second array 6..: the merged flush
-        const bool merged = GG_BWD_MERGE && gstride == 16 && seg2.cs2 == 16 && v_colors2 == v_xy + 6 && v_conic == v_xy + 2 &&
+        // (geometry and second-array gradients in one atomic request per Gaussian)
+        const bool merged = gstride == 16 && seg2.cs2 == 16 && v_colors2 == v_xy + 6 && v_conic == v_xy + 2 &&
                             v_opacity == v_xy + 5 && (reinterpret_cast<uintptr_t>(v_xy) & 63) == 0;
         if (merged)
-            hipLaunchKernelGGL((blend2_bwd_wide_kernel<true, 0, 32, false, true, GG_BWD_S16 != 0, GG_BWD_S16 != 0>), grid,
+            hipLaunchKernelGGL((blend2_bwd_wide_kernel<true, 0, 32, false, true, true, true>), grid,
                                block, 0, s, C, 0, 32, img_h, img_w, tiles_x, ntiles, ids, bins, rec, colors, background,
                                final_Ts, final_idx, v_out, v_xy, v_conic, v_colors, v_opacity, gstride, cstride, DetSlab(),
                                seg2);
         else
-            hipLaunchKernelGGL((blend2_bwd_wide_kernel<true, 0, 32, false, true, GG_BWD_S16 != 0>), grid, block, 0, s, C,
+            hipLaunchKernelGGL((blend2_bwd_wide_kernel<true, 0, 32, false, true, true>), grid, block, 0, s, C,
                                0, 32, img_h, img_w, tiles_x, ntiles, ids, bins, rec, colors, background, final_Ts, final_idx,
                                v_out, v_xy, v_conic, v_colors, v_opacity, gstride, cstride, DetSlab(), seg2);
         return;

@@ -66,9 +66,3 @@ __device__ __forceinline__ unsigned long long gg_stamp() {
 #define STAMP_BATCH() do { } while (0)
 #define STAMP_END() do { } while (0)
 #endif
-#ifdef GG_STAMPS
-#ifndef GG_EPI_SKIP
-#define GG_EPI_SKIP 0
-#endif
-extern "C" int gg_debug_epi_skip() { return GG_EPI_SKIP; }
-#endif

@@ -408,9 +408,6 @@ __host__ __device__ static inline int sh_nbases(int deg) {
 // clamp(sh + 0.5, 0, 1) (reference gaussian_splatting.py:731) written to columns 0..2 of a (N, 7) row, depth to
 // column 3, the normal to 4..6, and one byte per Gaussian saying which of the three clamps let the gradient
 // through (torch.clamp: min <= x <= max) for the backward.
-#ifndef GG_SH_NT
-#define GG_SH_NT 1   // the 300 B/Gaussian coefficient stream with non-temporal loads: 78 -> 70 us at 1 M Gaussians (r03)
-#endif
 template <int K, bool TAIL = false>
 __global__ __launch_bounds__(256) void sh_fwd_kernel(int N, int deg,
                                                      const float *__restrict__ viewdirs,
@@ -431,9 +428,10 @@ __global__ __launch_bounds__(256) void sh_fwd_kernel(int N, int deg,
     const float *src = coeffs + (size_t)base * ROW;
     float *st = stage[wave];
     if (nrows == SH_ROWS) {   // (16-byte copies measure the same: 0.093 ms)
+        // the 300 B/Gaussian coefficient stream with non-temporal loads: 78 -> 70 us at 1 M Gaussians
 #pragma unroll
         for (int e = 0; e < SH_ROWS * ROW; e += 64)
-            if (e + lane < SH_ROWS * ROW) st[e + lane] = GG_SH_NT ? __builtin_nontemporal_load(src + e + lane) : src[e + lane];
+            if (e + lane < SH_ROWS * ROW) st[e + lane] = __builtin_nontemporal_load(src + e + lane);
     } else {
         for (int e = lane; e < nrows * ROW; e += 64) st[e] = src[e];
     }

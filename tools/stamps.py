@@ -11,15 +11,9 @@ from gaussiangrasper_amd.camera import ring_cameras
 from gaussiangrasper_amd.scene import make_scene
 
 out = os.path.join(os.path.dirname(gg_build.OUT), "libgg_raster_stamps.so")
-if os.environ.get("STAMPS_LIB"):      # a prebuilt diagnostic variant (e.g. -DGG_EPI_SKIP=1)
-    out = os.path.abspath(os.environ["STAMPS_LIB"])
-else:
-    gg_build.build(force=True, extra_flags=("-DGG_STAMPS",), out=out)
+gg_build.build(force=True, extra_flags=("-DGG_STAMPS",), out=out)
 _lib.LIB_PATH = out
 lib = _lib.load()
-# a -DGG_EPI_SKIP=1 forward stores no final_T / final_idx: no backward may run on its outputs (the build says so)
-lib.gg_debug_epi_skip.restype = ctypes.c_int
-FWD_ONLY = lib.gg_debug_epi_skip() == 1
 dev = "cuda:0"
 h, w, n = 1200, 1600, 1_000_000
 sc = make_scene(n, config_index=3).to(dev)
@@ -55,10 +49,8 @@ for rep in range(2):
     if rep == 1:
         report("32-channel FORWARD (phases: 0 prologue, 1 staging, 4 walk, 7 epilogue; a batch = a chunk of 64 list entries)")
     lib.gg_debug_stamps(None, 1)
-    if not FWD_ONLY:
-        out_.backward(vo)
-if not FWD_ONLY:
-    report("32-channel backward")
+    out_.backward(vo)
+report("32-channel backward")
 tail = torch.rand(n, 7, device=dev).requires_grad_(True)
 vos = [torch.randn(h, w, 32, device=dev), torch.randn(h, w, 7, device=dev)]
 for rep in range(2):
@@ -69,7 +61,5 @@ for rep in range(2):
     if rep == 1:
         report("pair FORWARD (32 + 7)")
     lib.gg_debug_stamps(None, 1)
-    if not FWD_ONLY:
-        torch.autograd.backward(imgs, vos)
-if not FWD_ONLY:
-    report("pair backward (32 + 7)")
+    torch.autograd.backward(imgs, vos)
+report("pair backward (32 + 7)")
