@@ -105,6 +105,13 @@ SIGNATURES = {
     "gg_clip_query": (_I, [_I64, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _P, _F, _P, _P, _P, _SZ, _P]),
     "gg_grasp_contacts_workspace": (_SZ, [_I, _I]),
     "gg_grasp_contacts": (_I, [_I, _P, _P, _P, _I, _P] + [C.c_double] * 6 + [_P] * 8 + [_SZ, _P]),
+    "gg_backproject_workspace": (_SZ, [_I, _I, _I]),
+    "gg_backproject": (_I, [_I, _I, _I] + [_P] * 5 + [C.c_double] * 4 + [_P] * 4 + [_SZ, _P]),
+    "gg_subsample_workspace": (_SZ, [_I64]),
+    "gg_subsample": (_I, [_I64, _I64, C.c_uint64] + [_P] * 6 + [_SZ, _P]),
+    "gg_depth_normals": (_I, [_I, _I, _I, _P, _P, _P, _P, _P]),
+    "gg_knn_workspace": (_SZ, [_I, _P]),
+    "gg_knn": (_I, [_I, _P, _I, _P, _P, _P, _P, _P, _SZ, _P]),
     "gg_prof_enable": (_I, [_I]),
     "gg_prof_reset": (_I, []),
     "gg_prof_get": (_I, [_I, C.POINTER(C.c_int), C.POINTER(C.c_double)]),

@@ -108,6 +108,10 @@ extern "C" const char *gg_prof_name(int id) {
         case GG_K_TAIL_SPLIT: return "tail_split_kernel";
         case GG_K_QUERY: return "clip_query_kernel";
         case GG_K_GRASP: return "gg_grasp_contacts(all launches)";
+        case GG_K_BACKPROJECT: return "gg_backproject(all launches)";
+        case GG_K_NORMALS: return "depth_normals_kernel";
+        case GG_K_SUBSAMPLE: return "gg_subsample(all launches)";
+        case GG_K_KNN: return "gg_knn(all launches)";
         default: break;
     }
     if (id >= GG_K_BLEND_FWD && id < GG_K_BLEND_FWD + 6) {

@@ -255,8 +255,15 @@ def device_sampling_default() -> bool:
     return os.environ.get("GG_DEVICE_SAMPLING", "0") not in ("0", "false", "no", "")
 
 
+def device_knn_default() -> bool:
+    """GG_DEVICE_KNN=1: the model's k_nearest_sklearn runs gaussiangrasper_amd.prepare.knn_distances (default off)."""
+    import os
+    return os.environ.get("GG_DEVICE_KNN", "0") not in ("0", "false", "no", "")
+
+
 def make_fused_model_class(base, ops=_ops, background_override=lambda: None, fused_training: bool = False,
-                           loss_ops=None, mlp_class="default", device_sampling: Optional[bool] = None):
+                           loss_ops=None, mlp_class="default", device_sampling: Optional[bool] = None,
+                           device_knn: Optional[bool] = None):
     """Subclass of the reference's GaussianSplattingModel whose get_outputs uses `fused_view`.
     `base` is nerfstudio.models.gaussian_splatting.GaussianSplattingModel (or `stub.StubGaussianSplattingModel`,
     which restates the attributes used here, where nerfstudio is not installed).
@@ -269,9 +276,14 @@ def make_fused_model_class(base, ops=_ops, background_override=lambda: None, fus
     reference's module).
     device_sampling: draw the feature losses' pixel samples with gaussiangrasper_amd.sampling (same law, device
     generator, ~1 ms) instead of the reference module's helpers (same draws as the reference, ~0.3 s per full-size view
-    of host `torch.randperm`); None: GG_DEVICE_SAMPLING (default off)."""
+    of host `torch.randperm`); None: GG_DEVICE_SAMPLING (default off).
+    device_knn: `k_nearest_sklearn` (:315-331, the initial scales of populate_modules) becomes the exact grid search
+    of gaussiangrasper_amd.prepare.knn_distances on the device instead of sklearn's KD-tree on the host; same return
+    types (two float32 numpy arrays, indices as float32); None: GG_DEVICE_KNN (default off)."""
     if device_sampling is None:
         device_sampling = device_sampling_default()
+    if device_knn is None:
+        device_knn = device_knn_default()
 
     class FusedGaussianSplattingModel(base):
         """GaussianSplattingModel on the fused MI355X rasterizer call (gaussiangrasper_amd.plugin)."""
@@ -529,6 +541,12 @@ def make_fused_model_class(base, ops=_ops, background_override=lambda: None, fus
             self.xys_grad_norm, self.vis_counts, self.max_2Dsize = r.xys_grad_norm, r.vis_counts, r.max_2Dsize
             return info
 
+    if device_knn:
+        def k_nearest_sklearn(self, x: torch.Tensor, k: int):
+            from .prepare import knn_distances
+            dist, idx = knn_distances(x, k)
+            return dist.cpu().numpy(), idx.to(torch.float32).cpu().numpy()
+        FusedGaussianSplattingModel.k_nearest_sklearn = k_nearest_sklearn
     FusedGaussianSplattingModel.__qualname__ = "FusedGaussianSplattingModel"
     return FusedGaussianSplattingModel
 

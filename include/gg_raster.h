@@ -588,6 +588,61 @@ int gg_grasp_contacts(int num_points, const float *points, const float *normals,
                       int32_t *region_count, float *region_weight, float *collision_weight, uint8_t *feasible,
                       void *ws, size_t ws_bytes, gg_stream_t stream);
 
+/* ---- scene preparation from RGB-D frames (PARITY "Scene preparation") --------------------------------
+ * gg_backproject: depth frames to a base-frame point cloud (generate_data.py depth_image_to_point_cloud +
+ * merge_point_clouds).  Frames are F x H x W, frame-major then row-major:
+ *   depth fp64 [F][H][W] (metres), mask uint8 [F][H][W], rgb uint8 [F][H][W][3],
+ *   intrinsics fp64 [F][4] (fx, fy, cx, cy), c2w fp64 [F][4][4] (row-major camera-to-base).
+ * Pixel (f, v, u) is kept iff mask != 0 && d > d_lo && d < d_hi (NaN fails), then in fp64, no contraction:
+ *   X = ((u - cx) * d) / fx,  Y = ((v - cy) * d) / fy,  Z = d,
+ *   p_k = ((T[k][0] X + T[k][1] Y) + T[k][2] Z) + T[k][3],
+ * and kept iff z_lo < p_2 < z_hi.  Kept points go to points fp64 [.][3] / colors uint8 [.][3] in pixel order (the
+ * reference's boolean-index order); *count (device int64) = how many.  points / colors need room for F*H*W rows.
+ * No atomics decide a position: identical output call to call, and the same rows whatever frames share a call.
+ * `ws`: gg_backproject_workspace() bytes, 256-byte aligned (0 is returned for shapes out of range). */
+#define GG_PREP_MAX_ROWS (1 << 30)
+size_t gg_backproject_workspace(int num_frames, int height, int width);
+int gg_backproject(int num_frames, int height, int width, const double *depth, const uint8_t *mask, const uint8_t *rgb,
+                   const double *intrinsics, const double *c2w, double d_lo, double d_hi, double z_lo, double z_hi,
+                   double *points, uint8_t *colors, int64_t *count, void *ws, size_t ws_bytes, gg_stream_t stream);
+
+/* gg_subsample: exactly m = num / keep distinct rows of num (save_points3D's `num // 8` of np.random.choice, same law:
+ * a uniform subset), a pure function of (seed, num).  Row i has the key splitmix64(seed + (i + 1) * 0x9E3779B97F4A7C15)
+ * (the SplitMix64 output function; all keys distinct); the m rows with the smallest keys are written in ascending
+ * index order: out_index int64 [m], and, when given, out_points fp64 [m][3] / out_colors uint8 [m][3] gathered from
+ * points fp64 [num][3] / colors uint8 [num][3].  m == 0 does nothing.  `ws`: gg_subsample_workspace(num) bytes,
+ * 256-byte aligned. */
+size_t gg_subsample_workspace(int64_t num);
+int gg_subsample(int64_t num, int64_t keep, uint64_t seed, const double *points, const uint8_t *colors,
+                 double *out_points, uint8_t *out_colors, int64_t *out_index, void *ws, size_t ws_bytes,
+                 gg_stream_t stream);
+
+/* gg_depth_normals: world-frame normal maps of depth frames (generate_data.py cal_normal :204-229), fp64, no
+ * contraction.  depth fp64 [F][H][W] (metres), H, W >= 2; intrinsics / c2w as gg_backproject (fx, fy used).
+ *   d' = d < 0.01 ? 1e-5 : d;  du, dv = np.gradient(d') along columns / rows (interior (f[i+1] - f[i-1]) / 2, edges
+ *   one-sided);  a = -(du * (fx / d')), b = -(dv * (fy / d')), c = 1;  n = (a, b, c) / sqrt((a a + b b) + c c);
+ *   a row with a non-finite component becomes (0, 0, 1);  out_k = (R[k][0] n0 + R[k][1] n1) + R[k][2] n2, R = c2w[:3,:3].
+ * normals fp64 [F][H][W][3]. */
+int gg_depth_normals(int num_frames, int height, int width, const double *depth, const double *intrinsics,
+                     const double *c2w, double *normals, gg_stream_t stream);
+
+/* gg_knn: for every point, the k smallest sqrt(((dx dx + dy dy) + dz dz)) over all other points j != i (dx the fp64
+ * difference of the fp32 coordinates), rounded to fp32 at the end: dist fp32 [N][k] ascending, idx int64 [N][k] a
+ * neighbour set attaining them (ties by smallest index, except that among points at distance 0 any may be returned).
+ * Exact for any input of finite points.  points fp32 [N][3]; 1 <= k <= GG_KNN_MAX_K < N.
+ * grid (host, 4 doubles): lower corner x, y, z and cell edge (> 0); dims (host, 3 ints): cells per axis.  Points
+ * outside the grid go to its border cells: any grid gives the same result, a grid fitted to the bulk of the points
+ * gives it fast (gaussiangrasper_amd.prepare.knn_grid).  Cost: O(N x max points per cell) plus the cells walked;
+ * worst case per point one walk of every cell and point, O(N^2) in all when the grid crowds the cloud into a few
+ * cells.
+ * `ws`: gg_knn_workspace(N, dims) bytes, 256-byte aligned (0 for sizes out of range). */
+#define GG_KNN_MAX_K 8
+#define GG_KNN_MAX_POINTS (1 << 30)
+#define GG_KNN_MAX_CELLS (1 << 26)
+size_t gg_knn_workspace(int num_points, const int32_t *dims);
+int gg_knn(int num_points, const float *points, int k, const double *grid, const int32_t *dims, float *dist,
+           int64_t *idx, void *ws, size_t ws_bytes, gg_stream_t stream);
+
 /* ---- in-library kernel timing (measurement only; off by default) --------------------------------
  * When enabled, every launch of the kernels below is bracketed by a hipEvent pair recorded on the
  * launch stream, so bench.py can report the average duration of exactly that kernel over its
@@ -618,6 +673,10 @@ int gg_grasp_contacts(int num_points, const float *points, const float *normals,
 #define GG_K_VIEW_FWD 32      /* gg_view_fwd: activations + projection of a view in one kernel */
 #define GG_K_QUERY 33         /* gg_clip_query: weight packing + clip_query_kernel */
 #define GG_K_GRASP 34         /* gg_grasp_contacts: both passes and both per-grasp reductions */
+#define GG_K_BACKPROJECT 35   /* gg_backproject: count, scan and emit */
+#define GG_K_NORMALS 36       /* gg_depth_normals */
+#define GG_K_SUBSAMPLE 37     /* gg_subsample: radix select, scan and emit */
+#define GG_K_KNN 38           /* gg_knn: grid counting sort and shell search */
 #define GG_K_IDS 40           /* ids are below this */
 #define GG_PROF_NUM_KERNELS 32
 int gg_prof_enable(int on);
