@@ -28,10 +28,14 @@ Rank 0 prints ONE JSON line.
 render-only: project, SH, the four rasterize forwards and the fea_up MLP on every pixel; no
 collective.  Its line carries the same keys (metric "rendered views/sec (render-only) ...").
 
-The timed region runs with the in-library kernel timers OFF; one extra profiled step afterwards
-(hipEvent pairs from a pool, recorded on the launch stream) gives the per-kernel averages.
+A plain run does only what the headline needs: set-up, the warm-up, the timed steps, the --dump-outputs files
+and the line (metric, value, unit, ms_per_step, config, ...).  Everything else it can measure runs with `--full`
+only; --no-prof, --no-secondary, --no-cpu-baseline and --no-config5 thin out a --full run.
 
-Extra objects in the line:
+The timed region runs with the in-library kernel timers OFF; with --full, extra profiled steps afterwards
+(hipEvent pairs from a pool, recorded on the launch stream) give the per-kernel averages.
+
+Extra objects in the --full line:
   roofline     — the dominant kernel BY TOTAL TIME over the profiled step: achieved = algorithmic
                  bytes per launch / average launch duration (byte formulas: DESIGN.md §5), peak 8 TB/s;
                  `kernels` holds the same for every blend kernel; `whole_view` prices SURVEY §8d's
@@ -40,6 +44,9 @@ Extra objects in the line:
                  and weights from the PMC pass under profiles/).
   cpu_baseline — the CPU oracle ("port", C + OpenMP, all host cores) timed on ONE view of the same
                  workload (same operator sequence, fwd+bwd), rank 0, N=1 only.
+  kernels, kernel_time_fraction_of_wall, kernel_ms_per_view — from the profiled steps;
+  other_route  — the route that is not the headline's, measured the same way;
+  config5      — N=1, config 4: a short run of BASELINE config 5 with its own kernels, roofline and CPU sample.
 
 Test hooks (used only by tests/): `--backend gloo --device cpu --ops <module>` runs the same
 launcher / sharding / reduction code on CPU tensors with a non-product operator module (the line is
@@ -85,16 +92,20 @@ def parse(argv=None):
     ap.add_argument("--width", type=int, default=None)
     ap.add_argument("--feature-dim", type=int, default=None)
     ap.add_argument("--views-per-step", type=int, default=8)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the profiled steps (per-kernel times, roofline), the other route, the "
+                         "CPU baseline and, on one GPU, the config-5 object; without it a run sets up, warms up, "
+                         "times the steps, dumps its outputs if asked and prints the line")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-config5", action="store_true",
-                    help="skip the short BASELINE-config-5 (render-only) object of the default one-GPU line")
+                    help="skip the short BASELINE-config-5 (render-only) object of the --full one-GPU line")
     ap.add_argument("--no-prof", action="store_true", help="skip the profiled step (no per-kernel times)")
     ap.add_argument("--torch-profile", default=None, metavar="PATH",
                     help="after the timed steps, one more step under torch.profiler (shapes recorded); the per-operator "
                          "table goes to PATH — which torch operators launch what, beside the library's own kernels")
     ap.add_argument("--route", default="plugin", choices=("plugin", "shim"),
                     help="headline route: the nerfstudio plugin's fused operator (default) or the shim's "
-                         "four separate rasterize calls; the other one is measured as well")
+                         "four separate rasterize calls; with --full the other one is measured as well")
     ap.add_argument("--no-secondary", "--no-fused", dest="no_secondary", action="store_true",
                     help="skip the measurement of the other route")
     ap.add_argument("--no-overlap", action="store_true", help="one all-reduce after the last view")
@@ -581,7 +592,7 @@ def run_rank(args, rank: int, local_rank: int, world: int) -> int:
         return max_over_ranks(time.perf_counter() - t0)
 
     def measure(fused: bool, warmup: int):
-        """warm-up, the timed steps with the kernel timers OFF, then one profiled step"""
+        """warm-up, the timed steps with the kernel timers OFF, then (--full) the profiled steps"""
         fn = make_step(fused)
         for _ in range(warmup):
             one_step(fn)
@@ -597,7 +608,7 @@ def run_rank(args, rank: int, local_rank: int, world: int) -> int:
             dump_outputs(args.dump_outputs, last_images, per_gaussian)
             last_images.clear()
         kern, t_prof = {}, None
-        if lib is not None and not args.no_prof:               # all ranks take part (collectives)
+        if lib is not None and args.full and not args.no_prof:    # all ranks take part (collectives)
             saved, pipe_streams_box[0] = pipe_streams_box[0], None   # per-kernel times: one stream, no overlap
             one_step(fn)       # (untimed: the caching allocator's pool of THIS stream is empty after the pipelined steps,
             sync()             #  a first step on it pays for fresh hipMallocs — once 0.75 instead of 0.94 of wall)
@@ -619,7 +630,7 @@ def run_rank(args, rank: int, local_rank: int, world: int) -> int:
     plugin_first = args.route == "plugin"
     bucket.comm_stats()                                       # (drop what the probe / set-up left)
     elapsed, kernels, t_prof, grads = measure(fused=plugin_first, warmup=args.warmup)
-    comm = bucket.comm_stats() if world > 1 else None         # warm-up + timed + profiled steps of the headline route
+    comm = bucket.comm_stats() if world > 1 else None         # warm-up + timed (+ profiled) steps of the headline route
     if args.torch_profile and rank == 0:
         from torch.profiler import ProfilerActivity, profile
         fn = make_step(plugin_first)
@@ -632,7 +643,7 @@ def run_rank(args, rank: int, local_rank: int, world: int) -> int:
     if grads is not None:
         torch.save(grads, args.dump_grads)
     other = None
-    if not args.no_secondary and not selftest:
+    if args.full and not args.no_secondary and not selftest:
         o_t, o_k, _, _ = measure(fused=not plugin_first, warmup=1)
         other = {"route": "shim (four rasterize calls per view)" if plugin_first else "plugin (one fused operator per view)",
                  "value": total_views * args.steps / o_t, "unit": "views/s",
@@ -685,7 +696,7 @@ def run_rank(args, rank: int, local_rank: int, world: int) -> int:
                                       ("all-reduce per parameter, armed on the last view" if overlap else
                                        "one all-reduce after the last view")),
                               rccl=parse_rccl_log(rccl_log))
-    if rank == 0:
+    if rank == 0 and args.full:
         result["roofline"] = build_roofline(args, kernels, n_vis, n_isect, ms_per_view_rank) \
             if kernels else None
         result["kernels"] = {k: round(v["avg_ms"], 4) for k, v in sorted(kernels.items())}
@@ -701,11 +712,10 @@ def run_rank(args, rank: int, local_rank: int, world: int) -> int:
                     total_views, args.height, args.width)[0])
             except Exception as exc:  # noqa: BLE001
                 result["cpu_baseline"] = {"error": repr(exc)}
-    # BASELINE config 5 (render.sh's body at 5 M Gaussians, 128-dim feature, 1080p) rides along on the default
-    # one-GPU run as a short object, so that the driver's line carries it: 5 steps of 2 views through the plugin's
-    # model class in eval mode, its own kernel times, roofline and bounded CPU sample.  `--config 5` is the
-    # full-length form.
-    if world == 1 and not selftest and args.device == "cuda" and not args.no_config5:
+    # BASELINE config 5 (render.sh's body at 5 M Gaussians, 128-dim feature, 1080p) rides along on a --full
+    # one-GPU run as a short object: 5 steps of 2 views through the plugin's model class in eval mode, its own
+    # kernel times, roofline and bounded CPU sample.  `--config 5` is the full-length form.
+    if args.full and world == 1 and not selftest and args.device == "cuda" and not args.no_config5:
         del plugin_model, bucket, scene, cot, cameras
         ops.clear_bin_cache()
         ops.clear_grad_sinks()
@@ -805,7 +815,7 @@ def render_only_result(args, rank, world, dev, ops, lib, barrier, max_over_ranks
             dump_outputs(args.dump_outputs, images, {})
             del out, clip, last, images
         kernels = {}
-        if lib is not None and not args.no_prof:
+        if lib is not None and args.full and not args.no_prof:
             lib.gg_prof_reset()
             lib.gg_prof_enable(1)
             barrier()
@@ -842,6 +852,8 @@ def render_only_result(args, rank, world, dev, ops, lib, barrier, max_over_ranks
     if rank != 0:
         return None
     result["ms_per_view"] = ms_per_view
+    if not args.full:
+        return result
     mlp_bytes = 4 * 512 * args.height * args.width
     result["roofline"] = build_roofline(
         args, kernels, n_vis, n_isect, ms_per_view, extra_view_bytes=mlp_bytes,

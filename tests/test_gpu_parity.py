@@ -1104,6 +1104,43 @@ def test_two_ranks_of_the_hip_path_reduce_to_the_single_process_gradient(tmp_pat
                  atol_frac=2e-6)
 
 
+def test_bench_full_adds_kernel_times_roofline_and_the_other_route():
+    """bench.py with the product operators, config 4 and `--config 5`: the plain line is the headline alone; --full adds
+    the profiled steps' kernel table and roofline and (config 4) the other route's figure.  Not covered here: the CPU
+    baselines and the config5 object of a one-GPU --full line (5 M Gaussians whatever --points says)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+
+    def run(*extra):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--points", "30000", "--height", "200",
+               "--width", "304", "--views-per-step", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+               "--no-config5", *extra]
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1 and lines[0]["data"] == "synthetic" and lines[0]["value"] > 0
+        return lines[0]
+
+    plain = run()
+    assert not {"roofline", "kernels", "other_route", "cpu_baseline", "config5"} & set(plain)
+    full = run("--full")
+    assert full["metric"] == plain["metric"] and full["config"] == plain["config"]
+    assert any(k.startswith("blend_") for k in full["kernels"]) and full["kernel_ms_per_view"] > 0
+    assert full["roofline"]["kernel"] in full["kernels"] and full["roofline"]["achieved"] > 0
+    assert full["other_route"]["route"].startswith("shim") and full["other_route"]["value"] > 0
+    assert full["cpu_baseline"] is None and "config5" not in full
+    plain5 = run("--config", "5")
+    assert plain5["ms_per_view"] > 0 and not {"roofline", "kernels", "cpu_baseline"} & set(plain5)
+    full5 = run("--config", "5", "--full")
+    assert full5["metric"] == plain5["metric"] and full5["config"] == plain5["config"]
+    assert any(k.startswith("blend_") for k in full5["kernels"]) and full5["roofline"]["achieved"] > 0
+    assert full5["cpu_baseline"] is None
+
+
 def test_segments_and_activations_edge_cases():
     """nothing visible (every Gaussian behind the camera): background images and zero gradients; and an
     empty scene through the fused activation operator"""

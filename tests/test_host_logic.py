@@ -264,6 +264,25 @@ def test_bench_dump_outputs_are_the_last_steps_and_repeat_run_to_run(tmp_path):
     assert r.returncode != 0 and "--steps" in r.stderr
 
 
+def test_bench_plain_line_is_the_headline_and_full_adds_the_rest(tmp_path):
+    """a plain run prints the headline line only; the profiled-step, other-route and CPU objects come with --full.
+    With the self-test operators those objects are empty (no library to profile, no other route, no CPU baseline), so
+    this pins which keys each line carries, not what they hold: the contents and `--config 5` are checked on the GPU
+    (tests/test_gpu_parity.py::test_bench_full_adds_kernel_times_roofline_and_the_other_route)."""
+    extra = {"roofline", "kernels", "other_route", "cpu_baseline"}
+    r = _run_bench([], tmp_path, 1)
+    assert r.returncode == 0, r.stderr[-2000:]
+    plain = _json_lines(r.stdout)
+    assert len(plain) == 1 and not extra & set(plain[0])
+    assert plain[0]["steps"] == 1 and plain[0]["warmup"] == 1 and plain[0]["ms_per_step"] > 0
+    r = _run_bench(["--full"], tmp_path, 1)
+    assert r.returncode == 0, r.stderr[-2000:]
+    full = _json_lines(r.stdout)
+    assert len(full) == 1 and extra <= set(full[0])
+    assert {k: v for k, v in full[0].items() if k not in extra | {"value", "ms_per_step"}} == \
+        {k: v for k, v in plain[0].items() if k not in {"value", "ms_per_step"}}
+
+
 def test_bench_refuses_a_world_size_that_is_not_gpus(tmp_path):
     """no silent single-GPU fallback: WORLD_SIZE=1 with --gpus 2 is an error, not a 1-GPU run"""
     r = _run_bench([], tmp_path, 2, env_extra={"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})

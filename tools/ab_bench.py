@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """A/B measurement: run bench.py against ANOTHER build of the library (a kernel variant under test).
-Usage: python tools/ab_bench.py path/to/libvariant.so [bench.py flags].  Measurement tool only."""
+Usage: python tools/ab_bench.py path/to/libvariant.so [bench.py flags] (--full for the per-kernel times).
+Measurement tool only."""
 import os
 import sys
 
