@@ -112,6 +112,7 @@ extern "C" const char *gg_prof_name(int id) {
         case GG_K_NORMALS: return "depth_normals_kernel";
         case GG_K_SUBSAMPLE: return "gg_subsample(all launches)";
         case GG_K_KNN: return "gg_knn(all launches)";
+        case GG_K_OBJMASK: return "gg_object_masks(all launches)";
         default: break;
     }
     if (id >= GG_K_BLEND_FWD && id < GG_K_BLEND_FWD + 6) {

@@ -532,6 +532,41 @@ int gg_adam_step(int num_groups, const gg_adam_group_t *groups, int zero_grad, g
 int gg_hull_edit(int num_points, float *means, float *quats, int num_planes, const double *planes, double tol,
                  const float *rt, uint8_t *mask, int64_t *count_out, gg_stream_t stream);
 
+/* ---- per-view masks of the moved object (reference scripts/project_hull.py :83-121; DESIGN 3.14, PARITY "Scene
+ * update") -----------------------------------------------------------------------------------------------------------
+ * For every view v and pose (0 = before, 1 = after) — a job — in fp64, no contraction:
+ *   points:   q = p (before);  q_r = ((T_r0 x + T_r1 y) + T_r2 z) + T_r3 (after, get_transform :8-19, :105);
+ *   project:  c_r = ((E_r0 q0 + E_r1 q1) + E_r2 q2) + E_r3 with E = w2c[v] (inv(transform_matrix), :86-87, no axis
+ *             flip);  u = ((fx c0) + (cx c2)) / c2,  v = ((fy c1) + (cy c2)) / c2 (project_points_3d_to_2d :21-34,
+ *             distortion ignored), both truncated toward zero to int32 (`.astype(np.int32)`, :91-92);
+ *   dropped:  c2 <= 0, u or v not finite, or |u| or |v| >= 2^30 (the reference keeps points behind the camera,
+ *             mirrored; PARITY) — counted per job in dropped[v][pose];
+ *   hull:     the exact convex hull of the kept integer points (int64 cross products), possibly empty, a point or a
+ *             segment (cv2.convexHull, :36-46);
+ *   fill:     pixel (row y, col x) is set iff (x, y) lies in the CLOSED hull (boundary and degenerate hulls
+ *             included) — cv2.fillConvexPoly without the LINE_AA rim (PARITY);
+ *   dilate:   cv2.dilate with a k x k ones kernel, anchor k / 2, pixels outside the image contribute nothing; k = 0
+ *             or 1: none (get_dialated_mask :48-53);  union = before | after (finetune_mask3, :118-121);
+ *   boxes:    per view and mask m (0 before, 1 after, 2 union): boxes[v][m] = rmin, rmax, cmin, cmax of the set
+ *             pixels, centres[v][m] = 0.5 (rmax + rmin), 0.5 (cmax + cmin) (center1, :101-102); -1 / NaN when empty.
+ * points fp64 [M][3] (device); transform: HOST array of 12 doubles, [R | t] row-major 3 x 4; intrinsics fp64 [V][4]
+ * (fx, fy, cx, cy) and w2c fp64 [V][3][4] (device).  before / after / union_mask uint8 [V][H][W] (0 / 1), boxes int32
+ * [V][3][4], centres fp64 [V][3][2], dropped int32 [V][2]: every element written.
+ * The kept points of a job may span at most max_rows pixel rows (the row table of the hull pass); a job above that
+ * makes the call return GG_ERR_UNSUPPORTED naming the smallest such view, with nothing written to the outputs.  The
+ * call reads one status word back and synchronises the stream once, at its end.  Deterministic: integer work only.
+ * `ws`: gg_object_masks_workspace(V, max_rows) bytes (about 12 max_rows bytes per job), 256-byte aligned; 0 is
+ * returned for counts out of range. */
+#define GG_OBJMASK_MAX_VIEWS 16384
+#define GG_OBJMASK_MAX_ROWS 65536
+#define GG_OBJMASK_MAX_SIDE 32768
+#define GG_OBJMASK_MAX_DILATE 128
+size_t gg_object_masks_workspace(int num_views, int max_rows);
+int gg_object_masks(int num_points, const double *points, const double *transform, int num_views,
+                    const double *intrinsics, const double *w2c, int height, int width, int dilate, int max_rows,
+                    uint8_t *before, uint8_t *after, uint8_t *union_mask, int32_t *boxes, double *centres,
+                    int32_t *dropped, void *ws, size_t ws_bytes, gg_stream_t stream);
+
 /* ---- language query of the feature field ------------------------------------------------------------
  * fea_up followed by the CLIP comparison, with the 512-float fea_up output never written to memory:
  *   y   = relu(x @ w1^T + b1) @ w2^T + b2 per row, as gg_mlp_fwd_fast computes it (in_dim 32 / 64 / 128, hidden 128,
@@ -677,6 +712,7 @@ int gg_knn(int num_points, const float *points, int k, const double *grid, const
 #define GG_K_NORMALS 36       /* gg_depth_normals */
 #define GG_K_SUBSAMPLE 37     /* gg_subsample: radix select, scan and emit */
 #define GG_K_KNN 38           /* gg_knn: grid counting sort and shell search */
+#define GG_K_OBJMASK 39       /* gg_object_masks: all six launches */
 #define GG_K_IDS 40           /* ids are below this */
 #define GG_PROF_NUM_KERNELS 32
 int gg_prof_enable(int on);
