@@ -77,6 +77,11 @@ SIGNATURES = {
     "gg_blend_bwd": (_I, [_I, _I, _I, _I] + [_P] * 14 + [_I, _I, _P, _SZ, _I, _P]),
     "gg_shade_tail_bwd_split": (_I, [_I, _P, _I, _P, _P, _P, _P, _P]),
     "gg_view_bwd": (_I, [_I, _P, _I, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _F, _F, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gg_pose_grad_workspace": (_SZ, [_I]),
+    "gg_view_bwd_pose": (_I, [_I, _P, _I, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _F, _F, _I, _I] + [_P] * 9
+                         + [_P, _SZ, _P]),
+    "gg_project_pose_bwd": (_I, [_I, _P, _P, _F, _P, _P, _P, _F, _F, _I, _I, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P,
+                                 _SZ, _P]),
     "gg_sh_bwd_multi": (_I, [_I, _I, _I, _I, C.POINTER(_P), C.POINTER(_P), _P, _I, _P]),
     "gg_image_loss_workspace": (_SZ, [_I, _I]),
     "gg_image_loss_fwd": (_I, [_I, _I, _P, _I, _P, _P, _F, _P, _P, _SZ, _P]),

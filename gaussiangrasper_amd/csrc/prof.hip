@@ -113,6 +113,9 @@ extern "C" const char *gg_prof_name(int id) {
         case GG_K_SUBSAMPLE: return "gg_subsample(all launches)";
         case GG_K_KNN: return "gg_knn(all launches)";
         case GG_K_OBJMASK: return "gg_object_masks(all launches)";
+        case GG_K_VIEW_BWD_POSE: return "view_bwd_pose_kernel";
+        case GG_K_POSE_BWD: return "project_pose_bwd_kernel";
+        case GG_K_POSE_FINISH: return "pose_finish_kernel";
         default: break;
     }
     if (id >= GG_K_BLEND_FWD && id < GG_K_BLEND_FWD + 6) {

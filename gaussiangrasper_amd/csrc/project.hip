@@ -187,13 +187,17 @@ __global__ __launch_bounds__(1024) void count_finish_kernel(int nparts, const un
 }
 
 // the backward of one visible Gaussian: cotangents (v_xy, v_depth, v_conic) -> vm += d/d mean, vs = d/d scale,
-// vq4 = d/d quat.  Shared by project_bwd_kernel and view_bwd_kernel (one operation sequence, one result)
+// vq4 = d/d quat.  Shared by project_bwd_kernel and view_bwd_kernel (one operation sequence, one result).
+// POSE: also pv[24] = this Gaussian's share of the camera's gradient (the pose VJP):
+//   pv[0..11]  d/d viewmat (3 x 4, row-major)     pv[12..23] d/d full_proj rows 0, 1 and 3 (row 2 is not read)
+// written, not added to; the operations producing vm / vs / vq4 are the same with or without it (same bits).
+template <bool POSE = false>
 __device__ __forceinline__ void project_bwd_point(
     const int i, const float *__restrict__ means, const float *__restrict__ scales, const float glob_scale,
     const float *__restrict__ quats, const float *__restrict__ viewmat, const float *__restrict__ projmat,
     const float fx, const float fy, const int img_h, const int img_w, const float *__restrict__ conics,
     const float vxy0, const float vxy1, const float vdepth, const float ga, const float gb, const float gc,
-    float (&vm)[3], float (&vs)[3], float (&vq4)[4]) {
+    float (&vm)[3], float (&vs)[3], float (&vq4)[4], float *pv = nullptr) {
     {
         float V[12], P[16];
 #pragma unroll
@@ -217,6 +221,15 @@ __device__ __forceinline__ void project_bwd_point(
 #endif
 #pragma unroll
         for (int j = 0; j < 3; ++j) vm[j] += (P[j] * vhx + P[4 + j] * vhy) + P[12 + j] * vhw;
+        if constexpr (POSE) {     // h = P [p, 1]: d/d P[r, :] = vh_r [p, 1]
+            const float ph[4] = {px, py, pz, 1.0f};
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                pv[12 + c] = vhx * ph[c];
+                pv[16 + c] = vhy * ph[c];
+                pv[20 + c] = vhw * ph[c];
+            }
+        }
         // (2) depth
         float vz = vdepth;
 #pragma unroll
@@ -300,6 +313,23 @@ __device__ __forceinline__ void project_bwd_point(
         v_tz += (sgx * lim_x) * v_txc + (sgy * lim_y) * v_tyc;
 #pragma unroll
         for (int j = 0; j < 3; ++j) vm[j] += (V[j] * v_tx + V[4 + j] * v_ty) + V[8 + j] * v_tz;
+        if constexpr (POSE) {
+            // t = V [p, 1] (depth = t.z): d/d V[r, :] = v_t[r] [p, 1]; and Tm = J W with W = V[0:3, 0:3]: d/d W = J^T vT
+            const float vt[3] = {v_tx, v_ty, v_tz + vz};
+            const float p3[3] = {px, py, pz};
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) pv[4 * r + k] = vt[r] * p3[k];
+                pv[4 * r + 3] = vt[r];
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                pv[k] += J00 * vT[k];
+                pv[4 + k] += J11 * vT[3 + k];
+                pv[8 + k] += J02 * vT[k] + J12 * vT[3 + k];
+            }
+        }
         // (6)
         float vM[9];
 #pragma unroll
@@ -359,6 +389,177 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(
         v_scale[3 * (size_t)i + k] = vs[k];
     }
     reinterpret_cast<float4 *>(v_quat)[i] = make_float4(vq4[0], vq4[1], vq4[2], vq4[3]);
+}
+
+// ---- the pose VJP: 24 sums over the Gaussians, deterministic -------------------------------
+// No float atomics: every workgroup of 256 lanes leaves the sum of its lanes' pv[24] as one row of a slab (fixed order:
+// a wave's 64 lanes, then its four waves), and one workgroup adds the rows up in a fixed order in fp64
+// (pose_finish_kernel, a launch of its own).  Same inputs, same bits, whatever the scheduling.
+#define GG_POSE_SUMS 24
+__device__ __forceinline__ void pose_block_sum(const float (&pv)[GG_POSE_SUMS], float *__restrict__ row) {
+    __shared__ float s_w[4][GG_POSE_SUMS];
+    const int lane = threadIdx.x & 63;
+    // transpose-halving across the wave: the exchanges at lane distance 32, 16, 8 halve the values a lane holds
+    // (24 -> 12 -> 6 -> 3: 21 exchanges instead of 24 x 3), the last three sum 3 values over 8 lanes
+    const bool h5 = lane & 32, h4 = lane & 16, h3 = lane & 8;
+    float a[12], b[6], c[3];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+        const float give = h5 ? pv[k] : pv[12 + k], keep = h5 ? pv[12 + k] : pv[k];
+        a[k] = keep + __shfl_xor(give, 32, 64);
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const float give = h4 ? a[k] : a[6 + k], keep = h4 ? a[6 + k] : a[k];
+        b[k] = keep + __shfl_xor(give, 16, 64);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float give = h3 ? b[k] : b[3 + k], keep = h3 ? b[3 + k] : b[k];
+        c[k] = keep + __shfl_xor(give, 8, 64);
+    }
+#pragma unroll
+    for (int off = 4; off > 0; off >>= 1)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) c[k] += __shfl_xor(c[k], off, 64);
+    if ((lane & 7) == 0) {     // lanes 0, 8, ..., 56 hold the wave's sums of columns base .. base + 2
+        const int base = (h5 ? 12 : 0) + (h4 ? 6 : 0) + (h3 ? 3 : 0);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) s_w[threadIdx.x >> 6][base + k] = c[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < GG_POSE_SUMS) {
+        const int t = threadIdx.x;
+        row[t] = (s_w[0][t] + s_w[1][t]) + (s_w[2][t] + s_w[3][t]);
+    }
+}
+
+// one workgroup: the slab's rows (nrows x 24 floats) -> v_viewmat (12) and v_projmat (16, row 2 zero), written.
+// 1008 = 168 x 6 lanes: lane t reads float4 column t % 6 of rows t / 6, t / 6 + 168, ... (coalesced) into four fp64 sums,
+// then 192 lanes add 21 of those rows each, then 24 lanes the 8 parts: the order depends on nrows only
+#define GG_POSE_FIN_ROWS 168
+__global__ __launch_bounds__(1024) void pose_finish_kernel(int nrows, const float4 *__restrict__ slab,
+                                                           float *__restrict__ v_viewmat, float *__restrict__ v_projmat) {
+    __shared__ double s_row[GG_POSE_FIN_ROWS][GG_POSE_SUMS + 1];
+    __shared__ double s_part[8][GG_POSE_SUMS];
+    const int t = threadIdx.x;
+    if (t < 6 * GG_POSE_FIN_ROWS) {
+        const int q = t % 6, r0 = t / 6;
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+        // 12 guarded loads in flight per lane (a padding row adds 0.0, which changes no sum): the 3907 rows of 1 M
+        // Gaussians are two rounds of memory latency instead of a serial remainder loop's one round per row
+        for (int r = r0; r < nrows; r += 12 * GG_POSE_FIN_ROWS) {
+            float4 v[12];
+#pragma unroll
+            for (int u = 0; u < 12; ++u) {
+                const int rr = r + u * GG_POSE_FIN_ROWS;
+                v[u] = rr < nrows ? slab[(size_t)rr * 6 + q] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            }
+#pragma unroll
+            for (int u = 0; u < 12; ++u) {
+                a0 += (double)v[u].x;
+                a1 += (double)v[u].y;
+                a2 += (double)v[u].z;
+                a3 += (double)v[u].w;
+            }
+        }
+        s_row[r0][4 * q] = a0;
+        s_row[r0][4 * q + 1] = a1;
+        s_row[r0][4 * q + 2] = a2;
+        s_row[r0][4 * q + 3] = a3;
+    }
+    __syncthreads();
+    if (t < 8 * GG_POSE_SUMS) {
+        const int col = t % GG_POSE_SUMS, part = t / GG_POSE_SUMS;
+        double a = 0.0;
+        for (int k = 0; k < GG_POSE_FIN_ROWS / 8; ++k) a += s_row[part * (GG_POSE_FIN_ROWS / 8) + k][col];
+        s_part[part][col] = a;
+    }
+    __syncthreads();
+    if (t < GG_POSE_SUMS) {
+        double a = 0.0;
+        for (int part = 0; part < 8; ++part) a += s_part[part][t];
+        const float f = (float)a;
+        if (t < 12) v_viewmat[t] = f;                      // viewmat (3 x 4)
+        else if (t < 20) v_projmat[t - 12] = f;            // full_proj rows 0, 1
+        else v_projmat[t - 8] = f;                         // full_proj row 3
+    } else if (t < GG_POSE_SUMS + 4) {
+        v_projmat[8 + (t - GG_POSE_SUMS)] = 0.0f;          // row 2 (the clip-space z) is read by nothing
+    }
+}
+
+// the pose VJP alone over strided cotangents (gg_project_bwd_ex's layouts): the Gaussians get no gradient
+__global__ __launch_bounds__(256) void project_pose_bwd_kernel(
+    int N, const float *__restrict__ means, const float *__restrict__ scales, float glob_scale,
+    const float *__restrict__ quats, const float *__restrict__ viewmat, const float *__restrict__ projmat, float fx,
+    float fy, int img_h, int img_w, const int32_t *__restrict__ radii, const float *__restrict__ conics,
+    const float *__restrict__ v_xy, int xy_stride, const float *__restrict__ v_depth, const float *__restrict__ v_conic,
+    int conic_stride, float *__restrict__ slab) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    float pv[GG_POSE_SUMS];
+#pragma unroll
+    for (int k = 0; k < GG_POSE_SUMS; ++k) pv[k] = 0.0f;
+    if (i < N && radii[i] > 0) {
+        float vm[3] = {0, 0, 0}, vs[3], vq4[4];
+        const float *vcn = v_conic + (size_t)conic_stride * i;
+        project_bwd_point<true>(i, means, scales, glob_scale, quats, viewmat, projmat, fx, fy, img_h, img_w, conics,
+                                v_xy[(size_t)xy_stride * i], v_xy[(size_t)xy_stride * i + 1], v_depth[i], vcn[0], vcn[1],
+                                vcn[2], vm, vs, vq4, pv);
+    }
+    pose_block_sum(pv, slab + (size_t)GG_POSE_SUMS * blockIdx.x);
+}
+
+extern "C" size_t gg_pose_grad_workspace(int N) {
+    return sizeof(float) * GG_POSE_SUMS * (size_t)(N > 0 ? (N + 255) / 256 : 1);
+}
+// shared host checks of the two pose entries: outputs present; N == 0 writes zeros; the slab fits and is 16-byte aligned
+static int pose_outputs_check(const char *what, int N, float *v_viewmat, float *v_projmat, void *ws, size_t ws_bytes,
+                              hipStream_t s, bool &done) {
+    done = false;
+    GG_REQUIRE(N >= 0, "num_points < 0");
+    GG_REQUIRE(v_viewmat && v_projmat, "null pointer (v_viewmat / v_projmat)");
+    if (N == 0) {
+        done = true;
+        if (gg_fill_async(v_viewmat, 0, 12 * sizeof(float), s) != hipSuccess ||
+            gg_fill_async(v_projmat, 0, 16 * sizeof(float), s) != hipSuccess) {
+            gg_set_error("%s: zero fill failed", what);
+            return GG_ERR_LAUNCH;
+        }
+        return GG_OK;
+    }
+    if (ws == nullptr || ws_bytes < gg_pose_grad_workspace(N) || ((uintptr_t)ws & 15)) {
+        gg_set_error("%s: a 16-byte aligned workspace of gg_pose_grad_workspace() bytes expected", what);
+        return GG_ERR_WORKSPACE;
+    }
+    return GG_OK;
+}
+extern "C" int gg_project_pose_bwd(int N, const float *means3d, const float *scales, float glob_scale,
+                                   const float *quats_n, const float *viewmat, const float *projmat, float fx, float fy,
+                                   int img_height, int img_width, const int32_t *radii, const float *conics,
+                                   const float *v_xy, int v_xy_stride, const float *v_depth, const float *v_conic,
+                                   int v_conic_stride, float *v_viewmat, float *v_projmat, void *ws, size_t ws_bytes,
+                                   gg_stream_t stream) {
+    GG_REQUIRE(v_xy_stride >= 2 && v_conic_stride >= 3, "v_xy rows hold 2 values, v_conic rows 3");
+    GG_REQUIRE(img_height > 0 && img_width > 0, "empty image");
+    bool done;
+    const int st = pose_outputs_check("gg_project_pose_bwd", N, v_viewmat, v_projmat, ws, ws_bytes,
+                                      (hipStream_t)stream, done);
+    if (st != GG_OK || done) return st;
+    GG_REQUIRE(means3d && scales && quats_n && viewmat && projmat && radii && conics && v_xy && v_depth && v_conic,
+               "null pointer");
+    GG_REQUIRE(((uintptr_t)quats_n & 15) == 0, "quats_n must be 16-byte aligned");
+    const int blocks = (N + 255) / 256;
+    gg_prof_begin(GG_K_POSE_BWD, (hipStream_t)stream);
+    hipLaunchKernelGGL(project_pose_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, N, means3d, scales,
+                       glob_scale, quats_n, viewmat, projmat, fx, fy, img_height, img_width, radii, conics, v_xy,
+                       v_xy_stride, v_depth, v_conic, v_conic_stride, (float *)ws);
+    gg_prof_end(GG_K_POSE_BWD, (hipStream_t)stream);
+    gg_prof_begin(GG_K_POSE_FINISH, (hipStream_t)stream);
+    hipLaunchKernelGGL(pose_finish_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, blocks, (const float4 *)ws,
+                       v_viewmat, v_projmat);
+    gg_prof_end(GG_K_POSE_FINISH, (hipStream_t)stream);
+    GG_CHECK_LAUNCH();
+    return GG_OK;
 }
 
 // ---- spherical harmonics ---------------------------------------------------------------------
@@ -1207,7 +1408,10 @@ __global__ __launch_bounds__(256) void activate_bwd_kernel(
 // the step's gradient buffers.  The per-Gaussian arithmetic is project_bwd_point and activate_bwd_point above: same
 // operation sequence, same bits as the three kernels.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void view_bwd_kernel(
+// POSE (view_bwd_pose_kernel, gg_view_bwd_pose): the same, and the workgroup's row of the pose VJP's slab (pose_block_sum);
+// every lane of the last workgroup then reaches the reduction (padding lanes add zeros)
+template <bool POSE>
+__device__ __forceinline__ void view_bwd_body(
     int N, const float *__restrict__ rec, int rec_stride, const uint8_t *__restrict__ clamp_mask,
     const float *__restrict__ means, const float *__restrict__ scales, float glob_scale,
     const float4 *__restrict__ quats_raw, const float4 *__restrict__ quats_n, const float *__restrict__ opac,
@@ -1215,9 +1419,15 @@ __global__ __launch_bounds__(256) void view_bwd_kernel(
     const float *__restrict__ viewmat, const float *__restrict__ projmat, float fx, float fy, int img_h, int img_w,
     const int32_t *__restrict__ radii, const float *__restrict__ conics, float *__restrict__ v_rgb,
     float *__restrict__ v_means, float *__restrict__ v_log_scales, float4 *__restrict__ v_quats,
-    float *__restrict__ v_opacities) {
+    float *__restrict__ v_opacities, float *__restrict__ pose_slab) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N) return;
+    if constexpr (!POSE) {
+        if (i >= N) return;
+    }
+    float pv[POSE ? GG_POSE_SUMS : 1];
+#pragma unroll
+    for (int k = 0; k < (POSE ? GG_POSE_SUMS : 1); ++k) pv[k] = 0.0f;
+    if (!POSE || i < N) {
     const float *r = rec + (size_t)i * rec_stride;
     float t[13];
     if ((rec_stride & 3) == 0) {   // 16-byte aligned rows (the pair backward's 16-float records): four loads
@@ -1234,8 +1444,8 @@ __global__ __launch_bounds__(256) void view_bwd_kernel(
     for (int c = 0; c < 3; ++c) v_rgb[3 * (size_t)i + c] = ((m >> c) & 1u) ? t[6 + c] : 0.0f;
     float vm[3] = {0, 0, 0}, vs[3] = {0, 0, 0}, vq4[4] = {0, 0, 0, 0};
     if (radii[i] > 0)
-        project_bwd_point(i, means, scales, glob_scale, reinterpret_cast<const float *>(quats_n), viewmat, projmat, fx, fy, img_h,
-                          img_w, conics, t[0], t[1], t[9], t[2], t[3], t[4], vm, vs, vq4);
+        project_bwd_point<POSE>(i, means, scales, glob_scale, reinterpret_cast<const float *>(quats_n), viewmat, projmat,
+                                fx, fy, img_h, img_w, conics, t[0], t[1], t[9], t[2], t[3], t[4], vm, vs, vq4, pv);
 #pragma unroll
     for (int k = 0; k < 3; ++k) v_means[3 * (size_t)i + k] += vm[k];
     const float sc[3] = {scales[3 * (size_t)i], scales[3 * (size_t)i + 1], scales[3 * (size_t)i + 2]};
@@ -1248,6 +1458,37 @@ __global__ __launch_bounds__(256) void view_bwd_kernel(
     v_opacities[i] += g_op;
     const float4 p = v_quats[i];
     v_quats[i] = make_float4(p.x + out.x, p.y + out.y, p.z + out.z, p.w + out.w);
+    }
+    if constexpr (POSE) pose_block_sum(pv, pose_slab + (size_t)GG_POSE_SUMS * blockIdx.x);
+}
+#define GG_VIEW_BWD_PARAMS                                                                                              \
+    int N, const float *__restrict__ rec, int rec_stride, const uint8_t *__restrict__ clamp_mask,                       \
+        const float *__restrict__ means, const float *__restrict__ scales, float glob_scale,                            \
+        const float4 *__restrict__ quats_raw, const float4 *__restrict__ quats_n, const float *__restrict__ opac,       \
+        const int32_t *__restrict__ axis, const float *__restrict__ viewmat, const float *__restrict__ projmat,          \
+        float fx, float fy, int img_h, int img_w, const int32_t *__restrict__ radii, const float *__restrict__ conics,  \
+        float *__restrict__ v_rgb, float *__restrict__ v_means, float *__restrict__ v_log_scales,                       \
+        float4 *__restrict__ v_quats, float *__restrict__ v_opacities
+#define GG_VIEW_BWD_ARGS                                                                                                \
+    N, rec, rec_stride, clamp_mask, means, scales, glob_scale, quats_raw, quats_n, opac, axis, viewmat, projmat, fx, fy, \
+        img_h, img_w, radii, conics, v_rgb, v_means, v_log_scales, v_quats, v_opacities
+__global__ __launch_bounds__(256) void view_bwd_kernel(GG_VIEW_BWD_PARAMS) {
+    view_bwd_body<false>(GG_VIEW_BWD_ARGS, nullptr);
+}
+__global__ __launch_bounds__(256) void view_bwd_pose_kernel(GG_VIEW_BWD_PARAMS, float *__restrict__ pose_slab) {
+    view_bwd_body<true>(GG_VIEW_BWD_ARGS, pose_slab);
+}
+static int view_bwd_check(int N, const float *rec, int rec_stride, const uint8_t *clamp_mask, const float *means,
+                          const float *scales, const float *quats_raw, const float *quats_n, const float *opac,
+                          const int32_t *axis, const float *viewmat, const float *projmat, const int32_t *radii,
+                          const float *conics, float *v_rgb, float *v_means, float *v_log_scales, float *v_quats,
+                          float *v_opacities) {
+    GG_REQUIRE(rec && clamp_mask && means && scales && quats_raw && quats_n && opac && axis && viewmat && projmat && radii &&
+                   conics && v_rgb && v_means && v_log_scales && v_quats && v_opacities, "null pointer");
+    GG_REQUIRE((((uintptr_t)quats_raw | (uintptr_t)quats_n | (uintptr_t)v_quats) & 15) == 0,
+               "quaternion arrays must be 16-byte aligned");
+    GG_REQUIRE((rec_stride & 3) != 0 || ((uintptr_t)rec & 15) == 0, "records of a multiple of 4 floats must be 16-byte aligned");
+    return GG_OK;
 }
 extern "C" int gg_view_bwd(int N, const float *rec, int rec_stride, const uint8_t *clamp_mask, const float *means,
                            const float *scales, float glob_scale, const float *quats_raw, const float *quats_n, const float *opac,
@@ -1257,17 +1498,42 @@ extern "C" int gg_view_bwd(int N, const float *rec, int rec_stride, const uint8_
     GG_REQUIRE(N >= 0, "num_points < 0");
     GG_REQUIRE(rec_stride >= 13, "a record holds 13 values");
     if (N == 0) return GG_OK;
-    GG_REQUIRE(rec && clamp_mask && means && scales && quats_raw && quats_n && opac && axis && viewmat && projmat && radii &&
-                   conics && v_rgb && v_means && v_log_scales && v_quats && v_opacities, "null pointer");
-    GG_REQUIRE((((uintptr_t)quats_raw | (uintptr_t)quats_n | (uintptr_t)v_quats) & 15) == 0,
-               "quaternion arrays must be 16-byte aligned");
-    GG_REQUIRE((rec_stride & 3) != 0 || ((uintptr_t)rec & 15) == 0, "records of a multiple of 4 floats must be 16-byte aligned");
+    const int st = view_bwd_check(N, rec, rec_stride, clamp_mask, means, scales, quats_raw, quats_n, opac, axis, viewmat,
+                                  projmat, radii, conics, v_rgb, v_means, v_log_scales, v_quats, v_opacities);
+    if (st != GG_OK) return st;
     gg_prof_begin(GG_K_VIEW_BWD, (hipStream_t)stream);
     hipLaunchKernelGGL(view_bwd_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, N, rec, rec_stride,
                        clamp_mask, means, scales, glob_scale, (const float4 *)quats_raw, (const float4 *)quats_n, opac, axis, viewmat,
                        projmat, fx, fy, img_height, img_width, radii, conics, v_rgb, v_means, v_log_scales,
                        (float4 *)v_quats, v_opacities);
     gg_prof_end(GG_K_VIEW_BWD, (hipStream_t)stream);
+    GG_CHECK_LAUNCH();
+    return GG_OK;
+}
+extern "C" int gg_view_bwd_pose(int N, const float *rec, int rec_stride, const uint8_t *clamp_mask, const float *means,
+                                const float *scales, float glob_scale, const float *quats_raw, const float *quats_n,
+                                const float *opac, const int32_t *axis, const float *viewmat, const float *projmat, float fx,
+                                float fy, int img_height, int img_width, const int32_t *radii, const float *conics,
+                                float *v_rgb, float *v_means, float *v_log_scales, float *v_quats, float *v_opacities,
+                                float *v_viewmat, float *v_projmat, void *ws, size_t ws_bytes, gg_stream_t stream) {
+    GG_REQUIRE(rec_stride >= 13, "a record holds 13 values");
+    bool done;
+    int st = pose_outputs_check("gg_view_bwd_pose", N, v_viewmat, v_projmat, ws, ws_bytes, (hipStream_t)stream, done);
+    if (st != GG_OK || done) return st;
+    st = view_bwd_check(N, rec, rec_stride, clamp_mask, means, scales, quats_raw, quats_n, opac, axis, viewmat, projmat,
+                        radii, conics, v_rgb, v_means, v_log_scales, v_quats, v_opacities);
+    if (st != GG_OK) return st;
+    const int blocks = (N + 255) / 256;
+    gg_prof_begin(GG_K_VIEW_BWD_POSE, (hipStream_t)stream);
+    hipLaunchKernelGGL(view_bwd_pose_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, N, rec, rec_stride,
+                       clamp_mask, means, scales, glob_scale, (const float4 *)quats_raw, (const float4 *)quats_n, opac, axis,
+                       viewmat, projmat, fx, fy, img_height, img_width, radii, conics, v_rgb, v_means, v_log_scales,
+                       (float4 *)v_quats, v_opacities, (float *)ws);
+    gg_prof_end(GG_K_VIEW_BWD_POSE, (hipStream_t)stream);
+    gg_prof_begin(GG_K_POSE_FINISH, (hipStream_t)stream);
+    hipLaunchKernelGGL(pose_finish_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, blocks, (const float4 *)ws,
+                       v_viewmat, v_projmat);
+    gg_prof_end(GG_K_POSE_FINISH, (hipStream_t)stream);
     GG_CHECK_LAUNCH();
     return GG_OK;
 }

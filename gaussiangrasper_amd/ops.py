@@ -837,6 +837,7 @@ class ViewGeometry(Function):
                                                fx, fy, cx, cy, img_height, img_width, tile_bounds)
         tail = ShadeTail.forward(t, degrees_to_use, viewdirs, colors_all, depths, normals)
         ctx.parts = (a, p, t)
+        ctx.pose_meta = (viewmat.shape, viewmat.dtype, full_proj.shape, full_proj.dtype)
         ctx.counts = tuple(len(c.saved_tensors) for c in ctx.parts)
         ctx.save_for_backward(*a.saved_tensors, *p.saved_tensors, *t.saved_tensors)
         for c in ctx.parts:
@@ -909,22 +910,42 @@ class ViewGeometry(Function):
                                         base, 5, 1, stride, n)
                     and _is_record_view(v_tail, base, 6, 7, stride, n)
                     and (stride % 4 != 0 or base % 16 == 0))
+        # the camera's gradient: asked for when viewmat (6) or full_proj (7) requires grad — the camera
+        # optimizer's route (plugin.py: viewmat from the adjusted camera_to_worlds, full_proj = projmat @ viewmat)
+        pose = ctx.needs_input_grad[6] or ctx.needs_input_grad[7]
         if not fast:
+            if pose and not any(ctx.needs_input_grad[:5]):
+                # frozen Gaussians (pose.refine_camera): only the depth cotangent of the chain reaches the camera
+                vd = torch.zeros(n, device=dev) if v_tail is None else v_tail[:, 3].float()
+                vd = vd if v_depths is None else vd + _f32(v_depths)
+                return (None,) * 6 + ViewGeometry._pose_only(ctx, p, v_xys, vd, v_conics) + (None,) * 8
             g_t = ShadeTail.backward(t, v_tail if v_tail is not None else torch.zeros(n, 7, device=dev))
             vd = g_t[3] if v_depths is None else g_t[3] + _f32(v_depths)
             vn = g_t[4] if v_normals is None else g_t[4] + _f32(v_normals)
             g_p = ProjectGaussians.backward(p, v_xys, vd, None, v_conics, None, None)
             g_a = ActivateGaussians.backward(a, g_p[1], g_p[3], v_opac, None, vn)
-            return (g_p[0], g_a[1], g_a[2], g_a[3], g_t[2], None, None, None, None, None, None, None, None, None,
-                    None, None)
+            g_cam = ViewGeometry._pose_only(ctx, p, v_xys, vd, v_conics) if pose else (None, None)
+            return (g_p[0], g_a[1], g_a[2], g_a[3], g_t[2], None) + g_cam + (None,) * 8
         lib = _lib.load()
         glob_scale, fx, fy, _cx, _cy, img_height, img_width = p.scalars
         v_rgb = torch.empty(n, 3, dtype=torch.float32, device=dev)
         v_ls, v_q, v_o = (s_[1] for s_ in a.sinks)
-        _lib.check(lib.gg_view_bwd(
-            n, C.c_void_p(base), stride, _ptr(mask), _ptr(means), _ptr(scales_e), glob_scale, _ptr(q_raw), _ptr(quats_n),
-            _ptr(opac), _ptr(axis), _ptr(viewmat), _ptr(projmat), fx, fy, img_height, img_width, _ptr(radii),
-            _ptr(conics), _ptr(v_rgb), _ptr(p.sink[1]), _ptr(v_ls), _ptr(v_q), _ptr(v_o), _stream(dev)), "gg_view_bwd")
+        if pose:
+            v_vm, v_pm = torch.empty(12, dtype=torch.float32, device=dev), torch.empty(16, dtype=torch.float32, device=dev)
+            ws = _workspace(lib.gg_pose_grad_workspace(n), dev)
+            _lib.check(lib.gg_view_bwd_pose(
+                n, C.c_void_p(base), stride, _ptr(mask), _ptr(means), _ptr(scales_e), glob_scale, _ptr(q_raw),
+                _ptr(quats_n), _ptr(opac), _ptr(axis), _ptr(viewmat), _ptr(projmat), fx, fy, img_height, img_width,
+                _ptr(radii), _ptr(conics), _ptr(v_rgb), _ptr(p.sink[1]), _ptr(v_ls), _ptr(v_q), _ptr(v_o), _ptr(v_vm),
+                _ptr(v_pm), _ptr(ws), ws.numel(), _stream(dev)), "gg_view_bwd_pose")
+            g_cam = ViewGeometry._camera_grads(ctx, v_vm, v_pm)
+        else:
+            g_cam = (None, None)
+            _lib.check(lib.gg_view_bwd(
+                n, C.c_void_p(base), stride, _ptr(mask), _ptr(means), _ptr(scales_e), glob_scale, _ptr(q_raw),
+                _ptr(quats_n), _ptr(opac), _ptr(axis), _ptr(viewmat), _ptr(projmat), fx, fy, img_height, img_width,
+                _ptr(radii), _ptr(conics), _ptr(v_rgb), _ptr(p.sink[1]), _ptr(v_ls), _ptr(v_q), _ptr(v_o),
+                _stream(dev)), "gg_view_bwd")
         # the SH gradient: kept as its factors over the views of a step, or expanded now — ShadeTail.backward's rules
         param, buf, notify, defer = t.sink
         pending = _deferred_sh.get(id(param))
@@ -938,7 +959,40 @@ class ViewGeometry(Function):
         for param_, _buf, notify_, _defer in a.sinks:
             if notify_ is not None:
                 notify_(param_)
-        return (None,) * 16
+        return (None,) * 6 + g_cam + (None,) * 8
+
+    @staticmethod
+    def _pose_only(ctx, p, v_xys, v_depths, v_conics):
+        """(v_viewmat, v_full_proj) from the projection's cotangents alone (gg_project_pose_bwd): the fallback branch"""
+        means, scales, quats_n, viewmat, projmat, radii, conics = p.saved_tensors
+        glob_scale, fx, fy, _cx, _cy, img_height, img_width = p.scalars
+        dev, n = means.device, means.shape[0]
+        v_xys, xy_stride = (torch.zeros(n, 2, device=dev), 2) if v_xys is None else _rows_in_place(v_xys, 2)
+        v_conics, conic_stride = (torch.zeros(n, 3, device=dev), 3) if v_conics is None \
+            else _rows_in_place(v_conics, 3)
+        v_depths = _f32(v_depths)
+        lib = _lib.load()
+        v_vm, v_pm = torch.empty(12, dtype=torch.float32, device=dev), torch.empty(16, dtype=torch.float32, device=dev)
+        ws = _workspace(lib.gg_pose_grad_workspace(n), dev)
+        _lib.check(lib.gg_project_pose_bwd(
+            n, _ptr(means), _ptr(scales), glob_scale, _ptr(quats_n), _ptr(viewmat), _ptr(projmat), fx, fy, img_height,
+            img_width, _ptr(radii), _ptr(conics), _ptr(v_xys), xy_stride, _ptr(v_depths), _ptr(v_conics), conic_stride,
+            _ptr(v_vm), _ptr(v_pm), _ptr(ws), ws.numel(), _stream(dev)), "gg_project_pose_bwd")
+        return ViewGeometry._camera_grads(ctx, v_vm, v_pm)
+
+    @staticmethod
+    def _camera_grads(ctx, v_vm, v_pm):
+        """the 12 + 16 sums in the shapes and dtypes of the viewmat / full_proj the forward was given (a viewmat of more
+        than 12 elements: its first 12 were read, the rest gets zeros)"""
+        vm_shape, vm_dtype, pm_shape, pm_dtype = ctx.pose_meta
+        g_vm = v_vm
+        numel = 1
+        for d in vm_shape:
+            numel *= d
+        if numel > 12:
+            g_vm = torch.cat((v_vm, torch.zeros(numel - 12, dtype=torch.float32, device=v_vm.device)))
+        return (g_vm.reshape(vm_shape).to(vm_dtype) if ctx.needs_input_grad[6] else None,
+                v_pm.reshape(pm_shape).to(pm_dtype) if ctx.needs_input_grad[7] else None)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -124,6 +124,35 @@ class StubCameraOptimizer:
         return None
 
 
+class StubPoseCameraOptimizer(torch.nn.Module):
+    """Opt-in stand-in for CameraOptimizer with mode "SO3xR3" or "SE3" (nerfstudio/cameras/camera_optimizers.py:
+    a (num_cameras, 6) `pose_adjustment` parameter, zero at the start, [translation | rotation] tangents;
+    apply_to_camera :150-158 replaces camera_to_worlds by `c2w @ [exp(pose_adjustment[cam_idx]) ; 0 0 0 1]`;
+    get_param_groups puts the parameter in the "camera_opt" group).  The model's config must say the same mode
+    (`config.camera_optimizer.mode`): the plugin then derives every view's matrices from the adjusted pose."""
+
+    def __init__(self, num_cameras: int, mode: str = "SO3xR3", device="cpu"):
+        super().__init__()
+        if mode not in ("SO3xR3", "SE3"):
+            raise ValueError(f"mode must be SO3xR3 or SE3, got {mode!r}")
+        self.config = types.SimpleNamespace(mode=mode)
+        self.num_cameras = num_cameras
+        self.pose_adjustment = Parameter(torch.zeros(num_cameras, 6, device=device))
+
+    def forward(self, indices) -> torch.Tensor:
+        from .pose import exp_map
+        return exp_map(self.pose_adjustment[indices, :], self.config.mode)
+
+    def apply_to_camera(self, camera) -> None:
+        from .pose import homogeneous
+        assert camera.metadata is not None and "cam_idx" in camera.metadata, "Must provide id of camera in its metadata"
+        adj = homogeneous(self([camera.metadata["cam_idx"]])).to(camera.camera_to_worlds)
+        camera.camera_to_worlds = torch.bmm(camera.camera_to_worlds, adj)
+
+    def get_param_groups(self, param_groups: Dict) -> None:
+        param_groups["camera_opt"] = [self.pose_adjustment]
+
+
 def default_config(**over) -> types.SimpleNamespace:
     """GaussianSplattingModelConfig defaults (gaussian_splatting.py:150-196)"""
     cfg = dict(warmup_length=500, refine_every=100, resolution_schedule=250, num_downscales=2,

@@ -144,6 +144,34 @@ int gg_view_bwd(int num_points, const float *rec, int rec_stride, const uint8_t 
                 int img_width, const int32_t *radii, const float *conics, float *v_rgb, float *v_means,
                 float *v_log_scales, float *v_quats, float *v_opacities, gg_stream_t stream);
 
+/* ---- camera pose gradients (the camera optimizer's `apply_to_camera`, reference gaussian_splatting.py:638-640) -------
+ * The VJP of the projection with respect to the camera: for the visible Gaussians (radii > 0) the cotangents (v_xy,
+ * v_depth, v_conic — gg_project_bwd's convention) are carried to
+ *   v_viewmat (12 floats): d/d viewmat, 3 x 4 row-major (the world -> camera rows gg_project_fwd reads), and
+ *   v_projmat (16 floats): d/d projmat, 4 x 4 row-major (the full projection projmat @ viewmat of the pixel centres);
+ *                          row 2 (clip-space z) is read by nothing and is written as zeros.
+ * Both are sums over all Gaussians, WRITTEN (not added to).  The sums are deterministic: one row of 24 partial sums per
+ * workgroup of 256 Gaussians in `ws`, added up in a fixed order in fp64 by a one-workgroup launch — no float atomics,
+ * the same bits on every run.  ws: gg_pose_grad_workspace(num_points) bytes, 16-byte aligned.  num_points == 0 writes
+ * zeros.  Under GG_VJP_GSPLAT_COMPAT the simplified quantities of the means' VJP are used (no homogeneous-w term, no
+ * FOV-clamp derivative).  Intrinsics (fx, fy, cx, cy) get no gradient.
+ *
+ * gg_view_bwd_pose: gg_view_bwd (same arguments, the same per-Gaussian gradients bit for bit) plus the pose sums.
+ * gg_project_pose_bwd: the pose sums alone; v_xy / v_conic rows v_xy_stride / v_conic_stride floats apart (as
+ * gg_project_bwd_ex takes them), quats_n 16-byte aligned; the Gaussians get no gradient. */
+size_t gg_pose_grad_workspace(int num_points);
+int gg_view_bwd_pose(int num_points, const float *rec, int rec_stride, const uint8_t *clamp_mask, const float *means,
+                     const float *scales, float glob_scale, const float *quats_raw, const float *quats_n,
+                     const float *opac, const int32_t *axis, const float *viewmat, const float *projmat, float fx,
+                     float fy, int img_height, int img_width, const int32_t *radii, const float *conics, float *v_rgb,
+                     float *v_means, float *v_log_scales, float *v_quats, float *v_opacities, float *v_viewmat,
+                     float *v_projmat, void *ws, size_t ws_bytes, gg_stream_t stream);
+int gg_project_pose_bwd(int num_points, const float *means, const float *scales, float glob_scale,
+                        const float *quats_n, const float *viewmat, const float *projmat, float fx, float fy,
+                        int img_height, int img_width, const int32_t *radii, const float *conics, const float *v_xy,
+                        int v_xy_stride, const float *v_depth, const float *v_conic, int v_conic_stride,
+                        float *v_viewmat, float *v_projmat, void *ws, size_t ws_bytes, gg_stream_t stream);
+
 /* gg_activate_fwd + gg_project_fwd (glob_scale 1) + the intersection count in one pass over the Gaussians (round 4,
  * ops.ViewGeometry).  Outputs are those two entries' (bit for bit: shared device code) except that cov3d is not produced.
  * *num_intersects_out (device, int64) receives sum(num_tiles_hit).  `parts`: gg_view_fwd_workspace(num_points) bytes,
@@ -713,7 +741,10 @@ int gg_knn(int num_points, const float *points, int k, const double *grid, const
 #define GG_K_SUBSAMPLE 37     /* gg_subsample: radix select, scan and emit */
 #define GG_K_KNN 38           /* gg_knn: grid counting sort and shell search */
 #define GG_K_OBJMASK 39       /* gg_object_masks: all six launches */
-#define GG_K_IDS 40           /* ids are below this */
+#define GG_K_VIEW_BWD_POSE 40 /* gg_view_bwd_pose: view_bwd_kernel's pose variant (its finish launch: GG_K_POSE_FINISH) */
+#define GG_K_POSE_BWD 41      /* gg_project_pose_bwd: the pose-only pass over the Gaussians */
+#define GG_K_POSE_FINISH 42   /* the one-workgroup sum of the pose slab behind either */
+#define GG_K_IDS 43           /* ids are below this */
 #define GG_PROF_NUM_KERNELS 32
 int gg_prof_enable(int on);
 int gg_prof_reset(void);
