@@ -10,7 +10,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgg_raster.so")
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 _P, _I, _F, _I64, _SZ = C.c_void_p, C.c_int, C.c_float, C.c_int64, C.c_size_t
 
@@ -119,6 +119,10 @@ SIGNATURES = {
     "gg_depth_normals": (_I, [_I, _I, _I, _P, _P, _P, _P, _P]),
     "gg_knn_workspace": (_SZ, [_I, _P]),
     "gg_knn": (_I, [_I, _P, _I, _P, _P, _P, _P, _P, _SZ, _P]),
+    "gg_tsdf_integrate": (_I, [_P, _P, _F, _I, _I, _I] + [_P] * 8 + [_P]),
+    "gg_tsdf_mesh_workspace": (_SZ, [_P]),
+    "gg_tsdf_mesh_count": (_I, [_P, _P, _P, _P, _P, _SZ, _P]),
+    "gg_tsdf_mesh_emit": (_I, [_P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P, _P, _SZ, _P]),
     "gg_prof_enable": (_I, [_I]),
     "gg_prof_reset": (_I, []),
     "gg_prof_get": (_I, [_I, C.POINTER(C.c_int), C.POINTER(C.c_double)]),

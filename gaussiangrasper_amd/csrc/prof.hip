@@ -116,6 +116,8 @@ extern "C" const char *gg_prof_name(int id) {
         case GG_K_VIEW_BWD_POSE: return "view_bwd_pose_kernel";
         case GG_K_POSE_BWD: return "project_pose_bwd_kernel";
         case GG_K_POSE_FINISH: return "pose_finish_kernel";
+        case GG_K_TSDF_INTEGRATE: return "tsdf_integrate_kernel";
+        case GG_K_TSDF_MESH: return "gg_tsdf_mesh(all launches)";
         default: break;
     }
     if (id >= GG_K_BLEND_FWD && id < GG_K_BLEND_FWD + 6) {

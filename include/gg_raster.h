@@ -706,6 +706,68 @@ size_t gg_knn_workspace(int num_points, const int32_t *dims);
 int gg_knn(int num_points, const float *points, int k, const double *grid, const int32_t *dims, float *dist,
            int64_t *idx, void *ws, size_t ws_bytes, gg_stream_t stream);
 
+/* ---- mesh export: TSDF fusion and marching tetrahedra (PARITY "Mesh export") ------------------------
+ * The volume: dims (host, 3 ints) X, Y, Z lattice points, 1 <= each <= GG_TSDF_MAX_DIM, X Y Z <= GG_TSDF_MAX_POINTS;
+ * grid (host, 6 floats) origin x, y, z and voxel size x, y, z (> 0, finite).  Point (i, j, k) has index
+ * (i Y + j) Z + k (C order [X][Y][Z], z fastest) and sits at p_a = origin_a + (float)i_a * size_a (fp32, the
+ * product rounded, then the sum).  Every array below is fp32; colour arrays are [..][3].
+ *
+ * gg_tsdf_integrate: fuses num_views depth frames into tsdf / weight [X][Y][Z] (in / out) and, when rgb is not NULL,
+ * rgb [V][H][W][3] into color [X][Y][Z][3] / color_weight [X][Y][Z] (in / out; both NULL when rgb is NULL).
+ * depth [V][H][W]; intrinsics [V][4] fx, fy, cx, cy; w2c [V][3][4] world-to-camera with OpenCV axes (x right,
+ * y down, z forward).  trunc > 0 finite.  Per point, views in index order, fp32, no contraction:
+ *   c_r = ((E[r][0] x + E[r][1] y) + E[r][2] z) + E[r][3];         skip the view unless c_2 > 0;
+ *   u = (fx c_0) / c_2 + cx,  v = (fy c_1) / c_2 + cy;              skip unless 0 <= u < W and 0 <= v < H;
+ *   d = depth[view][floor(v)][floor(u)];                             skip unless d > 0 (0, < 0, NaN: no observation;
+ *                                                                    +inf: the ray saw nothing, free space);
+ *   dist = d - c_2;                                                  skip unless dist >= -trunc;
+ *   obs = min(1, dist / trunc);  W' = W + 1;  T' = (T W + obs) / W';
+ *   with rgb, when |dist| < trunc:  K' = K + 1;  C'_c = (C_c K + rgb_c) / K'   (colour weight K, colour C).
+ * One thread per point holds its state in registers across the views: no atomics, and V views in one call give the
+ * same bits as V calls of one view each.  A workgroup owns a 4 x 8 x 8 brick and skips a view for the whole brick
+ * only where a margin-padded test of the brick's corners (fp64) shows that no point of it can pass the tests above.
+ *
+ * gg_tsdf_mesh_count / gg_tsdf_mesh_emit: the zero level set by marching tetrahedra.  Cell (i, j, k) (each index <
+ * dim - 1) is cut into the 6 Kuhn tetrahedra around its main diagonal: tetrahedron t = permutation (a, b, c) of the
+ * axes in lexicographic order ((x,y,z), (x,z,y), (y,x,z), (y,z,x), (z,x,y), (z,y,x)) has the corners o, o + e_a,
+ * o + e_a + e_b, o + (1,1,1).  Every edge then joins a lattice point to a neighbour in one of 7 positive directions
+ * d = 0..6: +x, +y, +z, +xy, +xz, +yz, +xyz.
+ *   - A cell emits only if all 8 of its corners have weight > 0 (unobserved space is never meshed); tsdf must be
+ *     finite there.  A corner is inside when T < 0.
+ *   - Every sign-changing edge (a, b = a + delta_d) used by an emitting cell is one shared vertex:
+ *     t = T_a / (T_a - T_b);  g = (float)i_a + t * delta (per axis; delta 0 gives (float)i_a);
+ *     position = origin + g * size;  normal: the TSDF gradient at a and at b, per axis
+ *     (T[i+1] - T[i-1]) / (2 size) inside the volume, (T[1] - T[0]) / size and (T[n-1] - T[n-2]) / size at its
+ *     borders, 0 along an axis of one point; n = g_a + t (g_b - g_a); n / sqrt((n0 n0 + n1 n1) + n2 n2), or
+ *     (0, 0, 0) when that length is 0; colour: C_a + t (C_b - C_a).
+ *   - Triangles of one tetrahedron (corners 0..3 in the order above, case = sum of inside(corner k) << k):
+ *     one corner apart from the other three (one inside or one outside): the triangle on its three edges;
+ *     two inside (p < q), two outside (r < s): the quad pq-cut split as (pr, ps, qs), (pr, qs, qr).
+ *     The winding makes (v1 - v0) x (v2 - v0) point towards increasing TSDF (free space); it is fixed per
+ *     tetrahedron and case from the corners' lattice positions.  A zero at a corner gives degenerate triangles: they
+ *     are kept (no NaN, every index valid).
+ *   - Order: vertices ascending (point index, direction); faces ascending (cell, tetrahedron, triangle); the output
+ *     is a pure function of the input.  Faces are int32 vertex triples.
+ * gg_tsdf_mesh_count writes counts int64 [2] (device) = (num_vertices, num_faces) and keeps the edge masks and
+ * offsets in ws; gg_tsdf_mesh_emit then reads them from the same ws (the same dims and tsdf, unchanged in between)
+ * and writes vertices / normals [num_vertices][3], colors [num_vertices][3] (only when both color and colors are
+ * not NULL) and faces [num_faces][3]; num_vertices / num_faces are the capacities of those arrays (the counts read
+ * back): nothing is written past them.  A count of -1 means the prefix scan gave up (never expected).
+ * `ws`: gg_tsdf_mesh_workspace(dims) bytes (about 10 per point), 256-byte aligned; 0 for dims out of range. */
+#define GG_TSDF_MAX_POINTS (1 << 27)
+#define GG_TSDF_MAX_DIM 4096
+#define GG_TSDF_MAX_VIEWS (1 << 20)
+#define GG_TSDF_MAX_SIDE 32768
+int gg_tsdf_integrate(const int32_t *dims, const float *grid, float trunc, int num_views, int height, int width,
+                      const float *depth, const float *rgb, const float *intrinsics, const float *w2c, float *tsdf,
+                      float *weight, float *color, float *color_weight, gg_stream_t stream);
+size_t gg_tsdf_mesh_workspace(const int32_t *dims);
+int gg_tsdf_mesh_count(const int32_t *dims, const float *tsdf, const float *weight, int64_t *counts, void *ws,
+                       size_t ws_bytes, gg_stream_t stream);
+int gg_tsdf_mesh_emit(const int32_t *dims, const float *grid, const float *tsdf, const float *color, int64_t num_vertices,
+                      int64_t num_faces, float *vertices, float *normals, float *colors, int32_t *faces,
+                      const void *ws, size_t ws_bytes, gg_stream_t stream);
+
 /* ---- in-library kernel timing (measurement only; off by default) --------------------------------
  * When enabled, every launch of the kernels below is bracketed by a hipEvent pair recorded on the
  * launch stream, so bench.py can report the average duration of exactly that kernel over its
@@ -744,7 +806,9 @@ int gg_knn(int num_points, const float *points, int k, const double *grid, const
 #define GG_K_VIEW_BWD_POSE 40 /* gg_view_bwd_pose: view_bwd_kernel's pose variant (its finish launch: GG_K_POSE_FINISH) */
 #define GG_K_POSE_BWD 41      /* gg_project_pose_bwd: the pose-only pass over the Gaussians */
 #define GG_K_POSE_FINISH 42   /* the one-workgroup sum of the pose slab behind either */
-#define GG_K_IDS 43           /* ids are below this */
+#define GG_K_TSDF_INTEGRATE 43 /* gg_tsdf_integrate */
+#define GG_K_TSDF_MESH 44     /* gg_tsdf_mesh_count and gg_tsdf_mesh_emit: all their launches */
+#define GG_K_IDS 45           /* ids are below this */
 #define GG_PROF_NUM_KERNELS 32
 int gg_prof_enable(int on);
 int gg_prof_reset(void);
