@@ -118,6 +118,7 @@ extern "C" const char *gg_prof_name(int id) {
         case GG_K_POSE_FINISH: return "pose_finish_kernel";
         case GG_K_TSDF_INTEGRATE: return "tsdf_integrate_kernel";
         case GG_K_TSDF_MESH: return "gg_tsdf_mesh(all launches)";
+        case GG_K_GRASP_PROPOSE: return "gg_grasp_propose(all launches)";
         default: break;
     }
     if (id >= GG_K_BLEND_FWD && id < GG_K_BLEND_FWD + 6) {

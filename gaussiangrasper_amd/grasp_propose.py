@@ -1,0 +1,329 @@
+"""Grasp proposals: antipodal parallel-jaw candidates from the Gaussian field itself, as GraspGroup rows in the
+layout `grasp.contacts` reads, so that propose -> score -> filter runs on the device with nothing from outside the
+project.  One HIP call (`gg_grasp_propose`, csrc/grasp_propose.hip) tests every seed against every oriented point of
+the object in fp64; the contract is in include/gg_raster.h and PARITY.md "Grasp proposals".  This is a geometric
+sampler of this project's own, not a restatement of AnyGrasp: its candidates are a different set.
+
+    antipodal          the per-seed outputs of one gg_grasp_propose call (GraspProposals)
+    choose_seeds       the points that take part, thinned to at most max_seeds
+    propose_grasps     (M, 17) scene-frame rows of a model's object (model_points, choose_seeds, antipodal, compact)
+    grasp_object       proposals, then grasp.contacts and grasp.filter_grasps: (rows, GraspContacts, keep)
+    grasps_from_scene  scene frame -> world -> grasp frame, the inverse of grasp.grasps_to_scene
+    python -m gaussiangrasper_amd.grasp_propose --ckpt IN (--object-points obj.npy | --positives ...) --out grasps.npy
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes
+import json
+import math
+import sys
+from dataclasses import dataclass
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+from torch import Tensor
+
+from . import _lib
+from .grasp import (BAND, DEPTH_BASE, FINGER_WIDTH, GRASP_COLS, MIN_WEIGHT, MU, ArrayLike, GraspContacts,
+                    _check_grasp_array, _check_rotation, _f32_rows, _param, contacts, filter_grasps, model_points)
+from .ops import _ptr, _require_hip, _stream, _workspace as _ws
+
+# UNVERIFIED defaults (PARITY.md "Grasp proposals"), in grasp units (metres): max_width, depth and height are
+# recalled from graspnetAPI's gripper; tube_radius, min_width, clearance, min_align and num_approach are this
+# project's choices
+TUBE_RADIUS = 0.003
+MAX_WIDTH = 0.10
+MIN_WIDTH = 0.005
+CLEARANCE = 0.005
+DEPTH = 0.02
+HEIGHT = 0.02
+MIN_ALIGN = 0.0
+NUM_APPROACH = 8
+MAX_SEEDS = 4096
+MAX_APPROACH = 64            # GG_PROPOSE_MAX_APPROACH
+UP = (0.0, 0.0, 1.0)
+
+
+@dataclass
+class GraspProposals:
+    """Per-seed outputs of one gg_grasp_propose call, device tensors; S = number of seeds, K = num_approach."""
+    pair_idx: Tensor           # (S, 2) int32: the two contact points, -1 when the seed is not usable
+    tube_count: Tensor         # (S,) int32: points in the seed's tube, 0 when not usable
+    span: Tensor               # (S,) float32: distance between the contacts, NaN when not usable
+    valid: Tensor              # (S,) bool
+    rows: Tensor               # (S, K, 17) float32 GraspGroup rows, NaN for a seed that is not valid
+
+    def compact(self) -> Tensor:
+        """(M, 17) rows of the valid seeds, in seed order, then approach order."""
+        return self.rows[self.valid].reshape(-1, GRASP_COLS)
+
+
+# ------------------------------------------------------------------------------------------------
+# host side: frames (numpy, fp64)
+# ------------------------------------------------------------------------------------------------
+def grasps_from_scene(grasps: ArrayLike, cam_to_world: Optional[ArrayLike] = None,
+                      matrix: Optional[ArrayLike] = None, scale: float = 1.0) -> np.ndarray:
+    """The inverse of grasp.grasps_to_scene: scene-frame rows back to the grasp (camera) frame, or to the world frame
+    with cam_to_world None.  R = (M3 C3)^T R', t = C3^T (M3^T (t' / scale - M_t) - C_t), width, height and depth
+    divided by scale.  The same checks: C3, M3 and every finite R orthonormal within 1e-4.  Returns (M, 17)
+    float32."""
+    g = _check_grasp_array(grasps).astype(np.float64)
+    C = np.eye(4) if cam_to_world is None else np.asarray(cam_to_world, dtype=np.float64)
+    Mx = np.eye(4) if matrix is None else np.asarray(matrix, dtype=np.float64)
+    if C.shape != (4, 4):
+        raise ValueError(f"cam_to_world must be 4x4, got {C.shape}")
+    if Mx.shape not in ((3, 4), (4, 4)):
+        raise ValueError(f"matrix must be 3x4 or 4x4, got {Mx.shape}")
+    scale = float(scale)
+    if not (math.isfinite(scale) and scale > 0.0):
+        raise ValueError(f"scale must be finite and > 0, got {scale}")
+    _check_rotation(C[:3, :3], "cam_to_world rotation")
+    _check_rotation(Mx[:3, :3], "matrix rotation")
+    R = g[:, 4:13].reshape(-1, 3, 3)
+    fin = np.isfinite(R).all(axis=(1, 2))
+    _check_rotation(R[fin], "grasp rotation")
+    A = Mx[:3, :3] @ C[:3, :3]
+    out = g.copy()
+    out[:, 4:13] = (A.T @ R).reshape(-1, 9)
+    world = (g[:, 13:16] / scale - Mx[:3, 3]) @ Mx[:3, :3]          # M3^T x as a row vector: x M3
+    out[:, 13:16] = (world - C[:3, 3]) @ C[:3, :3]
+    out[:, 1:4] /= scale
+    return out.astype(np.float32)
+
+
+# ------------------------------------------------------------------------------------------------
+# device side: one gg_grasp_propose call
+# ------------------------------------------------------------------------------------------------
+def _check_params(tube_radius, max_width, min_width, clearance, depth, height, min_weight, min_align, up,
+                  num_approach) -> Tuple[tuple, tuple, int]:
+    r, w0 = _param("tube_radius", tube_radius), _param("min_width", min_width)
+    c, d = _param("clearance", clearance), _param("depth", depth)
+    W, h = float(max_width), float(height)
+    if not (math.isfinite(W) and W > 0.0):
+        raise ValueError(f"max_width must be finite and > 0, got {W}")
+    if not (math.isfinite(h) and h > 0.0):
+        raise ValueError(f"height must be finite and > 0, got {h}")
+    if 2.0 * c > W:
+        raise ValueError(f"clearance {c} on both sides exceeds max_width {W}")
+    mw, ma = float(min_weight), float(min_align)
+    if math.isnan(mw):
+        raise ValueError("min_weight must not be NaN")
+    if not 0.0 <= ma <= 1.0:
+        raise ValueError(f"min_align must be in [0, 1], got {ma}")
+    u = tuple(float(x) for x in np.asarray(up, dtype=np.float64).reshape(-1))
+    if len(u) != 3 or not all(math.isfinite(x) for x in u) or not any(x != 0.0 for x in u):
+        raise ValueError(f"up must be 3 finite numbers, not all zero, got {up}")
+    k = int(num_approach)
+    if k != num_approach or not 1 <= k <= MAX_APPROACH:
+        raise ValueError(f"num_approach must be an integer in 1..{MAX_APPROACH}, got {num_approach}")
+    return (r, W, w0, c, d, h, mw, ma), u, k
+
+
+def antipodal(points: Tensor, normals: Tensor, weights: Tensor, seeds: Tensor, tube_radius: float = TUBE_RADIUS,
+              max_width: float = MAX_WIDTH, min_width: float = MIN_WIDTH, clearance: float = CLEARANCE,
+              depth: float = DEPTH, height: float = HEIGHT, min_weight: float = MIN_WEIGHT,
+              min_align: float = MIN_ALIGN, up: Sequence[float] = UP,
+              num_approach: int = NUM_APPROACH) -> GraspProposals:
+    """Antipodal candidates of every seed against the oriented points (include/gg_raster.h gg_grasp_propose).
+    points / normals (N, 3), weights (N,) float32 and seeds (S,) int32 on the HIP device (no CPU path).  Per seed:
+    the farthest two points within tube_radius of the seed's normal line and max_width along it are the contacts;
+    the seed is valid when they are min_width .. max_width - 2 clearance apart and both contact normals are within
+    acos(min_align) of the line, and then gives num_approach rows around the closing axis, the first one
+    approaching from as near -up as the axis allows.  Lengths are in the points' units.  One call; nothing waits on
+    the host."""
+    args, u, k = _check_params(tube_radius, max_width, min_width, clearance, depth, height, min_weight, min_align,
+                               up, num_approach)
+    dev = _require_hip(points, normals, weights, seeds)
+    points = _f32_rows(points, "points", 3)
+    normals = _f32_rows(normals, "normals", 3)
+    weights = _f32_rows(weights, "weights", None)
+    if seeds.dtype != torch.int32 or seeds.ndim != 1:
+        raise ValueError(f"seeds must be an int32 (S,) tensor, got {seeds.dtype} {tuple(seeds.shape)}")
+    seeds = seeds.contiguous()
+    n, s = points.shape[0], seeds.shape[0]
+    if normals.shape[0] != n or weights.shape[0] != n:
+        raise ValueError(f"points has {n} rows, normals {normals.shape[0]}, weights {weights.shape[0]}")
+    lib = _lib.load()
+    res = GraspProposals(
+        pair_idx=torch.empty(s, 2, dtype=torch.int32, device=dev),
+        tube_count=torch.empty(s, dtype=torch.int32, device=dev),
+        span=torch.empty(s, dtype=torch.float32, device=dev),
+        valid=torch.empty(s, dtype=torch.uint8, device=dev),
+        rows=torch.empty(s, k, GRASP_COLS, dtype=torch.float32, device=dev))
+    nbytes = lib.gg_grasp_propose_workspace(n, s)
+    if s > 0 and nbytes == 0:
+        raise ValueError(f"{n} points x {s} seeds is beyond gg_grasp_propose's limits")
+    ws = _ws(nbytes, dev)
+    up3 = (ctypes.c_double * 3)(*u)
+    _lib.check(lib.gg_grasp_propose(n, _ptr(points), _ptr(normals), _ptr(weights), s, _ptr(seeds), *args,
+                                    ctypes.cast(up3, ctypes.c_void_p), k, _ptr(res.pair_idx), _ptr(res.tube_count),
+                                    _ptr(res.span), _ptr(res.valid), _ptr(res.rows), _ptr(ws),
+                                    ctypes.c_size_t(ws.numel()), _stream(dev)), "gg_grasp_propose")
+    res.valid = res.valid.bool()
+    return res
+
+
+def choose_seeds(weights: Tensor, max_seeds: int = MAX_SEEDS, seed: int = 0, min_weight: float = MIN_WEIGHT) -> Tensor:
+    """int32 indices of the points with (double)w > min_weight, ascending, thinned to at most max_seeds.  With P such
+    points, P <= max_seeds keeps all of them; otherwise prepare's gg_subsample picks the subset (its interface fits
+    unchanged: subsample_device_indices(P, keep, seed) with keep = ceil(P / max_seeds) gives P // keep positions, a
+    uniform subset by SplitMix64 keys of (seed, position), in ascending order), so between max_seeds / 2 and
+    max_seeds seeds come back.  Points and normals are not looked at: a seed whose point or normal is not finite is
+    simply not usable.  One read-back (P)."""
+    dev = _require_hip(weights)
+    if weights.ndim != 1:
+        raise ValueError(f"weights must be (N,), got {tuple(weights.shape)}")
+    m = int(max_seeds)
+    if m != max_seeds or m < 1:
+        raise ValueError(f"max_seeds must be an integer >= 1, got {max_seeds}")
+    if math.isnan(float(min_weight)):
+        raise ValueError("min_weight must not be NaN")
+    idx = torch.nonzero(weights.double() > float(min_weight)).reshape(-1)
+    p = idx.shape[0]
+    if p > m:
+        from .prepare import subsample_device_indices
+        idx = idx[subsample_device_indices(p, -(-p // m), int(seed)).to(dev)]
+    return idx.to(torch.int32)
+
+
+def propose_grasps(model_or_scene, mask: Optional[Tensor] = None, max_seeds: int = MAX_SEEDS,
+                   num_approach: int = NUM_APPROACH, up: Sequence[float] = UP, scale: float = 1.0,
+                   tube_radius: float = TUBE_RADIUS, max_width: float = MAX_WIDTH, min_width: float = MIN_WIDTH,
+                   clearance: float = CLEARANCE, depth: float = DEPTH, height: float = HEIGHT,
+                   min_weight: float = MIN_WEIGHT, min_align: float = MIN_ALIGN, seed: int = 0) -> Tensor:
+    """(M, 17) float32 candidates for the object `mask` selects (None: every Gaussian), on the device, in the SCENE
+    frame: grasp.model_points(model, mask), choose_seeds, antipodal, then the valid seeds' rows in seed order, then
+    approach order.  Lengths are given in grasp units (metres) and multiplied by `scale` (the scene's units per
+    metre), as score_grasps does; `up` is a direction of the scene frame."""
+    s = float(scale)
+    if not (math.isfinite(s) and s > 0.0):
+        raise ValueError(f"scale must be finite and > 0, got {s}")
+    pts, nrm, w = model_points(model_or_scene, mask)
+    seeds = choose_seeds(w, max_seeds, seed, min_weight)
+    res = antipodal(pts, nrm, w, seeds, _param("tube_radius", tube_radius) * s, float(max_width) * s,
+                    _param("min_width", min_width) * s, _param("clearance", clearance) * s,
+                    _param("depth", depth) * s, float(height) * s, min_weight, min_align, up, num_approach)
+    return res.compact()
+
+
+def grasp_object(model_or_scene, mask: Optional[Tensor] = None, scale: float = 1.0,
+                 depth_base: float = DEPTH_BASE, finger_width: float = FINGER_WIDTH, band: float = BAND,
+                 mu: float = MU, min_weight: float = MIN_WEIGHT, max_collision: Optional[float] = None,
+                 **propose) -> Tuple[Tensor, GraspContacts, Tensor]:
+    """From a model and an object mask to feasible grasps: (rows, contacts, keep), all on the device.  rows (M, 17):
+    propose_grasps(model, mask, scale=scale, **propose), scene frame.  contacts: grasp.contacts of those rows, in two
+    calls, because gg_grasp_contacts takes one point set for the contacts and the collision term alike while the two
+    want different ones: the finger contacts, patch normals, angles and region sums come from the OBJECT's points
+    (weights times mask: the fingers close on the object, not on the table under it), and collision_weight from the
+    WHOLE scene's points (model_points(model, None): what the fingers must not hit is everything, the object's own
+    Gaussians beside the contacts included).  feasible = the object call's friction-cone result and the scene
+    call's collision_weight <= max_collision (None: no limit).  keep: filter_grasps(rows, contacts), indices of
+    the feasible rows by score."""
+    rows = propose_grasps(model_or_scene, mask, scale=scale, min_weight=min_weight, **propose)
+    s = float(scale)
+    lengths = (_param("depth_base", depth_base) * s, _param("finger_width", finger_width) * s,
+               _param("band", band) * s)
+    mc = math.inf if max_collision is None else float(max_collision)
+    if math.isnan(mc):
+        raise ValueError("max_collision must not be NaN")
+    res = contacts(*model_points(model_or_scene, mask), rows, *lengths, mu, min_weight, None)
+    if mask is not None:
+        whole = contacts(*model_points(model_or_scene, None), rows, *lengths, mu, min_weight, None)
+        res.collision_weight = whole.collision_weight
+    res.feasible = res.feasible & (res.collision_weight.double() <= mc)
+    return rows, res, filter_grasps(rows, res)
+
+
+# ------------------------------------------------------------------------------------------------
+# command line: from a checkpoint and an object selection to feasible grasps
+# ------------------------------------------------------------------------------------------------
+def main(argv: Optional[Sequence[str]] = None) -> int:
+    ap = argparse.ArgumentParser(prog="python -m gaussiangrasper_amd.grasp_propose",
+                                 description="Propose parallel-jaw grasps on an object of a checkpoint's Gaussians "
+                                             "and keep those inside the friction cone at both contacts.")
+    ap.add_argument("--ckpt", required=True, help="step-*.ckpt of a splatting model")
+    ap.add_argument("--transform-json", default=None, help="JSON with transform_matrix and scale (world -> scene)")
+    ap.add_argument("--object-points", default=None, help="object point cloud (world frame): its convex hull "
+                                                          "selects the object's Gaussians")
+    ap.add_argument("--positives", default=None, help=".npy text embeddings: the query selects the Gaussians")
+    ap.add_argument("--negatives", default=None, help=".npy canonical negatives (LERF relevancy)")
+    ap.add_argument("--threshold", type=float, default=None, help="relevancy threshold for --positives")
+    ap.add_argument("--max-seeds", type=int, default=MAX_SEEDS, help="seed points at most")
+    ap.add_argument("--num-approach", type=int, default=NUM_APPROACH, help="approach directions per seed")
+    ap.add_argument("--up", type=float, nargs=3, default=list(UP), metavar=("X", "Y", "Z"),
+                    help="up direction, world frame")
+    ap.add_argument("--max-width", type=float, default=MAX_WIDTH, help="gripper opening, grasp units")
+    ap.add_argument("--mu", type=float, default=MU, help="friction coefficient")
+    ap.add_argument("--min-opacity", type=float, default=MIN_WEIGHT, help="a Gaussian takes part above it")
+    ap.add_argument("--max-collision", type=float, default=None, help="limit on the opacity inside the fingers")
+    ap.add_argument("--out", required=True, help="output .npy: feasible rows by score, world frame (scene frame "
+                                                 "without --transform-json: the two are the same then)")
+    ap.add_argument("--report", default=None, help="output .npz: every candidate (scene frame) and its outputs")
+    a = ap.parse_args(argv)
+    if bool(a.object_points) == bool(a.positives):
+        ap.error("one of --object-points and --positives is needed (they are alternatives)")
+    if a.positives and (a.threshold is None or not a.negatives):
+        ap.error("--positives needs --negatives and --threshold (LERF relevancy, query.select_gaussians)")
+    if (a.negatives or a.threshold is not None) and not a.positives:
+        ap.error("--negatives / --threshold need --positives")
+    for name in ("mu", "min_opacity"):
+        v = getattr(a, name)
+        if not (math.isfinite(v) and v >= 0.0):
+            ap.error(f"--{name.replace('_', '-')} must be finite and >= 0, got {v}")
+    if a.max_collision is not None and math.isnan(a.max_collision):
+        ap.error("--max-collision must not be NaN")
+    if a.max_seeds < 1:
+        ap.error(f"--max-seeds must be >= 1, got {a.max_seeds}")
+    try:
+        _check_params(TUBE_RADIUS, a.max_width, MIN_WIDTH, CLEARANCE, DEPTH, HEIGHT, a.min_opacity, MIN_ALIGN, a.up,
+                      a.num_approach)
+    except ValueError as exc:
+        ap.error(str(exc))
+    try:
+        matrix, scale = None, 1.0
+        if a.transform_json:
+            with open(a.transform_json) as f:
+                tj = json.load(f)
+            matrix, scale = np.asarray(tj["transform_matrix"], dtype=np.float64), float(tj["scale"])
+            if matrix.shape not in ((3, 4), (4, 4)):
+                raise ValueError(f"transform_matrix must be 3x4 or 4x4, got {matrix.shape}")
+            _check_rotation(matrix[:3, :3], "matrix rotation")
+        up = np.asarray(a.up, dtype=np.float64) if matrix is None else matrix[:3, :3] @ np.asarray(a.up)
+        from .interop import load_checkpoint
+        scene, mlp_state, _ = load_checkpoint(a.ckpt)
+        dev = torch.device("cuda")
+        scene = scene.to(dev)
+        if a.object_points:
+            from . import edit
+            pts = edit.filter_object_points(edit.object_points_to_scene(
+                edit.load_object_points(a.object_points), np.eye(4) if matrix is None else matrix, scale))
+            mask, _ = edit.select_and_move(scene.means.contiguous(), None, edit.hull_planes(pts))
+        else:
+            from . import query
+            keys = ("layers.0.weight", "layers.0.bias", "layers.2.weight", "layers.2.bias")
+            if any(k not in mlp_state for k in keys):
+                raise KeyError(f"{a.ckpt}: no fea_up weights for --positives")
+            w = tuple(mlp_state[k].to(dev) for k in keys)
+            pos = query._load_embeddings(a.positives, "positives")
+            neg = query._load_embeddings(a.negatives, "negatives")
+            mask = query.select_gaussians(scene, w, pos, neg, a.threshold)
+        rows, res, keep = grasp_object(scene, mask, scale=scale, mu=a.mu, min_weight=a.min_opacity,
+                                       max_collision=a.max_collision, max_seeds=a.max_seeds,
+                                       num_approach=a.num_approach, up=up, max_width=a.max_width)
+    except (KeyError, ValueError, OSError) as exc:
+        raise SystemExit(f"error: {exc}") from exc
+    rows_np = rows.cpu().numpy()
+    kept = rows_np[keep.cpu().numpy()]
+    np.save(a.out, grasps_from_scene(kept, None, matrix, scale))
+    if a.report:
+        np.savez(a.report, grasps_scene=rows_np,
+                 **{k: getattr(res, k).cpu().numpy() for k in ("contact_idx", "normals", "angles", "region_count",
+                                                               "region_weight", "collision_weight", "feasible")})
+    print(f"{len(kept)} of {len(rows_np)} proposed grasps feasible; wrote {a.out}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

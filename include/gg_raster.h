@@ -651,6 +651,48 @@ int gg_grasp_contacts(int num_points, const float *points, const float *normals,
                       int32_t *region_count, float *region_weight, float *collision_weight, uint8_t *feasible,
                       void *ws, size_t ws_bytes, gg_stream_t stream);
 
+/* ---- grasp proposals: antipodal candidates from the oriented points (PARITY "Grasp proposals") -------
+ * Every seed point against every oriented point, exact in fp64, with a deterministic reduction; the output rows
+ * have the GraspGroup layout and column meaning gg_grasp_contacts reads.
+ *   points, normals, weights: as for gg_grasp_contacts (normals any sign, any length); point j takes part iff p_j
+ *           and n_j are finite and (double)w_j > min_weight.
+ *   seeds:  num_seeds int32 indices into the points.  A seed is usable iff its index is in [0, num_points), its
+ *           point takes part and n.n > 0.  Seeds may repeat.
+ * Per usable seed i, p = points[i], n = normals[i], in fp64 from the fp32 inputs, no contraction, in this order:
+ *   nn = (n0 n0 + n1 n1) + n2 n2
+ *   per j taking part:  d_k = (double)p_jk - (double)p_k;  s = (n0 d0 + n1 d1) + n2 d2;  dd = (d0 d0 + d1 d1) + d2 d2;
+ *                       in the tube iff  dd nn - s s <= (r r) nn  and  s s <= (W W) nn
+ *   s_lo = min s over the tube, j_lo the smallest index reaching it; s_hi, j_hi likewise for the max; tube_count =
+ *   the number of points in the tube (the seed itself is in it with s = 0);  q = s_hi - s_lo
+ *   align(j) iff m_j > 0 and g_j g_j >= (min_align min_align)(nn m_j),
+ *                g_j = (n0 nj0 + n1 nj1) + n2 nj2,  m_j = (nj0 nj0 + nj1 nj1) + nj2 nj2
+ *   valid iff  q q >= (w0 w0) nn  and  q q <= ((W - 2c)(W - 2c)) nn  and  align(j_lo)  and  align(j_hi)
+ * (r tube_radius, W max_width, w0 min_width, c clearance).  No square root or division decides anything: indices,
+ * counts and valid are exact.  The farthest points along the line are the contacts, not the first hit (a trained
+ * object is full of interior Gaussians); the sign of n does not matter.  For a valid seed, K = num_approach rows:
+ *   b = n / sqrt(nn);  m = p + b ((s_lo + s_hi) / (2 sqrt(nn)));  span = q / sqrt(nn);  width = span + 2c
+ *   v = -up;  e = v - b (b . v);  if e.e < 1e-12 (v.v): v = the coordinate axis k with the smallest |b_k| (smallest k
+ *   on a tie), e recomputed;  a_0 = e / |e|;  c_0 = a_0 x b
+ *   phi_k = 2 pi k / K;  a_k = cos(phi_k) a_0 + sin(phi_k) c_0;  c_k = a_k x b;  R_k = columns (a_k, b, c_k)
+ *   t_k = m - (depth / 2) a_k;  score = |g_lo| |g_hi| / (nn sqrt(m_lo m_hi))
+ *   row = [score, width, height, depth, R_k row-major (9), t_k (3), 0]
+ * Outputs, every seed written: pair_idx int32 [S][2] (j_lo, j_hi; -1, -1 for a seed that is not usable);
+ * tube_count int32 [S] (0 when not usable); span fp32 [S] (NaN when not usable); valid uint8 [S]; rows fp32
+ * [S][K][17] (all NaN for a seed that is not valid).
+ * tube_radius, min_width, clearance, depth finite and >= 0; max_width, height finite and > 0; 2 clearance <=
+ * max_width; min_weight not NaN; min_align in [0, 1]; up: HOST array of 3 doubles, finite, not zero; num_approach in
+ * 1..GG_PROPOSE_MAX_APPROACH.  num_seeds == 0 does nothing; num_points == 0 makes every seed not usable.  No atomics:
+ * per-chunk extremes combined in a fixed order; the result does not depend on the launch geometry and is identical run
+ * to run.  `ws`: gg_grasp_propose_workspace() bytes, 256-byte aligned (0 is returned for counts out of range). */
+#define GG_PROPOSE_MAX_SEEDS (1 << 20)
+#define GG_PROPOSE_MAX_APPROACH 64
+size_t gg_grasp_propose_workspace(int num_points, int num_seeds);
+int gg_grasp_propose(int num_points, const float *points, const float *normals, const float *weights, int num_seeds,
+                     const int32_t *seeds, double tube_radius, double max_width, double min_width, double clearance,
+                     double depth, double height, double min_weight, double min_align, const double *up,
+                     int num_approach, int32_t *pair_idx, int32_t *tube_count, float *span, uint8_t *valid,
+                     float *rows, void *ws, size_t ws_bytes, gg_stream_t stream);
+
 /* ---- scene preparation from RGB-D frames (PARITY "Scene preparation") --------------------------------
  * gg_backproject: depth frames to a base-frame point cloud (generate_data.py depth_image_to_point_cloud +
  * merge_point_clouds).  Frames are F x H x W, frame-major then row-major:
@@ -808,7 +850,8 @@ int gg_tsdf_mesh_emit(const int32_t *dims, const float *grid, const float *tsdf,
 #define GG_K_POSE_FINISH 42   /* the one-workgroup sum of the pose slab behind either */
 #define GG_K_TSDF_INTEGRATE 43 /* gg_tsdf_integrate */
 #define GG_K_TSDF_MESH 44     /* gg_tsdf_mesh_count and gg_tsdf_mesh_emit: all their launches */
-#define GG_K_IDS 45           /* ids are below this */
+#define GG_K_GRASP_PROPOSE 45 /* gg_grasp_propose: search, per-seed reduction and rows */
+#define GG_K_IDS 46           /* ids are below this */
 #define GG_PROF_NUM_KERNELS 32
 int gg_prof_enable(int on);
 int gg_prof_reset(void);
