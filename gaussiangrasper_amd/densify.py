@@ -23,7 +23,7 @@ from torch import Tensor
 from torch.nn import Parameter
 
 from . import _lib
-from .ops import _ptr, _require_hip, _stream, _workspace
+from ._call import ptr as _ptr, require_hip as _require_hip, stream as _stream, workspace as _workspace
 
 # group name -> attribute, as GaussianSplattingModel.get_gaussian_param_groups (:562-571)
 GROUPS = {"xyz": "means", "color": "colors_all", "opacity": "opacities", "scaling": "scales",

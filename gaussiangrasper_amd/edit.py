@@ -16,21 +16,19 @@ have the planes pass them directly."""
 from __future__ import annotations
 
 import argparse
-import ctypes
 import json
 import os
 import sys
-from typing import Optional, Sequence, Tuple, Union
+from typing import Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 from torch import Tensor
 
 from . import _lib
+from ._call import ArrayLike, host_ptr, ptr as _ptr, require_hip as _require_hip, stream as _stream
+from .frames import load_transform_json, points_to_scene as object_points_to_scene, rigid_rows
 from .interop import MODEL_PREFIX
-from .ops import _ptr, _require_hip, _stream
-
-ArrayLike = Union[np.ndarray, Tensor, Sequence]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -90,26 +88,9 @@ def compose_transform(matrix: ArrayLike, scale: float, pose_from: ArrayLike, pos
     return T[:3, :].astype(np.float32)
 
 
-def object_points_to_scene(points: ArrayLike, matrix: ArrayLike, scale: float) -> np.ndarray:
-    """Object points into the scene's frame (update.py:148-149): [x, 1] @ matrix[:3, :].T, times scale."""
-    p = np.asarray(points, dtype=np.float64)[:, :3]
-    M = np.asarray(matrix, dtype=np.float64)
-    return (np.concatenate((p, np.ones((p.shape[0], 1))), axis=1) @ M[:3, :].T) * float(scale)
-
-
 # ------------------------------------------------------------------------------------------------
 # device side: one launch of gg_hull_edit
 # ------------------------------------------------------------------------------------------------
-def _rigid_host(transform: Optional[ArrayLike]):
-    if transform is None:
-        return None
-    t = transform.detach().cpu().numpy() if isinstance(transform, Tensor) else np.asarray(transform)
-    if t.shape not in ((3, 4), (4, 4)):
-        raise ValueError(f"transform must be [R | t] (3, 4) or homogeneous (4, 4), got {t.shape}")
-    rt = np.ascontiguousarray(t[:3, :], dtype=np.float32).reshape(12)
-    return rt
-
-
 def select_and_move(means: Tensor, quats: Optional[Tensor], planes: ArrayLike,
                     transform: Optional[ArrayLike] = None, tol: float = 0.0) -> Tuple[Tensor, Tensor]:
     """Select the Gaussians whose mean is inside the hull (every plane n.x + d <= tol) and, with a transform, move
@@ -129,7 +110,7 @@ def select_and_move(means: Tensor, quats: Optional[Tensor], planes: ArrayLike,
     n = means.shape[0]
     if quats is not None and quats.shape[0] != n:
         raise ValueError(f"means has {n} rows, quats {quats.shape[0]}")
-    rt = _rigid_host(transform)
+    rt = None if transform is None else rigid_rows(transform, np.float32)
     if rt is not None and quats is None:
         raise ValueError("a transform moves means and quats: pass quats")
     pl = torch.as_tensor(planes.detach() if isinstance(planes, Tensor) else np.asarray(planes))
@@ -138,8 +119,7 @@ def select_and_move(means: Tensor, quats: Optional[Tensor], planes: ArrayLike,
         raise ValueError(f"planes must be (F >= 4, 4) half-spaces (n0, n1, n2, d), got {tuple(pl.shape)}")
     mask = torch.empty(n, dtype=torch.uint8, device=dev)
     count = torch.empty((), dtype=torch.int64, device=dev)
-    rt_ptr = None if rt is None else rt.ctypes.data_as(ctypes.c_void_p)
-    _lib.check(_lib.load().gg_hull_edit(n, _ptr(means), _ptr(quats), pl.shape[0], _ptr(pl), float(tol), rt_ptr,
+    _lib.check(_lib.load().gg_hull_edit(n, _ptr(means), _ptr(quats), pl.shape[0], _ptr(pl), float(tol), host_ptr(rt),
                                         _ptr(mask), _ptr(count), _stream(dev)), "gg_hull_edit")
     return mask, count
 
@@ -223,8 +203,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     with open(a.transform_json) as f:
         tj = json.load(f)
     try:
-        n = edit_checkpoint(a.ckpt, load_object_points(a.object_points), tj["transform_matrix"], float(tj["scale"]),
-                            a.pose_from, a.pose_to, a.out, a.tol, a.outlier_factor)
+        n = edit_checkpoint(a.ckpt, load_object_points(a.object_points), *load_transform_json(tj), a.pose_from,
+                            a.pose_to, a.out, a.tol, a.outlier_factor)
     except (KeyError, ValueError) as exc:
         raise SystemExit(f"error: {exc}") from exc
     print(f"selected {n} Gaussians; wrote {a.out}")

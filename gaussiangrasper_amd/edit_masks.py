@@ -18,23 +18,21 @@ error."""
 from __future__ import annotations
 
 import argparse
-import ctypes
 import json
 import os
 import sys
 from dataclasses import dataclass
-from typing import List, Optional, Sequence, Tuple, Union
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 from torch import Tensor
 
 from . import _lib
+from ._call import ArrayLike, default_device, host_ptr, ptr as _ptr, stream as _stream, to_device, workspace as _ws
 from .edit import load_object_points, pose_to_matrix
-from .ops import _ptr, _stream, _workspace as _ws
+from .frames import rigid_rows
 from .prepare import camera_params
-
-ArrayLike = Union[np.ndarray, Tensor, Sequence]
 
 MAX_ROWS = 16384                 # default row-table capacity per (view, pose)
 MASK_NAMES = ("before", "after", "union")
@@ -53,34 +51,20 @@ class ObjectMasks:
     dropped: Tensor
 
 
-def _device() -> torch.device:
-    if not torch.cuda.is_available():
-        raise RuntimeError("gaussiangrasper_amd.edit_masks runs on a HIP device (PyTorch-ROCm 'cuda'); none is "
-                           "available. There is no CPU fallback.")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _on_device(x: ArrayLike, dev: torch.device) -> Tensor:
-    t = x.detach() if isinstance(x, Tensor) else torch.as_tensor(np.asarray(x, dtype=np.float64))
-    return t.to(device=dev, dtype=torch.float64).contiguous()
-
-
 def object_masks(points: ArrayLike, transform: ArrayLike, intrinsics: ArrayLike, w2c: ArrayLike, height: int,
                  width: int, dilate: int = 0, max_rows: int = MAX_ROWS) -> ObjectMasks:
     """Masks of the object's points P (M, 3) before and after the motion T ([R | t] (3, 4) or (4, 4)) in V views:
     intrinsics (V, 4) fx, fy, cx, cy and w2c (V, 3, 4) or (V, 4, 4) world-to-camera (OpenCV axes), all fp64.  One
     launch sequence and one status read-back; raises _lib.GGError when a view's projection spans more than max_rows
     pixel rows (nothing is returned then)."""
-    dev = points.device if isinstance(points, Tensor) and points.device.type == "cuda" else _device()
-    P = _on_device(points, dev)
+    dev = points.device if isinstance(points, Tensor) and points.device.type == "cuda" else \
+        default_device("edit_masks")
+    P = to_device(points, torch.float64, dev)
     if P.ndim != 2 or P.shape[1] != 3:
         raise ValueError(f"points must be (M, 3), got {tuple(P.shape)}")
-    T = transform.detach().cpu().numpy() if isinstance(transform, Tensor) else np.asarray(transform, np.float64)
-    if T.shape not in ((3, 4), (4, 4)):
-        raise ValueError(f"transform must be [R | t] (3, 4) or homogeneous (4, 4), got {T.shape}")
-    T = np.ascontiguousarray(T[:3, :], dtype=np.float64).reshape(12)
-    K = _on_device(intrinsics, dev)
-    E = _on_device(w2c, dev)
+    T = rigid_rows(transform, np.float64)
+    K = to_device(intrinsics, torch.float64, dev)
+    E = to_device(w2c, torch.float64, dev)
     if K.ndim != 2 or K.shape[1] != 4:
         raise ValueError(f"intrinsics must be (V, 4) fx, fy, cx, cy, got {tuple(K.shape)}")
     if E.ndim != 3 or E.shape[0] != K.shape[0] or E.shape[1:] not in ((3, 4), (4, 4)):
@@ -100,7 +84,7 @@ def object_masks(points: ArrayLike, transform: ArrayLike, intrinsics: ArrayLike,
     boxes = torch.empty((V, 3, 4), dtype=torch.int32, device=dev)
     centres = torch.empty((V, 3, 2), dtype=torch.float64, device=dev)
     dropped = torch.empty((V, 2), dtype=torch.int32, device=dev)
-    _lib.check(lib.gg_object_masks(P.shape[0], _ptr(P), T.ctypes.data_as(ctypes.c_void_p), V, _ptr(K), _ptr(E), h, w,
+    _lib.check(lib.gg_object_masks(P.shape[0], _ptr(P), host_ptr(T), V, _ptr(K), _ptr(E), h, w,
                                    int(dilate), int(max_rows), _ptr(m[0]), _ptr(m[1]), _ptr(m[2]), _ptr(boxes),
                                    _ptr(centres), _ptr(dropped), _ptr(ws), ws.numel(), _stream(dev)),
                "gg_object_masks")

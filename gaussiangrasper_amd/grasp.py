@@ -5,6 +5,7 @@ every candidate against every oriented point in fp64; the contract is in include
 
     load_grasps        (M, 17) GraspGroup rows [score, width, height, depth, R (9), t (3), object_id]
     grasps_to_scene    grasp frame -> world (camera pose) -> scene (the edit's transform_matrix and scale)
+    grasps_from_scene  its inverse
     model_points       means, smallest-axis normals and sigmoid(opacity) [x mask] of a model or scene
     contacts           the per-grasp outputs of gg_grasp_contacts (GraspContacts)
     filter_grasps      indices of the feasible grasps, by score, descending, stable
@@ -15,8 +16,6 @@ Grasp candidates come from outside the project (AnyGrasp): this module only scor
 from __future__ import annotations
 
 import argparse
-import ctypes
-import json
 import math
 import sys
 from dataclasses import dataclass
@@ -27,9 +26,10 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from .ops import _ptr, _require_hip, _stream
-
-ArrayLike = Union[np.ndarray, Tensor, Sequence]
+from ._call import (ArrayLike, f32_rows, nonneg, ptr as _ptr, require_hip as _require_hip, stream as _stream,
+                    workspace as _ws)
+from ._cli import REPORT_KEYS, add_object_options, check_object_options, object_mask
+from .frames import ORTHO_TOL, load_transform_json, rigid_to_scene  # noqa: F401
 
 GRASP_COLS = 17
 # UNVERIFIED defaults (PARITY.md "Grasp filtering"), in grasp units (metres): graspnetAPI's gripper drawing for
@@ -39,7 +39,6 @@ FINGER_WIDTH = 0.004
 BAND = 0.003
 MU = 0.5
 MIN_WEIGHT = 0.0
-ORTHO_TOL = 1e-4
 
 
 @dataclass
@@ -65,17 +64,20 @@ def load_grasps(path: str) -> np.ndarray:
     return np.ascontiguousarray(g, dtype=np.float32)
 
 
-def _check_grasp_array(grasps: ArrayLike) -> np.ndarray:
+def check_grasp_array(grasps: ArrayLike) -> np.ndarray:
+    """`grasps` as a host array, after checking that it is (M, 17)."""
     g = grasps.detach().cpu().numpy() if isinstance(grasps, Tensor) else np.asarray(grasps)
     if g.ndim != 2 or g.shape[1] != GRASP_COLS:
         raise ValueError(f"grasps must be (M, {GRASP_COLS}) GraspGroup rows, got {g.shape}")
     return g
 
 
-def _check_rotation(R: np.ndarray, what: str) -> None:
-    err = np.abs(np.swapaxes(R, -1, -2) @ R - np.eye(3)).max(initial=0.0)
-    if not err <= ORTHO_TOL:
-        raise ValueError(f"{what} is not orthonormal (max |R^T R - I| = {err:.3g} > {ORTHO_TOL:g})")
+def _map_grasps(grasps: ArrayLike, cam_to_world, matrix, scale: float, inverse: bool) -> np.ndarray:
+    g = check_grasp_array(grasps).astype(np.float64)
+    R, t, scale = rigid_to_scene(g[:, 4:13].reshape(-1, 3, 3), g[:, 13:16], cam_to_world, matrix, scale, inverse)
+    g[:, 4:13], g[:, 13:16] = R.reshape(-1, 9), t
+    g[:, 1:4] = g[:, 1:4] / scale if inverse else g[:, 1:4] * scale
+    return g.astype(np.float32)
 
 
 def grasps_to_scene(grasps: ArrayLike, cam_to_world: Optional[ArrayLike] = None, matrix: Optional[ArrayLike] = None,
@@ -85,28 +87,16 @@ def grasps_to_scene(grasps: ArrayLike, cam_to_world: Optional[ArrayLike] = None,
     edit.object_points_to_scene).  cam_to_world: 4x4 grasp frame -> world (None: identity); matrix: the scene's
     transform_matrix (3x4 or 4x4, None: identity).  Rows whose R is finite must be orthonormal within 1e-4, as must
     C3 and M3; rows with a non-finite entry pass through (they are not valid grasps).  Returns (M, 17) float32."""
-    g = _check_grasp_array(grasps).astype(np.float64)
-    C = np.eye(4) if cam_to_world is None else np.asarray(cam_to_world, dtype=np.float64)
-    Mx = np.eye(4) if matrix is None else np.asarray(matrix, dtype=np.float64)
-    if C.shape != (4, 4):
-        raise ValueError(f"cam_to_world must be 4x4, got {C.shape}")
-    if Mx.shape not in ((3, 4), (4, 4)):
-        raise ValueError(f"matrix must be 3x4 or 4x4, got {Mx.shape}")
-    scale = float(scale)
-    if not (math.isfinite(scale) and scale > 0.0):
-        raise ValueError(f"scale must be finite and > 0, got {scale}")
-    _check_rotation(C[:3, :3], "cam_to_world rotation")
-    _check_rotation(Mx[:3, :3], "matrix rotation")
-    R = g[:, 4:13].reshape(-1, 3, 3)
-    fin = np.isfinite(R).all(axis=(1, 2))
-    _check_rotation(R[fin], "grasp rotation")
-    A = Mx[:3, :3] @ C[:3, :3]
-    out = g.copy()
-    out[:, 4:13] = (A @ R).reshape(-1, 9)
-    t = g[:, 13:16]
-    out[:, 13:16] = scale * ((t @ C[:3, :3].T + C[:3, 3]) @ Mx[:3, :3].T + Mx[:3, 3])
-    out[:, 1:4] *= scale
-    return out.astype(np.float32)
+    return _map_grasps(grasps, cam_to_world, matrix, scale, False)
+
+
+def grasps_from_scene(grasps: ArrayLike, cam_to_world: Optional[ArrayLike] = None,
+                      matrix: Optional[ArrayLike] = None, scale: float = 1.0) -> np.ndarray:
+    """The inverse of grasps_to_scene: scene-frame rows back to the grasp (camera) frame, or to the world frame
+    with cam_to_world None.  R = (M3 C3)^T R', t = C3^T (M3^T (t' / scale - M_t) - C_t), width, height and depth
+    divided by scale.  The same checks: C3, M3 and every finite R orthonormal within 1e-4.  Returns (M, 17)
+    float32."""
+    return _map_grasps(grasps, cam_to_world, matrix, scale, True)
 
 
 def filter_grasps(grasps: ArrayLike, feasible: Union[GraspContacts, ArrayLike]) -> Tensor:
@@ -114,7 +104,7 @@ def filter_grasps(grasps: ArrayLike, feasible: Union[GraspContacts, ArrayLike]) 
     order.  On the device of `feasible`."""
     f = feasible.feasible if isinstance(feasible, GraspContacts) else torch.as_tensor(feasible)
     f = f.reshape(-1).to(torch.bool)
-    g = torch.as_tensor(_check_grasp_array(grasps) if not isinstance(grasps, Tensor) else grasps)
+    g = torch.as_tensor(check_grasp_array(grasps) if not isinstance(grasps, Tensor) else grasps)
     if g.ndim != 2 or g.shape[1] != GRASP_COLS or g.shape[0] != f.shape[0]:
         raise ValueError(f"grasps {tuple(g.shape)} and feasible {tuple(f.shape)} do not match")
     idx = torch.nonzero(f).reshape(-1)
@@ -126,21 +116,6 @@ def filter_grasps(grasps: ArrayLike, feasible: Union[GraspContacts, ArrayLike]) 
 # ------------------------------------------------------------------------------------------------
 # device side: one gg_grasp_contacts call
 # ------------------------------------------------------------------------------------------------
-def _f32_rows(t: Tensor, name: str, width: Optional[int]) -> Tensor:
-    shape_ok = t.ndim == 2 and t.shape[1] == width if width else t.ndim == 1
-    if t.dtype != torch.float32 or not shape_ok:
-        want = f"(N, {width})" if width else "(N,)"
-        raise ValueError(f"{name} must be a float32 {want} tensor, got {t.dtype} {tuple(t.shape)}")
-    return t.contiguous()
-
-
-def _param(name: str, v: float) -> float:
-    v = float(v)
-    if not (math.isfinite(v) and v >= 0.0):
-        raise ValueError(f"{name} must be finite and >= 0, got {v}")
-    return v
-
-
 def contacts(points: Tensor, normals: Tensor, weights: Tensor, grasps: Tensor, depth_base: float = DEPTH_BASE,
              finger_width: float = FINGER_WIDTH, band: float = BAND, mu: float = MU, min_weight: float = MIN_WEIGHT,
              max_collision: Optional[float] = None) -> GraspContacts:
@@ -149,18 +124,18 @@ def contacts(points: Tensor, normals: Tensor, weights: Tensor, grasps: Tensor, d
     float32 on the HIP device (no CPU path).  Lengths (depth_base, finger_width, band) are in the grasps' units.
     max_collision None: no collision limit.  One call; nothing waits on the host."""
     dev = _require_hip(points, normals, weights, grasps)
-    points = _f32_rows(points, "points", 3)
-    normals = _f32_rows(normals, "normals", 3)
-    weights = _f32_rows(weights, "weights", None)
-    grasps = _f32_rows(grasps, "grasps", GRASP_COLS)
+    points = f32_rows(points, "points", 3)
+    normals = f32_rows(normals, "normals", 3)
+    weights = f32_rows(weights, "weights", None)
+    grasps = f32_rows(grasps, "grasps", GRASP_COLS)
     n, m = points.shape[0], grasps.shape[0]
     if normals.shape[0] != n or weights.shape[0] != n:
         raise ValueError(f"points has {n} rows, normals {normals.shape[0]}, weights {weights.shape[0]}")
     mc = math.inf if max_collision is None else float(max_collision)
     if math.isnan(mc) or math.isnan(float(min_weight)):
         raise ValueError("min_weight and max_collision must not be NaN")
-    args = (_param("depth_base", depth_base), _param("finger_width", finger_width), _param("band", band),
-            _param("mu", mu), float(min_weight), mc)
+    args = (nonneg("depth_base", depth_base), nonneg("finger_width", finger_width), nonneg("band", band),
+            nonneg("mu", mu), float(min_weight), mc)
     lib = _lib.load()
     res = GraspContacts(
         contact_idx=torch.empty(m, 2, dtype=torch.int32, device=dev),
@@ -173,11 +148,11 @@ def contacts(points: Tensor, normals: Tensor, weights: Tensor, grasps: Tensor, d
     nbytes = lib.gg_grasp_contacts_workspace(n, m)
     if m > 0 and nbytes == 0:
         raise ValueError(f"{n} points x {m} grasps is beyond gg_grasp_contacts' limits")
-    ws = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
+    ws = _ws(nbytes, dev)
     _lib.check(lib.gg_grasp_contacts(n, _ptr(points), _ptr(normals), _ptr(weights), m, _ptr(grasps), *args,
                                      _ptr(res.contact_idx), _ptr(res.normals), _ptr(res.angles),
                                      _ptr(res.region_count), _ptr(res.region_weight), _ptr(res.collision_weight),
-                                     _ptr(res.feasible), _ptr(ws), ctypes.c_size_t(ws.numel()), _stream(dev)),
+                                     _ptr(res.feasible), _ptr(ws), ws.numel(), _stream(dev)),
                "gg_grasp_contacts")
     res.feasible = res.feasible.bool()
     return res
@@ -213,8 +188,8 @@ def score_grasps(model_or_scene, grasps: ArrayLike, mask: Optional[Tensor] = Non
     pts, nrm, w = model_points(model_or_scene, mask)
     g = grasps_to_scene(grasps, cam_to_world, matrix, scale)
     s = float(scale)
-    return contacts(pts, nrm, w, torch.from_numpy(g).to(pts.device), _param("depth_base", depth_base) * s,
-                    _param("finger_width", finger_width) * s, _param("band", band) * s, mu, min_weight,
+    return contacts(pts, nrm, w, torch.from_numpy(g).to(pts.device), nonneg("depth_base", depth_base) * s,
+                    nonneg("finger_width", finger_width) * s, nonneg("band", band) * s, mu, min_weight,
                     max_collision)
 
 
@@ -236,11 +211,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--grasps", required=True, help=".npy (M, 17) GraspGroup rows, grasp frame")
     ap.add_argument("--camera-pose", default=None, help=".npy 4x4, grasp frame -> world")
     ap.add_argument("--transform-json", default=None, help="JSON with transform_matrix and scale (world -> scene)")
-    ap.add_argument("--object-points", default=None, help="object point cloud (world frame): its convex hull "
-                                                          "restricts the Gaussians")
-    ap.add_argument("--positives", default=None, help=".npy text embeddings: the query restricts the Gaussians")
-    ap.add_argument("--negatives", default=None, help=".npy canonical negatives (LERF relevancy)")
-    ap.add_argument("--threshold", type=float, default=None, help="relevancy threshold for --positives")
+    add_object_options(ap, "the query restricts the Gaussians", "restricts the Gaussians")
     ap.add_argument("--mu", type=float, default=MU, help="friction coefficient")
     ap.add_argument("--band", type=float, default=BAND, help="contact patch depth, grasp units")
     ap.add_argument("--min-opacity", type=float, default=MIN_WEIGHT, help="a Gaussian takes part above it")
@@ -248,12 +219,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--out", required=True, help="output .npy: feasible rows, input frame, by score")
     ap.add_argument("--report", default=None, help="output .npz: every per-grasp output, scene frame")
     a = ap.parse_args(argv)
-    if a.object_points and a.positives:
-        ap.error("--object-points and --positives are alternatives")
-    if a.positives and (a.threshold is None or not a.negatives):
-        ap.error("--positives needs --negatives and --threshold (LERF relevancy, query.select_gaussians)")
-    if (a.negatives or a.threshold is not None) and not a.positives:
-        ap.error("--negatives / --threshold need --positives")
+    check_object_options(ap, a, "optional")
     for name in ("mu", "band", "min_opacity"):
         v = getattr(a, name)
         if not (math.isfinite(v) and v >= 0.0):
@@ -263,30 +229,11 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     try:
         grasps = load_grasps(a.grasps)
         cam = _load_matrix(a.camera_pose, (4, 4), "camera pose") if a.camera_pose else None
-        matrix, scale = None, 1.0
-        if a.transform_json:
-            with open(a.transform_json) as f:
-                tj = json.load(f)
-            matrix, scale = np.asarray(tj["transform_matrix"], dtype=np.float64), float(tj["scale"])
+        matrix, scale = load_transform_json(a.transform_json) if a.transform_json else (None, 1.0)
         from .interop import load_checkpoint
         scene, mlp_state, _ = load_checkpoint(a.ckpt)
-        dev = torch.device("cuda")
-        scene = scene.to(dev)
-        mask = None
-        if a.object_points:
-            from . import edit
-            pts = edit.filter_object_points(edit.object_points_to_scene(
-                edit.load_object_points(a.object_points), np.eye(4) if matrix is None else matrix, scale))
-            mask, _ = edit.select_and_move(scene.means.contiguous(), None, edit.hull_planes(pts))
-        elif a.positives:
-            from . import query
-            keys = ("layers.0.weight", "layers.0.bias", "layers.2.weight", "layers.2.bias")
-            if any(k not in mlp_state for k in keys):
-                raise KeyError(f"{a.ckpt}: no fea_up weights for --positives")
-            w = tuple(mlp_state[k].to(dev) for k in keys)
-            pos = query._load_embeddings(a.positives, "positives")
-            neg = query._load_embeddings(a.negatives, "negatives")
-            mask = query.select_gaussians(scene, w, pos, neg, a.threshold)
+        scene = scene.to(torch.device("cuda"))
+        mask = object_mask(a, scene, mlp_state, matrix, scale)
         res = score_grasps(scene, grasps, mask, cam, matrix, scale, band=a.band, mu=a.mu, min_weight=a.min_opacity,
                            max_collision=a.max_collision)
     except (KeyError, ValueError, OSError) as exc:
@@ -295,8 +242,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     np.save(a.out, grasps[keep])
     if a.report:
         np.savez(a.report, grasps_scene=grasps_to_scene(grasps, cam, matrix, scale),
-                 **{k: getattr(res, k).cpu().numpy() for k in ("contact_idx", "normals", "angles", "region_count",
-                                                               "region_weight", "collision_weight", "feasible")})
+                 **{k: getattr(res, k).cpu().numpy() for k in REPORT_KEYS})
     print(f"{len(keep)} of {len(grasps)} grasps feasible; wrote {a.out}")
     return 0
 

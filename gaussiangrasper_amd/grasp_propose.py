@@ -8,14 +8,13 @@ sampler of this project's own, not a restatement of AnyGrasp: its candidates are
     choose_seeds       the points that take part, thinned to at most max_seeds
     propose_grasps     (M, 17) scene-frame rows of a model's object (model_points, choose_seeds, antipodal, compact)
     grasp_object       proposals, then grasp.contacts and grasp.filter_grasps: (rows, GraspContacts, keep)
-    grasps_from_scene  scene frame -> world -> grasp frame, the inverse of grasp.grasps_to_scene
+    grasps_from_scene  scene frame -> world -> grasp frame (grasp.grasps_from_scene, handed on)
     python -m gaussiangrasper_amd.grasp_propose --ckpt IN (--object-points obj.npy | --positives ...) --out grasps.npy
 """
 from __future__ import annotations
 
 import argparse
 import ctypes
-import json
 import math
 import sys
 from dataclasses import dataclass
@@ -26,9 +25,12 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from .grasp import (BAND, DEPTH_BASE, FINGER_WIDTH, GRASP_COLS, MIN_WEIGHT, MU, ArrayLike, GraspContacts,
-                    _check_grasp_array, _check_rotation, _f32_rows, _param, contacts, filter_grasps, model_points)
-from .ops import _ptr, _require_hip, _stream, _workspace as _ws
+from ._call import (f32_rows, host_ptr, nonneg, positive, ptr as _ptr, require_hip as _require_hip,
+                    stream as _stream, workspace as _ws)
+from ._cli import REPORT_KEYS, add_object_options, check_object_options, object_mask
+from .frames import check_rotation, load_transform_json
+from .grasp import (BAND, DEPTH_BASE, FINGER_WIDTH, GRASP_COLS, MIN_WEIGHT, MU, GraspContacts, contacts, filter_grasps,
+                    grasps_from_scene, model_points)
 
 # UNVERIFIED defaults (PARITY.md "Grasp proposals"), in grasp units (metres): max_width, depth and height are
 # recalled from graspnetAPI's gripper; tube_radius, min_width, clearance, min_align and num_approach are this
@@ -61,50 +63,13 @@ class GraspProposals:
 
 
 # ------------------------------------------------------------------------------------------------
-# host side: frames (numpy, fp64)
-# ------------------------------------------------------------------------------------------------
-def grasps_from_scene(grasps: ArrayLike, cam_to_world: Optional[ArrayLike] = None,
-                      matrix: Optional[ArrayLike] = None, scale: float = 1.0) -> np.ndarray:
-    """The inverse of grasp.grasps_to_scene: scene-frame rows back to the grasp (camera) frame, or to the world frame
-    with cam_to_world None.  R = (M3 C3)^T R', t = C3^T (M3^T (t' / scale - M_t) - C_t), width, height and depth
-    divided by scale.  The same checks: C3, M3 and every finite R orthonormal within 1e-4.  Returns (M, 17)
-    float32."""
-    g = _check_grasp_array(grasps).astype(np.float64)
-    C = np.eye(4) if cam_to_world is None else np.asarray(cam_to_world, dtype=np.float64)
-    Mx = np.eye(4) if matrix is None else np.asarray(matrix, dtype=np.float64)
-    if C.shape != (4, 4):
-        raise ValueError(f"cam_to_world must be 4x4, got {C.shape}")
-    if Mx.shape not in ((3, 4), (4, 4)):
-        raise ValueError(f"matrix must be 3x4 or 4x4, got {Mx.shape}")
-    scale = float(scale)
-    if not (math.isfinite(scale) and scale > 0.0):
-        raise ValueError(f"scale must be finite and > 0, got {scale}")
-    _check_rotation(C[:3, :3], "cam_to_world rotation")
-    _check_rotation(Mx[:3, :3], "matrix rotation")
-    R = g[:, 4:13].reshape(-1, 3, 3)
-    fin = np.isfinite(R).all(axis=(1, 2))
-    _check_rotation(R[fin], "grasp rotation")
-    A = Mx[:3, :3] @ C[:3, :3]
-    out = g.copy()
-    out[:, 4:13] = (A.T @ R).reshape(-1, 9)
-    world = (g[:, 13:16] / scale - Mx[:3, 3]) @ Mx[:3, :3]          # M3^T x as a row vector: x M3
-    out[:, 13:16] = (world - C[:3, 3]) @ C[:3, :3]
-    out[:, 1:4] /= scale
-    return out.astype(np.float32)
-
-
-# ------------------------------------------------------------------------------------------------
 # device side: one gg_grasp_propose call
 # ------------------------------------------------------------------------------------------------
 def _check_params(tube_radius, max_width, min_width, clearance, depth, height, min_weight, min_align, up,
                   num_approach) -> Tuple[tuple, tuple, int]:
-    r, w0 = _param("tube_radius", tube_radius), _param("min_width", min_width)
-    c, d = _param("clearance", clearance), _param("depth", depth)
-    W, h = float(max_width), float(height)
-    if not (math.isfinite(W) and W > 0.0):
-        raise ValueError(f"max_width must be finite and > 0, got {W}")
-    if not (math.isfinite(h) and h > 0.0):
-        raise ValueError(f"height must be finite and > 0, got {h}")
+    r, w0 = nonneg("tube_radius", tube_radius), nonneg("min_width", min_width)
+    c, d = nonneg("clearance", clearance), nonneg("depth", depth)
+    W, h = positive("max_width", max_width), positive("height", height)
     if 2.0 * c > W:
         raise ValueError(f"clearance {c} on both sides exceeds max_width {W}")
     mw, ma = float(min_weight), float(min_align)
@@ -136,9 +101,9 @@ def antipodal(points: Tensor, normals: Tensor, weights: Tensor, seeds: Tensor, t
     args, u, k = _check_params(tube_radius, max_width, min_width, clearance, depth, height, min_weight, min_align,
                                up, num_approach)
     dev = _require_hip(points, normals, weights, seeds)
-    points = _f32_rows(points, "points", 3)
-    normals = _f32_rows(normals, "normals", 3)
-    weights = _f32_rows(weights, "weights", None)
+    points = f32_rows(points, "points", 3)
+    normals = f32_rows(normals, "normals", 3)
+    weights = f32_rows(weights, "weights", None)
     if seeds.dtype != torch.int32 or seeds.ndim != 1:
         raise ValueError(f"seeds must be an int32 (S,) tensor, got {seeds.dtype} {tuple(seeds.shape)}")
     seeds = seeds.contiguous()
@@ -158,9 +123,9 @@ def antipodal(points: Tensor, normals: Tensor, weights: Tensor, seeds: Tensor, t
     ws = _ws(nbytes, dev)
     up3 = (ctypes.c_double * 3)(*u)
     _lib.check(lib.gg_grasp_propose(n, _ptr(points), _ptr(normals), _ptr(weights), s, _ptr(seeds), *args,
-                                    ctypes.cast(up3, ctypes.c_void_p), k, _ptr(res.pair_idx), _ptr(res.tube_count),
+                                    host_ptr(up3), k, _ptr(res.pair_idx), _ptr(res.tube_count),
                                     _ptr(res.span), _ptr(res.valid), _ptr(res.rows), _ptr(ws),
-                                    ctypes.c_size_t(ws.numel()), _stream(dev)), "gg_grasp_propose")
+                                    ws.numel(), _stream(dev)), "gg_grasp_propose")
     res.valid = res.valid.bool()
     return res
 
@@ -197,14 +162,12 @@ def propose_grasps(model_or_scene, mask: Optional[Tensor] = None, max_seeds: int
     frame: grasp.model_points(model, mask), choose_seeds, antipodal, then the valid seeds' rows in seed order, then
     approach order.  Lengths are given in grasp units (metres) and multiplied by `scale` (the scene's units per
     metre), as score_grasps does; `up` is a direction of the scene frame."""
-    s = float(scale)
-    if not (math.isfinite(s) and s > 0.0):
-        raise ValueError(f"scale must be finite and > 0, got {s}")
+    s = positive("scale", scale)
     pts, nrm, w = model_points(model_or_scene, mask)
     seeds = choose_seeds(w, max_seeds, seed, min_weight)
-    res = antipodal(pts, nrm, w, seeds, _param("tube_radius", tube_radius) * s, float(max_width) * s,
-                    _param("min_width", min_width) * s, _param("clearance", clearance) * s,
-                    _param("depth", depth) * s, float(height) * s, min_weight, min_align, up, num_approach)
+    res = antipodal(pts, nrm, w, seeds, nonneg("tube_radius", tube_radius) * s, float(max_width) * s,
+                    nonneg("min_width", min_width) * s, nonneg("clearance", clearance) * s,
+                    nonneg("depth", depth) * s, float(height) * s, min_weight, min_align, up, num_approach)
     return res.compact()
 
 
@@ -223,8 +186,8 @@ def grasp_object(model_or_scene, mask: Optional[Tensor] = None, scale: float = 1
     the feasible rows by score."""
     rows = propose_grasps(model_or_scene, mask, scale=scale, min_weight=min_weight, **propose)
     s = float(scale)
-    lengths = (_param("depth_base", depth_base) * s, _param("finger_width", finger_width) * s,
-               _param("band", band) * s)
+    lengths = (nonneg("depth_base", depth_base) * s, nonneg("finger_width", finger_width) * s,
+               nonneg("band", band) * s)
     mc = math.inf if max_collision is None else float(max_collision)
     if math.isnan(mc):
         raise ValueError("max_collision must not be NaN")
@@ -245,11 +208,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                                              "and keep those inside the friction cone at both contacts.")
     ap.add_argument("--ckpt", required=True, help="step-*.ckpt of a splatting model")
     ap.add_argument("--transform-json", default=None, help="JSON with transform_matrix and scale (world -> scene)")
-    ap.add_argument("--object-points", default=None, help="object point cloud (world frame): its convex hull "
-                                                          "selects the object's Gaussians")
-    ap.add_argument("--positives", default=None, help=".npy text embeddings: the query selects the Gaussians")
-    ap.add_argument("--negatives", default=None, help=".npy canonical negatives (LERF relevancy)")
-    ap.add_argument("--threshold", type=float, default=None, help="relevancy threshold for --positives")
+    add_object_options(ap, "the query selects the Gaussians", "selects the object's Gaussians")
     ap.add_argument("--max-seeds", type=int, default=MAX_SEEDS, help="seed points at most")
     ap.add_argument("--num-approach", type=int, default=NUM_APPROACH, help="approach directions per seed")
     ap.add_argument("--up", type=float, nargs=3, default=list(UP), metavar=("X", "Y", "Z"),
@@ -262,12 +221,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                                                  "without --transform-json: the two are the same then)")
     ap.add_argument("--report", default=None, help="output .npz: every candidate (scene frame) and its outputs")
     a = ap.parse_args(argv)
-    if bool(a.object_points) == bool(a.positives):
-        ap.error("one of --object-points and --positives is needed (they are alternatives)")
-    if a.positives and (a.threshold is None or not a.negatives):
-        ap.error("--positives needs --negatives and --threshold (LERF relevancy, query.select_gaussians)")
-    if (a.negatives or a.threshold is not None) and not a.positives:
-        ap.error("--negatives / --threshold need --positives")
+    check_object_options(ap, a, "required")
     for name in ("mu", "min_opacity"):
         v = getattr(a, name)
         if not (math.isfinite(v) and v >= 0.0):
@@ -284,31 +238,15 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     try:
         matrix, scale = None, 1.0
         if a.transform_json:
-            with open(a.transform_json) as f:
-                tj = json.load(f)
-            matrix, scale = np.asarray(tj["transform_matrix"], dtype=np.float64), float(tj["scale"])
+            matrix, scale = load_transform_json(a.transform_json)
             if matrix.shape not in ((3, 4), (4, 4)):
                 raise ValueError(f"transform_matrix must be 3x4 or 4x4, got {matrix.shape}")
-            _check_rotation(matrix[:3, :3], "matrix rotation")
+            check_rotation(matrix[:3, :3], "matrix rotation")
         up = np.asarray(a.up, dtype=np.float64) if matrix is None else matrix[:3, :3] @ np.asarray(a.up)
         from .interop import load_checkpoint
         scene, mlp_state, _ = load_checkpoint(a.ckpt)
-        dev = torch.device("cuda")
-        scene = scene.to(dev)
-        if a.object_points:
-            from . import edit
-            pts = edit.filter_object_points(edit.object_points_to_scene(
-                edit.load_object_points(a.object_points), np.eye(4) if matrix is None else matrix, scale))
-            mask, _ = edit.select_and_move(scene.means.contiguous(), None, edit.hull_planes(pts))
-        else:
-            from . import query
-            keys = ("layers.0.weight", "layers.0.bias", "layers.2.weight", "layers.2.bias")
-            if any(k not in mlp_state for k in keys):
-                raise KeyError(f"{a.ckpt}: no fea_up weights for --positives")
-            w = tuple(mlp_state[k].to(dev) for k in keys)
-            pos = query._load_embeddings(a.positives, "positives")
-            neg = query._load_embeddings(a.negatives, "negatives")
-            mask = query.select_gaussians(scene, w, pos, neg, a.threshold)
+        scene = scene.to(torch.device("cuda"))
+        mask = object_mask(a, scene, mlp_state, matrix, scale)
         rows, res, keep = grasp_object(scene, mask, scale=scale, mu=a.mu, min_weight=a.min_opacity,
                                        max_collision=a.max_collision, max_seeds=a.max_seeds,
                                        num_approach=a.num_approach, up=up, max_width=a.max_width)
@@ -318,9 +256,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     kept = rows_np[keep.cpu().numpy()]
     np.save(a.out, grasps_from_scene(kept, None, matrix, scale))
     if a.report:
-        np.savez(a.report, grasps_scene=rows_np,
-                 **{k: getattr(res, k).cpu().numpy() for k in ("contact_idx", "normals", "angles", "region_count",
-                                                               "region_weight", "collision_weight", "feasible")})
+        np.savez(a.report, grasps_scene=rows_np, **{k: getattr(res, k).cpu().numpy() for k in REPORT_KEYS})
     print(f"{len(kept)} of {len(rows_np)} proposed grasps feasible; wrote {a.out}")
     return 0
 

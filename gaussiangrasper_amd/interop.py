@@ -68,6 +68,15 @@ def load_checkpoint(path: Union[str, os.PathLike]) -> Tuple[Scene, Dict[str, tor
     return scene, mlp, int(blob.get("step", 0))
 
 
+def fea_up_weights(mlp_state: Dict[str, torch.Tensor], device, name: str, what: str) -> Tuple[torch.Tensor, ...]:
+    """(w1, b1, w2, b2) on `device` from the fea_up state load_checkpoint returns for checkpoint `name`, as
+    query's functions take them; KeyError `name: no fea_up weights <what>` when the checkpoint has none."""
+    keys = [k[len("fea_up."):] for k in MLP_KEYS]
+    if any(k not in mlp_state for k in keys):
+        raise KeyError(f"{name}: no fea_up weights {what}")
+    return tuple(mlp_state[k].to(device) for k in keys)
+
+
 def state_dict_from_scene(scene: Scene, mlp_state: Optional[Dict[str, torch.Tensor]] = None
                           ) -> Dict[str, torch.Tensor]:
     out = {MODEL_PREFIX + k: getattr(scene, k).detach().cpu() for k in PARAM_KEYS}

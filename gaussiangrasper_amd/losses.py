@@ -18,7 +18,7 @@ from torch import Tensor
 from torch.autograd import Function
 
 from . import _lib
-from .ops import _f32, _ptr, _require_hip, _stream
+from ._call import f32 as _f32, ptr as _ptr, require_hip as _require_hip, stream as _stream
 
 
 class _CosineLoss(Function):

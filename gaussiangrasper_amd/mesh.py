@@ -18,7 +18,6 @@ No GPU work falls back to the host: a missing device is an error."""
 from __future__ import annotations
 
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -30,9 +29,10 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from .ops import _ptr, _require_hip, _stream, _workspace as _ws
-
-ArrayLike = Union[np.ndarray, Tensor, Sequence]
+from ._call import (ArrayLike, default_device, host_ptr, ptr as _ptr, require_hip as _require_hip, stream as _stream,
+                    workspace as _ws)
+from ._cli import add_object_options, check_object_options, object_mask
+from .frames import c2w_to_scene, directions_from_scene, homogeneous, load_transform_json, points_from_scene
 
 RESOLUTION = 128                 # the reference exporter's defaults
 DOWNSCALE = 2
@@ -56,29 +56,13 @@ class Mesh:
         return Mesh(f(self.vertices), f(self.faces), f(self.normals), f(self.colors))
 
 
-def _device() -> torch.device:
-    if not torch.cuda.is_available():
-        raise RuntimeError("gaussiangrasper_amd.mesh runs on a HIP device (PyTorch-ROCm 'cuda'); none is available. "
-                           "There is no CPU fallback.")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
 # ------------------------------------------------------------------------------------------------
 # frames: the one place camera axes are converted
 # ------------------------------------------------------------------------------------------------
-def _homogeneous(m: ArrayLike) -> np.ndarray:
-    a = np.asarray(m.detach().cpu().numpy() if isinstance(m, Tensor) else m, dtype=np.float64)
-    if a.shape[-2:] == (3, 4):
-        a = np.concatenate([a, np.broadcast_to([0.0, 0.0, 0.0, 1.0], a.shape[:-2] + (1, 4))], axis=-2)
-    if a.shape[-2:] != (4, 4):
-        raise ValueError(f"expected (.., 3, 4) or (.., 4, 4) camera matrices, got {a.shape}")
-    return a
-
-
 def opencv_w2c(c2w_gl: ArrayLike) -> np.ndarray:
     """(V, 3, 4) fp64 world-to-camera with OpenCV axes (x right, y down, z forward) of nerfstudio / OpenGL
     camera-to-world matrices (V, 3|4, 4) or one (3|4, 4): inv(c2w diag(1, -1, -1, 1))."""
-    a = _homogeneous(c2w_gl)
+    a = homogeneous(c2w_gl)
     one = a.ndim == 2
     a = a[None] if one else a
     w2c = np.linalg.inv(a @ GL_TO_CV)[:, :3, :]
@@ -87,44 +71,13 @@ def opencv_w2c(c2w_gl: ArrayLike) -> np.ndarray:
 
 def opencv_to_opengl_c2w(c2w_cv: ArrayLike) -> np.ndarray:
     """OpenCV camera-to-world (.., 3|4, 4) -> nerfstudio / OpenGL camera-to-world (.., 4, 4) (flip y and z)."""
-    return _homogeneous(c2w_cv) @ GL_TO_CV
+    return homogeneous(c2w_cv) @ GL_TO_CV
 
 
 def dataparser_transform(path_or_dict) -> Tuple[np.ndarray, float]:
     """(transform_matrix (4, 4) fp64, scale) of a nerfstudio dataparser_transforms.json (or its dict)."""
-    if isinstance(path_or_dict, dict):
-        tj = path_or_dict
-    else:
-        with open(path_or_dict) as f:
-            tj = json.load(f)
-    M = _homogeneous(np.asarray(tj["transform_matrix"], dtype=np.float64))
-    return M, float(tj["scale"])
-
-
-def c2w_to_scene(c2w: ArrayLike, matrix: ArrayLike, scale: float) -> np.ndarray:
-    """Camera-to-world poses (.., 3|4, 4) of the scan's raw frame in the checkpoint's frame: the same map that
-    edit.object_points_to_scene applies to points (x -> scale (M [x, 1])), applied to the camera centre, and M's
-    rotation applied to the camera axes.  Either axis convention (the map acts on the left)."""
-    a = _homogeneous(c2w)
-    M = _homogeneous(matrix)
-    out = np.array(a, dtype=np.float64)
-    out[..., :3, :3] = M[:3, :3] @ a[..., :3, :3]
-    out[..., :3, 3] = ((a[..., :3, 3] @ M[:3, :3].T) + M[:3, 3]) * float(scale)
-    return out
-
-
-def points_from_scene(points: ArrayLike, matrix: ArrayLike, scale: float) -> np.ndarray:
-    """Inverse of edit.object_points_to_scene: scene-frame points (N, 3) back to the scan's raw frame, fp64."""
-    p = np.asarray(points, dtype=np.float64)[:, :3] / float(scale)
-    M = _homogeneous(matrix)
-    return (p - M[:3, 3]) @ np.linalg.inv(M[:3, :3]).T
-
-
-def directions_from_scene(normals: ArrayLike, matrix: ArrayLike) -> np.ndarray:
-    """Unit directions (N, 3) of the scene frame in the scan's raw frame (the inverse rotation, renormalised)."""
-    n = np.asarray(normals, dtype=np.float64)[:, :3] @ np.linalg.inv(_homogeneous(matrix)[:3, :3]).T
-    ln = np.linalg.norm(n, axis=1, keepdims=True)
-    return np.where(ln > 0, n / np.where(ln > 0, ln, 1.0), 0.0)
+    M, scale = load_transform_json(path_or_dict)
+    return homogeneous(M), scale
 
 
 # ------------------------------------------------------------------------------------------------
@@ -158,21 +111,15 @@ class TSDFVolume:
         if not (np.isfinite(self.truncation) and self.truncation > 0):
             raise ValueError(f"truncation must be finite and > 0, got {truncation}")
         lib = _lib.load()
-        if lib.gg_tsdf_mesh_workspace(self._dims_ptr()) == 0:
+        if lib.gg_tsdf_mesh_workspace(host_ptr(self.dims)) == 0:
             raise ValueError(f"volume {self.dims.tolist()}: each side must be 1..4096 and the product at most 2^27 "
                              f"points (gg_raster.h GG_TSDF_MAX_*)")
-        self.device = torch.device(device) if device is not None else _device()
+        self.device = torch.device(device) if device is not None else default_device("mesh")
         shape = tuple(int(d) for d in self.dims)
         self.tsdf = torch.ones(shape, dtype=torch.float32, device=self.device)
         self.weight = torch.zeros(shape, dtype=torch.float32, device=self.device)
         self.color: Optional[Tensor] = None
         self.color_weight: Optional[Tensor] = None
-
-    def _dims_ptr(self):
-        return self.dims.ctypes.data_as(ctypes.c_void_p)
-
-    def _grid_ptr(self):
-        return self.grid.ctypes.data_as(ctypes.c_void_p)
 
     def integrate_w2c(self, depth: Tensor, intrinsics: ArrayLike, w2c: ArrayLike, rgb: Optional[Tensor] = None):
         """depth (V, H, W) or (H, W) (> 0 observed, +inf free space, 0 / NaN nothing), intrinsics (V, 4) fx, fy,
@@ -197,7 +144,7 @@ class TSDFVolume:
                 self.color = torch.zeros(tuple(int(x) for x in self.dims) + (3,), dtype=torch.float32, device=dev)
                 self.color_weight = torch.zeros_like(self.weight)
         _lib.check(_lib.load().gg_tsdf_integrate(
-            self._dims_ptr(), self._grid_ptr(), self.truncation, V, H, W, _ptr(d), _ptr(c), _ptr(K), _ptr(E),
+            host_ptr(self.dims), host_ptr(self.grid), self.truncation, V, H, W, _ptr(d), _ptr(c), _ptr(K), _ptr(E),
             _ptr(self.tsdf), _ptr(self.weight), _ptr(self.color if c is not None else None),
             _ptr(self.color_weight if c is not None else None), _stream(dev)), "gg_tsdf_integrate")
         return self
@@ -211,9 +158,9 @@ class TSDFVolume:
         """The zero level set of the observed cells (gg_tsdf_mesh_count, one read-back of the two counts,
         gg_tsdf_mesh_emit).  Colours when a frame with rgb was integrated."""
         dev, lib = self.device, _lib.load()
-        ws = _ws(lib.gg_tsdf_mesh_workspace(self._dims_ptr()), dev)
+        ws = _ws(lib.gg_tsdf_mesh_workspace(host_ptr(self.dims)), dev)
         counts = torch.empty(2, dtype=torch.int64, device=dev)
-        _lib.check(lib.gg_tsdf_mesh_count(self._dims_ptr(), _ptr(self.tsdf), _ptr(self.weight), _ptr(counts),
+        _lib.check(lib.gg_tsdf_mesh_count(host_ptr(self.dims), _ptr(self.tsdf), _ptr(self.weight), _ptr(counts),
                                           _ptr(ws), ws.numel(), _stream(dev)), "gg_tsdf_mesh_count")
         nv, nf = (int(x) for x in counts.cpu().tolist())
         if nv < 0 or nf < 0:
@@ -222,8 +169,8 @@ class TSDFVolume:
         nrms = torch.empty((nv, 3), dtype=torch.float32, device=dev)
         cols = torch.empty((nv, 3), dtype=torch.float32, device=dev) if self.color is not None else None
         faces = torch.empty((nf, 3), dtype=torch.int32, device=dev)
-        _lib.check(lib.gg_tsdf_mesh_emit(self._dims_ptr(), self._grid_ptr(), _ptr(self.tsdf), _ptr(self.color), nv,
-                                         nf, _ptr(verts), _ptr(nrms), _ptr(cols), _ptr(faces), _ptr(ws), ws.numel(),
+        _lib.check(lib.gg_tsdf_mesh_emit(host_ptr(self.dims), host_ptr(self.grid), _ptr(self.tsdf), _ptr(self.color),
+                                         nv, nf, _ptr(verts), _ptr(nrms), _ptr(cols), _ptr(faces), _ptr(ws), ws.numel(),
                                          _stream(dev)), "gg_tsdf_mesh_emit")
         return Mesh(verts, faces, nrms, cols)
 
@@ -252,7 +199,7 @@ def render_depth(model_or_scene, c2w: ArrayLike, intrinsics: ArrayLike, height: 
         means, scales, quats, opac, sh = means[mask], scales[mask], quats[mask], opac[mask], sh[mask]
     fx, fy, cx, cy = (float(x) for x in np.asarray(intrinsics, dtype=np.float64).reshape(4))
     h, w = int(height), int(width)
-    view = view_from_c2w(torch.as_tensor(_homogeneous(c2w)), fx, fy, cx, cy, h, w, dev)
+    view = view_from_c2w(torch.as_tensor(homogeneous(c2w)), fx, fy, cx, cy, h, w, dev)
     if means.shape[0] == 0:
         return (torch.full((h, w), float("inf"), device=dev), torch.zeros((h, w, 3), device=dev),
                 torch.zeros((h, w), device=dev))
@@ -307,7 +254,7 @@ def mesh_model(model_or_scene, cameras: Sequence[Tuple[ArrayLike, ArrayLike, int
             rendered = [render_depth(model_or_scene, c2w, K, hs, ws, mask, alpha_min) for c2w, K, _, _ in part]
             depth = torch.stack([r[0] for r in rendered])
             rgb = torch.stack([r[1] for r in rendered]) if color else None
-            vol.integrate(depth, np.stack([p[1] for p in part]), np.stack([_homogeneous(p[0]) for p in part]), rgb)
+            vol.integrate(depth, np.stack([p[1] for p in part]), np.stack([homogeneous(p[0]) for p in part]), rgb)
     return vol.extract()
 
 
@@ -315,20 +262,13 @@ def scan_frames(scan_dir: str, depth_units_per_metre: float = 1.0):
     """Frames of a scan directory as prepare reads them: yields (depth (H, W) fp32 metres, rgb (H, W, 3) fp32 in
     [0, 1], intrinsics (4,), c2w OpenCV (4, 4) in the scan's raw frame).  Pixels outside the boundary mask and sensor
     zeros are 0 (no observation)."""
-    from .prepare import ScanError, _frame_files, _read_frame, camera_params
-    tpath = os.path.join(scan_dir, "transforms.json")
-    if not os.path.exists(tpath):
-        raise ScanError(f"missing file: {tpath}")
-    with open(tpath) as f:
-        meta = json.load(f)
-    frames = meta.get("frames") or []
-    if not frames:
-        raise ScanError(f"{tpath} lists no frames")
+    from .prepare import camera_params, frame_files, read_frame, read_transforms
+    _, meta, frames = read_transforms(scan_dir)
     for fr in frames:
-        d, m, rgb = _read_frame(_frame_files(scan_dir, fr), float(depth_units_per_metre))
+        d, m, rgb = read_frame(frame_files(scan_dir, fr), float(depth_units_per_metre))
         d = np.where(m & np.isfinite(d) & (d > 0), d, 0.0).astype(np.float32)
         yield (d, rgb.astype(np.float32) / 255.0, np.asarray(camera_params(meta, fr)[:4], dtype=np.float64),
-               _homogeneous(np.asarray(fr["transform_matrix"], dtype=np.float64)))
+               homogeneous(np.asarray(fr["transform_matrix"], dtype=np.float64)))
 
 
 def mesh_scan(scan_dir: str, bbox=BBOX, resolution=RESOLUTION, truncation: Optional[float] = None,
@@ -435,7 +375,7 @@ def transforms_cameras(transforms_json: str) -> list:
     frames = meta.get("frames") or []
     if not frames:
         raise ValueError(f"{transforms_json} lists no frames")
-    return [(_homogeneous(np.asarray(fr["transform_matrix"], dtype=np.float64)),
+    return [(homogeneous(np.asarray(fr["transform_matrix"], dtype=np.float64)),
              np.asarray(camera_params(meta, fr)[:4], dtype=np.float64), int(fr.get("h", meta["h"])),
              int(fr.get("w", meta["w"]))) for fr in frames]
 
@@ -443,7 +383,7 @@ def transforms_cameras(transforms_json: str) -> list:
 def _checkpoint_mesh(a, bbox) -> Tuple[Mesh, Optional[Tuple[np.ndarray, float]]]:
     from .interop import load_checkpoint
     scene, mlp_state, _ = load_checkpoint(a.ckpt)
-    dev = _device()
+    dev = default_device("mesh")
     scene = scene.to(dev)
     tf = dataparser_transform(a.transform_json) if a.transform_json else None
     cams = []
@@ -451,17 +391,9 @@ def _checkpoint_mesh(a, bbox) -> Tuple[Mesh, Optional[Tuple[np.ndarray, float]]]
         if tf is not None:
             c2w_cv = c2w_to_scene(c2w_cv, *tf)
         cams.append((opencv_to_opengl_c2w(c2w_cv), K, h, w))
-    mask = None
-    if a.positives:
-        from . import query
-        keys = ("layers.0.weight", "layers.0.bias", "layers.2.weight", "layers.2.bias")
-        if any(k not in mlp_state for k in keys):
-            raise KeyError(f"{a.ckpt}: no fea_up weights for --positives")
-        w = tuple(mlp_state[k].to(dev) for k in keys)
-        mask = query.select_gaussians(scene, w, query._load_embeddings(a.positives, "positives"),
-                                      query._load_embeddings(a.negatives, "negatives"), a.threshold)
-        if not bool(mask.any()):
-            raise ValueError("the query selects no Gaussian")
+    mask = object_mask(a, scene, mlp_state)
+    if mask is not None and not bool(mask.any()):
+        raise ValueError("the query selects no Gaussian")
     mesh = mesh_model(scene, cams, bbox, a.resolution, a.downscale, mask)
     return mesh, tf
 
@@ -483,17 +415,14 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--resolution", type=int, default=RESOLUTION, help="lattice points per axis")
     ap.add_argument("--downscale", type=float, default=DOWNSCALE, help="render at 1 / K of each camera's size")
     ap.add_argument("--depth-units", type=float, default=1.0, help="with --scan: raw depth units per metre")
-    ap.add_argument("--positives", help=".npy text embeddings: mesh only the Gaussians the query selects")
-    ap.add_argument("--negatives", help=".npy canonical negatives (LERF relevancy)")
-    ap.add_argument("--threshold", type=float, default=None, help="relevancy threshold for --positives")
+    add_object_options(ap, "mesh only the Gaussians the query selects")
     ap.add_argument("--out-points", help="also write the mesh vertices as an (N, 3) float64 .npy (object points)")
     a = ap.parse_args(argv)
     if a.ckpt and not a.transforms:
         ap.error("--ckpt needs --transforms")
     if a.scan and (a.transforms or a.transform_json or a.positives):
         ap.error("--transforms, --transform-json and --positives go with --ckpt")
-    if a.positives and (a.threshold is None or not a.negatives):
-        ap.error("--positives needs --negatives and --threshold (LERF relevancy, query.select_gaussians)")
+    check_object_options(ap, a, "none")
     if a.resolution < 2 or a.downscale <= 0:
         ap.error("--resolution must be >= 2 and --downscale > 0")
     bbox = BBOX if a.bbox is None else (tuple(a.bbox[:3]), tuple(a.bbox[3:]))

@@ -19,7 +19,7 @@ from torch import Tensor, nn
 from torch.autograd import Function
 
 from . import _lib
-from .ops import _f32, _ptr, _require_hip, _stream
+from ._call import f32 as _f32, ptr as _ptr, require_hip as _require_hip, stream as _stream
 
 HIDDEN = 128
 SUPPORTED_IN = (8, 16, 32, 64, 128)     # fused forward kernels (W1 in registers; 128: W1 in LDS, W2 slices streamed)

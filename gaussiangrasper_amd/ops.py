@@ -22,43 +22,9 @@ from torch import Tensor
 from torch.autograd import Function
 
 from . import _lib
+from ._call import (f32 as _f32, i32 as _i32, ptr as _ptr, require_hip as _require_hip,  # noqa: F401
+                    stream as _stream, workspace as _workspace)
 from .constants import BLOCK, CLIP_THRESH_DEFAULT, deg_from_sh, num_sh_bases  # noqa: F401
-
-
-def _require_hip(*tensors: Tensor) -> torch.device:
-    dev = None
-    for t in tensors:
-        if not isinstance(t, Tensor):
-            raise TypeError(f"expected a torch.Tensor, got {type(t)}")
-        if t.device.type != "cuda":
-            raise RuntimeError(
-                "gaussiangrasper_amd operators run only on a HIP device (PyTorch-ROCm 'cuda'); "
-                f"got a tensor on '{t.device}'. There is no CPU fallback.")
-        if dev is None:
-            dev = t.device
-        elif t.device != dev:
-            raise RuntimeError(f"tensors on different devices: {dev} vs {t.device}")
-    return dev
-
-
-def _f32(t: Tensor) -> Tensor:
-    return t.contiguous() if t.dtype == torch.float32 else t.float().contiguous()
-
-
-def _i32(t: Tensor) -> Tensor:
-    return t.contiguous() if t.dtype == torch.int32 else t.int().contiguous()
-
-
-def _ptr(t: Optional[Tensor]):
-    return C.c_void_p(0 if t is None else t.data_ptr())
-
-
-def _stream(dev: torch.device):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _workspace(nbytes: int, dev: torch.device) -> Tensor:
-    return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
 
 
 # ------------------------------------------------------------------------------------------------

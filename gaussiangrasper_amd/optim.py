@@ -20,7 +20,7 @@ from typing import Iterable, List, Sequence
 import torch
 
 from . import _lib
-from .ops import _require_hip, _stream
+from ._call import require_hip as _require_hip, stream as _stream
 
 
 def _entries(opt: "FusedAdam"):

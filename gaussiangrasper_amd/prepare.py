@@ -24,16 +24,15 @@ import os
 import sys
 import time
 from concurrent.futures import ThreadPoolExecutor
-from typing import Dict, List, Optional, Sequence, Tuple, Union
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 from torch import Tensor
 
 from . import _lib
-from .ops import _ptr, _require_hip, _stream, _workspace as _ws
-
-ArrayLike = Union[np.ndarray, Tensor, Sequence]
+from ._call import (ArrayLike, default_device, ptr as _ptr, require_hip as _require_hip, stream as _stream, to_device,
+                    workspace as _ws)
 
 DEPTH_RANGE = (0.001, 1.2)       # depth_image_to_point_cloud :22
 Z_RANGE = (-0.3, -0.1)           # merge_point_clouds :39
@@ -43,18 +42,6 @@ POINTS3D_FMT = "%d %.6f %.6f %.6f %d %d %d"   # save_points3D :365-367
 COLMAP_DIR = os.path.join("colmap", "sparse", "0")
 
 _GOLDEN = np.uint64(0x9E3779B97F4A7C15)
-
-
-def _device() -> torch.device:
-    if not torch.cuda.is_available():
-        raise RuntimeError("gaussiangrasper_amd.prepare runs on a HIP device (PyTorch-ROCm 'cuda'); none is available. "
-                           "There is no CPU fallback.")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _on_device(x: ArrayLike, dtype: torch.dtype, dev: torch.device) -> Tensor:
-    t = x if isinstance(x, Tensor) else torch.as_tensor(np.asarray(x))
-    return t.to(device=dev, dtype=dtype).contiguous()
 
 
 # ------------------------------------------------------------------------------------------------
@@ -85,16 +72,16 @@ def subsample_indices(num: int, keep: int = KEEP, seed: int = 0) -> np.ndarray:
 # device calls
 # ------------------------------------------------------------------------------------------------
 def _frames_args(depth, intrinsics, c2w, dev):
-    d = _on_device(depth, torch.float64, dev)
+    d = to_device(depth, torch.float64, dev)
     if d.ndim == 2:
         d = d[None]
     if d.ndim != 3:
         raise ValueError(f"depth must be (F, H, W) or (H, W), got {tuple(d.shape)}")
     f = d.shape[0]
-    k = _on_device(intrinsics, torch.float64, dev).reshape(-1, 4)
+    k = to_device(intrinsics, torch.float64, dev).reshape(-1, 4)
     if k.shape[0] == 1 and f > 1:
         k = k.expand(f, 4).contiguous()
-    t = _on_device(c2w, torch.float64, dev).reshape(-1, 4, 4)
+    t = to_device(c2w, torch.float64, dev).reshape(-1, 4, 4)
     if t.shape[0] == 1 and f > 1:
         t = t.expand(f, 4, 4).contiguous()
     if k.shape[0] != f or t.shape[0] != f:
@@ -110,12 +97,12 @@ def backproject_frames(depth: ArrayLike, mask: ArrayLike, rgb: ArrayLike, intrin
     mask != 0 and d_lo < d < d_hi and its base-frame z is inside z_lo < z < z_hi.  Returns points (M, 3) float64 and
     colors (M, 3) uint8 on the device, frame-major then row-major, in tensors of their own (the F*H*W-row output
     buffers are released)."""
-    dev = _device()
+    dev = default_device("prepare")
     d, k, t = _frames_args(depth, intrinsics, c2w, dev)
     f, h, w = d.shape
     m = mask if isinstance(mask, Tensor) else torch.as_tensor(np.asarray(mask))
     m = (m != 0).to(device=dev, dtype=torch.uint8).reshape(-1, h, w).contiguous()
-    c = _on_device(rgb, torch.uint8, dev)
+    c = to_device(rgb, torch.uint8, dev)
     if m.shape[0] != f or tuple(c.shape) != (f, h, w, 3):
         raise ValueError(f"depth {tuple(d.shape)}, mask {tuple(m.shape)}, rgb {tuple(c.shape)}: need (F, H, W) and "
                          f"(F, H, W, 3)")
@@ -148,7 +135,7 @@ def subsample_device_indices(num: int, keep: int = KEEP, seed: int = 0) -> Tenso
     for rows that are not on the device (prepare_scene stages each batch's rows on the host)."""
     if num < 0 or keep < 1:
         raise ValueError(f"need num >= 0 and keep >= 1, got {num}, {keep}")
-    dev = _device()
+    dev = default_device("prepare")
     out_i = torch.empty(num // keep, dtype=torch.int64, device=dev)
     if num // keep:
         _subsample_call(num, keep, seed, None, None, None, None, out_i, dev)
@@ -180,7 +167,7 @@ def subsample(points: Tensor, colors: Tensor, keep: int = KEEP, seed: int = 0) -
 def depth_normals(depth: ArrayLike, intrinsics: ArrayLike, c2w: ArrayLike) -> Tensor:
     """cal_normal on the device (gg_depth_normals): world-frame unit normals (F, H, W, 3) float64 of depth frames
     (F, H, W) or (H, W) in metres; intrinsics (F, 4) / (4,) fx, fy, cx, cy; c2w (F, 4, 4) / (4, 4).  H, W >= 2."""
-    dev = _device()
+    dev = default_device("prepare")
     d, k, t = _frames_args(depth, intrinsics, c2w, dev)
     f, h, w = d.shape
     if h < 2 or w < 2:
@@ -244,7 +231,7 @@ def knn_distances(points: ArrayLike, k: int = 3) -> Tuple[Tensor, Tensor]:
         raise ValueError(f"{n} points: at most 2^30")
     if not bool(torch.isfinite(x).all()):
         raise ValueError("Input X contains NaN or infinity")
-    x = (x if x.device.type == "cuda" else x.to(_device())).contiguous()
+    x = (x if x.device.type == "cuda" else x.to(default_device("prepare"))).contiguous()
     dev = x.device
     grid, dims = knn_grid(x)
     grid_c = (ctypes.c_double * 4)(*grid.tolist())
@@ -343,7 +330,21 @@ class ScanError(ValueError):
     pass
 
 
-def _frame_files(scan: str, frame: Dict) -> Tuple[str, str, str, str]:
+def read_transforms(scan_dir: str) -> Tuple[str, Dict, List[Dict]]:
+    """(path, contents, frames) of a scan's transforms.json; ScanError when it is missing or lists no frames."""
+    tpath = os.path.join(scan_dir, "transforms.json")
+    if not os.path.exists(tpath):
+        raise ScanError(f"missing file: {tpath}")
+    with open(tpath) as f:
+        meta = json.load(f)
+    frames = meta.get("frames") or []
+    if not frames:
+        raise ScanError(f"{tpath} lists no frames")
+    return tpath, meta, frames
+
+
+def frame_files(scan: str, frame: Dict) -> Tuple[str, str, str, str]:
+    """(stem, image, depth, mask) paths of a frame of transforms.json; ScanError when one is missing."""
     stem = os.path.splitext(os.path.basename(frame["file_path"]))[0]
     image = os.path.join(scan, "images", stem + ".png")
     depth = os.path.join(scan, "depths", stem + ".npy")
@@ -386,7 +387,8 @@ def _check_sizes(files, hw: Tuple[int, int]) -> None:
             raise ScanError(f"{what} {path} has shape {tuple(shape)}, transforms.json gives h x w = {hw[0]} x {hw[1]}")
 
 
-def _read_frame(files, units: float):
+def read_frame(files, units: float):
+    """(depth (H, W) fp64 metres, mask (H, W) bool, rgb (H, W, 3) uint8) of a frame's frame_files."""
     from PIL import Image
     _, image, depth, mask = files
     rgb = np.asarray(Image.open(image).convert("RGB"))
@@ -405,19 +407,12 @@ def prepare_scene(scan_dir: str, out_dir: Optional[str] = None, keep: int = KEEP
     out_dir = out_dir or scan_dir
     if keep < 1 or frames_per_batch < 1 or not depth_units_per_metre > 0:
         raise ScanError("keep and frames_per_batch must be >= 1, depth_units_per_metre > 0")
-    tpath = os.path.join(scan_dir, "transforms.json")
-    if not os.path.exists(tpath):
-        raise ScanError(f"missing file: {tpath}")
-    with open(tpath) as f:
-        meta = json.load(f)
-    frames = meta.get("frames") or []
-    if not frames:
-        raise ScanError(f"{tpath} lists no frames")
+    tpath, meta, frames = read_transforms(scan_dir)
     for key in ("fl_x", "fl_y", "cx", "cy", "w", "h"):
         if key not in meta and not (key in ("fl_x", "fl_y", "cx", "cy") and all(key in fr for fr in frames)):
             raise ScanError(f"{tpath} has no top-level '{key}'")
     hw = (int(meta["h"]), int(meta["w"]))
-    files = [_frame_files(scan_dir, fr) for fr in frames]
+    files = [frame_files(scan_dir, fr) for fr in frames]
     for fl in files:
         _check_sizes(fl, hw)
     stems = [f[0] for f in files]
@@ -438,14 +433,14 @@ def prepare_scene(scan_dir: str, out_dir: Optional[str] = None, keep: int = KEEP
     c2w = np.array([np.asarray(fr["transform_matrix"], dtype=np.float64) for fr in frames])
     cams, cam_ids = camera_ids(meta, frames)
     intr = np.array([cams[i - 1][:4] for i in cam_ids], dtype=np.float64)
-    dev = _device()
+    dev = default_device("prepare")
     t_read = t_gpu = t_write = 0.0
     clouds, colours, pending = [], [], []
     with ThreadPoolExecutor(max_workers=max(1, min(READERS, os.cpu_count() or 1))) as pool:
         for b0 in range(0, len(frames), frames_per_batch):
             b1 = min(len(frames), b0 + frames_per_batch)
             t0 = time.perf_counter()
-            got = list(pool.map(lambda fl: _read_frame(fl, float(depth_units_per_metre)), files[b0:b1]))
+            got = list(pool.map(lambda fl: read_frame(fl, float(depth_units_per_metre)), files[b0:b1]))
             depth = torch.from_numpy(np.stack([g[0] for g in got]))
             mask = torch.from_numpy(np.stack([g[1] for g in got]).astype(np.uint8))
             rgb = torch.from_numpy(np.stack([g[2] for g in got]))

@@ -25,7 +25,7 @@ from __future__ import annotations
 import argparse
 import math
 import sys
-from typing import Optional, Sequence, Tuple, Union
+from typing import Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -33,14 +33,12 @@ import torch.nn.functional as F
 from torch import Tensor
 
 from . import _lib
+from ._call import ArrayLike, ptr as _ptr, require_hip as _require_hip, stream as _stream
 from .mlp import FAST_MAX_OUT, HIDDEN, mlp_forward
-from .ops import _ptr, _require_hip, _stream
 
 MAX_QUERIES = 8            # GG_QUERY_MAX: query rows per kernel launch (positives + negatives)
 KERNEL_IN = (32, 64, 128)
 DEFAULT_TEMPERATURE = 10.0
-
-ArrayLike = Union[np.ndarray, Tensor, Sequence]
 
 
 def _max_queries(out_dim: int) -> int:
@@ -235,12 +233,9 @@ def score_checkpoint(ckpt: str, positives: np.ndarray, negatives: Optional[np.nd
                      temperature: float = DEFAULT_TEMPERATURE, device: str = "cuda") -> np.ndarray:
     """(N, P) float32: relevancy with negatives, cosine similarity without, of every Gaussian's feature through the
     checkpoint's fea_up."""
-    from .interop import load_checkpoint
+    from .interop import fea_up_weights, load_checkpoint
     scene, mlp_state, _ = load_checkpoint(ckpt)
-    keys = ("layers.0.weight", "layers.0.bias", "layers.2.weight", "layers.2.bias")
-    if any(k not in mlp_state for k in keys):
-        raise KeyError(f"{ckpt}: no fea_up weights (_model.fea_up.layers.{{0,2}}.{{weight,bias}})")
-    w = tuple(mlp_state[k].to(device) for k in keys)
+    w = fea_up_weights(mlp_state, device, ckpt, "(_model.fea_up.layers.{0,2}.{weight,bias})")
     feat = scene.feature.to(device)
     if negatives is None or len(negatives) == 0:
         out = clip_similarity(feat, w, positives)
@@ -249,7 +244,8 @@ def score_checkpoint(ckpt: str, positives: np.ndarray, negatives: Optional[np.nd
     return out.cpu().numpy().astype(np.float32)
 
 
-def _load_embeddings(path: str, name: str) -> np.ndarray:
+def load_embeddings(path: str, name: str) -> np.ndarray:
+    """(K, C) float32 text embeddings of a .npy file (one embedding may be 1-D)."""
     e = np.asarray(np.load(path), dtype=np.float32)
     if e.ndim == 1:
         e = e[None]
@@ -273,8 +269,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         _check_temperature(a.temperature)
         if a.threshold is not None and not math.isfinite(a.threshold):
             raise ValueError(f"threshold must be finite, got {a.threshold}")
-        pos = _load_embeddings(a.positives, "positives")
-        neg = _load_embeddings(a.negatives, "negatives") if a.negatives else None
+        pos = load_embeddings(a.positives, "positives")
+        neg = load_embeddings(a.negatives, "negatives") if a.negatives else None
         scores = score_checkpoint(a.ckpt, pos, neg, a.temperature)
     except (KeyError, ValueError, OSError) as exc:
         raise SystemExit(f"error: {exc}") from exc
