@@ -1,22 +1,50 @@
-"""What the command lines of grasp, grasp_propose and mesh share: the options that say which Gaussians are the
-object (the convex hull of --object-points, or the LERF relevancy of --positives against --negatives above
---threshold), their cross-checks, the mask they select, and the per-grasp arrays of a --report file."""
+"""What the command lines of grasp, grasp_propose, mesh and cluster share: the options that say which Gaussians are
+the object (the convex hull of --object-points, or the LERF relevancy of --positives against --negatives above
+--threshold; of that selection, with --instance, one DBSCAN instance), their cross-checks, the mask they select, and
+the per-grasp arrays of a --report file."""
 from __future__ import annotations
+
+import argparse
+import math
 
 import numpy as np
 
 REPORT_KEYS = ("contact_idx", "normals", "angles", "region_count", "region_weight", "collision_weight", "feasible")
 
 
-def add_object_options(ap, query_does: str, hull_does: str = None) -> None:
+def instance_choice(text: str):
+    """--instance: "all", "largest" (rank 0) or a rank K >= 0."""
+    if text in ("all", "largest"):
+        return text
+    try:
+        k = int(text)
+    except ValueError:
+        k = -1
+    if k < 0:
+        raise argparse.ArgumentTypeError(f"expected all, largest or a rank >= 0, got {text!r}")
+    return k
+
+
+def add_object_options(ap, query_does: str, hull_does: str = None, instances: bool = True) -> None:
     """--object-points (only with `hull_does`), --positives, --negatives, --threshold; the two arguments end the
-    help strings of --positives and --object-points."""
+    help strings of --positives and --object-points.  With `instances`, also --instance and the --cluster-* options
+    that go with it."""
     if hull_does:
         ap.add_argument("--object-points", default=None, help="object point cloud (world frame): its convex hull "
                                                               + hull_does)
     ap.add_argument("--positives", default=None, help=".npy text embeddings: " + query_does)
     ap.add_argument("--negatives", default=None, help=".npy canonical negatives (LERF relevancy)")
     ap.add_argument("--threshold", type=float, default=None, help="relevancy threshold for --positives")
+    if instances:
+        ap.add_argument("--instance", type=instance_choice, default="all", metavar="{all,largest,K}",
+                        help="of the selection, keep one DBSCAN instance (cluster.object_instances): the heaviest, or "
+                             "the one of rank K; all: the selection as it is")
+        ap.add_argument("--cluster-eps", type=float, default=None,
+                        help="with --instance: neighbour radius, world units (default: derived from the selection)")
+        ap.add_argument("--cluster-eps-scale", type=float, default=None,
+                        help="with --instance: eps = this times the selection's median 3rd-neighbour distance")
+        ap.add_argument("--cluster-min-points", type=int, default=None,
+                        help="with --instance: neighbours within eps that make a core point")
 
 
 def check_object_options(ap, a, hull: str) -> None:
@@ -31,11 +59,46 @@ def check_object_options(ap, a, hull: str) -> None:
         ap.error("--positives needs --negatives and --threshold (LERF relevancy, query.select_gaussians)")
     if hull != "none" and (a.negatives or a.threshold is not None) and not a.positives:
         ap.error("--negatives / --threshold need --positives")
+    inst = getattr(a, "instance", "all")
+    given = [n for n in ("cluster_eps", "cluster_eps_scale", "cluster_min_points") if getattr(a, n, None) is not None]
+    if given and inst == "all":
+        ap.error("--" + given[0].replace("_", "-") + " needs --instance largest or --instance K")
+    if inst != "all" and not (getattr(a, "object_points", None) or a.positives):
+        ap.error("--instance needs a selection (--positives" + (")" if hull == "none" else " or --object-points)"))
+    for n in ("cluster_eps", "cluster_eps_scale"):
+        v = getattr(a, n, None)
+        if v is not None and not (math.isfinite(v) and v > 0.0):
+            ap.error(f"--{n.replace('_', '-')} must be finite and > 0, got {v}")
+    if getattr(a, "cluster_eps", None) is not None and getattr(a, "cluster_eps_scale", None) is not None:
+        ap.error("--cluster-eps and --cluster-eps-scale are alternatives")
+    if getattr(a, "cluster_min_points", None) is not None and a.cluster_min_points < 1:
+        ap.error(f"--cluster-min-points must be >= 1, got {a.cluster_min_points}")
 
 
 def object_mask(a, scene, mlp_state, matrix=None, scale: float = 1.0):
     """(N,) mask on the scene's device of the Gaussians the parsed options select, None without a selection.
-    matrix, scale: the world -> scene map of the object points (None: identity)."""
+    matrix, scale: the world -> scene map of the object points (None: identity).  With --instance largest or K,
+    that selection's instance of that rank (cluster.object_instances; --cluster-eps times scale)."""
+    mask = selection_mask(a, scene, mlp_state, matrix, scale)
+    inst = getattr(a, "instance", "all")
+    if inst == "all" or mask is None:
+        return mask
+    from . import cluster
+    kw = {}
+    if a.cluster_eps_scale is not None:
+        kw["eps_scale"] = a.cluster_eps_scale
+    if a.cluster_min_points is not None:
+        kw["min_points"] = a.cluster_min_points
+    found = cluster.object_instances(scene, mask, None if a.cluster_eps is None else a.cluster_eps * float(scale),
+                                     **kw)
+    rank = 0 if inst == "largest" else inst
+    if rank >= len(found):
+        raise ValueError(f"--instance {inst}: the selection has {len(found)} instances")
+    return cluster.instance_mask(found, rank)
+
+
+def selection_mask(a, scene, mlp_state, matrix=None, scale: float = 1.0):
+    """object_mask before --instance: the hull's or the query's Gaussians, None without a selection."""
     if getattr(a, "object_points", None):
         from . import edit
         pts = edit.filter_object_points(edit.object_points_to_scene(

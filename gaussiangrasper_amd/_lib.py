@@ -121,6 +121,9 @@ SIGNATURES = {
     "gg_depth_normals": (_I, [_I, _I, _I, _P, _P, _P, _P, _P]),
     "gg_knn_workspace": (_SZ, [_I, _P]),
     "gg_knn": (_I, [_I, _P, _I, _P, _P, _P, _P, _P, _SZ, _P]),
+    "gg_cluster_workspace": (_SZ, [_I, _P]),
+    "gg_cluster_dbscan": (_I, [_I, _P, _P, C.c_double, _I, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "gg_cluster_stats": (_I, [_I, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
     "gg_tsdf_integrate": (_I, [_P, _P, _F, _I, _I, _I] + [_P] * 8 + [_P]),
     "gg_tsdf_mesh_workspace": (_SZ, [_P]),
     "gg_tsdf_mesh_count": (_I, [_P, _P, _P, _P, _P, _SZ, _P]),

@@ -1,0 +1,123 @@
+// grid_sort.h — the uniform-grid counting sort shared by csrc/knn.hip and csrc/cluster.hip.
+//
+// The caller gives the grid (lower corner, cell edge, cells per axis); a point's cell is floor((p - lo) / cell) per
+// axis, clamped into the grid, so points outside the grid sit in its border cells.  Counts per cell (integer
+// atomics), exclusive offsets (prep_common.h scans), a scatter of (x, y, z, index) into cell order.  With FILTER the
+// sort takes only the points that are finite and, when a byte mask is given, have a non-zero byte; *total (device,
+// int64) then holds how many were taken.  Slot order within a cell follows the atomics.
+#pragma once
+#include "gg_common.h"
+#include "prep_common.h"
+
+struct KnGrid {
+    double lo[3], cell;
+    int dims[3];
+};
+
+__device__ __forceinline__ int kn_axis(double p, double lo, double cell, int dim) {
+    const double t = floor((p - lo) / cell);
+    return !(t >= 0.0) ? 0 : (t >= (double)(dim - 1) ? dim - 1 : (int)t);
+}
+
+__device__ __forceinline__ int kn_cell(const KnGrid &G, float x, float y, float z, int &cx, int &cy, int &cz) {
+    cx = kn_axis((double)x, G.lo[0], G.cell, G.dims[0]);
+    cy = kn_axis((double)y, G.lo[1], G.cell, G.dims[1]);
+    cz = kn_axis((double)z, G.lo[2], G.cell, G.dims[2]);
+    return (cz * G.dims[1] + cy) * G.dims[0] + cx;
+}
+
+template <bool FILTER>
+__device__ __forceinline__ bool kn_takes(float x, float y, float z, const uint8_t *__restrict__ active, int i) {
+    if (!FILTER) return true;
+    // x - x is 0 for a finite x and NaN for NaN and +-inf
+    return (active == nullptr || active[i] != 0) && (x - x) + (y - y) + (z - z) == 0.0f;
+}
+
+template <bool FILTER>
+static __global__ __launch_bounds__(256) void knn_count_kernel(int n, const float *__restrict__ points,
+                                                               const uint8_t *__restrict__ active, KnGrid G,
+                                                               int32_t *__restrict__ counts) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float x = points[3 * (size_t)i], y = points[3 * (size_t)i + 1], z = points[3 * (size_t)i + 2];
+    if (!kn_takes<FILTER>(x, y, z, active, i)) return;
+    int cx, cy, cz;
+    atomicAdd(&counts[kn_cell(G, x, y, z, cx, cy, cz)], 1);
+}
+
+// Slot order within a cell follows the atomics.  For gg_knn distances never depend on it, and neither do indices
+// except among exact duplicates: the search stops at the first k points at distance 0 it meets, so which of several
+// points at distance 0 is returned may differ from call to call.  Nothing gg_cluster_dbscan writes depends on it.
+template <bool FILTER>
+static __global__ __launch_bounds__(256) void knn_scatter_kernel(int n, const float *__restrict__ points,
+                                                                 const uint8_t *__restrict__ active, KnGrid G,
+                                                                 const int32_t *__restrict__ start,
+                                                                 int32_t *__restrict__ cursor,
+                                                                 float4 *__restrict__ sorted) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float x = points[3 * (size_t)i], y = points[3 * (size_t)i + 1], z = points[3 * (size_t)i + 2];
+    if (!kn_takes<FILTER>(x, y, z, active, i)) return;
+    int cx, cy, cz;
+    const int c = kn_cell(G, x, y, z, cx, cy, cz);
+    sorted[start[c] + atomicAdd(&cursor[c], 1)] = make_float4(x, y, z, __int_as_float(i));
+}
+
+struct KnWs {
+    int32_t *counts, *cursor, *start, *tile_sums, *tile_offs;
+    float4 *sorted;
+};
+
+static inline bool kn_dims_ok(const int32_t *dims) {
+    if (!dims) return false;
+    int64_t cells = 1;
+    for (int d = 0; d < 3; ++d) {
+        if (dims[d] < 1 || dims[d] > GG_KNN_MAX_CELLS) return false;
+        cells *= dims[d];
+        if (cells > GG_KNN_MAX_CELLS) return false;
+    }
+    return true;
+}
+
+// The sort's arrays behind `base` (nullptr: sizes only), every one 256-byte aligned; returns the bytes taken.
+static inline size_t kn_layout(int n, const int32_t *dims, KnWs *w, char *base) {
+    const int64_t cells = (int64_t)dims[0] * dims[1] * dims[2];
+    const int64_t tiles = (cells + PP_TILE - 1) / PP_TILE;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        char *p = base ? base + off : nullptr;
+        off += gg_align_up(bytes, 256);
+        return p;
+    };
+    KnWs t;
+    t.counts = (int32_t *)take((size_t)cells * 4);
+    t.cursor = (int32_t *)take((size_t)cells * 4);
+    t.start = (int32_t *)take((size_t)cells * 4);
+    t.tile_sums = (int32_t *)take((size_t)tiles * 4);
+    t.tile_offs = (int32_t *)take((size_t)tiles * 4);
+    t.sorted = (float4 *)take((size_t)n * 16);
+    if (w) *w = t;
+    return off;
+}
+
+// counts, start and sorted of the points (FILTER: of those that take part) on stream s; hipSuccess unless a fill
+// could not be launched.  Launch errors of the kernels are left for the caller's GG_CHECK_LAUNCH.
+template <bool FILTER>
+static inline hipError_t kn_sort(int n, const float *points, const uint8_t *active, const KnGrid &G, const KnWs &w,
+                                 int64_t *total, hipStream_t s) {
+    const int cells = G.dims[0] * G.dims[1] * G.dims[2];
+    const int tiles = (cells + PP_TILE - 1) / PP_TILE;
+    const unsigned pb = (unsigned)((n + 255) / 256);
+    hipError_t e = gg_fill_async(w.counts, 0, (size_t)cells * 4, s);
+    if (e == hipSuccess) e = gg_fill_async(w.cursor, 0, (size_t)cells * 4, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(knn_count_kernel<FILTER>, dim3(pb), dim3(256), 0, s, n, points, active, G, w.counts);
+    hipLaunchKernelGGL(pp_scan_reduce_kernel, dim3((unsigned)tiles), dim3(PP_THREADS), 0, s, w.counts, cells,
+                       w.tile_sums);
+    hipLaunchKernelGGL(pp_scan_single_kernel, dim3(1), dim3(PP_THREADS), 0, s, w.tile_sums, tiles, w.tile_offs, total);
+    hipLaunchKernelGGL(pp_scan_apply_kernel, dim3((unsigned)tiles), dim3(PP_THREADS), 0, s, w.counts, cells,
+                       w.tile_offs, w.start);
+    hipLaunchKernelGGL(knn_scatter_kernel<FILTER>, dim3(pb), dim3(256), 0, s, n, points, active, G, w.start, w.cursor,
+                       w.sorted);
+    return hipSuccess;
+}

@@ -2,10 +2,10 @@
 // gaussian_splatting.py:315-331, whose distances set the first log-scales).  The contract is in
 // include/gg_raster.h (gg_knn) and PARITY.md "Scene preparation"; the design in DESIGN.md §3.13.
 //
-// Uniform grid, counting sort: the caller gives the grid (lower corner, cell edge, cells per axis); a point's cell
-// is floor((p - lo) / cell) per axis, clamped into the grid, so points outside the grid sit in its border cells.
-// Counts per cell (integer atomics), exclusive offsets (prep_common.h scans), a scatter of (x, y, z, index) into
-// cell order.  One lane per sorted slot then searches Chebyshev shells of cells around its own cell, r = 0, 1, ...
+// Uniform grid, counting sort (grid_sort.h, shared with csrc/cluster.hip): the caller gives the grid (lower corner,
+// cell edge, cells per axis); a point's cell is floor((p - lo) / cell) per axis, clamped into the grid, so points
+// outside the grid sit in its border cells.  Counts per cell (integer atomics), exclusive offsets (prep_common.h
+// scans), a scatter of (x, y, z, index) into cell order.  One lane per sorted slot then searches Chebyshev shells of cells around its own cell, r = 0, 1, ...
 // and stops after shell r when its k-th squared distance is <= b^2, b a lower bound of the distance to every cell
 // outside the searched cube:
 //   b = min over the faces of the cube that have cells beyond them of the distance from p to that face plane,
@@ -24,50 +24,9 @@
 #include <math.h>
 
 #include "gg_common.h"
-#include "prep_common.h"
+#include "grid_sort.h"
 
 #define KN_SLOP 1e-12
-
-struct KnGrid {
-    double lo[3], cell;
-    int dims[3];
-};
-
-__device__ __forceinline__ int kn_axis(double p, double lo, double cell, int dim) {
-    const double t = floor((p - lo) / cell);
-    return !(t >= 0.0) ? 0 : (t >= (double)(dim - 1) ? dim - 1 : (int)t);
-}
-
-__device__ __forceinline__ int kn_cell(const KnGrid &G, float x, float y, float z, int &cx, int &cy, int &cz) {
-    cx = kn_axis((double)x, G.lo[0], G.cell, G.dims[0]);
-    cy = kn_axis((double)y, G.lo[1], G.cell, G.dims[1]);
-    cz = kn_axis((double)z, G.lo[2], G.cell, G.dims[2]);
-    return (cz * G.dims[1] + cy) * G.dims[0] + cx;
-}
-
-__global__ __launch_bounds__(256) void knn_count_kernel(int n, const float *__restrict__ points, KnGrid G,
-                                                        int32_t *__restrict__ counts) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    int cx, cy, cz;
-    atomicAdd(&counts[kn_cell(G, points[3 * (size_t)i], points[3 * (size_t)i + 1], points[3 * (size_t)i + 2], cx, cy,
-                              cz)],
-              1);
-}
-
-// Slot order within a cell follows the atomics.  Distances never depend on it, and neither do indices except
-// among exact duplicates: the search stops at the first k points at distance 0 it meets, so which of several
-// points at distance 0 is returned may differ from call to call.
-__global__ __launch_bounds__(256) void knn_scatter_kernel(int n, const float *__restrict__ points, KnGrid G,
-                                                          const int32_t *__restrict__ start,
-                                                          int32_t *__restrict__ cursor, float4 *__restrict__ sorted) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float x = points[3 * (size_t)i], y = points[3 * (size_t)i + 1], z = points[3 * (size_t)i + 2];
-    int cx, cy, cz;
-    const int c = kn_cell(G, x, y, z, cx, cy, cz);
-    sorted[start[c] + atomicAdd(&cursor[c], 1)] = make_float4(x, y, z, __int_as_float(i));
-}
 
 template <int K>
 __device__ __forceinline__ void kn_visit(int c, const int32_t *__restrict__ start, const int32_t *__restrict__ counts,
@@ -154,42 +113,6 @@ __global__ __launch_bounds__(256) void knn_search_kernel(int n, KnGrid G, const 
     }
 }
 
-struct KnWs {
-    int32_t *counts, *cursor, *start, *tile_sums, *tile_offs;
-    float4 *sorted;
-};
-
-static bool kn_dims_ok(const int32_t *dims) {
-    if (!dims) return false;
-    int64_t cells = 1;
-    for (int d = 0; d < 3; ++d) {
-        if (dims[d] < 1 || dims[d] > GG_KNN_MAX_CELLS) return false;
-        cells *= dims[d];
-        if (cells > GG_KNN_MAX_CELLS) return false;
-    }
-    return true;
-}
-
-static size_t kn_layout(int n, const int32_t *dims, KnWs *w, char *base) {
-    const int64_t cells = (int64_t)dims[0] * dims[1] * dims[2];
-    const int64_t tiles = (cells + PP_TILE - 1) / PP_TILE;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char *p = base ? base + off : nullptr;
-        off += gg_align_up(bytes, 256);
-        return p;
-    };
-    KnWs t;
-    t.counts = (int32_t *)take((size_t)cells * 4);
-    t.cursor = (int32_t *)take((size_t)cells * 4);
-    t.start = (int32_t *)take((size_t)cells * 4);
-    t.tile_sums = (int32_t *)take((size_t)tiles * 4);
-    t.tile_offs = (int32_t *)take((size_t)tiles * 4);
-    t.sorted = (float4 *)take((size_t)n * 16);
-    if (w) *w = t;
-    return off;
-}
-
 extern "C" size_t gg_knn_workspace(int num_points, const int32_t *dims) {
     if (num_points < 0 || num_points > GG_KNN_MAX_POINTS || !kn_dims_ok(dims)) return 0;
     return kn_layout(num_points, dims, nullptr, nullptr);
@@ -220,27 +143,15 @@ extern "C" int gg_knn(int num_points, const float *points, int k, const double *
         G.dims[d] = dims[d];
     }
     G.cell = grid[3];
-    const int cells = dims[0] * dims[1] * dims[2];
-    const int tiles = (cells + PP_TILE - 1) / PP_TILE;
     const unsigned pb = (unsigned)((num_points + 255) / 256);
     hipStream_t s = (hipStream_t)stream;
     gg_prof_begin(GG_K_KNN, s);
-    hipError_t e = gg_fill_async(w.counts, 0, (size_t)cells * 4, s);
-    if (e == hipSuccess) e = gg_fill_async(w.cursor, 0, (size_t)cells * 4, s);
+    const hipError_t e = kn_sort<false>(num_points, points, nullptr, G, w, nullptr, s);
     if (e != hipSuccess) {
         gg_prof_end(GG_K_KNN, s);
         gg_set_error("%s: fill failed: %s", __func__, hipGetErrorString(e));
         return GG_ERR_LAUNCH;
     }
-    hipLaunchKernelGGL(knn_count_kernel, dim3(pb), dim3(256), 0, s, num_points, points, G, w.counts);
-    hipLaunchKernelGGL(pp_scan_reduce_kernel, dim3((unsigned)tiles), dim3(PP_THREADS), 0, s, w.counts, cells,
-                       w.tile_sums);
-    hipLaunchKernelGGL(pp_scan_single_kernel, dim3(1), dim3(PP_THREADS), 0, s, w.tile_sums, tiles, w.tile_offs,
-                       (int64_t *)nullptr);
-    hipLaunchKernelGGL(pp_scan_apply_kernel, dim3((unsigned)tiles), dim3(PP_THREADS), 0, s, w.counts, cells,
-                       w.tile_offs, w.start);
-    hipLaunchKernelGGL(knn_scatter_kernel, dim3(pb), dim3(256), 0, s, num_points, points, G, w.start, w.cursor,
-                       w.sorted);
     switch (k) {
 #define KN_CASE(KK)                                                                                                  \
     case KK:                                                                                                         \

@@ -1,4 +1,4 @@
-// prep_common.h — ordered workgroup scans shared by csrc/prepare.hip and csrc/knn.hip.
+// prep_common.h — ordered workgroup scans shared by csrc/prepare.hip, csrc/knn.hip and csrc/cluster.hip.
 //
 // A workgroup of PP_THREADS lanes owns PP_TILE = PP_THREADS x PP_ITEMS consecutive items, PP_ITEMS consecutive
 // items per lane; pp_block_scan gives each lane the number of items before its own in the tile.  Exclusive

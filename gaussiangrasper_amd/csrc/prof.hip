@@ -119,6 +119,8 @@ extern "C" const char *gg_prof_name(int id) {
         case GG_K_TSDF_INTEGRATE: return "tsdf_integrate_kernel";
         case GG_K_TSDF_MESH: return "gg_tsdf_mesh(all launches)";
         case GG_K_GRASP_PROPOSE: return "gg_grasp_propose(all launches)";
+        case GG_K_CLUSTER: return "gg_cluster_dbscan(all launches)";
+        case GG_K_CLUSTER_STATS: return "gg_cluster_stats(all launches)";
         default: break;
     }
     if (id >= GG_K_BLEND_FWD && id < GG_K_BLEND_FWD + 6) {

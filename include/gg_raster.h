@@ -748,6 +748,46 @@ size_t gg_knn_workspace(int num_points, const int32_t *dims);
 int gg_knn(int num_points, const float *points, int k, const double *grid, const int32_t *dims, float *dist,
            int64_t *idx, void *ws, size_t ws_bytes, gg_stream_t stream);
 
+/* ---- object instances: DBSCAN of a point set and per-cluster statistics (PARITY "Object instances") ---
+ * gg_cluster_dbscan.  points fp32 [N][3]; active uint8 [N] or NULL (all).  A point takes part (is active) iff its
+ * byte is non-zero and its three coordinates are finite.  eps > 0 finite (fp64), min_points >= 1.
+ *   neighbours:  active i and j are neighbours iff  (dx dx + dy dy) + dz dz <= eps eps,  all in fp64, dx the fp64
+ *                difference of the fp32 coordinates (gg_knn's order).  No square root, no division: exact.
+ *   core:        neighbour count, the point itself included, >= min_points (sklearn's min_samples convention).
+ *   clusters:    the connected components of the core points under the neighbour relation, numbered 0, 1, ... in
+ *                ascending order of the smallest point index among their core points.
+ *   border:      a non-core active point with at least one core neighbour takes the smallest cluster number among
+ *                its core neighbours.  Every other point, inactive ones included, gets label -1.
+ * Outputs: labels int32 [N]; core uint8 [N]; neighbor_count int32 [N] (0 for inactive points); num_clusters, one
+ * int32 on the device.  They are a pure function of the inputs: nothing depends on the schedule or on the grid, and
+ * two calls give the same bits.  They equal the labels and core_sample_indices_ of sklearn.cluster.DBSCAN(eps,
+ * min_samples) on the fp64 cast of the points wherever no pair sits within rounding of eps.
+ * grid (host, 4 doubles) / dims (host, 3 ints): as for gg_knn.  The sort uses the cell edge max(cell, eps)
+ * (1 + 2^-20), so that the 27 cells around a point hold all its neighbours; points outside the grid go to its border
+ * cells.  Any grid gives the same result; one fitted to the cloud with cells of about eps gives it fast
+ * (gaussiangrasper_amd.cluster.cluster_grid).
+ * Cost: (active points) x (points within the 27 cells around each) x 3 passes (count, union, roots).  An eps so
+ * large that the cloud falls into a few cells is quadratic: the caller must avoid it.  The union-find is lock-free
+ * (32-bit device-scope atomicCAS / atomicMin, parents only decrease); no thread waits on another.
+ * Everything runs on `stream`; nothing is read back.  num_points == 0 returns GG_OK and launches nothing.
+ * `ws`: gg_cluster_workspace(N, dims) bytes, 256-byte aligned (0 for sizes out of range); a short or NULL workspace
+ * is GG_ERR_INVALID_ARG.
+ *
+ * gg_cluster_stats: per cluster c in [0, num_clusters), over the points with labels[i] == c (labels outside that
+ * range are skipped):  count int64 [K] (exact);  weight fp64 [K] = sum of (double)weights[i];  centroid fp64 [K][3] =
+ * (sum of (double)w_i (double)p_i) / weight (each product exact; NaN for weight 0);  bbox fp32 [K][6] = min x, y, z
+ * then max x, y, z (exact; NaN for a cluster without members).  Integer atomics for count and, through an
+ * order-preserving encoding, for bbox; fp64 atomic sums for weight and centroid, whose last bits may differ from
+ * call to call.  points must be finite where a label is in range.  num_clusters == 0 does nothing. */
+#define GG_CLUSTER_MAX_POINTS (1 << 30)
+size_t gg_cluster_workspace(int num_points, const int32_t *dims);
+int gg_cluster_dbscan(int num_points, const float *points, const uint8_t *active, double eps, int min_points,
+                      const double *grid, const int32_t *dims, int32_t *labels, uint8_t *core, int32_t *neighbor_count,
+                      int32_t *num_clusters, void *ws, size_t ws_bytes, gg_stream_t stream);
+int gg_cluster_stats(int num_points, const float *points, const float *weights, const int32_t *labels,
+                     int num_clusters, int64_t *count, double *weight, double *centroid, float *bbox,
+                     gg_stream_t stream);
+
 /* ---- mesh export: TSDF fusion and marching tetrahedra (PARITY "Mesh export") ------------------------
  * The volume: dims (host, 3 ints) X, Y, Z lattice points, 1 <= each <= GG_TSDF_MAX_DIM, X Y Z <= GG_TSDF_MAX_POINTS;
  * grid (host, 6 floats) origin x, y, z and voxel size x, y, z (> 0, finite).  Point (i, j, k) has index
@@ -851,7 +891,9 @@ int gg_tsdf_mesh_emit(const int32_t *dims, const float *grid, const float *tsdf,
 #define GG_K_TSDF_INTEGRATE 43 /* gg_tsdf_integrate */
 #define GG_K_TSDF_MESH 44     /* gg_tsdf_mesh_count and gg_tsdf_mesh_emit: all their launches */
 #define GG_K_GRASP_PROPOSE 45 /* gg_grasp_propose: search, per-seed reduction and rows */
-#define GG_K_IDS 46           /* ids are below this */
+#define GG_K_CLUSTER 46       /* gg_cluster_dbscan: sort, core, union, roots, relabel */
+#define GG_K_CLUSTER_STATS 47 /* gg_cluster_stats: all three launches */
+#define GG_K_IDS 48           /* ids are below this */
 #define GG_PROF_NUM_KERNELS 32
 int gg_prof_enable(int on);
 int gg_prof_reset(void);
