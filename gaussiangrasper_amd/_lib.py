@@ -124,6 +124,10 @@ SIGNATURES = {
     "gg_cluster_workspace": (_SZ, [_I, _P]),
     "gg_cluster_dbscan": (_I, [_I, _P, _P, C.c_double, _I, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "gg_cluster_stats": (_I, [_I, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "gg_cloud_frames_workspace": (_SZ, [_I, _P]),
+    "gg_cloud_frames": (_I, [_I, _P, _P, C.c_double, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "gg_icp_step_workspace": (_SZ, [_I, _I, _P]),
+    "gg_icp_step": (_I, [_I, _P, _P, _I] + [_P] * 8 + [C.c_double, C.c_double, _I, _P, _P, _P, _P, _SZ, _P]),
     "gg_tsdf_integrate": (_I, [_P, _P, _F, _I, _I, _I] + [_P] * 8 + [_P]),
     "gg_tsdf_mesh_workspace": (_SZ, [_P]),
     "gg_tsdf_mesh_count": (_I, [_P, _P, _P, _P, _P, _SZ, _P]),

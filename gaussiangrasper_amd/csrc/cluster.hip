@@ -10,8 +10,8 @@
 //   roots    core: labels[i] = find(i), flag the roots;  border: labels[i] = min find(j) over core neighbours j
 //   relabel  ordered scan of the root flags (prep_common.h) -> dense ids in ascending root order; num_clusters
 // The grid's cell edge is max(cell, eps) (1 + 2^-20), so the cells of two neighbours differ by at most 1 per axis
-// (cl_cell_edge): clamping into the grid is monotone and 1-Lipschitz in the cell index, so that holds for points
-// outside the grid too.  The 27 cells are a superset of every point's neighbours; the exact fp64 test decides.
+// (kn_radius_cell, grid_sort.h): clamping into the grid is monotone and 1-Lipschitz in the cell index, so that holds
+// for points outside the grid too.  The 27 cells are a superset of every point's neighbours; the exact fp64 test decides.
 // A row of 3 cells along x is contiguous in slot order, so a lane walks 9 slot ranges.
 //
 // Union-find.  parent[] is indexed by point.  Invariant: parent[v] <= v, with equality exactly for roots.  Two
@@ -29,10 +29,6 @@
 
 #include "gg_common.h"
 #include "grid_sort.h"
-
-// 2^-20 of slack covers the rounding of (p - lo) / cell: |quotient| < 2^27 inside the grid, two roundings of 2^-53
-// relative each, against a real difference of at most 1 / (1 + 2^-20) between neighbours.
-static inline double cl_cell_edge(double cell, double eps) { return fmax(cell, eps) * (1.0 + 0x1p-20); }
 
 __device__ __forceinline__ int cl_load(const int32_t *p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -69,21 +65,8 @@ template <class F>
 __device__ __forceinline__ void cl_neighbours(const KnGrid &G, const int32_t *__restrict__ start,
                                               const int32_t *__restrict__ counts, const float4 *__restrict__ sorted,
                                               const float4 q, double eps2, F f) {
-    int cx, cy, cz;
-    kn_cell(G, q.x, q.y, q.z, cx, cy, cz);
-    const int X = G.dims[0], Y = G.dims[1], Z = G.dims[2];
-    const int x0 = max(0, cx - 1), x1 = min(X - 1, cx + 1);
-    const double px = (double)q.x, py = (double)q.y, pz = (double)q.z;
-    for (int z = max(0, cz - 1); z <= min(Z - 1, cz + 1); ++z)
-        for (int y = max(0, cy - 1); y <= min(Y - 1, cy + 1); ++y) {
-            const int row = (z * Y + y) * X;
-            const int a = start[row + x0], e = start[row + x1] + counts[row + x1];
-            for (int j = a; j < e; ++j) {
-                const float4 o = sorted[j];
-                const double dx = (double)o.x - px, dy = (double)o.y - py, dz = (double)o.z - pz;
-                if ((dx * dx + dy * dy) + dz * dz <= eps2) f(j, __float_as_int(o.w));
-            }
-        }
+    kn_ball(G, start, counts, sorted, (double)q.x, (double)q.y, (double)q.z, eps2,
+            [&](int j, const float4 &o, double) { f(j, __float_as_int(o.w)); });
 }
 
 __global__ __launch_bounds__(256) void cl_init_kernel(int n, int32_t *__restrict__ labels, uint8_t *__restrict__ core,
@@ -230,7 +213,7 @@ extern "C" int gg_cluster_dbscan(int num_points, const float *points, const uint
         G.lo[d] = grid[d];
         G.dims[d] = dims[d];
     }
-    G.cell = cl_cell_edge(grid[3], eps);
+    G.cell = kn_radius_cell(grid[3], eps);
     GG_REQUIRE(isfinite(G.cell), "eps too large for the grid");
     const double eps2 = eps * eps;
     const int n = num_points;

@@ -5,7 +5,11 @@
 // atomics), exclusive offsets (prep_common.h scans), a scatter of (x, y, z, index) into cell order.  With FILTER the
 // sort takes only the points that are finite and, when a byte mask is given, have a non-zero byte; *total (device,
 // int64) then holds how many were taken.  Slot order within a cell follows the atomics.
+// kn_ball walks the sorted points within a radius of a query point (csrc/cluster.hip, csrc/register.hip): with a
+// cell edge of kn_radius_cell the 27 cells around the query's cell hold them all.
 #pragma once
+#include <math.h>
+
 #include "gg_common.h"
 #include "prep_common.h"
 
@@ -24,6 +28,37 @@ __device__ __forceinline__ int kn_cell(const KnGrid &G, float x, float y, float 
     cy = kn_axis((double)y, G.lo[1], G.cell, G.dims[1]);
     cz = kn_axis((double)z, G.lo[2], G.cell, G.dims[2]);
     return (cz * G.dims[1] + cy) * G.dims[0] + cx;
+}
+
+// The cell edge of a sort that is searched within `radius`: max(cell, radius) (1 + 2^-20), so that the cells of two
+// points within the radius differ by at most 1 per axis.  2^-20 of slack covers the rounding of (p - lo) / cell:
+// |quotient| < 2^27 inside the grid, two roundings of 2^-53 relative each, against a real difference of at most
+// 1 / (1 + 2^-20) between neighbours.  Clamping into the grid is monotone and 1-Lipschitz in the cell index, so it
+// holds for points outside the grid too.
+static inline double kn_radius_cell(double cell, double radius) { return fmax(cell, radius) * (1.0 + 0x1p-20); }
+
+// f(slot j, sorted[j], squared distance) for every sorted point o with (dx dx + dy dy) + dz dz <= r2 in fp64, dx the
+// fp64 difference o - q; q = (px, py, pz), fp64, need not be a sorted point.  The grid's cell edge
+// must be kn_radius_cell(., sqrt(r2)).  A row of 3 cells along x is contiguous in slot order: 9 slot ranges.
+template <class F>
+__device__ __forceinline__ void kn_ball(const KnGrid &G, const int32_t *__restrict__ start,
+                                        const int32_t *__restrict__ counts, const float4 *__restrict__ sorted, double px,
+                                        double py, double pz, double r2, F f) {
+    const int X = G.dims[0], Y = G.dims[1], Z = G.dims[2];
+    const int cx = kn_axis(px, G.lo[0], G.cell, X), cy = kn_axis(py, G.lo[1], G.cell, Y);
+    const int cz = kn_axis(pz, G.lo[2], G.cell, Z);
+    const int x0 = max(0, cx - 1), x1 = min(X - 1, cx + 1);
+    for (int zz = max(0, cz - 1); zz <= min(Z - 1, cz + 1); ++zz)
+        for (int yy = max(0, cy - 1); yy <= min(Y - 1, cy + 1); ++yy) {
+            const int row = (zz * Y + yy) * X;
+            const int a = start[row + x0], e = start[row + x1] + counts[row + x1];
+            for (int j = a; j < e; ++j) {
+                const float4 o = sorted[j];
+                const double dx = (double)o.x - px, dy = (double)o.y - py, dz = (double)o.z - pz;
+                const double d2 = (dx * dx + dy * dy) + dz * dz;
+                if (d2 <= r2) f(j, o, d2);
+            }
+        }
 }
 
 template <bool FILTER>

@@ -12,6 +12,7 @@ the contracts are in include/gg_raster.h and PARITY.md "Scene preparation", the 
     gen_image_info :163-181 (c2w, not w2c)                            write_images_txt
     gen_camera_info :185-201                                          write_cameras_txt (values of transforms.json)
     k_nearest_sklearn :315-331                                        knn_distances (gg_knn)
+    coloricp :47-83 (defined, never called)                           --refine-poses (register.refine_scan_poses)
     python -m gaussiangrasper_amd.prepare --scan DIR [--out DIR] [...]
 
 No GPU work falls back to the host: a missing device is an error."""
@@ -399,11 +400,14 @@ def read_frame(files, units: float):
 def prepare_scene(scan_dir: str, out_dir: Optional[str] = None, keep: int = KEEP, seed: int = 0,
                   depth_units_per_metre: float = 1.0, depth_range: Tuple[float, float] = DEPTH_RANGE,
                   z_range: Tuple[float, float] = Z_RANGE, frames_per_batch: int = 16, normal_vis: bool = False,
-                  force: bool = False) -> Dict:
+                  force: bool = False, refine_poses: bool = False, refine_options: Optional[Dict] = None) -> Dict:
     """Scan directory (transforms.json, images/, depths/, boundary_mask/) -> colmap/sparse/0/{cameras, images,
     points3D}.txt and normals/<stem>.npy (+ normal_vis/<stem>.png) under out_dir (default: the scan directory).
     Frames are paired by the stem of each frame's file_path; depth in metres is raw / depth_units_per_metre.
-    Returns counts and the timing breakdown (seconds: read, gpu, write)."""
+    refine_poses (off by default): the frames' poses are first refined by frame-to-model coloured ICP
+    (register.refine_scan_poses, keyword arguments in refine_options); the refined camera-to-base matrices go into
+    images.txt, the seed cloud and the normal maps, and transforms_refined.json and refine_report.json are written
+    next to them.  Returns counts and the timing breakdown (seconds: read, gpu, write)."""
     out_dir = out_dir or scan_dir
     if keep < 1 or frames_per_batch < 1 or not depth_units_per_metre > 0:
         raise ScanError("keep and frames_per_batch must be >= 1, depth_units_per_metre > 0")
@@ -423,6 +427,8 @@ def prepare_scene(scan_dir: str, out_dir: Optional[str] = None, keep: int = KEEP
     outputs += [os.path.join(out_dir, "normals", s + ".npy") for s in stems]
     if normal_vis:
         outputs += [os.path.join(out_dir, "normal_vis", s + ".png") for s in stems]
+    if refine_poses:
+        outputs += [os.path.join(out_dir, n) for n in ("transforms_refined.json", "refine_report.json")]
     existing = [p for p in outputs if os.path.exists(p)]
     if existing and not force:
         raise ScanError(f"{len(existing)} output file(s) exist, e.g. {existing[0]}: pass force=True (--force)")
@@ -435,6 +441,12 @@ def prepare_scene(scan_dir: str, out_dir: Optional[str] = None, keep: int = KEEP
     intr = np.array([cams[i - 1][:4] for i in cam_ids], dtype=np.float64)
     dev = default_device("prepare")
     t_read = t_gpu = t_write = 0.0
+    refined = None
+    if refine_poses:
+        t0 = time.perf_counter()
+        c2w, refined = _refine_poses(files, float(depth_units_per_metre), intr, c2w, depth_range, z_range,
+                                     refine_options or {})
+        t_gpu += time.perf_counter() - t0
     clouds, colours, pending = [], [], []
     with ThreadPoolExecutor(max_workers=max(1, min(READERS, os.cpu_count() or 1))) as pool:
         for b0 in range(0, len(frames), frames_per_batch):
@@ -474,12 +486,34 @@ def prepare_scene(scan_dir: str, out_dir: Optional[str] = None, keep: int = KEEP
     write_cameras_txt(outputs[0], meta, cams)
     write_images_txt(outputs[1], list(c2w), [os.path.basename(fr["file_path"]) for fr in frames], cam_ids)
     write_points3d_txt(outputs[2], sp, sc)
+    if refined is not None:
+        out_meta = dict(meta)
+        out_meta["frames"] = [dict(fr, transform_matrix=T.tolist()) for fr, T in zip(frames, c2w)]
+        with open(os.path.join(out_dir, "transforms_refined.json"), "w") as f:
+            json.dump(out_meta, f, indent=1)
+        with open(os.path.join(out_dir, "refine_report.json"), "w") as f:
+            json.dump([dict(row, name=os.path.basename(fr["file_path"])) for row, fr in zip(refined.report, frames)],
+                      f, indent=1)
     t2 = time.perf_counter()
     t_gpu += t1 - t0
     t_write += t2 - t1
     return {"frames": len(frames), "height": hw[0], "width": hw[1], "points": int(allp.shape[0]),
             "seed_points": int(sp.shape[0]), "read_s": t_read, "gpu_s": t_gpu, "write_s": t_write,
-            "out_dir": out_dir}
+            "out_dir": out_dir, **({"refined_frames": int(sum(refined.accepted)) - 1} if refined is not None else {})}
+
+
+def _refine_poses(files, units: float, intr: np.ndarray, c2w: np.ndarray, depth_range, z_range, options: Dict):
+    """(refined c2w (F, 4, 4), the ScanRefinement): every frame back-projected on its own at its given pose,
+    voxel-downsampled at the finest voxel size, then register.refine_scan_poses."""
+    from .register import VOXEL_RADIUS, refine_scan_poses, voxel_downsample
+    finest = min(options.get("voxel_radius", VOXEL_RADIUS)) * float(options.get("scale", 1.0))
+    clouds = []
+    for k, fl in enumerate(files):
+        d, m, rgb = read_frame(fl, units)
+        pts, cols = backproject_frames(d[None], m[None], rgb[None], intr[k:k + 1], c2w[k:k + 1], depth_range, z_range)
+        clouds.append(voxel_downsample(pts, cols.double() / 255.0, finest))
+    ref = refine_scan_poses(clouds, **options)
+    return np.array([ref.corrections[k] @ c2w[k] for k in range(len(files))]), ref
 
 
 def _write_normal(out_dir: str, stem: str, n: np.ndarray, vis: bool) -> None:
@@ -502,11 +536,15 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--frames-per-batch", type=int, default=16)
     ap.add_argument("--normal-vis", action="store_true", help="also write normal_vis/<stem>.png")
     ap.add_argument("--force", action="store_true", help="overwrite existing outputs")
+    ap.add_argument("--refine-poses", action="store_true",
+                    help="refine the frames' poses by frame-to-model coloured ICP first; also writes "
+                         "transforms_refined.json and refine_report.json")
     a = ap.parse_args(argv)
     try:
         r = prepare_scene(a.scan, a.out, keep=a.keep, seed=a.seed, depth_units_per_metre=a.depth_units_per_metre,
                           depth_range=tuple(a.depth_range), z_range=tuple(a.z_range),
-                          frames_per_batch=a.frames_per_batch, normal_vis=a.normal_vis, force=a.force)
+                          frames_per_batch=a.frames_per_batch, normal_vis=a.normal_vis, force=a.force,
+                          refine_poses=a.refine_poses)
     except ScanError as exc:
         print(f"error: {exc}", file=sys.stderr)
         return 2

@@ -788,6 +788,65 @@ int gg_cluster_stats(int num_points, const float *points, const float *weights, 
                      int num_clusters, int64_t *count, double *weight, double *centroid, float *bbox,
                      gg_stream_t stream);
 
+/* ---- registration: coloured ICP (PARITY "Registration") ------------------------------------------------
+ * Park, Zhou, Koltun, "Colored Point Cloud Registration Revisited" (ICCV 2017); the reference's coloricp
+ * (scripts/generate_data.py:47-83) runs Open3D's implementation of it.
+ *
+ * gg_cloud_frames: per-point surface frames of a cloud.  points fp32 [N][3]; intensity fp32 [N] (the mean of r, g, b
+ * in [0, 1]); radius > 0 finite (fp64); grid / dims as for gg_knn (the sort's cell edge is max(cell, radius)
+ * (1 + 2^-20): any grid gives the same result).  A point with a non-finite coordinate is invalid and nobody's
+ * neighbour: count 0, valid 0, normal NaN, gradient 0.  For every other point i:
+ *   neighbours:  j is a neighbour iff (dx dx + dy dy) + dz dz <= radius radius, in fp64 on the fp64 differences of
+ *                the fp32 coordinates, i itself included.  count int32 [N] = how many.
+ *   count < 3:   normal NaN, gradient 0, valid 0.  Otherwise valid 1 and:
+ *   normal:      the covariance of the neighbours about their mean, fp64, two passes; the unit eigenvector of its
+ *                smallest eigenvalue (cyclic Jacobi sweeps; the first axis among equal eigenvalues), signed so that
+ *                its largest-magnitude component is positive (first index on ties).
+ *   gradient d:  for each neighbour j != i with u = q_j - p_i the row A = u - (u.n) n, b = I_j - I_i, and one row
+ *                A = (count - 1) n, b = 0;  d = (A^T A)^-1 A^T b in fp64 with the fp64 normal before it is rounded.
+ *                d = 0 when count < 4 or the system is singular, which means here: det(A^T A) is not above
+ *                2^-40 (count - 1)^2 (tr / 2)^2, tr the sum of the squared lengths of the neighbours' rows (det equals
+ *                (count - 1)^2 times the determinant of the rows' 2 x 2 tangential moment, which (tr / 2)^2 bounds).
+ * Outputs: normals fp32 [N][3], gradients fp32 [N][3], count int32 [N], valid uint8 [N].  count and valid are exact;
+ * the fp64 sums run in the sort's slot order, which follows integer atomics, so normals and gradients may differ in
+ * their last bits from call to call.  Every neighbour within the radius is used (Open3D's hybrid search stops at the
+ * 30 nearest).  Cost: N x (points within the 27 cells around each) x 3 passes.
+ * `ws`: gg_cloud_frames_workspace(N, dims) bytes, 256-byte aligned (0 for sizes out of range).
+ *
+ * gg_icp_step: one Gauss-Newton linearisation of the coloured-ICP objective.  source fp32 [M][3], source_intensity
+ * fp32 [M]; the target's points fp32 [N][3], intensity fp32 [N] and gg_cloud_frames' normals, gradients and valid;
+ * grid / dims of the target as above (cell edge max(cell, max_dist) (1 + 2^-20)); transform (host, 12 finite
+ * doubles): the row-major 3 x 4 source-to-target [R | t]; max_dist > 0 finite; 0 <= lambda_geometric <= 1.
+ * Per source point p = (x, y, z), all fp64, nothing contracted to an FMA:
+ *   s_r = ((R[r][0] x + R[r][1] y) + R[r][2] z) + t[r];
+ *   correspondent: the target point q with valid != 0 and finite coordinates that has the smallest
+ *   (dx dx + dy dy) + dz dz <= max_dist max_dist (d = q - s), the smaller index among equal distances; none (-1)
+ *   when there is no such point or s is not finite.
+ *   With n, d, I_q of the correspondent, I_s of the source point, a = sqrt(lambda), b = sqrt(1 - lambda),
+ *   r_G = (s - q).n,  s' = s - r_G n,  I_proj = I_q + d.(s' - q),  g = -(d - (d.n) n):
+ *     geometric row    a [s x n, n],  residual a r_G;      photometric row  b [s x g, g],  residual b (I_s - I_proj);
+ *   the unknown is [omega (3), v (3)]: the update is [Rodrigues(omega) | v] applied on the left.
+ * sums (device, fp64 [32]): the 21 upper-triangle entries of J^T J, row-major; the 6 entries of J^T r; the number of
+ * source points with a correspondent; sum of squared distances; sum of r_G^2; sum of (I_s - I_proj)^2; one spare, 0.
+ * abs_sums (device, fp64 [32], may be NULL): the same sums with every product replaced by its absolute value.
+ * corr (device, int32 [M], may be NULL): each source point's correspondent or -1.
+ * The sums are formed in a fixed order (lanes of a wave, waves of a block, blocks) without floating-point atomics,
+ * and a correspondent never depends on the sort's slot order: the same inputs give the same bits.
+ * reuse_sort != 0: `ws` still holds the sort a previous call made for the same points, valid, grid, dims and
+ * max_dist, and it is not made again.
+ * `ws`: gg_icp_step_workspace(M, N, dims) bytes, 256-byte aligned (0 for sizes out of range). */
+#define GG_REGISTER_MAX_POINTS (1 << 30)
+size_t gg_cloud_frames_workspace(int num_points, const int32_t *dims);
+int gg_cloud_frames(int num_points, const float *points, const float *intensity, double radius, const double *grid,
+                    const int32_t *dims, float *normals, float *gradients, int32_t *count, uint8_t *valid, void *ws,
+                    size_t ws_bytes, gg_stream_t stream);
+size_t gg_icp_step_workspace(int num_source, int num_target, const int32_t *dims);
+int gg_icp_step(int num_source, const float *source, const float *source_intensity, int num_target,
+                const float *points, const float *intensity, const float *normals, const float *gradients,
+                const uint8_t *valid, const double *grid, const int32_t *dims, const double *transform,
+                double max_dist, double lambda_geometric, int reuse_sort, double *sums, double *abs_sums,
+                int32_t *corr, void *ws, size_t ws_bytes, gg_stream_t stream);
+
 /* ---- mesh export: TSDF fusion and marching tetrahedra (PARITY "Mesh export") ------------------------
  * The volume: dims (host, 3 ints) X, Y, Z lattice points, 1 <= each <= GG_TSDF_MAX_DIM, X Y Z <= GG_TSDF_MAX_POINTS;
  * grid (host, 6 floats) origin x, y, z and voxel size x, y, z (> 0, finite).  Point (i, j, k) has index
@@ -893,7 +952,9 @@ int gg_tsdf_mesh_emit(const int32_t *dims, const float *grid, const float *tsdf,
 #define GG_K_GRASP_PROPOSE 45 /* gg_grasp_propose: search, per-seed reduction and rows */
 #define GG_K_CLUSTER 46       /* gg_cluster_dbscan: sort, core, union, roots, relabel */
 #define GG_K_CLUSTER_STATS 47 /* gg_cluster_stats: all three launches */
-#define GG_K_IDS 48           /* ids are below this */
+#define GG_K_CLOUD_FRAMES 48  /* gg_cloud_frames: init, sort and the frames kernel */
+#define GG_K_ICP_STEP 49      /* gg_icp_step: the sort (unless reused), the step kernel and its finishing workgroup */
+#define GG_K_IDS 50           /* ids are below this */
 #define GG_PROF_NUM_KERNELS 32
 int gg_prof_enable(int on);
 int gg_prof_reset(void);
