@@ -15,7 +15,7 @@ calls of one view share ONE binning (tile sort), cached on the identity+version 
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -37,8 +37,43 @@ from .constants import BLOCK, CLIP_THRESH_DEFAULT, deg_from_sh, num_sh_bases  # 
 # (`colors_all` into SphericalHarmonics, `feature` into NDRasterizeGaussians, as at reference
 # :730,:747-753), the backward kernel adds into that buffer itself and returns no gradient for the
 # input.  Off unless a sink is registered: plain autograd semantics otherwise.
-_grad_sinks = {}        # id(param) -> (param, buffer, notify, defer)
-_deferred_sh = {}       # id(param) -> [(degrees_to_use, num_bases, viewdirs, v_rgb), ...] waiting for expansion
+class KeptView(NamedTuple):
+    """A view's SH gradient as its factors (12 B per Gaussian), waiting to be expanded into the sink's buffer."""
+    degrees_to_use: int
+    num_bases: int
+    viewdirs: Tensor
+    v_rgb: Tensor           # the colour cotangent, clamp mask applied
+
+
+_grad_sinks = {}        # id(param) -> GradSink
+_kept_sh = {}           # id(param) -> [KeptView, ...] of one (degrees_to_use, num_bases); outlives a re-registration
+
+
+class GradSink:
+    """Where the backward kernels add the gradient of leaf `param` (register_grad_sink)."""
+    __slots__ = ("param", "buffer", "notify", "defer")
+
+    def __init__(self, param: Tensor, buffer: Tensor, notify=None, defer=None):
+        self.param, self.buffer, self.notify, self.defer = param, buffer, notify, defer
+
+    def done(self) -> None:
+        """An accumulation into `buffer` has been enqueued."""
+        if self.notify is not None:
+            self.notify(self.param)
+
+    def keeps_sh(self) -> bool:
+        """Keep a view's SH gradient as its factors (or add it now): while more views follow or something is kept."""
+        return self.defer is not None and (self.defer() or bool(_kept_sh.get(id(self.param))))
+
+    def keep_sh(self, degrees_to_use: int, num_bases: int, viewdirs: Tensor, v_rgb: Tensor) -> None:
+        """Keep one view; views kept with another degree or basis count are expanded first (one expansion takes one),
+        everything when no view follows (no `defer`: ViewGeometry's one kernel leaves factors and always comes here)."""
+        kept = _kept_sh.get(id(self.param))
+        if kept and (kept[0].degrees_to_use, kept[0].num_bases) != (degrees_to_use, num_bases):
+            flush_grad_sinks()
+        _kept_sh.setdefault(id(self.param), []).append(KeptView(degrees_to_use, num_bases, viewdirs, v_rgb))
+        if self.defer is None or not self.defer():
+            flush_grad_sinks()
 
 
 def register_grad_sink(param: Tensor, buffer: Tensor, notify=None, defer=None) -> None:
@@ -53,44 +88,48 @@ def register_grad_sink(param: Tensor, buffer: Tensor, notify=None, defer=None) -
         raise ValueError("a gradient sink needs a leaf tensor that requires grad")
     if buffer.shape != param.shape or buffer.dtype != torch.float32 or not buffer.is_contiguous():
         raise ValueError("sink buffer must be a contiguous fp32 tensor of the parameter's shape")
-    _grad_sinks[id(param)] = (param, buffer, notify, defer)
+    _grad_sinks[id(param)] = GradSink(param, buffer, notify, defer)
 
 
 def clear_grad_sinks() -> None:
     _grad_sinks.clear()
-    _deferred_sh.clear()
+    _kept_sh.clear()
 
 
 def discard_deferred_grads() -> None:
     """Forget kept-but-not-expanded contributions (the caller zeroes the gradients they belong to)."""
-    _deferred_sh.clear()
+    _kept_sh.clear()
 
 
 def flush_grad_sinks() -> None:
     """Expand every kept SH contribution into its buffer now (gg_sh_bwd_multi) and fire the sinks' `notify`."""
-    for key in list(_deferred_sh):
-        pending = _deferred_sh.pop(key)
+    for key in list(_kept_sh):
+        kept = _kept_sh.pop(key)
         sink = _grad_sinks.get(key)
-        if sink is None or not pending:
+        if sink is None or not kept:
             continue
-        param, buf, notify = sink[0], sink[1], sink[2]
-        dev = buf.device
-        lib = _lib.load()
-        deg, k = pending[0][0], pending[0][1]
-        n = buf.shape[0]
-        nv = len(pending)
-        vd = (C.c_void_p * nv)(*[_ptr(p[2]) for p in pending])
-        vc = (C.c_void_p * nv)(*[_ptr(p[3]) for p in pending])
-        _lib.check(lib.gg_sh_bwd_multi(n, k, deg, nv, vd, vc, _ptr(buf), 1, _stream(dev)), "gg_sh_bwd_multi")
-        if notify is not None:
-            notify(param)
+        buf = sink.buffer
+        views = (C.c_void_p * len(kept))(*[_ptr(v.viewdirs) for v in kept])
+        v_rgbs = (C.c_void_p * len(kept))(*[_ptr(v.v_rgb) for v in kept])
+        _lib.check(_lib.load().gg_sh_bwd_multi(buf.shape[0], kept[0].num_bases, kept[0].degrees_to_use, len(kept),
+                                               views, v_rgbs, _ptr(buf), 1, _stream(buf.device)), "gg_sh_bwd_multi")
+        sink.done()
 
 
-def _sink_for(t: Tensor):
-    hit = _grad_sinks.get(id(t))
-    if hit is None or hit[0] is not t:
-        return None
-    return hit
+def _dense_f32(t: Tensor) -> bool:
+    return t.dtype == torch.float32 and t.is_contiguous()
+
+
+def _sink_for(t: Tensor, eligible: bool = True) -> Optional[GradSink]:
+    """The sink registered for this very tensor, where the calling operator can add into one (`eligible`)."""
+    hit = _grad_sinks.get(id(t)) if eligible else None
+    return hit if hit is not None and hit.param is t else None
+
+
+def _sinks_for_all(*tensors: Tensor):
+    """The sinks of fp32 contiguous tensors, all of them or None: one accumulate switch for the kernel."""
+    sinks = [_sink_for(t, _dense_f32(t)) for t in tensors]
+    return sinks if all(k is not None for k in sinks) else None
 
 
 # ------------------------------------------------------------------------------------------------
@@ -171,7 +210,7 @@ class ProjectGaussians(Function):
         if viewmat.numel() < 12 or projmat.numel() != 16:
             raise ValueError("viewmat must hold >= 12 and projmat exactly 16 elements")
         dev = _require_hip(means3d, scales, quats, viewmat, projmat)
-        ctx.sink = _sink_for(means3d) if (means3d.dtype == torch.float32 and means3d.is_contiguous()) else None
+        ctx.sink = _sink_for(means3d, _dense_f32(means3d))
         means3d, scales, quats = _f32(means3d), _f32(scales), _f32(quats)
         viewmat, projmat = _f32(viewmat), _f32(projmat)
         lib = _lib.load()
@@ -204,14 +243,13 @@ class ProjectGaussians(Function):
         dev = means3d.device
         n = means3d.shape[0]
         # v_xys / v_conics usually are columns of the blend backward's interleaved record: read in place
-        v_xys, xy_stride = (torch.zeros(n, 2, device=dev), 2) if v_xys is None else _rows_in_place(v_xys, 2)
-        v_conics, conic_stride = (torch.zeros(n, 3, device=dev), 3) if v_conics is None \
-            else _rows_in_place(v_conics, 3)
+        v_xys, xy_stride = _rows_or_zeros(v_xys, n, 2, dev)
+        v_conics, conic_stride = _rows_or_zeros(v_conics, n, 3, dev)
         v_depths = torch.zeros(n, device=dev) if v_depths is None else _f32(v_depths)
         v_scale = torch.empty(n, 3, dtype=torch.float32, device=dev)
         v_quat = torch.empty(n, 4, dtype=torch.float32, device=dev)
         sink = ctx.sink
-        v_mean3d = sink[1] if sink is not None else torch.empty(n, 3, dtype=torch.float32, device=dev)
+        v_mean3d = sink.buffer if sink is not None else torch.empty(n, 3, dtype=torch.float32, device=dev)
         lib = _lib.load()
         _lib.check(lib.gg_project_bwd_ex(
             n, _ptr(means3d), _ptr(scales), glob_scale, _ptr(quats), _ptr(viewmat), _ptr(projmat),
@@ -219,8 +257,7 @@ class ProjectGaussians(Function):
             _ptr(v_depths), _ptr(v_conics), conic_stride, _ptr(v_mean3d), 1 if sink is not None else 0,
             _ptr(v_scale), _ptr(v_quat), _stream(dev)), "gg_project_bwd_ex")
         if sink is not None:          # the means' gradient went straight into the registered buffer
-            if sink[2] is not None:
-                sink[2](sink[0])
+            sink.done()
             v_mean3d = None
         return (v_mean3d, v_scale, None, v_quat, None, None, None, None, None, None, None, None,
                 None, None)
@@ -248,7 +285,7 @@ class SphericalHarmonics(Function):
                                  _ptr(colors), _stream(dev)), "gg_sh_fwd")
         ctx.degrees_to_use, ctx.num_bases = int(degrees_to_use), k
         ctx.save_for_backward(viewdirs)
-        ctx.sink = _sink_for(coeffs) if coeffs.dtype == torch.float32 else None
+        ctx.sink = _sink_for(coeffs, coeffs.dtype == torch.float32)
         return colors
 
     @staticmethod
@@ -257,23 +294,15 @@ class SphericalHarmonics(Function):
         dev, n = viewdirs.device, viewdirs.shape[0]
         v_colors = _f32(v_colors)
         lib = _lib.load()
-        if ctx.sink is not None:      # add into the registered gradient buffer, hand autograd nothing
-            param, buf, notify, defer = ctx.sink
-            pending = _deferred_sh.get(id(param))
-            if defer is not None and (defer() or pending):
-                # keep (view directions, colour cotangent) and expand the step's views in one pass (see ShadeTail)
-                if pending and (pending[0][0], pending[0][1]) != (ctx.degrees_to_use, ctx.num_bases):
-                    flush_grad_sinks()
-                _deferred_sh.setdefault(id(param), []).append((ctx.degrees_to_use, ctx.num_bases, viewdirs,
-                                                               v_colors))
-                if not defer():
-                    flush_grad_sinks()
+        sink = ctx.sink
+        if sink is not None:          # add into the registered gradient buffer, hand autograd nothing
+            if sink.keeps_sh():       # expand the step's views in one pass (see ShadeTail)
+                sink.keep_sh(ctx.degrees_to_use, ctx.num_bases, viewdirs, v_colors)
                 return None, None, None
             _lib.check(lib.gg_sh_bwd_accumulate(n, ctx.num_bases, ctx.degrees_to_use, _ptr(viewdirs),
-                                                _ptr(v_colors), _ptr(buf), _stream(dev)),
+                                                _ptr(v_colors), _ptr(sink.buffer), _stream(dev)),
                        "gg_sh_bwd_accumulate")
-            if notify is not None:
-                notify(param)
+            sink.done()
             return None, None, None
         v_coeffs = torch.empty(n, ctx.num_bases, 3, dtype=torch.float32, device=dev)
         _lib.check(lib.gg_sh_bwd(n, ctx.num_bases, ctx.degrees_to_use, _ptr(viewdirs),
@@ -290,6 +319,11 @@ def _rows_in_place(t: Tensor, width: int):
         return t, t.stride(0)
     t = _f32(t).reshape(-1, width)
     return t, width
+
+
+def _rows_or_zeros(v: Optional[Tensor], n: int, width: int, dev: torch.device):
+    """_rows_in_place of a (N, width) cotangent; zeros for one that nobody produced (None)."""
+    return (torch.zeros(n, width, device=dev), width) if v is None else _rows_in_place(v, width)
 
 
 class ShadeTail(Function):
@@ -317,45 +351,35 @@ class ShadeTail(Function):
                                                  _stream(dev)), "gg_shade_tail_fwd")
         ctx.degrees_to_use, ctx.num_bases = int(degrees_to_use), k
         ctx.save_for_backward(viewdirs, mask)
-        ctx.sink = _sink_for(coeffs) if coeffs.dtype == torch.float32 else None
+        ctx.sink = _sink_for(coeffs, coeffs.dtype == torch.float32)
         return tail
 
     @staticmethod
     def backward(ctx, v_tail: Tensor):
         viewdirs, mask = ctx.saved_tensors
         dev, n = viewdirs.device, viewdirs.shape[0]
-        if v_tail.dtype != torch.float32 or v_tail.stride(1) != 1 or v_tail.stride(0) < 7:
-            v_tail = _f32(v_tail)      # rows of a wider record are read in place; anything else is copied
-        stride = v_tail.stride(0)
+        v_tail, stride = _rows_in_place(v_tail, 7)
         v_depths = torch.empty(n, dtype=torch.float32, device=dev)
         v_normals = torch.empty(n, 3, dtype=torch.float32, device=dev)
         lib = _lib.load()
-        if ctx.sink is not None:
-            param, buf, notify, defer = ctx.sink
-            pending = _deferred_sh.get(id(param))
-            if defer is not None and (defer() or pending):
-                # keep this view's SH gradient as its factors; expand all kept views once (the last view of the
-                # step, or flush_grad_sinks()).  Same degree / basis count as what is already kept, or flush first
-                if pending and (pending[0][0], pending[0][1]) != (ctx.degrees_to_use, ctx.num_bases):
-                    flush_grad_sinks()
-                v_rgb = torch.empty(n, 3, dtype=torch.float32, device=dev)
-                _lib.check(lib.gg_shade_tail_bwd_split(n, _ptr(v_tail), stride, _ptr(mask), _ptr(v_rgb),
-                                                       _ptr(v_depths), _ptr(v_normals), _stream(dev)),
-                           "gg_shade_tail_bwd_split")
-                _deferred_sh.setdefault(id(param), []).append((ctx.degrees_to_use, ctx.num_bases, viewdirs, v_rgb))
-                if not defer():
-                    flush_grad_sinks()
-                return None, None, None, v_depths, v_normals
-            _lib.check(lib.gg_shade_tail_bwd(n, ctx.num_bases, ctx.degrees_to_use, _ptr(viewdirs), _ptr(v_tail),
-                                             stride, _ptr(mask), _ptr(buf), 1, _ptr(v_depths), _ptr(v_normals),
-                                             _stream(dev)), "gg_shade_tail_bwd")
-            if notify is not None:
-                notify(param)
+        sink = ctx.sink
+        if sink is not None and sink.keeps_sh():
+            # keep this view's SH gradient as its factors; all kept views are expanded once (the last view of the
+            # step, or flush_grad_sinks())
+            v_rgb = torch.empty(n, 3, dtype=torch.float32, device=dev)
+            _lib.check(lib.gg_shade_tail_bwd_split(n, _ptr(v_tail), stride, _ptr(mask), _ptr(v_rgb),
+                                                   _ptr(v_depths), _ptr(v_normals), _stream(dev)),
+                       "gg_shade_tail_bwd_split")
+            sink.keep_sh(ctx.degrees_to_use, ctx.num_bases, viewdirs, v_rgb)
             return None, None, None, v_depths, v_normals
-        v_coeffs = torch.empty(n, ctx.num_bases, 3, dtype=torch.float32, device=dev)
+        v_coeffs = sink.buffer if sink is not None \
+            else torch.empty(n, ctx.num_bases, 3, dtype=torch.float32, device=dev)
         _lib.check(lib.gg_shade_tail_bwd(n, ctx.num_bases, ctx.degrees_to_use, _ptr(viewdirs), _ptr(v_tail), stride,
-                                         _ptr(mask), _ptr(v_coeffs), 0, _ptr(v_depths), _ptr(v_normals),
-                                         _stream(dev)), "gg_shade_tail_bwd")
+                                         _ptr(mask), _ptr(v_coeffs), 1 if sink is not None else 0, _ptr(v_depths),
+                                         _ptr(v_normals), _stream(dev)), "gg_shade_tail_bwd")
+        if sink is not None:
+            sink.done()
+            v_coeffs = None
         return None, None, v_coeffs, v_depths, v_normals
 
 
@@ -504,6 +528,19 @@ def bin_and_sort_gaussians(xys: Tensor, depths: Tensor, radii: Tensor, num_tiles
 # ------------------------------------------------------------------------------------------------
 # Rasterize
 # ------------------------------------------------------------------------------------------------
+def _blend_with_lists(bins: Binning, launch) -> bool:
+    """Enqueue the forward blend (`launch()` reads bins.gaussian_ids_sorted / tile_bins when called), then make the
+    lists' length known: a speculative binning's count is checked only with the blend already queued, and rebuilt
+    lists (capacity too small: rare) mean blending once more.  False: nothing is visible, there is no image."""
+    for attempt in range(2):
+        if bins.num_intersects is not None and bins.num_intersects < 1:
+            return False
+        launch()
+        if not bins.resolve():
+            break
+    return bins.num_intersects >= 1
+
+
 def _rasterize_forward(ctx, xys, depths, radii, conics, num_tiles_hit, colors, opacity,
                        img_height, img_width, background, three_channel_only):
     if colors.dtype == torch.uint8:
@@ -525,7 +562,7 @@ def _rasterize_forward(ctx, xys, depths, radii, conics, num_tiles_hit, colors, o
     dev = _require_hip(xys, depths, radii, conics, num_tiles_hit, colors, opacity, background)
     n, ch = xys.size(0), colors.size(1)
     # wide colour gradients can go straight into a registered buffer (32-channel rows stay dense)
-    ctx.sink = _sink_for(colors) if (ch > 3 and colors.dtype == torch.float32 and colors.is_contiguous()) else None
+    ctx.sink = _sink_for(colors, ch > 3 and _dense_f32(colors))
     img_height, img_width = int(img_height), int(img_width)
     xys_c, conics_c = _f32(xys), _f32(conics)
     colors_c, opacity_c, background = _f32(colors), _f32(opacity), _f32(background)
@@ -535,31 +572,21 @@ def _rasterize_forward(ctx, xys, depths, radii, conics, num_tiles_hit, colors, o
     ctx.opacity_shape = tuple(opacity.shape)
     lib = _lib.load()
     ws = _workspace(lib.gg_blend_workspace(n), dev)
-    out_img = final_Ts = final_idx = None
-    for attempt in range(2):
-        if bins.num_intersects is not None and bins.num_intersects < 1:
-            ctx.num_intersects = bins.num_intersects
-            out_img = torch.ones(img_height, img_width, ch, device=dev) * background
-            ctx.save_for_backward(xys_c, conics_c, colors_c, opacity_c)
-            return out_img
-        if out_img is None:
-            out_img = torch.empty(img_height, img_width, ch, dtype=torch.float32, device=dev)
-            final_Ts = torch.empty(img_height, img_width, dtype=torch.float32, device=dev)
-            final_idx = torch.empty(img_height, img_width, dtype=torch.int32, device=dev)
+    out_img = torch.empty(img_height, img_width, ch, dtype=torch.float32, device=dev)
+    final_Ts = torch.empty(img_height, img_width, dtype=torch.float32, device=dev)
+    final_idx = torch.empty(img_height, img_width, dtype=torch.int32, device=dev)
+
+    def launch():
         _lib.check(lib.gg_blend_fwd(ch, n, img_height, img_width, _ptr(bins.gaussian_ids_sorted),
                                     _ptr(bins.tile_bins), _ptr(xys_c), _ptr(conics_c), _ptr(colors_c),
                                     _ptr(opacity_c), _ptr(background), _ptr(out_img), _ptr(final_Ts),
-                                    _ptr(final_idx), _ptr(ws), ws.numel(), _stream(dev)),
-                   "gg_blend_fwd")
-        # the count of a speculative binning is checked only now, with the blend already queued;
-        # rebuilt lists (capacity too small: rare) mean blending once more
-        if not bins.resolve():
-            break
+                                    _ptr(final_idx), _ptr(ws), ws.numel(), _stream(dev)), "gg_blend_fwd")
+
+    visible = _blend_with_lists(bins, launch)
     ctx.num_intersects = bins.num_intersects
-    if bins.num_intersects < 1:
-        out_img = torch.ones(img_height, img_width, ch, device=dev) * background
+    if not visible:
         ctx.save_for_backward(xys_c, conics_c, colors_c, opacity_c)
-        return out_img
+        return torch.ones(img_height, img_width, ch, device=dev) * background
     # ws holds the packed per-Gaussian records of this call: the backward reuses them
     ctx.save_for_backward(xys_c, conics_c, colors_c, opacity_c, background,
                           bins.gaussian_ids_sorted, bins.tile_bins, final_Ts, final_idx, ws)
@@ -641,7 +668,7 @@ def _rasterize_backward(ctx, v_out_img):
         else:
             rec_g = torch.empty(n, 6, dtype=torch.float32, device=dev)
             if sink is not None:       # atomics add into the caller's gradient buffer: no memset, no add
-                v_colors = sink[1]
+                v_colors = sink.buffer
                 flags |= 2
             else:
                 v_colors = torch.empty(n, ch, dtype=torch.float32, device=dev)   # own allocation: aligned rows
@@ -653,8 +680,7 @@ def _rasterize_backward(ctx, v_out_img):
                    cstride, ws, flags, ctx.num_intersects)
         if flags & 2:
             v_colors = None
-            if sink[2] is not None:
-                sink[2](sink[0])
+            sink.done()
     return (v_xy, None, None, v_conic, None, v_colors, v_opacity.reshape(ctx.opacity_shape),
             None, None, None)
 
@@ -670,9 +696,7 @@ class RasterizeGaussians(Function):
         return _rasterize_forward(ctx, xys, depths, radii, conics, num_tiles_hit, colors, opacity,
                                   img_height, img_width, background, True)
 
-    @staticmethod
-    def backward(ctx, v_out_img):
-        return _rasterize_backward(ctx, v_out_img)
+    backward = staticmethod(_rasterize_backward)
 
 
 class NDRasterizeGaussians(Function):
@@ -685,9 +709,7 @@ class NDRasterizeGaussians(Function):
         return _rasterize_forward(ctx, xys, depths, radii, conics, num_tiles_hit, colors, opacity,
                                   img_height, img_width, background, False)
 
-    @staticmethod
-    def backward(ctx, v_out_img):
-        return _rasterize_backward(ctx, v_out_img)
+    backward = staticmethod(_rasterize_backward)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -717,10 +739,7 @@ class ActivateGaussians(Function):
                                                _stream(dev)), "gg_activate_fwd")
         ctx.save_for_backward(q, scales, opac, axis)
         ctx.opacity_shape = tuple(opacities.shape)
-        # all three registered, or none: one accumulate switch for the kernel
-        sinks = [_sink_for(t) if (t.dtype == torch.float32 and t.is_contiguous()) else None
-                 for t in (log_scales, quats, opacities)]
-        ctx.sinks = sinks if all(k is not None for k in sinks) else None
+        ctx.sinks = _sinks_for_all(log_scales, quats, opacities)
         ctx.mark_non_differentiable(viewdirs)
         return scales, quats_n, opac.reshape(ctx.opacity_shape), viewdirs, normals
 
@@ -734,20 +753,16 @@ class ActivateGaussians(Function):
         # v_opac usually is column 5 of the blend backward's interleaved record: read in place
         v_opac, opac_stride = (torch.zeros(n, 1, device=dev), 1) if v_opac is None \
             else _rows_in_place(v_opac.reshape(n, 1), 1)
-        if ctx.sinks is not None:     # add straight into the registered gradient buffers
-            v_ls, v_q, v_o = (k[1] for k in ctx.sinks)
-        else:
-            v_ls = torch.empty(n, 3, dtype=torch.float32, device=dev)
-            v_q = torch.empty(n, 4, dtype=torch.float32, device=dev)
-            v_o = torch.empty(n, 1, dtype=torch.float32, device=dev)
+        e = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        # with sinks: add straight into the registered gradient buffers
+        v_ls, v_q, v_o = (k.buffer for k in ctx.sinks) if ctx.sinks is not None else (e(n, 3), e(n, 4), e(n, 1))
         _lib.check(_lib.load().gg_activate_bwd_ex(
             n, _ptr(q), _ptr(scales), _ptr(opac), _ptr(axis), _ptr(v_scales), _ptr(v_quats_n), _ptr(v_opac),
             opac_stride, _ptr(v_normals), _ptr(v_ls), _ptr(v_q), _ptr(v_o), 1 if ctx.sinks is not None else 0,
             _stream(dev)), "gg_activate_bwd_ex")
         if ctx.sinks is not None:
-            for param, _buf, notify, _defer in ctx.sinks:
-                if notify is not None:
-                    notify(param)
+            for sink in ctx.sinks:
+                sink.done()
             return None, None, None, None, None
         return None, v_ls, v_q, v_o.reshape(ctx.opacity_shape), None
 
@@ -771,6 +786,12 @@ class _PartCtx:
 
     def set_materialize_grads(self, value):
         pass
+
+
+def _pose_outputs(lib, n: int, dev: torch.device):
+    """(v_viewmat (12,), v_full_proj (16,), workspace) of the kernels that sum the camera's gradient"""
+    return (torch.empty(12, dtype=torch.float32, device=dev), torch.empty(16, dtype=torch.float32, device=dev),
+            _workspace(lib.gg_pose_grad_workspace(n), dev))
 
 
 def _is_record_view(t: Optional[Tensor], base: int, offset: int, width: int, stride: int, n: int) -> bool:
@@ -825,10 +846,8 @@ class ViewGeometry(Function):
             raise ValueError("expected means (N,3), scales (N,3), quats (N,4), opacities (N,1)")
         if viewmat.numel() < 12 or full_proj.numel() != 16:
             raise ValueError("viewmat must hold >= 12 and projmat exactly 16 elements")
-        a.sinks = [_sink_for(t_) if (t_.dtype == torch.float32 and t_.is_contiguous()) else None
-                   for t_ in (log_scales, quats, opacities)]
-        a.sinks = a.sinks if all(k is not None for k in a.sinks) else None
-        p.sink = _sink_for(means) if (means.dtype == torch.float32 and means.is_contiguous()) else None
+        a.sinks = _sinks_for_all(log_scales, quats, opacities)
+        p.sink = _sink_for(means, _dense_f32(means))
         m, s_, q, o = _f32(means), _f32(log_scales), _f32(quats), _f32(opacities)
         c, vm, pm = _f32(cam_pos).reshape(-1), _f32(viewmat), _f32(full_proj)
         f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
@@ -895,36 +914,22 @@ class ViewGeometry(Function):
         lib = _lib.load()
         glob_scale, fx, fy, _cx, _cy, img_height, img_width = p.scalars
         v_rgb = torch.empty(n, 3, dtype=torch.float32, device=dev)
-        v_ls, v_q, v_o = (s_[1] for s_ in a.sinks)
-        if pose:
-            v_vm, v_pm = torch.empty(12, dtype=torch.float32, device=dev), torch.empty(16, dtype=torch.float32, device=dev)
-            ws = _workspace(lib.gg_pose_grad_workspace(n), dev)
-            _lib.check(lib.gg_view_bwd_pose(
-                n, C.c_void_p(base), stride, _ptr(mask), _ptr(means), _ptr(scales_e), glob_scale, _ptr(q_raw),
+        v_ls, v_q, v_o = (k.buffer for k in a.sinks)
+        args = (n, C.c_void_p(base), stride, _ptr(mask), _ptr(means), _ptr(scales_e), glob_scale, _ptr(q_raw),
                 _ptr(quats_n), _ptr(opac), _ptr(axis), _ptr(viewmat), _ptr(projmat), fx, fy, img_height, img_width,
-                _ptr(radii), _ptr(conics), _ptr(v_rgb), _ptr(p.sink[1]), _ptr(v_ls), _ptr(v_q), _ptr(v_o), _ptr(v_vm),
-                _ptr(v_pm), _ptr(ws), ws.numel(), _stream(dev)), "gg_view_bwd_pose")
+                _ptr(radii), _ptr(conics), _ptr(v_rgb), _ptr(p.sink.buffer), _ptr(v_ls), _ptr(v_q), _ptr(v_o))
+        if pose:
+            v_vm, v_pm, ws = _pose_outputs(lib, n, dev)
+            _lib.check(lib.gg_view_bwd_pose(*args, _ptr(v_vm), _ptr(v_pm), _ptr(ws), ws.numel(), _stream(dev)),
+                       "gg_view_bwd_pose")
             g_cam = ViewGeometry._camera_grads(ctx, v_vm, v_pm)
         else:
             g_cam = (None, None)
-            _lib.check(lib.gg_view_bwd(
-                n, C.c_void_p(base), stride, _ptr(mask), _ptr(means), _ptr(scales_e), glob_scale, _ptr(q_raw),
-                _ptr(quats_n), _ptr(opac), _ptr(axis), _ptr(viewmat), _ptr(projmat), fx, fy, img_height, img_width,
-                _ptr(radii), _ptr(conics), _ptr(v_rgb), _ptr(p.sink[1]), _ptr(v_ls), _ptr(v_q), _ptr(v_o),
-                _stream(dev)), "gg_view_bwd")
-        # the SH gradient: kept as its factors over the views of a step, or expanded now — ShadeTail.backward's rules
-        param, buf, notify, defer = t.sink
-        pending = _deferred_sh.get(id(param))
-        if pending and (pending[0][0], pending[0][1]) != (t.degrees_to_use, t.num_bases):
-            flush_grad_sinks()
-        _deferred_sh.setdefault(id(param), []).append((t.degrees_to_use, t.num_bases, viewdirs, v_rgb))
-        if defer is None or not defer():
-            flush_grad_sinks()              # (expands what is kept — this view included — and notifies the sink)
-        if p.sink[2] is not None:
-            p.sink[2](p.sink[0])
-        for param_, _buf, notify_, _defer in a.sinks:
-            if notify_ is not None:
-                notify_(param_)
+            _lib.check(lib.gg_view_bwd(*args, _stream(dev)), "gg_view_bwd")
+        # the kernel leaves the SH gradient as its factors: always kept, expanded at once unless more views follow
+        t.sink.keep_sh(t.degrees_to_use, t.num_bases, viewdirs, v_rgb)
+        for sink in (p.sink, *a.sinks):
+            sink.done()
         return (None,) * 6 + g_cam + (None,) * 8
 
     @staticmethod
@@ -933,13 +938,11 @@ class ViewGeometry(Function):
         means, scales, quats_n, viewmat, projmat, radii, conics = p.saved_tensors
         glob_scale, fx, fy, _cx, _cy, img_height, img_width = p.scalars
         dev, n = means.device, means.shape[0]
-        v_xys, xy_stride = (torch.zeros(n, 2, device=dev), 2) if v_xys is None else _rows_in_place(v_xys, 2)
-        v_conics, conic_stride = (torch.zeros(n, 3, device=dev), 3) if v_conics is None \
-            else _rows_in_place(v_conics, 3)
+        v_xys, xy_stride = _rows_or_zeros(v_xys, n, 2, dev)
+        v_conics, conic_stride = _rows_or_zeros(v_conics, n, 3, dev)
         v_depths = _f32(v_depths)
         lib = _lib.load()
-        v_vm, v_pm = torch.empty(12, dtype=torch.float32, device=dev), torch.empty(16, dtype=torch.float32, device=dev)
-        ws = _workspace(lib.gg_pose_grad_workspace(n), dev)
+        v_vm, v_pm, ws = _pose_outputs(lib, n, dev)
         _lib.check(lib.gg_project_pose_bwd(
             n, _ptr(means), _ptr(scales), glob_scale, _ptr(quats_n), _ptr(viewmat), _ptr(projmat), fx, fy, img_height,
             img_width, _ptr(radii), _ptr(conics), _ptr(v_xys), xy_stride, _ptr(v_depths), _ptr(v_conics), conic_stride,
@@ -994,8 +997,7 @@ class RasterizeSegments(Function):
             assert b.shape[0] == c.shape[1], f"incorrect shape of background color tensor, expected shape {c.shape[1]}"
         xys_c, conics_c, opacity_c = _f32(xys), _f32(conics), _f32(opacity)
         cols_c, bgs_c = [_f32(c) for c in cols], [_f32(b) for b in bgs]
-        ctx.sinks = [(_sink_for(c) if (c.shape[1] > 8 and c.dtype == torch.float32 and c.is_contiguous()) else None)
-                     for c in cols]
+        ctx.sinks = [_sink_for(c, c.shape[1] > 8 and _dense_f32(c)) for c in cols]
         bins = bin_and_sort_gaussians(xys, depths, radii, num_tiles_hit, img_height, img_width, speculative=True)
         lib = _lib.load()
         # splits may come as (splits, packed): `packed` = a blend workspace that already holds these Gaussians' records
@@ -1011,12 +1013,11 @@ class RasterizeSegments(Function):
         final_Ts = torch.empty(img_height, img_width, dtype=torch.float32, device=dev)
         final_idx = torch.empty(img_height, img_width, dtype=torch.int32, device=dev)
         outs = [torch.empty(img_height, img_width, c.shape[1], dtype=torch.float32, device=dev) for c in cols_c]
-        for attempt in range(2):
-            if bins.num_intersects is not None and bins.num_intersects < 1:
-                break
-            # a >= 32-channel array carries a <= 8-channel one through its first forward walk
-            wide = next((i for i, c in enumerate(cols_c) if c.shape[1] >= 32), None)
-            small = next((i for i, c in enumerate(cols_c) if c.shape[1] <= 8), None) if wide is not None else None
+        # a >= 32-channel array carries a <= 8-channel one through its first forward walk
+        wide = next((i for i, c in enumerate(cols_c) if c.shape[1] >= 32), None)
+        small = next((i for i, c in enumerate(cols_c) if c.shape[1] <= 8), None) if wide is not None else None
+
+        def launch():
             if small is not None and packed is not None:
                 _lib.check(lib.gg_blend_fwd_pair_packed(
                     cols_c[wide].shape[1], cols_c[small].shape[1], n, img_height, img_width,
@@ -1039,8 +1040,8 @@ class RasterizeSegments(Function):
                                             _ptr(bins.tile_bins), _ptr(xys_c), _ptr(conics_c), _ptr(c),
                                             _ptr(opacity_c), _ptr(b), _ptr(o), _ptr(final_Ts), _ptr(final_idx),
                                             _ptr(ws), ws.numel(), _stream(dev)), "gg_blend_fwd")
-            if not bins.resolve():
-                break
+
+        visible = _blend_with_lists(bins, launch)
         ctx.num_intersects = bins.num_intersects
         ctx.img = (img_height, img_width)
         ctx.opacity_shape = tuple(opacity.shape)
@@ -1058,7 +1059,7 @@ class RasterizeSegments(Function):
                 out_map.append((i, start, start + sz))
                 start += sz
         ctx.out_map = out_map
-        if bins.num_intersects < 1:
+        if not visible:
             outs = [torch.ones(img_height, img_width, c.shape[1], device=dev) * b for c, b in zip(cols_c, bgs_c)]
             ctx.save_for_backward(xys_c, conics_c, opacity_c, *cols_c)
         else:
@@ -1118,7 +1119,7 @@ class RasterizeSegments(Function):
             sink = ctx.sinks[wide]
             flags = 1
             if sink is not None:
-                v_colors = sink[1]
+                v_colors = sink.buffer
                 flags |= 2
             else:
                 v_colors = torch.empty(n, cols[wide].shape[1], dtype=torch.float32, device=dev)
@@ -1136,8 +1137,7 @@ class RasterizeSegments(Function):
                 "gg_blend_bwd_pair")
             grads[rider] = rec_g[:, 6:gwidth]
             if flags & 2:
-                if sink[2] is not None:
-                    sink[2](sink[0])
+                sink.done()
             else:
                 grads[wide] = v_colors
             order = [i for i in range(k) if i not in (wide, rider)]
@@ -1150,7 +1150,7 @@ class RasterizeSegments(Function):
             if i == rider:
                 v_colors, cstride = rec_g[:, 6:gwidth], gstride
             elif sink is not None:
-                v_colors, cstride = sink[1], 0
+                v_colors, cstride = sink.buffer, 0
                 flags |= 2
             else:
                 v_colors, cstride = torch.empty(n, ch, dtype=torch.float32, device=dev), 0
@@ -1159,8 +1159,7 @@ class RasterizeSegments(Function):
                        ws, flags, ctx.num_intersects)
             first = False
             if flags & 2:
-                if sink[2] is not None:
-                    sink[2](sink[0])
+                sink.done()
             else:
                 grads[i] = v_colors
         seg_grads = []
