@@ -3,7 +3,7 @@
 // DESIGN.md §3.4-3.5).
 #include <stdlib.h>
 
-#include "blend_common.h"
+#include "blend_launch.h"
 
 // ---------------------------------------------------------------------------------------------
 // prep: pack xys / conics / opacity into 32-byte records (one gather per list entry later)
@@ -25,42 +25,17 @@ extern "C" size_t gg_blend_workspace(int num_points) {
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
-void gg_launch_blend2_fwd(int width, int C, int off, int n, int img_h, int img_w, int tiles_x,
-                          int ntiles, const int32_t *ids, const int2 *bins, const GRec *rec,
-                          const float *colors, const float *background, float *out_img,
-                          float *final_Ts, int32_t *final_idx, int write_final, hipStream_t s);
-void gg_launch_blend2_bwd(int width, int C, int off, int n, int img_h, int img_w, int tiles_x,
-                          int ntiles, const int32_t *ids, const int2 *bins, const GRec *rec,
-                          const float *colors, const float *background, const float *final_Ts,
-                          const int32_t *final_idx, const float *v_out, float *v_xy, float *v_conic,
-                          float *v_colors, float *v_opacity, int gstride, int cstride, hipStream_t s,
-                          DetSlab det);
 size_t gg_sort_pairs_workspace(int64_t n);   // binning.hip: stable LSD radix sort of (key, value) pairs
 int gg_sort_pairs(int64_t n, uint32_t *keys, uint32_t *vals, int bits, void *ws, size_t ws_bytes, hipStream_t s);
-#ifdef GG_ABLATION
-void gg_launch_blend2_bwd_ablate(int abl, int C, int off, int img_h, int img_w, int tiles_x,
-                                 int ntiles, const int32_t *ids, const int2 *bins, const GRec *rec,
-                                 const float *colors, const float *background, const float *final_Ts,
-                                 const int32_t *final_idx, const float *v_out, float *v_xy,
-                                 float *v_conic, float *v_colors, float *v_opacity, int gstride, int cstride, hipStream_t s);
-#endif
 
-void gg_launch_blend2_bwd_pair(int C, int img_h, int img_w, int tiles_x, int ntiles, const int32_t *ids,
-                               const int2 *bins, const GRec *rec, const float *colors, const float *background,
-                               const float *final_Ts, const int32_t *final_idx, const float *v_out, float *v_xy,
-                               float *v_conic, float *v_colors, float *v_opacity, int gstride, int cstride,
-                               const float *colors2, int C2, const float *background2,
-                               const float *const *v_out2_parts, const int *v_out2_channels, int num_parts,
-                               float *v_colors2, int cstride2, hipStream_t s);
-void gg_launch_blend2_fwd_pair(int C, int img_h, int img_w, int tiles_x, int ntiles, const int32_t *ids,
-                               const int2 *bins, const GRec *rec, const float *colors, const float *background,
-                               float *out_img, float *final_Ts, int32_t *final_idx, const float *colors2, int C2,
-                               const float *background2, float *out_img2, hipStream_t s, int ncb, bool fast,
-                               unsigned bytes1, unsigned bytes2);
-void gg_launch_blend2_fwd_blocks(int ncb, int C, int off, int img_h, int img_w, int tiles_x, int ntiles,
-                                 const int32_t *ids, const int2 *bins, const GRec *rec, const float *colors,
-                                 const float *background, float *out_img, float *final_Ts, int32_t *final_idx,
-                                 int write_final, hipStream_t s);
+// GG_REQUIRE under the name of the public entry (`entry`) instead of the helper's __func__
+#define BLEND_REQUIRE(cond, msg)                 \
+    do {                                         \
+        if (!(cond)) {                           \
+            gg_set_error("%s: %s", entry, msg);  \
+            return GG_ERR_INVALID_ARG;           \
+        }                                        \
+    } while (0)
 
 // Channel chunking: calls with <= 3 channels (rgb / depth / normal) use the narrow kernels with
 // the colours inside the LDS record; anything wider is processed in chunks of 32 channels on the
@@ -90,34 +65,74 @@ extern "C" int gg_debug_set_fwd_blocks(int pair_blocks, int chunk_blocks) {
     g_fwd_blocks_chunk = chunk_blocks >= 2 && chunk_blocks <= 4 ? chunk_blocks : 1;
     return prev;
 }
-// the forward walks of channels [off, C) of a wide array beyond its first walk: as many 32-channel blocks per walk as
-// the policy allows (16-byte aligned rows), then the usual chunks
-static void fwd_remaining_chunks(int C, int off, int img_h, int img_w, int tiles_x, int ntiles, const int32_t *ids,
-                                 const int32_t *tile_bins, const GRec *rec, const float *colors, const float *background,
-                                 float *out_img, float *final_Ts, int32_t *final_idx, bool first_writes_final,
-                                 hipStream_t s) {
-    const bool aligned = (C % 4 == 0) && ((reinterpret_cast<uintptr_t>(out_img) & 15) == 0);
-    bool first = first_writes_final;
-    while (off < C) {
-        const int blocks = (C - off) / 32;
-        const int ncb = aligned && (off % 4 == 0) ? min(blocks, g_fwd_blocks_chunk) : 1;
-        if (ncb >= 2) {
-            gg_prof_begin(GG_K_BLEND_FWD + gg_width_index(32), s);
-            gg_launch_blend2_fwd_blocks(ncb, C, off, img_h, img_w, tiles_x, ntiles, ids, (const int2 *)tile_bins, rec,
-                                        colors, background, out_img, final_Ts, final_idx, first, s);
-            gg_prof_end(GG_K_BLEND_FWD + gg_width_index(32), s);
-            off += 32 * ncb;
-        } else {
-            const int w = chunk_width(C - off);
-            const int n = min(w, C - off);
-            gg_prof_begin(GG_K_BLEND_FWD + gg_width_index(w), s);
-            gg_launch_blend2_fwd(w, C, off, n, img_h, img_w, tiles_x, ntiles, ids, (const int2 *)tile_bins, rec, colors,
-                                 background, out_img, final_Ts, final_idx, first, s);
-            gg_prof_end(GG_K_BLEND_FWD + gg_width_index(w), s);
-            off += n;
-        }
-        first = false;
+
+// The chunk plan: f(chunk, index) for every walk of channels [off0, C), in launch order.  max_blocks > 1 (forward
+// walks with 16-byte aligned rows) lets a walk take up to that many full 32-channel blocks; the backward walks, and
+// with them the deterministic slab's columns (det_chunks), take one chunk each.
+template <typename F>
+static void for_each_chunk(int C, int off0, int max_blocks, F &&f) {
+    int index = 0;
+    for (int off = off0; off < C; ++index) {
+        const int blocks = off % 4 == 0 ? min((C - off) / 32, max_blocks) : 1;
+        const int w = blocks >= 2 ? 32 : chunk_width(C - off);
+        const BlendChunk ch = {off, w, min(w, C - off), blocks >= 2 ? blocks : 1};
+        f(ch, index);
+        off += ch.n * ch.blocks;
     }
+}
+static bool rows_aligned16(int C, const void *rows) { return C % 4 == 0 && (reinterpret_cast<uintptr_t>(rows) & 15) == 0; }
+
+// What every blend entry is handed besides its colour arrays and outputs.
+struct BlendCall {
+    int N, img_h, img_w;
+    const int32_t *ids, *tile_bins;
+    const float *xys, *conics, *opacity;
+    void *ws;
+    size_t ws_bytes;
+    gg_stream_t stream;
+};
+// The prologue of every entry: validate, check the workspace, pack the records unless the workspace holds them
+// already (records_ready: gg_blend_fwd_pair_packed, GG_BWD_WS_FROM_FORWARD), compute the tile grid, fill the walk.
+// ptrs_always / ptrs_points: the entry's own pointers that must be set whatever N is / when N > 0.  A backward
+// entry has nothing to do for N == 0: the prologue returns GG_OK before it looks at pointers, and the entry returns.
+static int blend_begin(const char *entry, const BlendCall &c, bool backward, bool ptrs_always, bool ptrs_points,
+                       bool records_ready, BlendWalk &w) {
+    BLEND_REQUIRE(c.N >= 0, "num_points < 0");
+    BLEND_REQUIRE(c.img_h > 0 && c.img_w > 0, "empty image");
+    if (backward && c.N == 0) return GG_OK;
+    BLEND_REQUIRE(c.tile_bins && ptrs_always, "null pointer");
+    BLEND_REQUIRE(c.N == 0 || (c.ids && ptrs_points), "null pointer");
+    if (c.ws == nullptr || c.ws_bytes < gg_blend_workspace(c.N)) {
+        gg_set_error("%s: workspace too small", entry);
+        return GG_ERR_WORKSPACE;
+    }
+    w.s = (hipStream_t)c.stream;
+    if (c.N > 0 && !records_ready) {
+        gg_prof_begin(GG_K_BLEND_PREP, w.s);
+        hipLaunchKernelGGL(blend_prep_kernel, dim3((c.N + 255) / 256), dim3(256), 0, w.s, c.N, c.xys, c.conics,
+                           c.opacity, (GRec *)c.ws);
+        gg_prof_end(GG_K_BLEND_PREP, w.s);
+    }
+    w.img_h = c.img_h;
+    w.img_w = c.img_w;
+    w.tiles_x = (c.img_w + GG_BLOCK - 1) / GG_BLOCK;
+    w.ntiles = w.tiles_x * ((c.img_h + GG_BLOCK - 1) / GG_BLOCK);
+    w.ids = c.ids;
+    w.bins = (const int2 *)c.tile_bins;
+    w.rec = (const GRec *)c.ws;
+    return GG_OK;
+}
+
+// the forward walks of channels [off0, C) of `src`: as many 32-channel blocks per walk as the policy allows (16-byte
+// aligned rows), then the usual chunks; the first of them writes final_Ts / final_idx when asked to
+static void fwd_chunks(const BlendWalk &w, const BlendColors &src, int off0, const BlendFwdOut &out,
+                       bool first_writes_final) {
+    const int max_blocks = rows_aligned16(src.C, out.out_img) ? g_fwd_blocks_chunk : 1;
+    for_each_chunk(src.C, off0, max_blocks, [&](const BlendChunk &ch, int index) {
+        gg_prof_begin(GG_K_BLEND_FWD + gg_width_index(ch.width), w.s);
+        gg_launch_blend2_fwd(w, src, ch, out, first_writes_final && index == 0);
+        gg_prof_end(GG_K_BLEND_FWD + gg_width_index(ch.width), w.s);
+    });
 }
 
 #ifdef GG_ABLATION
@@ -138,77 +153,50 @@ extern "C" int gg_blend_fwd(int C, int N, int img_h, int img_w, const int32_t *i
                             float *out_img, float *final_Ts, int32_t *final_idx, void *ws,
                             size_t ws_bytes, gg_stream_t stream) {
     GG_REQUIRE(C >= 1, "channels < 1");
-    GG_REQUIRE(N >= 0, "num_points < 0");
-    GG_REQUIRE(img_h > 0 && img_w > 0, "empty image");
-    GG_REQUIRE(tile_bins && background && out_img && final_Ts && final_idx, "null pointer");
-    GG_REQUIRE(N == 0 || (ids && xys && conics && colors && opacity), "null pointer");
-    if (ws == nullptr || ws_bytes < gg_blend_workspace(N)) {
-        gg_set_error("gg_blend_fwd: workspace too small");
-        return GG_ERR_WORKSPACE;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    GRec *rec = (GRec *)ws;
-    if (N > 0) {
-        gg_prof_begin(GG_K_BLEND_PREP, s);
-        hipLaunchKernelGGL(blend_prep_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, xys, conics,
-                           opacity, rec);
-        gg_prof_end(GG_K_BLEND_PREP, s);
-    }
-    const int tiles_x = (img_w + GG_BLOCK - 1) / GG_BLOCK, tiles_y = (img_h + GG_BLOCK - 1) / GG_BLOCK;
-    const int ntiles = tiles_x * tiles_y;
-    fwd_remaining_chunks(C, 0, img_h, img_w, tiles_x, ntiles, ids, tile_bins, rec, colors, background, out_img, final_Ts,
-                         final_idx, true, s);
+    BlendWalk w;
+    const int rc = blend_begin(__func__, {N, img_h, img_w, ids, tile_bins, xys, conics, opacity, ws, ws_bytes, stream},
+                               false, background && out_img && final_Ts && final_idx,
+                               xys && conics && colors && opacity, false, w);
+    if (rc != GG_OK) return rc;
+    fwd_chunks(w, {C, colors, background}, 0, {out_img, final_Ts, final_idx}, true);
     GG_CHECK_LAUNCH();
     return GG_OK;
 }
 
-static int blend_fwd_pair_impl(int C, int C2, int N, int img_h, int img_w, const int32_t *ids,
-                                 const int32_t *tile_bins, const float *xys, const float *conics,
-                                 const float *colors, const float *colors2, const float *opacity,
-                                 const float *background, const float *background2, float *out_img,
-                                 float *out_img2, float *final_Ts, int32_t *final_idx, void *ws,
-                                 size_t ws_bytes, gg_stream_t stream, bool fast, bool records_ready = false) {
-    GG_REQUIRE(C >= 32, "the first colour array needs >= 32 channels (its first chunk carries the second array)");
-    GG_REQUIRE(C2 >= 1 && C2 <= 8, "the second colour array has 1..8 channels");
-    GG_REQUIRE(N >= 0, "num_points < 0");
-    GG_REQUIRE(img_h > 0 && img_w > 0, "empty image");
-    GG_REQUIRE(tile_bins && background && background2 && out_img && out_img2 && final_Ts && final_idx,
-               "null pointer");
-    GG_REQUIRE(N == 0 || (ids && colors && colors2 && (records_ready || (xys && conics && opacity))), "null pointer");
-    if (ws == nullptr || ws_bytes < gg_blend_workspace(N)) {
-        gg_set_error("gg_blend_fwd_pair: workspace too small");
-        return GG_ERR_WORKSPACE;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    GRec *rec = (GRec *)ws;
-    if (N > 0 && !records_ready) {
-        gg_prof_begin(GG_K_BLEND_PREP, s);
-        hipLaunchKernelGGL(blend_prep_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, xys, conics,
-                           opacity, rec);
-        gg_prof_end(GG_K_BLEND_PREP, s);
-    }
-    const int tiles_x = (img_w + GG_BLOCK - 1) / GG_BLOCK, tiles_y = (img_h + GG_BLOCK - 1) / GG_BLOCK;
-    const int ntiles = tiles_x * tiles_y;
+// first array (>= 32 channels) and second array (<= 8) of the pair entries
+struct BlendPairIn {
+    BlendColors src, src2;
+};
+
+static int blend_fwd_pair_impl(const char *entry, const BlendCall &c, const BlendPairIn &in, const BlendFwdOut &out,
+                               float *out_img2, bool fast, bool records_ready) {
+    const int C = in.src.C, C2 = in.src2.C, N = c.N;
+    BLEND_REQUIRE(C >= 32, "the first colour array needs >= 32 channels (its first chunk carries the second array)");
+    BLEND_REQUIRE(C2 >= 1 && C2 <= 8, "the second colour array has 1..8 channels");
+    BlendWalk w;
+    const int rc = blend_begin(entry, c, false,
+                               in.src.background && in.src2.background && out.out_img && out_img2 && out.final_Ts &&
+                                   out.final_idx,
+                               in.src.colors && in.src2.colors && (records_ready || (c.xys && c.conics && c.opacity)),
+                               records_ready, w);
+    if (rc != GG_OK) return rc;
     // the batched kernel (fp32-grade images, not the exact summation order) needs 16-byte aligned image rows; without
     // them the exact-order kernel runs (its scalar-store epilogue takes any layout)
     // ... and reads the colour rows through buffer descriptors with 32-bit offsets (id x row bytes as a 24-bit multiply)
     const uint64_t bytes1 = (uint64_t)(N > 0 ? N : 1) * (uint64_t)C * 4u, bytes2 = (uint64_t)(N > 0 ? N : 1) * (uint64_t)C2 * 4u;
-    fast = fast && (C % 4 == 0) && ((reinterpret_cast<uintptr_t>(out_img) & 15) == 0) &&
-           ((reinterpret_cast<uintptr_t>(background) & 15) == 0) && N < (1 << 24) && C < (1 << 20) &&
-           bytes1 < ((uint64_t)1 << 32) && bytes2 < ((uint64_t)1 << 32);
+    const bool aligned = rows_aligned16(C, out.out_img);
+    fast = fast && aligned && ((reinterpret_cast<uintptr_t>(in.src.background) & 15) == 0) && N < (1 << 24) &&
+           C < (1 << 20) && bytes1 < ((uint64_t)1 << 32) && bytes2 < ((uint64_t)1 << 32);
     // the pair walk takes 1, 2 or 4 blocks of the first array (aligned rows)
     int pair_blocks = 1;
-    if (!fast && (C % 4 == 0) && ((reinterpret_cast<uintptr_t>(out_img) & 15) == 0)) {
+    if (!fast && aligned) {
         if (g_fwd_blocks_pair >= 4 && C >= 128) pair_blocks = 4;
         else if (g_fwd_blocks_pair >= 2 && C >= 64) pair_blocks = 2;
     }
-    gg_prof_begin(GG_K_BLEND_FWD_PAIR, s);
-    gg_launch_blend2_fwd_pair(C, img_h, img_w, tiles_x, ntiles, ids, (const int2 *)tile_bins, rec, colors,
-                              background, out_img, final_Ts, final_idx, colors2, C2, background2, out_img2, s,
-                              pair_blocks, fast, (unsigned)bytes1, (unsigned)bytes2);
-    gg_prof_end(GG_K_BLEND_FWD_PAIR, s);
-    fwd_remaining_chunks(C, 32 * pair_blocks, img_h, img_w, tiles_x, ntiles, ids, tile_bins, rec, colors, background,
-                         out_img, final_Ts, final_idx, false, s);
+    gg_prof_begin(GG_K_BLEND_FWD_PAIR, w.s);
+    gg_launch_blend2_fwd_pair(w, in.src, in.src2, out, out_img2, pair_blocks, fast, (unsigned)bytes1, (unsigned)bytes2);
+    gg_prof_end(GG_K_BLEND_FWD_PAIR, w.s);
+    fwd_chunks(w, in.src, 32 * pair_blocks, out, false);
     GG_CHECK_LAUNCH();
     return GG_OK;
 }
@@ -219,8 +207,9 @@ extern "C" int gg_blend_fwd_pair(int C, int C2, int N, int img_h, int img_w, con
                                  const float *background, const float *background2, float *out_img,
                                  float *out_img2, float *final_Ts, int32_t *final_idx, void *ws,
                                  size_t ws_bytes, gg_stream_t stream) {
-    return blend_fwd_pair_impl(C, C2, N, img_h, img_w, ids, tile_bins, xys, conics, colors, colors2, opacity, background,
-                               background2, out_img, out_img2, final_Ts, final_idx, ws, ws_bytes, stream, false);
+    return blend_fwd_pair_impl(__func__, {N, img_h, img_w, ids, tile_bins, xys, conics, opacity, ws, ws_bytes, stream},
+                               {{C, colors, background}, {C2, colors2, background2}}, {out_img, final_Ts, final_idx},
+                               out_img2, false, false);
 }
 
 extern "C" int gg_blend_fwd_pair_fast(int C, int C2, int N, int img_h, int img_w, const int32_t *ids,
@@ -229,8 +218,9 @@ extern "C" int gg_blend_fwd_pair_fast(int C, int C2, int N, int img_h, int img_w
                                       const float *background, const float *background2, float *out_img,
                                       float *out_img2, float *final_Ts, int32_t *final_idx, void *ws,
                                       size_t ws_bytes, gg_stream_t stream) {
-    return blend_fwd_pair_impl(C, C2, N, img_h, img_w, ids, tile_bins, xys, conics, colors, colors2, opacity, background,
-                               background2, out_img, out_img2, final_Ts, final_idx, ws, ws_bytes, stream, true);
+    return blend_fwd_pair_impl(__func__, {N, img_h, img_w, ids, tile_bins, xys, conics, opacity, ws, ws_bytes, stream},
+                               {{C, colors, background}, {C2, colors2, background2}}, {out_img, final_Ts, final_idx},
+                               out_img2, true, false);
 }
 
 // gg_blend_fwd_pair / gg_blend_fwd_pair_fast on a workspace that ALREADY holds the packed records of these Gaussians
@@ -240,9 +230,9 @@ extern "C" int gg_blend_fwd_pair_packed(int C, int C2, int N, int img_h, int img
                                         const float *background, const float *background2, float *out_img,
                                         float *out_img2, float *final_Ts, int32_t *final_idx, void *ws,
                                         size_t ws_bytes, int fast, gg_stream_t stream) {
-    return blend_fwd_pair_impl(C, C2, N, img_h, img_w, ids, tile_bins, nullptr, nullptr, colors, colors2, nullptr,
-                               background, background2, out_img, out_img2, final_Ts, final_idx, ws, ws_bytes, stream,
-                               fast != 0, true);
+    return blend_fwd_pair_impl(__func__, {N, img_h, img_w, ids, tile_bins, nullptr, nullptr, nullptr, ws, ws_bytes, stream},
+                               {{C, colors, background}, {C2, colors2, background2}}, {out_img, final_Ts, final_idx},
+                               out_img2, fast != 0, true);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -255,9 +245,9 @@ struct DetWs {
     void *sort_ws;
     size_t sort_bytes, bytes;
 };
-static int det_chunks(int C) {
+static int det_chunks(int C) {   // the backward walks of C channels: bwd_chunks launches exactly these
     int nc = 0;
-    for (int off = 0; off < C; ++nc) off += min(chunk_width(C - off), C - off);
+    for_each_chunk(C, 0, 1, [&](const BlendChunk &, int) { ++nc; });
     return nc;
 }
 static DetWs det_ws_layout(void *ws, int N, int C, int64_t I) {
@@ -337,79 +327,113 @@ __global__ __launch_bounds__(256) void det_reduce_kernel(int N, int C, int nchun
     }
 }
 
-static int blend_bwd_impl(int C, int N, int img_h, int img_w, const int32_t *ids,
-                          const int32_t *tile_bins, const float *xys, const float *conics,
-                          const float *colors, const float *opacity, const float *background,
-                          const float *final_Ts, const int32_t *final_idx, const float *v_out,
-                          float *v_xy, float *v_conic, float *v_colors, float *v_opacity,
-                          int geom_stride, int color_stride, void *ws, size_t ws_bytes,
-                          int flags, gg_stream_t stream, bool deterministic, int64_t I, void *det_ws,
-                          size_t det_ws_bytes) {
-    const bool ws_from_forward = (flags & GG_BWD_WS_FROM_FORWARD) != 0;
-    const bool acc_colors = (flags & GG_BWD_ACCUMULATE_COLORS) != 0;
-    const bool acc_geom = (flags & GG_BWD_ACCUMULATE_GEOM) != 0;
-    GG_REQUIRE(C >= 1, "channels < 1");
-    GG_REQUIRE(N >= 0, "num_points < 0");
-    GG_REQUIRE(img_h > 0 && img_w > 0, "empty image");
-    if (N == 0) return GG_OK;
-    GG_REQUIRE(ids && tile_bins && xys && conics && colors && opacity && background && final_Ts &&
-                   final_idx && v_out && v_xy && v_conic && v_colors && v_opacity,
-               "null pointer");
-    if (ws == nullptr || ws_bytes < gg_blend_workspace(N)) {
-        gg_set_error("gg_blend_bwd: workspace too small");
-        return GG_ERR_WORKSPACE;
+// ---------------------------------------------------------------------------------------------
+// backward
+// ---------------------------------------------------------------------------------------------
+// The kernels accumulate with atomics, so the gradient arrays start at zero.  Which regions a call clears:
+//   geometry   interleaved records {xy, conic, opacity[, colours | second array]} of gstride floats per Gaussian: the
+//              whole records; dense: v_xy, v_conic, v_opacity.  GG_BWD_ACCUMULATE_GEOM (a later segment of a
+//              multi-segment call): none — the geometry gradients, and colours inside the record, keep what the
+//              earlier segments added.
+//   colours    the (stride-padded) rows, unless GG_BWD_ACCUMULATE_COLORS is set or a single-array call has them inside
+//              the record.  A pair call always clears its first array's rows.
+//   second     the pair call's second array (g2), unless it lives inside the record.
+// One fill covers everything when a single-array call laid dense arrays back to back: v_xy | v_conic | v_opacity |
+// v_colors.  The order is the one the entries have always issued: a single-array call clears dense colours between
+// v_conic and v_opacity, a pair call after the second array.
+struct BlendFills {
+    int count;
+    struct {
+        float *p;
+        size_t floats;
+    } f[5];
+};
+static int grad_zero_plan(const char *entry, const BlendGradOut &g, int C, const BlendGrad2 *g2, int C2, int flags,
+                          size_t n, BlendFills &fills) {
+    const bool acc_colors = (flags & GG_BWD_ACCUMULATE_COLORS) != 0, acc_geom = (flags & GG_BWD_ACCUMULATE_GEOM) != 0;
+    const bool colors_in_record = !g2 && g.gstride > 0 && g.cstride == g.gstride && g.v_colors == g.v_xy + 6;
+    const bool second_in_record = g2 && g.gstride > 0 && g2->cstride == g.gstride && g2->v_colors == g.v_xy + 6;
+    BLEND_REQUIRE(g.gstride == 0 || g.gstride >= 6, "geom_stride must be 0 (dense) or >= 6");
+    BLEND_REQUIRE(g.cstride == 0 || g.cstride >= C, "color_stride must be 0 (dense) or >= channels");
+    BLEND_REQUIRE(!g2 || g2->cstride == 0 || g2->cstride >= C2, "color_stride2 must be 0 (dense) or >= channels2");
+    BLEND_REQUIRE(!acc_colors || !colors_in_record,
+                  "GG_BWD_ACCUMULATE_COLORS needs v_colors outside the interleaved geometry record");
+    BLEND_REQUIRE(g.gstride == 0 || (g.v_conic == g.v_xy + 2 && g.v_opacity == g.v_xy + 5),
+                  "interleaved geometry gradients: v_conic = v_xy + 2 and v_opacity = v_xy + 5 expected");
+    BLEND_REQUIRE(!second_in_record || g.gstride >= 6 + C2, "the record is too short for the second array's gradients");
+    fills.count = 0;
+    auto add = [&](float *p, size_t floats) {
+        fills.f[fills.count].p = p;
+        fills.f[fills.count++].floats = floats;
+    };
+    const bool zero_colors = !acc_colors && !colors_in_record;
+    const size_t crow = g.cstride ? g.cstride : C;
+    if (!g2 && !acc_geom && zero_colors && g.gstride == 0 && g.cstride == 0 && g.v_conic == g.v_xy + 2 * n &&
+        g.v_opacity == g.v_conic + 3 * n && g.v_colors == g.v_opacity + n) {
+        add(g.v_xy, (6 + (size_t)C) * n);
+        return GG_OK;
     }
-    hipStream_t s = (hipStream_t)stream;
-    GRec *rec = (GRec *)ws;
-    if (!ws_from_forward) {
-        gg_prof_begin(GG_K_BLEND_PREP, s);
-        hipLaunchKernelGGL(blend_prep_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, xys, conics,
-                           opacity, rec);
-        gg_prof_end(GG_K_BLEND_PREP, s);
+    const bool colors_first = !g2 && !acc_geom && g.gstride == 0;   // ... before v_opacity
+    if (!acc_geom) {
+        if (g.gstride > 0) {
+            add(g.v_xy, (size_t)g.gstride * n);
+        } else {
+            add(g.v_xy, 2 * n);
+            add(g.v_conic, 3 * n);
+            if (colors_first && zero_colors) add(g.v_colors, crow * n);
+            add(g.v_opacity, n);
+        }
     }
-    // the kernels accumulate with atomics: the four gradient arrays start at zero (one memset when
-    // the caller laid them out back to back: v_xy | v_conic | v_opacity | v_colors)
-    GG_REQUIRE(geom_stride == 0 || geom_stride >= 6, "geom_stride must be 0 (dense) or >= 6");
-    GG_REQUIRE(color_stride == 0 || color_stride >= C, "color_stride must be 0 (dense) or >= channels");
-    GG_REQUIRE(!acc_colors || !(color_stride == geom_stride && geom_stride > 0 && v_colors == v_xy + 6),
-               "GG_BWD_ACCUMULATE_COLORS needs v_colors outside the interleaved geometry record");
-    bool fail;
-    const size_t n = (size_t)N;
-    if (acc_geom) {
-        // a later segment of a multi-segment call: the geometry gradients (and colours that live in
-        // the same record) keep what the earlier segments added; separate colour arrays are cleared
-        GG_REQUIRE(geom_stride == 0 || (v_conic == v_xy + 2 && v_opacity == v_xy + 5),
-                   "interleaved geometry gradients: v_conic = v_xy + 2 and v_opacity = v_xy + 5 expected");
-        fail = false;
-        const bool in_record = geom_stride > 0 && color_stride == geom_stride && v_colors == v_xy + 6;
-        if (!in_record && !acc_colors)
-            fail = gg_fill_async(v_colors, 0, sizeof(float) * (color_stride ? color_stride : C) * n, s) !=
-                   hipSuccess;
-    } else if (geom_stride > 0) {
-        // interleaved records {xy, conic, opacity[, colours]} of geom_stride floats per Gaussian
-        GG_REQUIRE(v_conic == v_xy + 2 && v_opacity == v_xy + 5, "interleaved geometry gradients: "
-                   "v_conic = v_xy + 2 and v_opacity = v_xy + 5 expected");
-        fail = gg_fill_async(v_xy, 0, sizeof(float) * geom_stride * n, s) != hipSuccess;
-        if (!(color_stride == geom_stride && v_colors == v_xy + 6) && !acc_colors)   // colours live elsewhere
-            fail |= gg_fill_async(v_colors, 0, sizeof(float) * (color_stride ? color_stride : C) * n, s) !=
-                    hipSuccess;
-    } else if (!acc_colors && color_stride == 0 && v_conic == v_xy + 2 * n && v_opacity == v_conic + 3 * n &&
-               v_colors == v_opacity + n) {
-        fail = gg_fill_async(v_xy, 0, sizeof(float) * (6 + (size_t)C) * n, s) != hipSuccess;
-    } else {
-        fail = gg_fill_async(v_xy, 0, sizeof(float) * 2 * n, s) != hipSuccess;
-        fail |= gg_fill_async(v_conic, 0, sizeof(float) * 3 * n, s) != hipSuccess;
-        if (!acc_colors)
-            fail |= gg_fill_async(v_colors, 0, sizeof(float) * (color_stride ? color_stride : C) * n, s) !=
-                    hipSuccess;
-        fail |= gg_fill_async(v_opacity, 0, sizeof(float) * n, s) != hipSuccess;
-    }
+    if (g2 && !second_in_record) add(g2->v_colors, (size_t)(g2->cstride ? g2->cstride : C2) * n);
+    if (!colors_first && zero_colors) add(g.v_colors, crow * n);
+    return GG_OK;
+}
+static int zero_grads(const char *entry, const BlendGradOut &g, int C, const BlendGrad2 *g2, int C2, int flags, size_t n,
+                      hipStream_t s) {
+    BlendFills fills;
+    const int rc = grad_zero_plan(entry, g, C, g2, C2, flags, n, fills);
+    if (rc != GG_OK) return rc;
+    bool fail = false;
+    for (int k = 0; k < fills.count; ++k)
+        fail |= gg_fill_async(fills.f[k].p, 0, sizeof(float) * fills.f[k].floats, s) != hipSuccess;
     if (fail) {
-        gg_set_error("gg_blend_bwd: memset failed");
+        gg_set_error("%s: memset failed", entry);
         return GG_ERR_LAUNCH;
     }
-    const int tiles_x = (img_w + GG_BLOCK - 1) / GG_BLOCK, tiles_y = (img_h + GG_BLOCK - 1) / GG_BLOCK;
-    const int ntiles = tiles_x * tiles_y;
+    return GG_OK;
+}
+
+// the backward walks of channels [off0, C) of `src`, one chunk each (the plan det_chunks counts), adding to `g` — or,
+// with a slab (det.p), storing into the columns of their chunk
+static void bwd_chunks(const BlendWalk &w, const BlendColors &src, int off0, const BlendBwdIn &in, const BlendGradOut &g,
+                       DetSlab det) {
+    for_each_chunk(src.C, off0, 1, [&](const BlendChunk &ch, int index) {
+        det.coff = ch.off;
+        det.goff = src.C + 6 * index;
+        gg_prof_begin(GG_K_BLEND_BWD + gg_width_index(ch.width), w.s);
+#ifdef GG_ABLATION
+        if ((ch.width == 3 && g_ablate > 0 && g_ablate < 10) || (ch.width == 32 && ch.n == 32 && g_ablate > 10))
+            gg_launch_blend2_bwd_ablate(g_ablate, w, src, ch, in, g);
+        else
+#endif
+            gg_launch_blend2_bwd(w, src, ch, in, g, det);
+        gg_prof_end(GG_K_BLEND_BWD + gg_width_index(ch.width), w.s);
+    });
+}
+
+// gg_blend_bwd, and gg_blend_bwd_deterministic (det_ws != nullptr or I == 0 with `deterministic`)
+static int blend_bwd_impl(const char *entry, const BlendCall &c, const BlendColors &src, const BlendBwdIn &in,
+                          const BlendGradOut &g, int flags, bool deterministic, int64_t I, void *det_ws) {
+    const int C = src.C, N = c.N;
+    BLEND_REQUIRE(C >= 1, "channels < 1");
+    BlendWalk w;
+    int rc = blend_begin(entry, c, true, true,
+                         c.xys && c.conics && src.colors && c.opacity && src.background && in.final_Ts && in.final_idx &&
+                             in.v_out && g.v_xy && g.v_conic && g.v_colors && g.v_opacity,
+                         (flags & GG_BWD_WS_FROM_FORWARD) != 0, w);
+    if (rc != GG_OK || N == 0) return rc;
+    rc = zero_grads(entry, g, C, nullptr, 0, flags, (size_t)N, w.s);
+    if (rc != GG_OK) return rc;
     DetSlab det = DetSlab();
     DetWs dw;
     const int nchunks = det_chunks(C);
@@ -418,47 +442,26 @@ static int blend_bwd_impl(int C, int N, int img_h, int img_w, const int32_t *ids
         dw = det_ws_layout(det_ws, N, C, I);
         det.p = dw.slab;
         det.ks = C + 6 * nchunks;
-        if (gg_fill_async(dw.slab, 0, sizeof(float) * 4 * (size_t)det.ks * (size_t)I, s) != hipSuccess ||
-            gg_fill_async(dw.seg, 0, 8 * (size_t)N, s) != hipSuccess) {
+        if (gg_fill_async(dw.slab, 0, sizeof(float) * 4 * (size_t)det.ks * (size_t)I, w.s) != hipSuccess ||
+            gg_fill_async(dw.seg, 0, 8 * (size_t)N, w.s) != hipSuccess) {
             gg_set_error("gg_blend_bwd_deterministic: memset failed");
             return GG_ERR_LAUNCH;
         }
     }
-    int chunk = 0;
-    for (int off = 0; off < C; ++chunk) {
-        const int w = chunk_width(C - off);
-        const int n = min(w, C - off);
-        det.coff = off;
-        det.goff = C + 6 * chunk;
-        gg_prof_begin(GG_K_BLEND_BWD + gg_width_index(w), s);
-#ifdef GG_ABLATION
-        if ((w == 3 && g_ablate > 0 && g_ablate < 10) || (w == 32 && n == 32 && g_ablate > 10))
-            gg_launch_blend2_bwd_ablate(g_ablate, C, off, img_h, img_w, tiles_x, ntiles, ids,
-                                        (const int2 *)tile_bins, rec, colors, background, final_Ts,
-                                        final_idx, v_out, v_xy, v_conic, v_colors, v_opacity, geom_stride,
-                                        color_stride, s);
-        else
-#endif
-            gg_launch_blend2_bwd(w, C, off, n, img_h, img_w, tiles_x, ntiles, ids,
-                                 (const int2 *)tile_bins, rec, colors, background, final_Ts,
-                                 final_idx, v_out, v_xy, v_conic, v_colors, v_opacity, geom_stride,
-                                 color_stride, s, det);
-        gg_prof_end(GG_K_BLEND_BWD + gg_width_index(w), s);
-        off += n;
-    }
+    bwd_chunks(w, src, 0, in, g, det);
     if (deterministic) {
         const unsigned nb = (unsigned)((I + 255) / 256);
-        hipLaunchKernelGGL(det_pairs_kernel, dim3(nb), dim3(256), 0, s, I, ids, dw.keys, dw.vals);
+        hipLaunchKernelGGL(det_pairs_kernel, dim3(nb), dim3(256), 0, w.s, I, c.ids, dw.keys, dw.vals);
         int bits = 1;
         while (((int64_t)1 << bits) < (int64_t)N) ++bits;
-        const int rc = gg_sort_pairs(I, dw.keys, dw.vals, bits, dw.sort_ws, dw.sort_bytes, s);
+        rc = gg_sort_pairs(I, dw.keys, dw.vals, bits, dw.sort_ws, dw.sort_bytes, w.s);
         if (rc != GG_OK) {
             gg_set_error("gg_blend_bwd_deterministic: sort failed");
             return rc;
         }
-        hipLaunchKernelGGL(det_edges_kernel, dim3(nb), dim3(256), 0, s, I, N, dw.keys, dw.seg);
-        hipLaunchKernelGGL(det_reduce_kernel, dim3((N + 3) / 4), dim3(256), 0, s, N, C, nchunks, det.ks, dw.slab,
-                           dw.vals, dw.seg, v_xy, v_conic, v_colors, v_opacity, geom_stride, color_stride);
+        hipLaunchKernelGGL(det_edges_kernel, dim3(nb), dim3(256), 0, w.s, I, N, dw.keys, dw.seg);
+        hipLaunchKernelGGL(det_reduce_kernel, dim3((N + 3) / 4), dim3(256), 0, w.s, N, C, nchunks, det.ks, dw.slab,
+                           dw.vals, dw.seg, g.v_xy, g.v_conic, g.v_colors, g.v_opacity, g.gstride, g.cstride);
     }
     GG_CHECK_LAUNCH();
     return GG_OK;
@@ -471,96 +474,9 @@ extern "C" int gg_blend_bwd(int C, int N, int img_h, int img_w, const int32_t *i
                             float *v_xy, float *v_conic, float *v_colors, float *v_opacity,
                             int geom_stride, int color_stride, void *ws, size_t ws_bytes,
                             int flags, gg_stream_t stream) {
-    return blend_bwd_impl(C, N, img_h, img_w, ids, tile_bins, xys, conics, colors, opacity, background, final_Ts,
-                          final_idx, v_out, v_xy, v_conic, v_colors, v_opacity, geom_stride, color_stride, ws,
-                          ws_bytes, flags, stream, false, 0, nullptr, 0);
-}
-
-static int blend_bwd_pair_impl(int C, int C2, int N, int img_h, int img_w, const int32_t *ids,
-                                 const int32_t *tile_bins, const float *xys, const float *conics,
-                                 const float *colors, const float *colors2, const float *opacity,
-                                 const float *background, const float *background2, const float *final_Ts,
-                                 const int32_t *final_idx, const float *v_out, const float *const *v_out2_parts,
-                                 const int *v_out2_channels, int num_parts, float *v_xy,
-                                 float *v_conic, float *v_colors, float *v_colors2, float *v_opacity,
-                                 int geom_stride, int color_stride, int color_stride2, void *ws, size_t ws_bytes,
-                                 int flags, gg_stream_t stream) {
-    const bool ws_from_forward = (flags & GG_BWD_WS_FROM_FORWARD) != 0;
-    const bool acc_colors = (flags & GG_BWD_ACCUMULATE_COLORS) != 0;
-    GG_REQUIRE((flags & GG_BWD_ACCUMULATE_GEOM) == 0, "gg_blend_bwd_pair writes the geometry gradients itself");
-    GG_REQUIRE(C >= 32, "the first colour array needs >= 32 channels (its first chunk carries the second array)");
-    GG_REQUIRE(C2 >= 1 && C2 <= 8, "the second colour array has 1..8 channels");
-    GG_REQUIRE(N >= 0, "num_points < 0");
-    GG_REQUIRE(img_h > 0 && img_w > 0, "empty image");
-    if (N == 0) return GG_OK;
-    GG_REQUIRE(ids && tile_bins && xys && conics && colors && colors2 && opacity && background && background2 &&
-                   final_Ts && final_idx && v_out && v_out2_parts && v_out2_channels && v_xy && v_conic && v_colors &&
-                   v_colors2 && v_opacity,
-               "null pointer");
-    GG_REQUIRE(num_parts >= 1 && num_parts <= 3, "the second cotangent comes as 1..3 images");
-    {
-        int total = 0;
-        for (int k = 0; k < num_parts; ++k) {
-            GG_REQUIRE(v_out2_parts[k] != nullptr && v_out2_channels[k] >= 1, "empty part of the second cotangent");
-            total += v_out2_channels[k];
-        }
-        GG_REQUIRE(total == C2, "the parts of the second cotangent must add up to channels2");
-    }
-    GG_REQUIRE(geom_stride == 0 || geom_stride >= 6, "geom_stride must be 0 (dense) or >= 6");
-    GG_REQUIRE(color_stride == 0 || color_stride >= C, "color_stride must be 0 (dense) or >= channels");
-    GG_REQUIRE(color_stride2 == 0 || color_stride2 >= C2, "color_stride2 must be 0 (dense) or >= channels2");
-    GG_REQUIRE(geom_stride == 0 || (v_conic == v_xy + 2 && v_opacity == v_xy + 5),
-               "interleaved geometry gradients: v_conic = v_xy + 2 and v_opacity = v_xy + 5 expected");
-    if (ws == nullptr || ws_bytes < gg_blend_workspace(N)) {
-        gg_set_error("gg_blend_bwd_pair: workspace too small");
-        return GG_ERR_WORKSPACE;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    GRec *rec = (GRec *)ws;
-    if (!ws_from_forward) {
-        gg_prof_begin(GG_K_BLEND_PREP, s);
-        hipLaunchKernelGGL(blend_prep_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, xys, conics, opacity, rec);
-        gg_prof_end(GG_K_BLEND_PREP, s);
-    }
-    const size_t n = (size_t)N;
-    const bool in_record = geom_stride > 0 && color_stride2 == geom_stride && v_colors2 == v_xy + 6;
-    GG_REQUIRE(!in_record || geom_stride >= 6 + C2, "the record is too short for the second array's gradients");
-    bool fail = false;
-    if (geom_stride > 0) {
-        fail |= gg_fill_async(v_xy, 0, sizeof(float) * geom_stride * n, s) != hipSuccess;
-    } else {
-        fail |= gg_fill_async(v_xy, 0, sizeof(float) * 2 * n, s) != hipSuccess;
-        fail |= gg_fill_async(v_conic, 0, sizeof(float) * 3 * n, s) != hipSuccess;
-        fail |= gg_fill_async(v_opacity, 0, sizeof(float) * n, s) != hipSuccess;
-    }
-    if (!in_record)
-        fail |= gg_fill_async(v_colors2, 0, sizeof(float) * (color_stride2 ? color_stride2 : C2) * n, s) != hipSuccess;
-    if (!acc_colors)
-        fail |= gg_fill_async(v_colors, 0, sizeof(float) * (color_stride ? color_stride : C) * n, s) != hipSuccess;
-    if (fail) {
-        gg_set_error("gg_blend_bwd_pair: memset failed");
-        return GG_ERR_LAUNCH;
-    }
-    const int tiles_x = (img_w + GG_BLOCK - 1) / GG_BLOCK, tiles_y = (img_h + GG_BLOCK - 1) / GG_BLOCK;
-    const int ntiles = tiles_x * tiles_y;
-    gg_prof_begin(GG_K_BLEND_BWD_PAIR, s);
-    gg_launch_blend2_bwd_pair(C, img_h, img_w, tiles_x, ntiles, ids, (const int2 *)tile_bins, rec, colors, background,
-                              final_Ts, final_idx, v_out, v_xy, v_conic, v_colors, v_opacity, geom_stride,
-                              color_stride, colors2, C2, background2, v_out2_parts, v_out2_channels, num_parts,
-                              v_colors2, color_stride2, s);
-    gg_prof_end(GG_K_BLEND_BWD_PAIR, s);
-    for (int off = 32; off < C;) {   // further chunks of the first array: their own walks, adding to the same arrays
-        const int w = chunk_width(C - off);
-        const int nn = min(w, C - off);
-        gg_prof_begin(GG_K_BLEND_BWD + gg_width_index(w), s);
-        gg_launch_blend2_bwd(w, C, off, nn, img_h, img_w, tiles_x, ntiles, ids, (const int2 *)tile_bins, rec, colors,
-                             background, final_Ts, final_idx, v_out, v_xy, v_conic, v_colors, v_opacity, geom_stride,
-                             color_stride, s, DetSlab());
-        gg_prof_end(GG_K_BLEND_BWD + gg_width_index(w), s);
-        off += nn;
-    }
-    GG_CHECK_LAUNCH();
-    return GG_OK;
+    return blend_bwd_impl(__func__, {N, img_h, img_w, ids, tile_bins, xys, conics, opacity, ws, ws_bytes, stream},
+                          {C, colors, background}, {final_Ts, final_idx, v_out},
+                          {v_xy, v_conic, v_colors, v_opacity, geom_stride, color_stride}, flags, false, 0, nullptr);
 }
 
 extern "C" int gg_blend_bwd_pair(int C, int C2, int N, int img_h, int img_w, const int32_t *ids,
@@ -572,10 +488,36 @@ extern "C" int gg_blend_bwd_pair(int C, int C2, int N, int img_h, int img_w, con
                                  float *v_conic, float *v_colors, float *v_colors2, float *v_opacity,
                                  int geom_stride, int color_stride, int color_stride2, void *ws, size_t ws_bytes,
                                  int flags, gg_stream_t stream) {
-    return blend_bwd_pair_impl(C, C2, N, img_h, img_w, ids, tile_bins, xys, conics, colors, colors2, opacity, background,
-                               background2, final_Ts, final_idx, v_out, v_out2_parts, v_out2_channels, num_parts, v_xy,
-                               v_conic, v_colors, v_colors2, v_opacity, geom_stride, color_stride, color_stride2, ws,
-                               ws_bytes, flags, stream);
+    const char *entry = __func__;
+    const BlendColors src = {C, colors, background}, src2 = {C2, colors2, background2};
+    const BlendBwdIn in = {final_Ts, final_idx, v_out};
+    const BlendGradOut g = {v_xy, v_conic, v_colors, v_opacity, geom_stride, color_stride};
+    const BlendGrad2 g2 = {v_out2_parts, v_out2_channels, num_parts, v_colors2, color_stride2};
+    BLEND_REQUIRE((flags & GG_BWD_ACCUMULATE_GEOM) == 0, "gg_blend_bwd_pair writes the geometry gradients itself");
+    BLEND_REQUIRE(C >= 32, "the first colour array needs >= 32 channels (its first chunk carries the second array)");
+    BLEND_REQUIRE(C2 >= 1 && C2 <= 8, "the second colour array has 1..8 channels");
+    BlendWalk w;
+    int rc = blend_begin(entry, {N, img_h, img_w, ids, tile_bins, xys, conics, opacity, ws, ws_bytes, stream}, true, true,
+                         xys && conics && colors && colors2 && opacity && background && background2 && final_Ts &&
+                             final_idx && v_out && v_out2_parts && v_out2_channels && v_xy && v_conic && v_colors &&
+                             v_colors2 && v_opacity,
+                         (flags & GG_BWD_WS_FROM_FORWARD) != 0, w);
+    if (rc != GG_OK || N == 0) return rc;
+    BLEND_REQUIRE(num_parts >= 1 && num_parts <= 3, "the second cotangent comes as 1..3 images");
+    int total = 0;
+    for (int k = 0; k < num_parts; ++k) {
+        BLEND_REQUIRE(v_out2_parts[k] != nullptr && v_out2_channels[k] >= 1, "empty part of the second cotangent");
+        total += v_out2_channels[k];
+    }
+    BLEND_REQUIRE(total == C2, "the parts of the second cotangent must add up to channels2");
+    rc = zero_grads(entry, g, C, &g2, C2, flags, (size_t)N, w.s);
+    if (rc != GG_OK) return rc;
+    gg_prof_begin(GG_K_BLEND_BWD_PAIR, w.s);
+    gg_launch_blend2_bwd_pair(w, src, in, g, src2, g2);
+    gg_prof_end(GG_K_BLEND_BWD_PAIR, w.s);
+    bwd_chunks(w, src, 32, in, g, DetSlab());   // further chunks of the first array: their own walks, same arrays
+    GG_CHECK_LAUNCH();
+    return GG_OK;
 }
 
 extern "C" int gg_blend_bwd_deterministic(int C, int N, int img_h, int img_w, const int32_t *ids,
@@ -593,7 +535,8 @@ extern "C" int gg_blend_bwd_deterministic(int C, int N, int img_h, int img_w, co
         gg_set_error("gg_blend_bwd_deterministic: deterministic workspace too small");
         return GG_ERR_WORKSPACE;
     }
-    return blend_bwd_impl(C, N, img_h, img_w, ids, tile_bins, xys, conics, colors, opacity, background, final_Ts,
-                          final_idx, v_out, v_xy, v_conic, v_colors, v_opacity, geom_stride, color_stride, ws,
-                          ws_bytes, flags, stream, true, num_intersects, det_ws, det_ws_bytes);
+    return blend_bwd_impl(__func__, {N, img_h, img_w, ids, tile_bins, xys, conics, opacity, ws, ws_bytes, stream},
+                          {C, colors, background}, {final_Ts, final_idx, v_out},
+                          {v_xy, v_conic, v_colors, v_opacity, geom_stride, color_stride}, flags, true, num_intersects,
+                          det_ws);
 }

@@ -24,7 +24,9 @@
 // Bit-exactness: blended contributions are `acc = fma(colour, vis, acc)` with vis = 0 for pixels
 // that skip the Gaussian; fma(c, 0, acc) == acc for finite c, so the unconditional form equals
 // the oracle's conditional one (colours must be finite, as everywhere).
-#include "blend_common.h"
+#include <type_traits>
+
+#include "blend_launch.h"
 
 #define GRP 4          // survivors per loop iteration
 #define KEEP(x) asm volatile("" ::"v"(x))   // measurement builds: keep a value alive
@@ -1778,135 +1780,104 @@ __global__ __launch_bounds__(64 * GG_WPB_WIDE_BWD) __attribute__((amdgpu_waves_p
 }
 
 // =============================================================================================
-// launchers used by the C ABI in blend.hip
+// launchers used by the C ABI in blend.hip (blend_launch.h).  launch_fwd / launch_bwd are the one place where a
+// kernel family's argument list is written.
 // =============================================================================================
-#define B2_FWD_ARGS C, off, n, img_h, img_w, tiles_x, ntiles, ids, bins, rec, colors, background, \
-                    out_img, final_Ts, final_idx, write_final
-void gg_launch_blend2_fwd(int width, int C, int off, int n, int img_h, int img_w, int tiles_x,
-                          int ntiles, const int32_t *ids, const int2 *bins, const GRec *rec,
-                          const float *colors, const float *background, float *out_img,
-                          float *final_Ts, int32_t *final_idx, int write_final, hipStream_t s) {
-    dim3 grid(gg_blend_grid(ntiles, GG_WPB_OTHER)), block(64 * GG_WPB_OTHER);
-    if (width == 1)
-        hipLaunchKernelGGL((blend2_fwd_kernel<1, false, true>), grid, block, 0, s, B2_FWD_ARGS);
-    else if (width == 2)
-        hipLaunchKernelGGL((blend2_fwd_kernel<2, false, true>), grid, block, 0, s, B2_FWD_ARGS);
-    else if (width == 3)
-        hipLaunchKernelGGL((blend2_fwd_kernel<3, false, true>), grid, block, 0, s, B2_FWD_ARGS);
-    else if (width == 8)
-        hipLaunchKernelGGL((blend2_fwd_kernel<8, false, true>), grid, block, 0, s, B2_FWD_ARGS);
-    else if (n == 32)
-        hipLaunchKernelGGL((blend2_fwd_kernel<32, true, true>), grid, block, 0, s, B2_FWD_ARGS);
-    else
-        hipLaunchKernelGGL((blend2_fwd_kernel<32, true, false>), grid, block, 0, s, B2_FWD_ARGS);
+template <typename K>
+static void launch_fwd(K kernel, const BlendWalk &w, const BlendColors &src, const BlendChunk &ch,
+                       const BlendFwdOut &out, int write_final, const Seg2 &seg2 = Seg2()) {
+    hipLaunchKernelGGL(kernel, dim3(gg_blend_grid(w.ntiles, GG_WPB_OTHER)), dim3(64 * GG_WPB_OTHER), 0, w.s, src.C,
+                       ch.off, ch.n, w.img_h, w.img_w, w.tiles_x, w.ntiles, w.ids, w.bins, w.rec, src.colors,
+                       src.background, out.out_img, out.final_Ts, out.final_idx, write_final, seg2);
+}
+// tail: DetSlab (narrow kernels), or DetSlab and Seg2B (wide kernels); wpb: GG_WPB_OTHER / GG_WPB_WIDE_BWD
+template <typename K, typename... Tail>
+static void launch_bwd(K kernel, int wpb, const BlendWalk &w, const BlendColors &src, const BlendChunk &ch,
+                       const BlendBwdIn &in, const BlendGradOut &g, const Tail &...tail) {
+    hipLaunchKernelGGL(kernel, dim3(gg_blend_grid(w.ntiles, wpb)), dim3(64 * wpb), 0, w.s, src.C, ch.off, ch.n,
+                       w.img_h, w.img_w, w.tiles_x, w.ntiles, w.ids, w.bins, w.rec, src.colors, src.background,
+                       in.final_Ts, in.final_idx, in.v_out, g.v_xy, g.v_conic, g.v_colors, g.v_opacity, g.gstride,
+                       g.cstride, tail...);
+}
+// the narrow widths: f(std::integral_constant<int, W>) for a chunk of width W = 1, 2, 3 or 8; false for the wide ones
+template <typename F>
+static bool narrow_width(int width, F &&f) {
+    switch (width) {
+        case 1: f(std::integral_constant<int, 1>()); return true;
+        case 2: f(std::integral_constant<int, 2>()); return true;
+        case 3: f(std::integral_constant<int, 3>()); return true;
+        case 8: f(std::integral_constant<int, 8>()); return true;
+        default: return false;
+    }
+}
+// 16-byte aligned colour rows and cotangent rows: what the 16-slot wide backward builds need
+static bool rows_aligned16(const BlendColors &src, const BlendBwdIn &in) {
+    return src.C % 4 == 0 && (reinterpret_cast<uintptr_t>(src.colors) & 15) == 0 &&
+           (reinterpret_cast<uintptr_t>(in.v_out) & 15) == 0;
 }
 
-// several 32-channel blocks in one walk (channels [off, off + 32 ncb)); 16-byte aligned rows (the launcher's caller
-// checks), ncb = 2, 3 or 4
-void gg_launch_blend2_fwd_blocks(int ncb, int C, int off, int img_h, int img_w, int tiles_x, int ntiles,
-                                 const int32_t *ids, const int2 *bins, const GRec *rec, const float *colors,
-                                 const float *background, float *out_img, float *final_Ts, int32_t *final_idx,
-                                 int write_final, hipStream_t s) {
-    dim3 grid(gg_blend_grid(ntiles, GG_WPB_OTHER)), block(64 * GG_WPB_OTHER);
-    const int n = 32;
-    if (ncb == 2)
-        hipLaunchKernelGGL((blend2_fwd_kernel<32, true, true, false, 0, 2>), grid, block, 0, s, B2_FWD_ARGS);
-    else if (ncb == 3)
-        hipLaunchKernelGGL((blend2_fwd_kernel<32, true, true, false, 0, 3>), grid, block, 0, s, B2_FWD_ARGS);
-    else
-        hipLaunchKernelGGL((blend2_fwd_kernel<32, true, true, false, 0, 4>), grid, block, 0, s, B2_FWD_ARGS);
+// one walk of the plan; several 32-channel blocks (ch.blocks = 2, 3 or 4: channels [off, off + 32 blocks)) need
+// 16-byte aligned rows (the plan checks)
+void gg_launch_blend2_fwd(const BlendWalk &w, const BlendColors &src, const BlendChunk &ch, const BlendFwdOut &out,
+                          int write_final) {
+    auto go = [&](auto kernel) { launch_fwd(kernel, w, src, ch, out, write_final); };
+    if (narrow_width(ch.width, [&](auto W) { go(blend2_fwd_kernel<decltype(W)::value, false, true>); })) return;
+    if (ch.blocks == 2) go(blend2_fwd_kernel<32, true, true, false, 0, 2>);
+    else if (ch.blocks == 3) go(blend2_fwd_kernel<32, true, true, false, 0, 3>);
+    else if (ch.blocks == 4) go(blend2_fwd_kernel<32, true, true, false, 0, 4>);
+    else if (ch.n == 32) go(blend2_fwd_kernel<32, true, true>);
+    else go(blend2_fwd_kernel<32, true, false>);
 }
 
 // ncb: 32-channel blocks of the first array in this walk (1, 2 or 4; channels [0, 32 ncb)); fast: the batched fp16
 // two-piece kernel for the first block + second array (ncb is then 1)
-void gg_launch_blend2_fwd_pair(int C, int img_h, int img_w, int tiles_x, int ntiles, const int32_t *ids,
-                               const int2 *bins, const GRec *rec, const float *colors, const float *background,
-                               float *out_img, float *final_Ts, int32_t *final_idx, const float *colors2, int C2,
-                               const float *background2, float *out_img2, hipStream_t s, int ncb, bool fast,
-                               unsigned bytes1, unsigned bytes2) {
-    dim3 grid(gg_blend_grid(ntiles, GG_WPB_OTHER)), block(64 * GG_WPB_OTHER);
+void gg_launch_blend2_fwd_pair(const BlendWalk &w, const BlendColors &src, const BlendColors &src2,
+                               const BlendFwdOut &out, float *out_img2, int ncb, bool fast, unsigned bytes1,
+                               unsigned bytes2) {
     Seg2 seg2;
-    seg2.colors = colors2;
-    seg2.background = background2;
+    seg2.colors = src2.colors;
+    seg2.background = src2.background;
     seg2.out_img = out_img2;
-    seg2.C2 = C2;
-    seg2.nch2 = C2;
+    seg2.C2 = src2.C;
+    seg2.nch2 = src2.C;
     if (fast) {
-        hipLaunchKernelGGL(blend2_fwd_batch_kernel, dim3(gg_blend_grid(ntiles, 1)), dim3(64), 0, s, C, img_h, img_w, tiles_x,
-                           ntiles, ids, bins, rec, colors, background, out_img, final_Ts, final_idx, seg2, bytes1, bytes2);
+        hipLaunchKernelGGL(blend2_fwd_batch_kernel, dim3(gg_blend_grid(w.ntiles, 1)), dim3(64), 0, w.s, src.C, w.img_h,
+                           w.img_w, w.tiles_x, w.ntiles, w.ids, w.bins, w.rec, src.colors, src.background, out.out_img,
+                           out.final_Ts, out.final_idx, seg2, bytes1, bytes2);
         return;
     }
-#define B2_FPAIR(L) hipLaunchKernelGGL((blend2_fwd_kernel<32, true, true, true, L>), grid, block, 0, s, C, 0, 32, \
-        img_h, img_w, tiles_x, ntiles, ids, bins, rec, colors, background, out_img, final_Ts, final_idx, 1, seg2)
+    auto go = [&](auto kernel) { launch_fwd(kernel, w, src, BlendChunk{0, 32, 32, ncb}, out, 1, seg2); };
 #ifdef GG_ABLATION
     switch (g_fwd_abl) {   // measurement twin: wrong images on purpose
-        case 1: B2_FPAIR(1); return;
-        case 2: B2_FPAIR(2); return;
-        case 3: B2_FPAIR(3); return;
-        case 4: B2_FPAIR(4); return;
+        case 1: go(blend2_fwd_kernel<32, true, true, true, 1>); return;
+        case 2: go(blend2_fwd_kernel<32, true, true, true, 2>); return;
+        case 3: go(blend2_fwd_kernel<32, true, true, true, 3>); return;
+        case 4: go(blend2_fwd_kernel<32, true, true, true, 4>); return;
         default: break;
     }
 #endif
-    if (ncb == 2) {
-        hipLaunchKernelGGL((blend2_fwd_kernel<32, true, true, true, 0, 2>), grid, block, 0, s, C, 0, 32, img_h,
-                           img_w, tiles_x, ntiles, ids, bins, rec, colors, background, out_img, final_Ts, final_idx, 1, seg2);
-        return;
-    }
-    if (ncb == 4) {
-        hipLaunchKernelGGL((blend2_fwd_kernel<32, true, true, true, 0, 4>), grid, block, 0, s, C, 0, 32, img_h,
-                           img_w, tiles_x, ntiles, ids, bins, rec, colors, background, out_img, final_Ts, final_idx, 1, seg2);
-        return;
-    }
-    B2_FPAIR(0);
+    if (ncb == 2) go(blend2_fwd_kernel<32, true, true, true, 0, 2>);
+    else if (ncb == 4) go(blend2_fwd_kernel<32, true, true, true, 0, 4>);
+    else go(blend2_fwd_kernel<32, true, true, true, 0>);
 }
 
-#define B2_BWDW_ARGS C, off, n, img_h, img_w, tiles_x, ntiles, ids, bins, rec, colors, background, \
-                     final_Ts, final_idx, v_out, v_xy, v_conic, v_colors, v_opacity, gstride, cstride, det
-#define B2_BWDN_ARGS C, off, n, img_h, img_w, tiles_x, ntiles, ids, bins, rec, colors, background, \
-                     final_Ts, final_idx, v_out, v_xy, v_conic, v_colors, v_opacity, gstride, cstride, det
-void gg_launch_blend2_bwd(int width, int C, int off, int n, int img_h, int img_w, int tiles_x,
-                          int ntiles, const int32_t *ids, const int2 *bins, const GRec *rec,
-                          const float *colors, const float *background, const float *final_Ts,
-                          const int32_t *final_idx, const float *v_out, float *v_xy, float *v_conic,
-                          float *v_colors, float *v_opacity, int gstride, int cstride, hipStream_t s,
-                          DetSlab det) {
-    dim3 grid(gg_blend_grid(ntiles, GG_WPB_OTHER)), block(64 * GG_WPB_OTHER);
-    dim3 gridw(gg_blend_grid(ntiles, GG_WPB_WIDE_BWD)), blockw(64 * GG_WPB_WIDE_BWD);   // the wide kernels
+void gg_launch_blend2_bwd(const BlendWalk &w, const BlendColors &src, const BlendChunk &ch, const BlendBwdIn &in,
+                          const BlendGradOut &g, const DetSlab &det) {
+    auto narrow = [&](auto kernel) { launch_bwd(kernel, GG_WPB_OTHER, w, src, ch, in, g, det); };
+    auto wide = [&](auto kernel) { launch_bwd(kernel, GG_WPB_WIDE_BWD, w, src, ch, in, g, det, Seg2B()); };
     if (det.p) {   // deterministic mode: same kernels with the atomics replaced by slab stores
-        if (width == 1)
-            hipLaunchKernelGGL((blend2_bwd_narrow_kernel<1, 0, true>), grid, block, 0, s, B2_BWDN_ARGS);
-        else if (width == 2)
-            hipLaunchKernelGGL((blend2_bwd_narrow_kernel<2, 0, true>), grid, block, 0, s, B2_BWDN_ARGS);
-        else if (width == 3)
-            hipLaunchKernelGGL((blend2_bwd_narrow_kernel<3, 0, true>), grid, block, 0, s, B2_BWDN_ARGS);
-        else if (width == 8)
-            hipLaunchKernelGGL((blend2_bwd_narrow_kernel<8, 0, true>), grid, block, 0, s, B2_BWDN_ARGS);
-        else if (n == 32)
-            hipLaunchKernelGGL((blend2_bwd_wide_kernel<true, 0, 32, true>), gridw, blockw, 0, s, B2_BWDW_ARGS);
-        else   // partial 32-channel chunk: one masked variant is enough for this mode
-            hipLaunchKernelGGL((blend2_bwd_wide_kernel<false, 0, 32, true>), gridw, blockw, 0, s, B2_BWDW_ARGS);
+        if (narrow_width(ch.width, [&](auto W) { narrow(blend2_bwd_narrow_kernel<decltype(W)::value, 0, true>); })) return;
+        if (ch.n == 32) wide(blend2_bwd_wide_kernel<true, 0, 32, true>);
+        else wide(blend2_bwd_wide_kernel<false, 0, 32, true>);   // partial chunk: one masked variant is enough here
         return;
     }
-    if (width == 1)
-        hipLaunchKernelGGL((blend2_bwd_narrow_kernel<1>), grid, block, 0, s, B2_BWDN_ARGS);
-    else if (width == 2)
-        hipLaunchKernelGGL((blend2_bwd_narrow_kernel<2>), grid, block, 0, s, B2_BWDN_ARGS);
-    else if (width == 3)
-        hipLaunchKernelGGL((blend2_bwd_narrow_kernel<3>), grid, block, 0, s, B2_BWDN_ARGS);
-    else if (width == 8)
-        hipLaunchKernelGGL((blend2_bwd_narrow_kernel<8>), grid, block, 0, s, B2_BWDN_ARGS);
-    else if (n == 32 && C % 4 == 0 && off % 4 == 0 && (reinterpret_cast<uintptr_t>(colors) & 15) == 0 &&
-             (reinterpret_cast<uintptr_t>(v_out) & 15) == 0)   // the 16-slot build (four waves per SIMD)
-        hipLaunchKernelGGL((blend2_bwd_wide_kernel<true, 0, 32, false, false, true>), gridw, blockw, 0, s,
-                           B2_BWDW_ARGS);
-    else if (n == 32)
-        hipLaunchKernelGGL((blend2_bwd_wide_kernel<true>), gridw, blockw, 0, s, B2_BWDW_ARGS);
-    else if (n <= 8)
-        hipLaunchKernelGGL((blend2_bwd_wide_kernel<false, 0, 8>), gridw, blockw, 0, s, B2_BWDW_ARGS);
-    else if (n <= 16)
-        hipLaunchKernelGGL((blend2_bwd_wide_kernel<false, 0, 16>), gridw, blockw, 0, s, B2_BWDW_ARGS);
-    else
-        hipLaunchKernelGGL((blend2_bwd_wide_kernel<false, 0, 32>), gridw, blockw, 0, s, B2_BWDW_ARGS);
+    if (narrow_width(ch.width, [&](auto W) { narrow(blend2_bwd_narrow_kernel<decltype(W)::value>); })) return;
+    if (ch.n == 32 && ch.off % 4 == 0 && rows_aligned16(src, in))   // the 16-slot build (four waves per SIMD)
+        wide(blend2_bwd_wide_kernel<true, 0, 32, false, false, true>);
+    else if (ch.n == 32) wide(blend2_bwd_wide_kernel<true>);
+    else if (ch.n <= 8) wide(blend2_bwd_wide_kernel<false, 0, 8>);
+    else if (ch.n <= 16) wide(blend2_bwd_wide_kernel<false, 0, 16>);
+    else wide(blend2_bwd_wide_kernel<false, 0, 32>);
 }
 
 #ifdef GG_ABLATION
@@ -1921,91 +1892,69 @@ extern "C" int gg_debug_set_pair_ablation(int level) {
     return prev;
 }
 #endif
-// first 32 channels of `colors` + a second array of <= 8 channels in one walk (gg_blend_bwd_pair)
-void gg_launch_blend2_bwd_pair(int C, int img_h, int img_w, int tiles_x, int ntiles, const int32_t *ids,
-                               const int2 *bins, const GRec *rec, const float *colors, const float *background,
-                               const float *final_Ts, const int32_t *final_idx, const float *v_out, float *v_xy,
-                               float *v_conic, float *v_colors, float *v_opacity, int gstride, int cstride,
-                               const float *colors2, int C2, const float *background2,
-                               const float *const *v_out2_parts, const int *v_out2_channels, int num_parts,
-                               float *v_colors2, int cstride2, hipStream_t s) {
-    dim3 grid(gg_blend_grid(ntiles, GG_WPB_WIDE_BWD)), block(64 * GG_WPB_WIDE_BWD);
+// first 32 channels of `src` + a second array of <= 8 channels in one walk (gg_blend_bwd_pair)
+void gg_launch_blend2_bwd_pair(const BlendWalk &w, const BlendColors &src, const BlendBwdIn &in, const BlendGradOut &g,
+                               const BlendColors &src2, const BlendGrad2 &g2) {
     Seg2B seg2;
-    seg2.colors = colors2;
-    seg2.background = background2;
+    seg2.colors = src2.colors;
+    seg2.background = src2.background;
     for (int k = 0; k < 3; ++k) {
-        seg2.v_out[k] = k < num_parts ? v_out2_parts[k] : v_out2_parts[0];
-        seg2.vo_w[k] = k < num_parts ? v_out2_channels[k] : 0;   // (channels >= channels2 are never read)
+        seg2.v_out[k] = k < g2.num_parts ? g2.v_out_parts[k] : g2.v_out_parts[0];
+        seg2.vo_w[k] = k < g2.num_parts ? g2.v_out_channels[k] : 0;   // (channels >= channels2 are never read)
     }
-    seg2.v_colors = v_colors2;
-    seg2.C2 = C2;
-    seg2.nch2 = C2;
-    seg2.cs2 = cstride2 ? cstride2 : C2;
-#define B2_PAIR(L) hipLaunchKernelGGL((blend2_bwd_wide_kernel<true, L, 32, false, true>), grid, block, 0, s, C, 0, 32, \
-        img_h, img_w, tiles_x, ntiles, ids, bins, rec, colors, background, final_Ts, final_idx, v_out, v_xy, \
-        v_conic, v_colors, v_opacity, gstride, cstride, DetSlab(), seg2)
+    seg2.v_colors = g2.v_colors;
+    seg2.C2 = src2.C;
+    seg2.nch2 = src2.C;
+    seg2.cs2 = g2.cstride ? g2.cstride : src2.C;
+    auto go = [&](auto kernel) {
+        launch_bwd(kernel, GG_WPB_WIDE_BWD, w, src, BlendChunk{0, 32, 32, 1}, in, g, DetSlab(), seg2);
+    };
 #ifdef GG_ABLATION
     const bool ablated = g_pair_ablate != 0;   // the ablated builds are the 32-slot ones
 #else
     const bool ablated = false;
 #endif
-    if (!ablated && C % 4 == 0 && (reinterpret_cast<uintptr_t>(colors) & 15) == 0 &&
-        (reinterpret_cast<uintptr_t>(v_out) & 15) == 0) {   // the 16-slot build (four waves per SIMD)
+    if (!ablated && rows_aligned16(src, in)) {   // the 16-slot build (four waves per SIMD)
         // one 16-float record per Gaussian on a 64-byte boundary, geometry 0..5 | second array 6..: the merged flush
         // (geometry and second-array gradients in one atomic request per Gaussian)
-        const bool merged = gstride == 16 && seg2.cs2 == 16 && v_colors2 == v_xy + 6 && v_conic == v_xy + 2 &&
-                            v_opacity == v_xy + 5 && (reinterpret_cast<uintptr_t>(v_xy) & 63) == 0;
-        if (merged)
-            hipLaunchKernelGGL((blend2_bwd_wide_kernel<true, 0, 32, false, true, true, true>), grid,
-                               block, 0, s, C, 0, 32, img_h, img_w, tiles_x, ntiles, ids, bins, rec, colors, background,
-                               final_Ts, final_idx, v_out, v_xy, v_conic, v_colors, v_opacity, gstride, cstride, DetSlab(),
-                               seg2);
-        else
-            hipLaunchKernelGGL((blend2_bwd_wide_kernel<true, 0, 32, false, true, true>), grid, block, 0, s, C,
-                               0, 32, img_h, img_w, tiles_x, ntiles, ids, bins, rec, colors, background, final_Ts, final_idx,
-                               v_out, v_xy, v_conic, v_colors, v_opacity, gstride, cstride, DetSlab(), seg2);
+        const bool merged = g.gstride == 16 && seg2.cs2 == 16 && g2.v_colors == g.v_xy + 6 && g.v_conic == g.v_xy + 2 &&
+                            g.v_opacity == g.v_xy + 5 && (reinterpret_cast<uintptr_t>(g.v_xy) & 63) == 0;
+        if (merged) go(blend2_bwd_wide_kernel<true, 0, 32, false, true, true, true>);
+        else go(blend2_bwd_wide_kernel<true, 0, 32, false, true, true>);
         return;
     }
 #ifdef GG_ABLATION
     switch (g_pair_ablate) {   // measurement twin (tools/kbench.py): wrong results on purpose
-        case 1: B2_PAIR(1); return;
-        case 2: B2_PAIR(2); return;
-        case 3: B2_PAIR(3); return;
-        case 4: B2_PAIR(4); return;
-        case 5: B2_PAIR(5); return;
-        case 6: B2_PAIR(6); return;
+        case 1: go(blend2_bwd_wide_kernel<true, 1, 32, false, true>); return;
+        case 2: go(blend2_bwd_wide_kernel<true, 2, 32, false, true>); return;
+        case 3: go(blend2_bwd_wide_kernel<true, 3, 32, false, true>); return;
+        case 4: go(blend2_bwd_wide_kernel<true, 4, 32, false, true>); return;
+        case 5: go(blend2_bwd_wide_kernel<true, 5, 32, false, true>); return;
+        case 6: go(blend2_bwd_wide_kernel<true, 6, 32, false, true>); return;
         default: break;
     }
 #endif
-    B2_PAIR(0);
+    go(blend2_bwd_wide_kernel<true, 0, 32, false, true>);
 }
 
 #ifdef GG_ABLATION
-// measurement-only entry (tools/kbench.py): ablated builds of the 3-channel backward
-void gg_launch_blend2_bwd_ablate(int abl, int C, int off, int img_h, int img_w, int tiles_x,
-                                 int ntiles, const int32_t *ids, const int2 *bins, const GRec *rec,
-                                 const float *colors, const float *background, const float *final_Ts,
-                                 const int32_t *final_idx, const float *v_out, float *v_xy,
-                                 float *v_conic, float *v_colors, float *v_opacity, int gstride, int cstride, hipStream_t s) {
-    dim3 grid(gg_blend_grid(ntiles, GG_WPB_OTHER)), block(64 * GG_WPB_OTHER);
-    dim3 gridw(gg_blend_grid(ntiles, GG_WPB_WIDE_BWD)), blockw(64 * GG_WPB_WIDE_BWD);   // the wide kernels
-    const int n = 3;   // B2_BWDN_ARGS: the ablated narrow builds are the 3-channel ones
-    const DetSlab det = DetSlab();
+// measurement-only entry (tools/kbench.py): ablated builds of the 3-channel and of the full 32-channel backward
+void gg_launch_blend2_bwd_ablate(int abl, const BlendWalk &w, const BlendColors &src, const BlendChunk &ch,
+                                 const BlendBwdIn &in, const BlendGradOut &g) {
+    auto narrow = [&](auto kernel) { launch_bwd(kernel, GG_WPB_OTHER, w, src, ch, in, g, DetSlab()); };
+    auto wide = [&](auto kernel) { launch_bwd(kernel, GG_WPB_WIDE_BWD, w, src, ch, in, g, DetSlab(), Seg2B()); };
     switch (abl) {
-#define B2_WABL(L) hipLaunchKernelGGL((blend2_bwd_wide_kernel<true, L>), gridw, blockw, 0, s, C, off, 32, \
-        img_h, img_w, tiles_x, ntiles, ids, bins, rec, colors, background, final_Ts, final_idx, v_out, \
-        v_xy, v_conic, v_colors, v_opacity, gstride, cstride, det)
-        case 11: B2_WABL(1); break;
-        case 12: B2_WABL(2); break;
-        case 13: B2_WABL(3); break;
-        case 14: B2_WABL(4); break;
-        case 15: B2_WABL(5); break;
-        case 16: B2_WABL(6); break;
-        case 1: hipLaunchKernelGGL((blend2_bwd_narrow_kernel<3, 1>), grid, block, 0, s, B2_BWDN_ARGS); break;
-        case 2: hipLaunchKernelGGL((blend2_bwd_narrow_kernel<3, 2>), grid, block, 0, s, B2_BWDN_ARGS); break;
-        case 3: hipLaunchKernelGGL((blend2_bwd_narrow_kernel<3, 3>), grid, block, 0, s, B2_BWDN_ARGS); break;
-        case 4: hipLaunchKernelGGL((blend2_bwd_narrow_kernel<3, 4>), grid, block, 0, s, B2_BWDN_ARGS); break;
-        default: hipLaunchKernelGGL((blend2_bwd_narrow_kernel<3, 0>), grid, block, 0, s, B2_BWDN_ARGS); break;
+        case 11: wide(blend2_bwd_wide_kernel<true, 1>); break;
+        case 12: wide(blend2_bwd_wide_kernel<true, 2>); break;
+        case 13: wide(blend2_bwd_wide_kernel<true, 3>); break;
+        case 14: wide(blend2_bwd_wide_kernel<true, 4>); break;
+        case 15: wide(blend2_bwd_wide_kernel<true, 5>); break;
+        case 16: wide(blend2_bwd_wide_kernel<true, 6>); break;
+        case 1: narrow(blend2_bwd_narrow_kernel<3, 1>); break;
+        case 2: narrow(blend2_bwd_narrow_kernel<3, 2>); break;
+        case 3: narrow(blend2_bwd_narrow_kernel<3, 3>); break;
+        case 4: narrow(blend2_bwd_narrow_kernel<3, 4>); break;
+        default: narrow(blend2_bwd_narrow_kernel<3, 0>); break;
     }
 }
 // resident workgroups per CU of the backward kernels (tools/kbench.py prints them)

@@ -1,5 +1,5 @@
-// blend_common.h — device helpers shared by the blend kernels (blend.hip: v1 kernels + C ABI,
-// blend2.hip: v2 kernels).
+// blend_common.h — records and device helpers shared by blend.hip (C ABI, launch plan, record packing and the
+// deterministic reduction) and blend2.hip (the blend kernels and their launchers; host interface: blend_launch.h).
 #pragma once
 #include "gg_common.h"
 
