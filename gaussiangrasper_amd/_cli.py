@@ -10,6 +10,46 @@ import math
 import numpy as np
 
 REPORT_KEYS = ("contact_idx", "normals", "angles", "region_count", "region_weight", "collision_weight", "feasible")
+CLEAR_KEYS = ("body_weight", "sweep_weight", "body_count", "sweep_count", "clear")     # only with --gripper
+
+
+def add_clearance_options(ap) -> None:
+    """--gripper, --approach, --max-body-collision, --max-sweep-collision (grasp.clearance)."""
+    ap.add_argument("--gripper", default=None, metavar="{default,FILE.json}",
+                    help="also test the whole gripper against the whole scene: graspnetAPI's drawing (default) or a "
+                         "JSON list of parts (grasp.load_gripper)")
+    ap.add_argument("--approach", type=float, default=None, metavar="METRES",
+                    help="with --gripper: length of the straight approach that is swept, grasp units (default 0)")
+    ap.add_argument("--max-body-collision", type=float, default=None,
+                    help="with --gripper: limit on the opacity inside the gripper at the final pose")
+    ap.add_argument("--max-sweep-collision", type=float, default=None,
+                    help="with --gripper: limit on the opacity the gripper passes through on its approach")
+
+
+def check_clearance_options(ap, a) -> None:
+    """ap.error unless the clearance options are complete and in range; a.approach None becomes 0."""
+    for n in ("approach", "max_body_collision", "max_sweep_collision"):
+        v = getattr(a, n)
+        if v is None:
+            continue
+        opt = "--" + n.replace("_", "-")
+        if not a.gripper:
+            ap.error(f"{opt} needs --gripper")
+        if math.isnan(v):
+            ap.error(f"{opt} must not be NaN")
+    if a.approach is not None and not (math.isfinite(a.approach) and a.approach >= 0.0):
+        ap.error(f"--approach must be finite and >= 0, got {a.approach}")
+    if a.approach is None:
+        a.approach = 0.0
+
+
+def report_arrays(res) -> dict:
+    """The per-grasp arrays of a --report file: REPORT_KEYS of a GraspContacts, and CLEAR_KEYS of its .clearance
+    when it has one."""
+    out = {k: getattr(res, k).cpu().numpy() for k in REPORT_KEYS}
+    if res.clearance is not None:
+        out.update({k: getattr(res.clearance, k).cpu().numpy() for k in CLEAR_KEYS})
+    return out
 
 
 def instance_choice(text: str):

@@ -14,17 +14,7 @@
 // chunk: the smallest index wins), and fp64 sums are added in chunk order.  C depends on (N, M) only.
 // Two passes over the points, because the patches need the contacts: pass 1 (region count, contacts, weights),
 // reduce, pass 2 (patch normal sums), finalize.
-#include <math.h>
-
-#include "gg_common.h"
-
-#define GC_TILE 256              // grasps per workgroup (one per lane)
-#define GC_STAGE 256             // points per LDS stage
-#define GC_TARGET_BLOCKS 2048    // chunks x grasp tiles aimed for: 8 workgroups per CU
-#define GC_MIN_CHUNK 512         // fewest points a chunk is given
-#define GC_MARGIN 1e-6           // relative widening of the cull box (>> the fp64 test's rounding)
-#define GC_MAX_COND 1e3          // max|R| max|R^-T| above this: no cull for that grasp
-#define GC_ROW 17
+#include "grasp_common.h"
 
 struct GcParams {
     double depth_base, finger_width, band, min_weight, max_collision, max_angle;
@@ -35,15 +25,6 @@ struct GcGrasp {
     double depth, hw, hh, lo1, hi1;
     float lo[3], hi[3];          // fp32 cull box: empty for a grasp that is not valid
 };
-
-__device__ __forceinline__ float gc_down(double x) {
-    float f = (float)x;
-    return (double)f > x ? nextafterf(f, -INFINITY) : f;
-}
-__device__ __forceinline__ float gc_up(double x) {
-    float f = (float)x;
-    return (double)f < x ? nextafterf(f, INFINITY) : f;
-}
 
 // `row` may be null (a lane past the last grasp): the grasp is then not valid.
 __device__ void gc_load(const float *row, const GcParams &P, GcGrasp &g) {
@@ -341,21 +322,6 @@ __global__ __launch_bounds__(256) void grasp_finalize_kernel(int M, int C, const
     angles[2 * (size_t)g] = (float)al;
     angles[2 * (size_t)g + 1] = (float)ar;
     feasible[g] = (fmax(al, ar) <= P.max_angle && ws.gcw[g] <= P.max_collision) ? 1 : 0;
-}
-
-// C chunks of len points (len a multiple of GC_STAGE), from (N, M) only, so that a call's summation order never
-// depends on the device.
-static void gc_chunks(int N, int M, int *C, int *len) {
-    *C = 0;
-    *len = 0;
-    if (N <= 0 || M <= 0) return;
-    const int tiles = (M + GC_TILE - 1) / GC_TILE;
-    int c = GC_TARGET_BLOCKS / tiles;
-    c = max(1, min(c, (N + GC_MIN_CHUNK - 1) / GC_MIN_CHUNK));
-    int l = (N + c - 1) / c;
-    l = (l + GC_STAGE - 1) / GC_STAGE * GC_STAGE;
-    *len = l;
-    *C = (N + l - 1) / l;
 }
 
 static size_t gc_layout(int N, int M, GcWs *w, char *base) {

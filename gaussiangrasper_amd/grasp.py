@@ -10,12 +10,17 @@ every candidate against every oriented point in fp64; the contract is in include
     contacts           the per-grasp outputs of gg_grasp_contacts (GraspContacts)
     filter_grasps      indices of the feasible grasps, by score, descending, stable
     score_grasps       all of the above on a model in one call
+    default_gripper    the whole gripper as boxes whose bounds are affine in a row's sizes (box_part, check_gripper,
+                       scale_gripper, load_gripper: models of one's own)
+    clearance          what such a gripper holds at the final pose and sweeps on its approach, per part
+                       (gg_grasp_clearance, csrc/grasp_clear.hip, PARITY.md "Gripper clearance"; GraspClearance)
     python -m gaussiangrasper_amd.grasp --ckpt IN --grasps grasps.npy [...] --out kept.npy
 
 Grasp candidates come from outside the project (AnyGrasp): this module only scores them."""
 from __future__ import annotations
 
 import argparse
+import json
 import math
 import sys
 from dataclasses import dataclass
@@ -26,9 +31,10 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._call import (ArrayLike, f32_rows, nonneg, ptr as _ptr, require_hip as _require_hip, stream as _stream,
-                    workspace as _ws)
-from ._cli import REPORT_KEYS, add_object_options, check_object_options, object_mask
+from ._call import (ArrayLike, f32_rows, host_ptr, nonneg, positive, ptr as _ptr, require_hip as _require_hip,
+                    stream as _stream, workspace as _ws)
+from ._cli import (add_clearance_options, add_object_options, check_clearance_options, check_object_options,
+                   object_mask, report_arrays)
 from .frames import ORTHO_TOL, load_transform_json, rigid_to_scene  # noqa: F401
 
 GRASP_COLS = 17
@@ -39,6 +45,7 @@ FINGER_WIDTH = 0.004
 BAND = 0.003
 MU = 0.5
 MIN_WEIGHT = 0.0
+MAX_PARTS = 8                # GG_CLEAR_MAX_PARTS
 
 
 @dataclass
@@ -51,6 +58,18 @@ class GraspContacts:
     region_weight: Tensor      # (M,) float32
     collision_weight: Tensor   # (M,) float32
     feasible: Tensor           # (M,) bool
+    clearance: Optional["GraspClearance"] = None     # set by score_grasps / grasp_object when a gripper is given
+
+
+@dataclass
+class GraspClearance:
+    """Per-grasp outputs of one gg_grasp_clearance call, device tensors; M = number of grasps, P = gripper parts."""
+    body_count: Tensor         # (M, P) int32: points inside each part at the final pose
+    body_weight: Tensor        # (M, P) float32: their weight
+    sweep_count: Tensor        # (M, P) int32: points each part passes through over the approach
+    sweep_weight: Tensor       # (M, P) float32
+    valid: Tensor              # (M,) bool: the row is finite with width > 0 and height > 0
+    clear: Tensor              # (M,) bool: valid and both totals within their limits
 
 
 # ------------------------------------------------------------------------------------------------
@@ -114,6 +133,84 @@ def filter_grasps(grasps: ArrayLike, feasible: Union[GraspContacts, ArrayLike]) 
 
 
 # ------------------------------------------------------------------------------------------------
+# host side: the gripper model of gg_grasp_clearance (numpy, fp64)
+# ------------------------------------------------------------------------------------------------
+def check_gripper(parts: ArrayLike) -> np.ndarray:
+    """`parts` as a contiguous float64 (P, 6, 4) array, after checking that P is in 1..MAX_PARTS and every coefficient
+    finite.  parts[p][k] = (c0, cw, cd, ch) of bound k of (x_lo, x_hi, y_lo, y_hi, z_lo, z_hi), gripper frame:
+    bound = c0 + cw width + cd depth + ch height of the grasp row."""
+    g = np.ascontiguousarray(np.asarray(parts, dtype=np.float64))
+    if g.ndim != 3 or g.shape[1:] != (6, 4) or not 1 <= g.shape[0] <= MAX_PARTS:
+        raise ValueError(f"a gripper is (P, 6, 4) coefficients with P in 1..{MAX_PARTS}, got {g.shape}")
+    if not np.isfinite(g).all():
+        raise ValueError("gripper coefficients must be finite")
+    return g
+
+
+def box_part(x: Sequence[float], y: Sequence[float], z: Sequence[float]) -> np.ndarray:
+    """(6, 4) coefficients of a box fixed in the gripper frame, whatever the row's sizes: x, y, z are (lo, hi) along
+    the approach, closing and height axes, in the grasps' units.  A wrist, a camera housing."""
+    bounds = [float(v) for lohi in (x, y, z) for v in lohi]
+    if len(bounds) != 6 or not np.isfinite(bounds).all():
+        raise ValueError("box_part takes three finite (lo, hi) pairs")
+    part = np.zeros((6, 4))
+    part[:, 0] = bounds
+    return part
+
+
+def scale_gripper(parts: ArrayLike, scale: float) -> np.ndarray:
+    """The gripper with every constant term times `scale` (lengths in scene units); the size coefficients stay, as
+    the rows' sizes are scaled themselves."""
+    g = check_gripper(parts).copy()
+    g[:, :, 0] *= float(scale)
+    return g
+
+
+def default_gripper(depth_base: float = DEPTH_BASE, finger_width: float = FINGER_WIDTH, tail_length: float = 0.04,
+                    tail_width: Optional[float] = None, tail_height: Optional[float] = None,
+                    scale: float = 1.0) -> np.ndarray:
+    """(4, 6, 4) model of graspnetAPI's gripper drawing as recalled (UNVERIFIED, PARITY.md "Gripper clearance"), with
+    w, h, depth the row's width, height and depth and fw = finger_width:
+        left finger   x [-depth_base, depth]                   y [-w/2 - fw, -w/2]      z [-h/2, h/2]
+        right finger  x [-depth_base, depth]                   y [w/2, w/2 + fw]        z [-h/2, h/2]
+        palm          x [-depth_base - fw, -depth_base]        y [-w/2 - fw, w/2 + fw]  z [-h/2, h/2]
+        tail          x [-depth_base - fw - tail_length, -depth_base - fw]
+                      y [-tail_width/2, tail_width/2]          z [-tail_height/2, tail_height/2]
+    tail_width and tail_height default to fw.  The parts are disjoint up to shared faces.  Lengths are in grasp
+    units (metres) and multiplied by `scale`."""
+    db, fw = nonneg("depth_base", depth_base), nonneg("finger_width", finger_width)
+    tl = nonneg("tail_length", tail_length)
+    tw = fw if tail_width is None else nonneg("tail_width", tail_width)
+    th = fw if tail_height is None else nonneg("tail_height", tail_height)
+    c0, cw, cd, ch = 0, 1, 2, 3
+    g = np.zeros((4, 6, 4))
+    for p, sign in ((0, -1.0), (1, 1.0)):                     # the fingers
+        g[p, 0, c0], g[p, 1, cd] = -db, 1.0
+        inner, outer = (3, 2) if sign < 0 else (2, 3)
+        g[p, inner, cw] = g[p, outer, cw] = 0.5 * sign
+        g[p, outer, c0] = fw * sign
+    g[2, 0, c0], g[2, 1, c0] = -db - fw, -db                  # the palm
+    g[2, 2, c0], g[2, 2, cw], g[2, 3, c0], g[2, 3, cw] = -fw, -0.5, fw, 0.5
+    g[:3, 4, ch], g[:3, 5, ch] = -0.5, 0.5
+    g[3, :, c0] = [-db - fw - tl, -db - fw, -0.5 * tw, 0.5 * tw, -0.5 * th, 0.5 * th]       # the tail
+    return scale_gripper(g, positive("scale", scale))
+
+
+def load_gripper(path: str) -> np.ndarray:
+    """A gripper from a JSON file: a list of parts, each six rows (x_lo, x_hi, y_lo, y_hi, z_lo, z_hi) of four
+    coefficients (c0, cw, cd, ch).  `json.dump(gripper.tolist(), f)` writes one."""
+    with open(path) as f:
+        try:
+            parts = json.load(f)
+        except json.JSONDecodeError as exc:
+            raise ValueError(f"{path}: not JSON: {exc}") from exc
+    try:
+        return check_gripper(parts)
+    except (TypeError, ValueError) as exc:
+        raise ValueError(f"{path}: {exc}") from exc
+
+
+# ------------------------------------------------------------------------------------------------
 # device side: one gg_grasp_contacts call
 # ------------------------------------------------------------------------------------------------
 def contacts(points: Tensor, normals: Tensor, weights: Tensor, grasps: Tensor, depth_base: float = DEPTH_BASE,
@@ -158,6 +255,67 @@ def contacts(points: Tensor, normals: Tensor, weights: Tensor, grasps: Tensor, d
     return res
 
 
+def _limit(name: str, v: Optional[float]) -> float:
+    v = math.inf if v is None else float(v)
+    if math.isnan(v):
+        raise ValueError(f"{name} must not be NaN")
+    return v
+
+
+def clearance(points: Tensor, weights: Tensor, grasps: Tensor, gripper: ArrayLike, approach: float = 0.0,
+              min_weight: float = MIN_WEIGHT, max_body: Optional[float] = None,
+              max_sweep: Optional[float] = None) -> GraspClearance:
+    """What the whole gripper (`gripper`: (P, 6, 4) coefficients, check_gripper) of every grasp holds at its final pose
+    (body) and passes through on the straight way there from `approach` back along -a (sweep), per part, as point
+    counts and weights (include/gg_raster.h gg_grasp_clearance).  points (N, 3), weights (N,), grasps (M, 17): float32
+    on the HIP device (no CPU path).  The gripper's constant terms and approach are in the grasps' units.  clear: the
+    row is valid and the body / sweep weight over all parts is <= max_body / max_sweep (None: no limit).  One call;
+    nothing waits on the host."""
+    dev = _require_hip(points, weights, grasps)
+    points = f32_rows(points, "points", 3)
+    weights = f32_rows(weights, "weights", None)
+    grasps = f32_rows(grasps, "grasps", GRASP_COLS)
+    n, m = points.shape[0], grasps.shape[0]
+    if weights.shape[0] != n:
+        raise ValueError(f"points has {n} rows, weights {weights.shape[0]}")
+    parts = check_gripper(gripper)
+    p = parts.shape[0]
+    if math.isnan(float(min_weight)):
+        raise ValueError("min_weight must not be NaN")
+    args = (nonneg("approach", approach), float(min_weight), _limit("max_body", max_body),
+            _limit("max_sweep", max_sweep))
+    lib = _lib.load()
+    res = GraspClearance(
+        body_count=torch.empty(m, p, dtype=torch.int32, device=dev),
+        body_weight=torch.empty(m, p, dtype=torch.float32, device=dev),
+        sweep_count=torch.empty(m, p, dtype=torch.int32, device=dev),
+        sweep_weight=torch.empty(m, p, dtype=torch.float32, device=dev),
+        valid=torch.empty(m, dtype=torch.uint8, device=dev),
+        clear=torch.empty(m, dtype=torch.uint8, device=dev))
+    nbytes = lib.gg_grasp_clearance_workspace(n, m, p)
+    if m > 0 and nbytes == 0:
+        raise ValueError(f"{n} points x {m} grasps is beyond gg_grasp_clearance's limits")
+    ws = _ws(nbytes, dev)
+    _lib.check(lib.gg_grasp_clearance(n, _ptr(points), _ptr(weights), m, _ptr(grasps), p, host_ptr(parts), *args,
+                                      _ptr(res.body_count), _ptr(res.body_weight), _ptr(res.sweep_count),
+                                      _ptr(res.sweep_weight), _ptr(res.valid), _ptr(res.clear), _ptr(ws), ws.numel(),
+                                      _stream(dev)), "gg_grasp_clearance")
+    res.valid, res.clear = res.valid.bool(), res.clear.bool()
+    return res
+
+
+def apply_clearance(res: GraspContacts, scene_points: Tensor, scene_weights: Tensor, rows: Tensor, gripper: ArrayLike,
+                    scale: float, approach: float, min_weight: float, max_body: Optional[float],
+                    max_sweep: Optional[float]) -> GraspContacts:
+    """`res` with the clearance of scene-frame `rows` against the whole scene's points: the gripper's constant terms
+    and approach (grasp units) times `scale`; res.clearance set and res.feasible &= clear."""
+    s = float(scale)
+    res.clearance = clearance(scene_points, scene_weights, rows, scale_gripper(gripper, s),
+                              nonneg("approach", approach) * s, min_weight, max_body, max_sweep)
+    res.feasible = res.feasible & res.clearance.clear
+    return res
+
+
 @torch.no_grad()
 def model_points(model_or_scene, mask: Optional[Tensor] = None):
     """(points, normals, weights) of a model or scene: the means, the smallest-axis normals as the renderer forms
@@ -182,15 +340,24 @@ def score_grasps(model_or_scene, grasps: ArrayLike, mask: Optional[Tensor] = Non
                  cam_to_world: Optional[ArrayLike] = None, matrix: Optional[ArrayLike] = None, scale: float = 1.0,
                  depth_base: float = DEPTH_BASE, finger_width: float = FINGER_WIDTH, band: float = BAND,
                  mu: float = MU, min_weight: float = MIN_WEIGHT,
-                 max_collision: Optional[float] = None) -> GraspContacts:
+                 max_collision: Optional[float] = None, gripper: Optional[ArrayLike] = None, approach: float = 0.0,
+                 max_body: Optional[float] = None, max_sweep: Optional[float] = None) -> GraspContacts:
     """Candidates in the grasp frame, scored against the model's Gaussians in one call: grasps_to_scene, then
-    contacts on model_points.  depth_base, finger_width and band are in grasp units and scaled with the grasps."""
+    contacts on model_points.  depth_base, finger_width and band are in grasp units and scaled with the grasps.
+    With a `gripper` (default_gripper(), or any check_gripper model; grasp units), also clearance of the whole
+    gripper and its approach against the WHOLE scene's points (model_points(model, None), whatever `mask` is):
+    feasible &= clear, and the record is returned as .clearance."""
     pts, nrm, w = model_points(model_or_scene, mask)
     g = grasps_to_scene(grasps, cam_to_world, matrix, scale)
     s = float(scale)
-    return contacts(pts, nrm, w, torch.from_numpy(g).to(pts.device), nonneg("depth_base", depth_base) * s,
-                    nonneg("finger_width", finger_width) * s, nonneg("band", band) * s, mu, min_weight,
-                    max_collision)
+    rows = torch.from_numpy(g).to(pts.device)
+    res = contacts(pts, nrm, w, rows, nonneg("depth_base", depth_base) * s,
+                   nonneg("finger_width", finger_width) * s, nonneg("band", band) * s, mu, min_weight,
+                   max_collision)
+    if gripper is None:
+        return res
+    w_all = w if mask is None else model_points(model_or_scene, None)[2]
+    return apply_clearance(res, pts, w_all, rows, gripper, s, approach, min_weight, max_body, max_sweep)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -201,6 +368,13 @@ def _load_matrix(path: str, shape, name: str) -> np.ndarray:
     if a.shape != shape:
         raise ValueError(f"{name} {path}: expected {shape}, got {a.shape}")
     return a
+
+
+def load_gripper_option(text: Optional[str]) -> Optional[np.ndarray]:
+    """--gripper: None without it, default_gripper() for "default", else load_gripper(FILE.json)."""
+    if not text:
+        return None
+    return default_gripper() if text == "default" else load_gripper(text)
 
 
 def main(argv: Optional[Sequence[str]] = None) -> int:
@@ -216,6 +390,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--band", type=float, default=BAND, help="contact patch depth, grasp units")
     ap.add_argument("--min-opacity", type=float, default=MIN_WEIGHT, help="a Gaussian takes part above it")
     ap.add_argument("--max-collision", type=float, default=None, help="limit on the opacity inside the fingers")
+    add_clearance_options(ap)
     ap.add_argument("--out", required=True, help="output .npy: feasible rows, input frame, by score")
     ap.add_argument("--report", default=None, help="output .npz: every per-grasp output, scene frame")
     a = ap.parse_args(argv)
@@ -226,8 +401,10 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             ap.error(f"--{name.replace('_', '-')} must be finite and >= 0, got {v}")
     if a.max_collision is not None and math.isnan(a.max_collision):
         ap.error("--max-collision must not be NaN")
+    check_clearance_options(ap, a)
     try:
         grasps = load_grasps(a.grasps)
+        gripper = load_gripper_option(a.gripper)
         cam = _load_matrix(a.camera_pose, (4, 4), "camera pose") if a.camera_pose else None
         matrix, scale = load_transform_json(a.transform_json) if a.transform_json else (None, 1.0)
         from .interop import load_checkpoint
@@ -235,14 +412,14 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         scene = scene.to(torch.device("cuda"))
         mask = object_mask(a, scene, mlp_state, matrix, scale)
         res = score_grasps(scene, grasps, mask, cam, matrix, scale, band=a.band, mu=a.mu, min_weight=a.min_opacity,
-                           max_collision=a.max_collision)
+                           max_collision=a.max_collision, gripper=gripper, approach=a.approach,
+                           max_body=a.max_body_collision, max_sweep=a.max_sweep_collision)
     except (KeyError, ValueError, OSError) as exc:
         raise SystemExit(f"error: {exc}") from exc
     keep = filter_grasps(grasps, res).cpu().numpy()
     np.save(a.out, grasps[keep])
     if a.report:
-        np.savez(a.report, grasps_scene=grasps_to_scene(grasps, cam, matrix, scale),
-                 **{k: getattr(res, k).cpu().numpy() for k in REPORT_KEYS})
+        np.savez(a.report, grasps_scene=grasps_to_scene(grasps, cam, matrix, scale), **report_arrays(res))
     print(f"{len(keep)} of {len(grasps)} grasps feasible; wrote {a.out}")
     return 0
 

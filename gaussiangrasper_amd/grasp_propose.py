@@ -27,10 +27,11 @@ from torch import Tensor
 from . import _lib
 from ._call import (f32_rows, host_ptr, nonneg, positive, ptr as _ptr, require_hip as _require_hip,
                     stream as _stream, workspace as _ws)
-from ._cli import REPORT_KEYS, add_object_options, check_object_options, object_mask
+from ._cli import (add_clearance_options, add_object_options, check_clearance_options, check_object_options,
+                   object_mask, report_arrays)
 from .frames import check_rotation, load_transform_json
-from .grasp import (BAND, DEPTH_BASE, FINGER_WIDTH, GRASP_COLS, MIN_WEIGHT, MU, GraspContacts, contacts, filter_grasps,
-                    grasps_from_scene, model_points)
+from .grasp import (BAND, DEPTH_BASE, FINGER_WIDTH, GRASP_COLS, MIN_WEIGHT, MU, GraspContacts, apply_clearance,
+                    contacts, filter_grasps, grasps_from_scene, load_gripper_option, model_points)
 
 # UNVERIFIED defaults (PARITY.md "Grasp proposals"), in grasp units (metres): max_width, depth and height are
 # recalled from graspnetAPI's gripper; tube_radius, min_width, clearance, min_align and num_approach are this
@@ -174,7 +175,8 @@ def propose_grasps(model_or_scene, mask: Optional[Tensor] = None, max_seeds: int
 def grasp_object(model_or_scene, mask: Optional[Tensor] = None, scale: float = 1.0,
                  depth_base: float = DEPTH_BASE, finger_width: float = FINGER_WIDTH, band: float = BAND,
                  mu: float = MU, min_weight: float = MIN_WEIGHT, max_collision: Optional[float] = None,
-                 **propose) -> Tuple[Tensor, GraspContacts, Tensor]:
+                 gripper=None, approach: float = 0.0, max_body: Optional[float] = None,
+                 max_sweep: Optional[float] = None, **propose) -> Tuple[Tensor, GraspContacts, Tensor]:
     """From a model and an object mask to feasible grasps: (rows, contacts, keep), all on the device.  rows (M, 17):
     propose_grasps(model, mask, scale=scale, **propose), scene frame.  contacts: grasp.contacts of those rows, in two
     calls, because gg_grasp_contacts takes one point set for the contacts and the collision term alike while the two
@@ -182,8 +184,11 @@ def grasp_object(model_or_scene, mask: Optional[Tensor] = None, scale: float = 1
     (weights times mask: the fingers close on the object, not on the table under it), and collision_weight from the
     WHOLE scene's points (model_points(model, None): what the fingers must not hit is everything, the object's own
     Gaussians beside the contacts included).  feasible = the object call's friction-cone result and the scene
-    call's collision_weight <= max_collision (None: no limit).  keep: filter_grasps(rows, contacts), indices of
-    the feasible rows by score."""
+    call's collision_weight <= max_collision (None: no limit).  With a `gripper` (grasp.default_gripper(), or any
+    grasp.check_gripper model; grasp units, times scale), also grasp.clearance of the whole gripper and of its
+    straight approach of length `approach` against the WHOLE scene's points: feasible &= clear (body weight <=
+    max_body, sweep weight <= max_sweep; None: no limit), and the record is contacts.clearance.  keep:
+    filter_grasps(rows, contacts), indices of the feasible rows by score."""
     rows = propose_grasps(model_or_scene, mask, scale=scale, min_weight=min_weight, **propose)
     s = float(scale)
     lengths = (nonneg("depth_base", depth_base) * s, nonneg("finger_width", finger_width) * s,
@@ -196,6 +201,9 @@ def grasp_object(model_or_scene, mask: Optional[Tensor] = None, scale: float = 1
         whole = contacts(*model_points(model_or_scene, None), rows, *lengths, mu, min_weight, None)
         res.collision_weight = whole.collision_weight
     res.feasible = res.feasible & (res.collision_weight.double() <= mc)
+    if gripper is not None:
+        pts, _, w = model_points(model_or_scene, None)
+        apply_clearance(res, pts, w, rows, gripper, s, approach, min_weight, max_body, max_sweep)
     return rows, res, filter_grasps(rows, res)
 
 
@@ -217,6 +225,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--mu", type=float, default=MU, help="friction coefficient")
     ap.add_argument("--min-opacity", type=float, default=MIN_WEIGHT, help="a Gaussian takes part above it")
     ap.add_argument("--max-collision", type=float, default=None, help="limit on the opacity inside the fingers")
+    add_clearance_options(ap)
     ap.add_argument("--out", required=True, help="output .npy: feasible rows by score, world frame (scene frame "
                                                  "without --transform-json: the two are the same then)")
     ap.add_argument("--report", default=None, help="output .npz: every candidate (scene frame) and its outputs")
@@ -228,6 +237,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             ap.error(f"--{name.replace('_', '-')} must be finite and >= 0, got {v}")
     if a.max_collision is not None and math.isnan(a.max_collision):
         ap.error("--max-collision must not be NaN")
+    check_clearance_options(ap, a)
     if a.max_seeds < 1:
         ap.error(f"--max-seeds must be >= 1, got {a.max_seeds}")
     try:
@@ -236,6 +246,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     except ValueError as exc:
         ap.error(str(exc))
     try:
+        gripper = load_gripper_option(a.gripper)
         matrix, scale = None, 1.0
         if a.transform_json:
             matrix, scale = load_transform_json(a.transform_json)
@@ -248,7 +259,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         scene = scene.to(torch.device("cuda"))
         mask = object_mask(a, scene, mlp_state, matrix, scale)
         rows, res, keep = grasp_object(scene, mask, scale=scale, mu=a.mu, min_weight=a.min_opacity,
-                                       max_collision=a.max_collision, max_seeds=a.max_seeds,
+                                       max_collision=a.max_collision, gripper=gripper, approach=a.approach,
+                                       max_body=a.max_body_collision, max_sweep=a.max_sweep_collision,
+                                       max_seeds=a.max_seeds,
                                        num_approach=a.num_approach, up=up, max_width=a.max_width)
     except (KeyError, ValueError, OSError) as exc:
         raise SystemExit(f"error: {exc}") from exc
@@ -256,7 +269,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     kept = rows_np[keep.cpu().numpy()]
     np.save(a.out, grasps_from_scene(kept, None, matrix, scale))
     if a.report:
-        np.savez(a.report, grasps_scene=rows_np, **{k: getattr(res, k).cpu().numpy() for k in REPORT_KEYS})
+        np.savez(a.report, grasps_scene=rows_np, **report_arrays(res))
     print(f"{len(kept)} of {len(rows_np)} proposed grasps feasible; wrote {a.out}")
     return 0
 

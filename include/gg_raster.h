@@ -693,6 +693,48 @@ int gg_grasp_propose(int num_points, const float *points, const float *normals, 
                      int num_approach, int32_t *pair_idx, int32_t *tube_count, float *span, uint8_t *valid,
                      float *rows, void *ws, size_t ws_bytes, gg_stream_t stream);
 
+/* ---- gripper clearance: the whole gripper and its way in against the points (PARITY "Gripper
+ * clearance") ----------------------------------------------------------------------------------------------------
+ * Every grasp candidate against every point, exact in fp64, with a deterministic reduction.  Where
+ * gg_grasp_contacts' collision_weight looks inside the two finger boxes at the final pose, this call looks at a model
+ * of the whole gripper, at the final pose (body) and over the straight approach that leads to it (sweep).
+ *   grasps: as for gg_grasp_contacts: num_grasps x 17 fp32 rows, gripper frame (a, b, c) = the columns of R.  A row is
+ *           valid iff every entry is finite, width > 0 and height > 0 (depth may have either sign).
+ *   points: num_points x 3 fp32; weights: num_points fp32.  A point takes part iff p is finite and
+ *           (double)w > min_weight.  There are no normals.
+ *   parts:  HOST array of num_parts x 6 x 4 doubles.  The gripper is num_parts boxes of the gripper frame; part p's
+ *           bounds (x_lo, x_hi, y_lo, y_hi, z_lo, z_hi) = parts[p][0..5] are affine in the row's own sizes:
+ *               bound = ((c0 + cw width) + cd depth) + ch height      with (c0, cw, cd, ch) = parts[p][k][0..3],
+ *           in fp64 in that order, so one model serves candidates of every opening and finger length.  A part with
+ *           lo > hi on some axis, or with a bound that is not finite, is empty for that row: it counts nothing, body or
+ *           sweep (data, not an error).
+ * Per valid grasp and point taking part, in fp64 from the fp32 inputs, no contraction:
+ *   d_k = (double)p_k - (double)t_k;  u_j = (R[0][j] d_0 + R[1][j] d_1) + R[2][j] d_2     (as gg_grasp_contacts)
+ *   body of part p:   x_lo <= u_0 <= x_hi,  y_lo <= u_1 <= y_hi,  z_lo <= u_2 <= z_hi     (every face closed)
+ *   sweep of part p:  x_s <= u_0 < x_lo with x_s = x_lo - approach, u_1 and u_2 as for the body.  The gripper reaches t
+ *                     from t - approach a, translating along +a, so in its own frame every part sweeps that extension
+ *                     of itself; the interval is half-open, so body and sweep never share a point, and approach == 0
+ *                     gives zero sweeps.
+ * Parts are tested independently: a point inside two overlapping parts counts in both, so a model's parts should be
+ * disjoint up to faces.  Outputs, every grasp written:
+ *   body_count / sweep_count int32 [M][P]: the points in the body / sweep of each part;
+ *   body_weight / sweep_weight fp32 [M][P]: the fp64 sum of their w, rounded to fp32;
+ *   valid uint8 [M];  clear uint8 [M]: valid, sum_p body <= max_body and sum_p sweep <= max_sweep, the totals taken
+ *   in fp64, in part order, from the fp64 part sums before they are rounded.
+ * A row that is not valid gets zero counts, zero weights and valid = clear = 0 (data, not an error).
+ * num_parts in 1..GG_CLEAR_MAX_PARTS and every coefficient finite; approach finite and >= 0; min_weight, max_body and
+ * max_sweep not NaN (+inf: no limit).  num_grasps == 0 does nothing; num_points == 0 writes zeros and clear = valid.
+ * No atomics: per-chunk partials combined in a fixed order, identical run to run.  No square root or division decides
+ * anything: counts are exact.  `ws`: gg_grasp_clearance_workspace() bytes, 256-byte aligned (0 is returned for counts
+ * out of range: the limits are GG_GRASP_MAX and GG_GRASP_MAX_POINTS). */
+#define GG_CLEAR_MAX_PARTS 8
+size_t gg_grasp_clearance_workspace(int num_points, int num_grasps, int num_parts);
+int gg_grasp_clearance(int num_points, const float *points, const float *weights, int num_grasps, const float *grasps,
+                       int num_parts, const double *parts, double approach, double min_weight, double max_body,
+                       double max_sweep, int32_t *body_count, float *body_weight, int32_t *sweep_count,
+                       float *sweep_weight, uint8_t *valid, uint8_t *clear, void *ws, size_t ws_bytes,
+                       gg_stream_t stream);
+
 /* ---- scene preparation from RGB-D frames (PARITY "Scene preparation") --------------------------------
  * gg_backproject: depth frames to a base-frame point cloud (generate_data.py depth_image_to_point_cloud +
  * merge_point_clouds).  Frames are F x H x W, frame-major then row-major:
@@ -954,7 +996,8 @@ int gg_tsdf_mesh_emit(const int32_t *dims, const float *grid, const float *tsdf,
 #define GG_K_CLUSTER_STATS 47 /* gg_cluster_stats: all three launches */
 #define GG_K_CLOUD_FRAMES 48  /* gg_cloud_frames: init, sort and the frames kernel */
 #define GG_K_ICP_STEP 49      /* gg_icp_step: the sort (unless reused), the step kernel and its finishing workgroup */
-#define GG_K_IDS 50           /* ids are below this */
+#define GG_K_GRASP_CLEAR 50   /* gg_grasp_clearance: the pass and the per-grasp reduction */
+#define GG_K_IDS 51           /* ids are below this */
 #define GG_PROF_NUM_KERNELS 32
 int gg_prof_enable(int on);
 int gg_prof_reset(void);
