@@ -11,6 +11,8 @@ import numpy as np
 
 REPORT_KEYS = ("contact_idx", "normals", "angles", "region_count", "region_weight", "collision_weight", "feasible")
 CLEAR_KEYS = ("body_weight", "sweep_weight", "body_count", "sweep_count", "clear")     # only with --gripper
+NMS_KEYS = ("keep", "suppressor", "support")             # only with --nms-translation, as nms_keep, ...
+NMS_ROTATION_DEGREES = 30.0                              # grasp.NMS_ROTATION
 
 
 def add_clearance_options(ap) -> None:
@@ -43,12 +45,45 @@ def check_clearance_options(ap, a) -> None:
         a.approach = 0.0
 
 
+def add_nms_options(ap) -> None:
+    """--nms-translation, --nms-rotation, --nms-no-symmetry, --top-k (grasp.nms)."""
+    ap.add_argument("--nms-translation", type=float, default=None, metavar="METRES",
+                    help="keep distinct grasps only: of the feasible rows, best first, drop one that is within this "
+                         "distance (grasp units) and --nms-rotation of a kept one")
+    ap.add_argument("--nms-rotation", type=float, default=None, metavar="DEGREES",
+                    help=f"with --nms-translation: the rotation that still counts as near (default "
+                         f"{NMS_ROTATION_DEGREES:g})")
+    ap.add_argument("--nms-no-symmetry", action="store_true",
+                    help="with --nms-translation: a pose and its half turn about the approach axis are two grasps")
+    ap.add_argument("--top-k", type=int, default=None, metavar="K",
+                    help="with --nms-translation: write the best K distinct grasps only")
+
+
+def check_nms_options(ap, a) -> None:
+    """ap.error unless the NMS options are complete and in range; a.nms_rotation None becomes the default."""
+    if a.nms_translation is None:
+        for n, given in (("nms_rotation", a.nms_rotation is not None), ("nms_no_symmetry", a.nms_no_symmetry),
+                         ("top_k", a.top_k is not None)):
+            if given:
+                ap.error("--" + n.replace("_", "-") + " needs --nms-translation")
+    elif not (math.isfinite(a.nms_translation) and a.nms_translation >= 0.0):
+        ap.error(f"--nms-translation must be finite and >= 0, got {a.nms_translation}")
+    if a.nms_rotation is not None and not 0.0 <= a.nms_rotation <= 180.0:        # NaN fails
+        ap.error(f"--nms-rotation must be in 0..180 degrees, got {a.nms_rotation}")
+    if a.top_k is not None and a.top_k < 1:
+        ap.error(f"--top-k must be >= 1, got {a.top_k}")
+    if a.nms_rotation is None:
+        a.nms_rotation = NMS_ROTATION_DEGREES
+
+
 def report_arrays(res) -> dict:
-    """The per-grasp arrays of a --report file: REPORT_KEYS of a GraspContacts, and CLEAR_KEYS of its .clearance
-    when it has one."""
+    """The per-grasp arrays of a --report file: REPORT_KEYS of a GraspContacts, CLEAR_KEYS of its .clearance when it
+    has one, and NMS_KEYS of its .nms, as nms_keep, nms_suppressor and nms_support, when it has one."""
     out = {k: getattr(res, k).cpu().numpy() for k in REPORT_KEYS}
     if res.clearance is not None:
         out.update({k: getattr(res.clearance, k).cpu().numpy() for k in CLEAR_KEYS})
+    if getattr(res, "nms", None) is not None:
+        out.update({"nms_" + k: getattr(res.nms, k).cpu().numpy() for k in NMS_KEYS})
     return out
 
 

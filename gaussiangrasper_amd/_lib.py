@@ -116,6 +116,8 @@ SIGNATURES = {
     "gg_grasp_propose": (_I, [_I, _P, _P, _P, _I, _P] + [C.c_double] * 8 + [_P, _I] + [_P] * 5 + [_P, _SZ, _P]),
     "gg_grasp_clearance_workspace": (_SZ, [_I, _I, _I]),
     "gg_grasp_clearance": (_I, [_I, _P, _P, _I, _P, _I, _P] + [C.c_double] * 4 + [_P] * 6 + [_P, _SZ, _P]),
+    "gg_grasp_nms_workspace": (_SZ, [_I]),
+    "gg_grasp_nms": (_I, [_I, _P, _I, _P, C.c_double, C.c_double, _I] + [_P] * 4 + [_P, _SZ, _P]),
     "gg_backproject_workspace": (_SZ, [_I, _I, _I]),
     "gg_backproject": (_I, [_I, _I, _I] + [_P] * 5 + [C.c_double] * 4 + [_P] * 4 + [_SZ, _P]),
     "gg_subsample_workspace": (_SZ, [_I64]),

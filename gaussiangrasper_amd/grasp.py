@@ -14,6 +14,8 @@ every candidate against every oriented point in fp64; the contract is in include
                        scale_gripper, load_gripper: models of one's own)
     clearance          what such a gripper holds at the final pose and sweeps on its approach, per part
                        (gg_grasp_clearance, csrc/grasp_clear.hip, PARITY.md "Gripper clearance"; GraspClearance)
+    nms                distinct grasps: greedy pose-distance suppression of the active rows, best score first
+                       (gg_grasp_nms, csrc/grasp_nms.hip, PARITY.md "Grasp NMS"; GraspNMS)
     python -m gaussiangrasper_amd.grasp --ckpt IN --grasps grasps.npy [...] --out kept.npy
 
 Grasp candidates come from outside the project (AnyGrasp): this module only scores them."""
@@ -33,8 +35,8 @@ from torch import Tensor
 from . import _lib
 from ._call import (ArrayLike, f32_rows, host_ptr, nonneg, positive, ptr as _ptr, require_hip as _require_hip,
                     stream as _stream, workspace as _ws)
-from ._cli import (add_clearance_options, add_object_options, check_clearance_options, check_object_options,
-                   object_mask, report_arrays)
+from ._cli import (add_clearance_options, add_nms_options, add_object_options, check_clearance_options,
+                   check_nms_options, check_object_options, object_mask, report_arrays)
 from .frames import ORTHO_TOL, load_transform_json, rigid_to_scene  # noqa: F401
 
 GRASP_COLS = 17
@@ -46,6 +48,11 @@ BAND = 0.003
 MU = 0.5
 MIN_WEIGHT = 0.0
 MAX_PARTS = 8                # GG_CLEAR_MAX_PARTS
+# UNVERIFIED defaults (PARITY.md "Grasp NMS"): graspnetAPI's GraspGroup.nms thresholds as recalled, 3 cm and 30 degrees
+NMS_TRANSLATION = 0.03
+NMS_ROTATION = math.pi / 6.0
+NMS_MAX_CANDIDATES = 16384
+NMS_MAX_ORDER = 65536        # GG_NMS_MAX_ORDER
 
 
 @dataclass
@@ -59,6 +66,7 @@ class GraspContacts:
     collision_weight: Tensor   # (M,) float32
     feasible: Tensor           # (M,) bool
     clearance: Optional["GraspClearance"] = None     # set by score_grasps / grasp_object when a gripper is given
+    nms: Optional["GraspNMS"] = None                 # set by score_grasps / grasp_object with nms_translation
 
 
 @dataclass
@@ -70,6 +78,16 @@ class GraspClearance:
     sweep_weight: Tensor       # (M, P) float32
     valid: Tensor              # (M,) bool: the row is finite with width > 0 and height > 0
     clear: Tensor              # (M,) bool: valid and both totals within their limits
+
+
+@dataclass
+class GraspNMS:
+    """Outputs of one gg_grasp_nms call, device tensors; M = number of grasps, K = number of kept rows."""
+    keep: Tensor               # (M,) bool
+    suppressor: Tensor         # (M,) int32: -1 kept, the kept row that suppressed it, -2 not active / not a pose
+    order: Tensor              # (K,) int64: the kept rows, best first
+    support: Tensor            # (M,) int32: for a kept row 1 + the rows it suppressed, 0 elsewhere.  Many active poses
+                               # around a kept one: the grasp tolerates pose error (a ranking aid, not a filter)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -304,6 +322,91 @@ def clearance(points: Tensor, weights: Tensor, grasps: Tensor, gripper: ArrayLik
     return res
 
 
+def nms_order(grasps: Tensor, active: Optional[Tensor] = None,
+              max_candidates: int = NMS_MAX_CANDIDATES) -> Tensor:
+    """The int32 order grasp.nms walks: the active rows (None: all) whose score (fp32 column 0) is not NaN, by score
+    descending, equal scores by ascending index (a stable sort), cut to the best max_candidates.  On the device of
+    `grasps`."""
+    m = grasps.shape[0]
+    k = int(max_candidates)
+    if k != max_candidates or not 1 <= k <= NMS_MAX_ORDER:
+        raise ValueError(f"max_candidates must be an integer in 1..{NMS_MAX_ORDER}, got {max_candidates}")
+    score = grasps[:, 0].float()
+    take = ~torch.isnan(score)
+    if active is not None:
+        active = active.reshape(-1)
+        if active.shape[0] != m:
+            raise ValueError(f"active has {active.shape[0]} entries for {m} grasps")
+        take = take & active.to(device=score.device, dtype=torch.bool)
+    idx = torch.nonzero(take).reshape(-1)
+    by_score = torch.sort(score[idx], descending=True, stable=True).indices
+    return idx[by_score][:k].to(torch.int32)
+
+
+def nms_support(keep: Tensor, suppressor: Tensor) -> Tensor:
+    """(M,) int32: for a kept row 1 + how often it is named in `suppressor`, 0 for every other row."""
+    m = keep.shape[0]
+    named = torch.bincount(suppressor[suppressor >= 0].long(), minlength=m)[:m]
+    return torch.where(keep, named + 1, torch.zeros_like(named)).to(torch.int32)
+
+
+def nms(grasps: Tensor, active: Union[None, GraspContacts, Tensor] = None, translation: float = NMS_TRANSLATION,
+        rotation: float = NMS_ROTATION, symmetric: bool = True, scale: float = 1.0,
+        max_candidates: int = NMS_MAX_CANDIDATES) -> GraspNMS:
+    """Distinct grasps of the active rows (include/gg_raster.h gg_grasp_nms): walking nms_order(grasps, active,
+    max_candidates), a row is kept unless a kept row before it is near, i.e. within `translation` (grasp units, times
+    `scale`) of it and turned by at most `rotation` radians against it, or, with `symmetric`, against its half turn
+    about the approach axis (the same parallel-jaw pose with the fingers swapped).  Both limits are inclusive.
+    grasps (M, 17) float32 on the HIP device (no CPU path); active: (M,) bool, or a GraspContacts, whose .feasible is
+    used; None: every row.  The pair matrix takes max_candidates^2 / 8 bytes of workspace.  One call and one
+    read-back (the number of kept rows)."""
+    dev = _require_hip(grasps)
+    grasps = f32_rows(grasps, "grasps", GRASP_COLS)
+    m = grasps.shape[0]
+    if isinstance(active, GraspContacts):
+        active = active.feasible
+    elif active is not None:
+        active = torch.as_tensor(active)
+    t = nonneg("translation", translation) * positive("scale", scale)
+    rot = float(rotation)
+    if not 0.0 <= rot <= math.pi:
+        raise ValueError(f"rotation must be in [0, pi] radians, got {rotation}")
+    order = nms_order(grasps, active, max_candidates)
+    a = order.shape[0]
+    lib = _lib.load()
+    keep = torch.empty(m, dtype=torch.uint8, device=dev)
+    suppressor = torch.empty(m, dtype=torch.int32, device=dev)
+    kept = torch.empty(a, dtype=torch.int32, device=dev)
+    num_kept = torch.zeros(1, dtype=torch.int32, device=dev)
+    if m > 0:
+        ws = _ws(lib.gg_grasp_nms_workspace(a), dev)
+        _lib.check(lib.gg_grasp_nms(m, _ptr(grasps), a, _ptr(order), t, math.cos(rot), 1 if symmetric else 0,
+                                    _ptr(keep), _ptr(suppressor), _ptr(kept), _ptr(num_kept), _ptr(ws), ws.numel(),
+                                    _stream(dev)), "gg_grasp_nms")
+    keep = keep.bool()
+    return GraspNMS(keep=keep, suppressor=suppressor, order=kept[:int(num_kept.item())].long(),
+                    support=nms_support(keep, suppressor))
+
+
+def check_top_k(nms_translation: Optional[float], top_k: Optional[int]) -> Optional[int]:
+    """top_k as an int >= 1 or None; it needs nms_translation."""
+    if top_k is None:
+        return None
+    if nms_translation is None:
+        raise ValueError("top_k needs nms_translation: without NMS the best rows are copies of one grasp")
+    if int(top_k) != top_k or int(top_k) < 1:
+        raise ValueError(f"top_k must be an integer >= 1, got {top_k}")
+    return int(top_k)
+
+
+def apply_nms(res: GraspContacts, rows: Tensor, translation: float, rotation: float, symmetric: bool,
+              scale: float, top_k: Optional[int]) -> Tensor:
+    """res.nms = nms(rows, res, ...) over the feasible rows (translation in grasp units, times scale); returns
+    res.nms.order[:top_k]."""
+    res.nms = nms(rows, res, translation, rotation, symmetric, scale)
+    return res.nms.order[:top_k]
+
+
 def apply_clearance(res: GraspContacts, scene_points: Tensor, scene_weights: Tensor, rows: Tensor, gripper: ArrayLike,
                     scale: float, approach: float, min_weight: float, max_body: Optional[float],
                     max_sweep: Optional[float]) -> GraspContacts:
@@ -341,12 +444,17 @@ def score_grasps(model_or_scene, grasps: ArrayLike, mask: Optional[Tensor] = Non
                  depth_base: float = DEPTH_BASE, finger_width: float = FINGER_WIDTH, band: float = BAND,
                  mu: float = MU, min_weight: float = MIN_WEIGHT,
                  max_collision: Optional[float] = None, gripper: Optional[ArrayLike] = None, approach: float = 0.0,
-                 max_body: Optional[float] = None, max_sweep: Optional[float] = None) -> GraspContacts:
+                 max_body: Optional[float] = None, max_sweep: Optional[float] = None,
+                 nms_translation: Optional[float] = None, nms_rotation: float = NMS_ROTATION,
+                 nms_symmetric: bool = True, top_k: Optional[int] = None) -> GraspContacts:
     """Candidates in the grasp frame, scored against the model's Gaussians in one call: grasps_to_scene, then
     contacts on model_points.  depth_base, finger_width and band are in grasp units and scaled with the grasps.
     With a `gripper` (default_gripper(), or any check_gripper model; grasp units), also clearance of the whole
     gripper and its approach against the WHOLE scene's points (model_points(model, None), whatever `mask` is):
-    feasible &= clear, and the record is returned as .clearance."""
+    feasible &= clear, and the record is returned as .clearance.  With `nms_translation` (grasp units), also nms of
+    the feasible rows, returned as .nms; with top_k its .order is cut to the best top_k.  Without nms_translation
+    there is no NMS call and .nms is None."""
+    top_k = check_top_k(nms_translation, top_k)
     pts, nrm, w = model_points(model_or_scene, mask)
     g = grasps_to_scene(grasps, cam_to_world, matrix, scale)
     s = float(scale)
@@ -354,10 +462,12 @@ def score_grasps(model_or_scene, grasps: ArrayLike, mask: Optional[Tensor] = Non
     res = contacts(pts, nrm, w, rows, nonneg("depth_base", depth_base) * s,
                    nonneg("finger_width", finger_width) * s, nonneg("band", band) * s, mu, min_weight,
                    max_collision)
-    if gripper is None:
-        return res
-    w_all = w if mask is None else model_points(model_or_scene, None)[2]
-    return apply_clearance(res, pts, w_all, rows, gripper, s, approach, min_weight, max_body, max_sweep)
+    if gripper is not None:
+        w_all = w if mask is None else model_points(model_or_scene, None)[2]
+        apply_clearance(res, pts, w_all, rows, gripper, s, approach, min_weight, max_body, max_sweep)
+    if nms_translation is not None:
+        res.nms.order = apply_nms(res, rows, nms_translation, nms_rotation, nms_symmetric, s, top_k)
+    return res
 
 
 # ------------------------------------------------------------------------------------------------
@@ -377,6 +487,14 @@ def load_gripper_option(text: Optional[str]) -> Optional[np.ndarray]:
     return default_gripper() if text == "default" else load_gripper(text)
 
 
+def nms_summary(feasible: int, total: int, res: GraspContacts, written: int, what: str) -> str:
+    """The command lines' summary: how many rows are feasible and, with NMS, how many survive it."""
+    line = f"{feasible} of {total} {what} feasible"
+    if res.nms is not None:
+        line += f", {int(res.nms.keep.sum())} distinct after NMS, {written} written"
+    return line
+
+
 def main(argv: Optional[Sequence[str]] = None) -> int:
     ap = argparse.ArgumentParser(prog="python -m gaussiangrasper_amd.grasp",
                                  description="Filter grasp candidates (GraspGroup rows) by the friction cone at both "
@@ -391,6 +509,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--min-opacity", type=float, default=MIN_WEIGHT, help="a Gaussian takes part above it")
     ap.add_argument("--max-collision", type=float, default=None, help="limit on the opacity inside the fingers")
     add_clearance_options(ap)
+    add_nms_options(ap)
     ap.add_argument("--out", required=True, help="output .npy: feasible rows, input frame, by score")
     ap.add_argument("--report", default=None, help="output .npz: every per-grasp output, scene frame")
     a = ap.parse_args(argv)
@@ -402,6 +521,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     if a.max_collision is not None and math.isnan(a.max_collision):
         ap.error("--max-collision must not be NaN")
     check_clearance_options(ap, a)
+    check_nms_options(ap, a)
     try:
         grasps = load_grasps(a.grasps)
         gripper = load_gripper_option(a.gripper)
@@ -413,14 +533,16 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         mask = object_mask(a, scene, mlp_state, matrix, scale)
         res = score_grasps(scene, grasps, mask, cam, matrix, scale, band=a.band, mu=a.mu, min_weight=a.min_opacity,
                            max_collision=a.max_collision, gripper=gripper, approach=a.approach,
-                           max_body=a.max_body_collision, max_sweep=a.max_sweep_collision)
+                           max_body=a.max_body_collision, max_sweep=a.max_sweep_collision,
+                           nms_translation=a.nms_translation, nms_rotation=math.radians(a.nms_rotation),
+                           nms_symmetric=not a.nms_no_symmetry, top_k=a.top_k)
     except (KeyError, ValueError, OSError) as exc:
         raise SystemExit(f"error: {exc}") from exc
-    keep = filter_grasps(grasps, res).cpu().numpy()
+    keep = (filter_grasps(grasps, res) if res.nms is None else res.nms.order).cpu().numpy()
     np.save(a.out, grasps[keep])
     if a.report:
         np.savez(a.report, grasps_scene=grasps_to_scene(grasps, cam, matrix, scale), **report_arrays(res))
-    print(f"{len(keep)} of {len(grasps)} grasps feasible; wrote {a.out}")
+    print(f"{nms_summary(int(res.feasible.sum()), len(grasps), res, len(keep), 'grasps')}; wrote {a.out}")
     return 0
 
 

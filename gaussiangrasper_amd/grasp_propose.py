@@ -27,11 +27,12 @@ from torch import Tensor
 from . import _lib
 from ._call import (f32_rows, host_ptr, nonneg, positive, ptr as _ptr, require_hip as _require_hip,
                     stream as _stream, workspace as _ws)
-from ._cli import (add_clearance_options, add_object_options, check_clearance_options, check_object_options,
-                   object_mask, report_arrays)
+from ._cli import (add_clearance_options, add_nms_options, add_object_options, check_clearance_options,
+                   check_nms_options, check_object_options, object_mask, report_arrays)
 from .frames import check_rotation, load_transform_json
-from .grasp import (BAND, DEPTH_BASE, FINGER_WIDTH, GRASP_COLS, MIN_WEIGHT, MU, GraspContacts, apply_clearance,
-                    contacts, filter_grasps, grasps_from_scene, load_gripper_option, model_points)
+from .grasp import (BAND, DEPTH_BASE, FINGER_WIDTH, GRASP_COLS, MIN_WEIGHT, MU, NMS_ROTATION, GraspContacts,
+                    apply_clearance, apply_nms, check_top_k, contacts, filter_grasps, grasps_from_scene,
+                    load_gripper_option, model_points, nms_summary)
 
 # UNVERIFIED defaults (PARITY.md "Grasp proposals"), in grasp units (metres): max_width, depth and height are
 # recalled from graspnetAPI's gripper; tube_radius, min_width, clearance, min_align and num_approach are this
@@ -176,7 +177,9 @@ def grasp_object(model_or_scene, mask: Optional[Tensor] = None, scale: float = 1
                  depth_base: float = DEPTH_BASE, finger_width: float = FINGER_WIDTH, band: float = BAND,
                  mu: float = MU, min_weight: float = MIN_WEIGHT, max_collision: Optional[float] = None,
                  gripper=None, approach: float = 0.0, max_body: Optional[float] = None,
-                 max_sweep: Optional[float] = None, **propose) -> Tuple[Tensor, GraspContacts, Tensor]:
+                 max_sweep: Optional[float] = None, nms_translation: Optional[float] = None,
+                 nms_rotation: float = NMS_ROTATION, nms_symmetric: bool = True, top_k: Optional[int] = None,
+                 **propose) -> Tuple[Tensor, GraspContacts, Tensor]:
     """From a model and an object mask to feasible grasps: (rows, contacts, keep), all on the device.  rows (M, 17):
     propose_grasps(model, mask, scale=scale, **propose), scene frame.  contacts: grasp.contacts of those rows, in two
     calls, because gg_grasp_contacts takes one point set for the contacts and the collision term alike while the two
@@ -188,7 +191,12 @@ def grasp_object(model_or_scene, mask: Optional[Tensor] = None, scale: float = 1
     grasp.check_gripper model; grasp units, times scale), also grasp.clearance of the whole gripper and of its
     straight approach of length `approach` against the WHOLE scene's points: feasible &= clear (body weight <=
     max_body, sweep weight <= max_sweep; None: no limit), and the record is contacts.clearance.  keep:
-    filter_grasps(rows, contacts), indices of the feasible rows by score."""
+    filter_grasps(rows, contacts), indices of the feasible rows by score.  With `nms_translation` (grasp units, times
+    scale), also grasp.nms of the feasible rows (near: within nms_translation and nms_rotation radians, with
+    nms_symmetric also of the half turn about the approach axis): the record is contacts.nms and keep becomes its
+    order[:top_k], the distinct grasps best first, a subsequence of what filter_grasps gives.  Without
+    nms_translation there is no NMS call and contacts.nms is None; top_k then is an error."""
+    top_k = check_top_k(nms_translation, top_k)
     rows = propose_grasps(model_or_scene, mask, scale=scale, min_weight=min_weight, **propose)
     s = float(scale)
     lengths = (nonneg("depth_base", depth_base) * s, nonneg("finger_width", finger_width) * s,
@@ -204,6 +212,8 @@ def grasp_object(model_or_scene, mask: Optional[Tensor] = None, scale: float = 1
     if gripper is not None:
         pts, _, w = model_points(model_or_scene, None)
         apply_clearance(res, pts, w, rows, gripper, s, approach, min_weight, max_body, max_sweep)
+    if nms_translation is not None:
+        return rows, res, apply_nms(res, rows, nms_translation, nms_rotation, nms_symmetric, s, top_k)
     return rows, res, filter_grasps(rows, res)
 
 
@@ -226,6 +236,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--min-opacity", type=float, default=MIN_WEIGHT, help="a Gaussian takes part above it")
     ap.add_argument("--max-collision", type=float, default=None, help="limit on the opacity inside the fingers")
     add_clearance_options(ap)
+    add_nms_options(ap)
     ap.add_argument("--out", required=True, help="output .npy: feasible rows by score, world frame (scene frame "
                                                  "without --transform-json: the two are the same then)")
     ap.add_argument("--report", default=None, help="output .npz: every candidate (scene frame) and its outputs")
@@ -238,6 +249,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     if a.max_collision is not None and math.isnan(a.max_collision):
         ap.error("--max-collision must not be NaN")
     check_clearance_options(ap, a)
+    check_nms_options(ap, a)
     if a.max_seeds < 1:
         ap.error(f"--max-seeds must be >= 1, got {a.max_seeds}")
     try:
@@ -261,7 +273,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         rows, res, keep = grasp_object(scene, mask, scale=scale, mu=a.mu, min_weight=a.min_opacity,
                                        max_collision=a.max_collision, gripper=gripper, approach=a.approach,
                                        max_body=a.max_body_collision, max_sweep=a.max_sweep_collision,
-                                       max_seeds=a.max_seeds,
+                                       nms_translation=a.nms_translation,
+                                       nms_rotation=math.radians(a.nms_rotation),
+                                       nms_symmetric=not a.nms_no_symmetry, top_k=a.top_k, max_seeds=a.max_seeds,
                                        num_approach=a.num_approach, up=up, max_width=a.max_width)
     except (KeyError, ValueError, OSError) as exc:
         raise SystemExit(f"error: {exc}") from exc
@@ -270,7 +284,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     np.save(a.out, grasps_from_scene(kept, None, matrix, scale))
     if a.report:
         np.savez(a.report, grasps_scene=rows_np, **report_arrays(res))
-    print(f"{len(kept)} of {len(rows_np)} proposed grasps feasible; wrote {a.out}")
+    print(f"{nms_summary(int(res.feasible.sum()), len(rows_np), res, len(kept), 'proposed grasps')}; wrote {a.out}")
     return 0
 
 

@@ -735,6 +735,39 @@ int gg_grasp_clearance(int num_points, const float *points, const float *weights
                        float *sweep_weight, uint8_t *valid, uint8_t *clear, void *ws, size_t ws_bytes,
                        gg_stream_t stream);
 
+/* ---- grasp NMS: distinct grasps from an ordered set (PARITY "Grasp NMS") ------------------------------
+ * Greedy pose-distance non-maximum suppression over GraspGroup rows, in the caller's order; exact in fp64 and a pure
+ * function of its inputs.
+ *   grasps: as for gg_grasp_contacts: num_grasps x 17 fp32 rows, R row-major in columns 4..12, t in columns 13..15.
+ *           Only R and t are read; a row takes part iff all 12 of those entries are finite.
+ *   order:  num_order int32 row indices on the device, distinct, best first.  An entry outside [0, num_grasps) is
+ *           skipped.  Repeated entries are the caller's error: they may give an unspecified `keep` for that row, never
+ *           an access out of bounds.
+ * Rows i and j that take part are NEAR iff both of the following hold, in fp64 from the fp32 inputs, no contraction:
+ *   d_k = (double)t_ik - (double)t_jk;  dd = (d0 d0 + d1 d1) + d2 d2;  dd <= translation * translation;
+ *   c_k = (Ri[0][k] Rj[0][k] + Ri[1][k] Rj[1][k]) + Ri[2][k] Rj[2][k] for the columns k = 0, 1, 2;
+ *   tr = (c0 + c1) + c2;  tr_s = (c0 - c1) - c2 (the trace against Rj diag(1, -1, -1): the same parallel-jaw pose
+ *   turned half a turn about its approach axis);  bound = 1 + 2 cos_rotation;
+ *   tr >= bound, or symmetric != 0 and tr_s >= bound.
+ * A rotation by the angle theta has tr = 1 + 2 cos theta, so cos_rotation = cos(largest angle that still counts as
+ * near).  Both comparisons are inclusive.  No square root, acos or division decides anything.
+ * The walk goes through `order` from the front: a row that takes part is KEPT iff no kept row earlier in `order` is
+ * near it.  A suppressed row suppresses nothing.  Outputs, every element written:
+ *   keep uint8 [num_grasps];
+ *   suppressor int32 [num_grasps]: -1 for a kept row; for a suppressed row the row index of the first kept row in
+ *           `order` that is near it; -2 for a row that is not in `order` or does not take part;
+ *   kept int32 [num_order]: the kept row indices in `order`'s order, then -1 to the end;
+ *   num_kept: device int32 [1].
+ * translation finite and >= 0; cos_rotation in [-1, 1].  num_order == 0 writes keep = 0, suppressor = -2 and
+ * num_kept = 0 (order, kept and ws may be null); with num_grasps == 0 as well the call does nothing and every pointer
+ * may be null.  No atomics: identical output call to call.  `ws`: gg_grasp_nms_workspace() bytes, 256-byte aligned,
+ * under num_order^2 / 8 + 64 num_order + 1024 bytes (0 is returned for num_order < 0 or > GG_NMS_MAX_ORDER). */
+#define GG_NMS_MAX_ORDER 65536
+size_t gg_grasp_nms_workspace(int num_order);
+int gg_grasp_nms(int num_grasps, const float *grasps, int num_order, const int32_t *order, double translation,
+                 double cos_rotation, int symmetric, uint8_t *keep, int32_t *suppressor, int32_t *kept,
+                 int32_t *num_kept, void *ws, size_t ws_bytes, gg_stream_t stream);
+
 /* ---- scene preparation from RGB-D frames (PARITY "Scene preparation") --------------------------------
  * gg_backproject: depth frames to a base-frame point cloud (generate_data.py depth_image_to_point_cloud +
  * merge_point_clouds).  Frames are F x H x W, frame-major then row-major:
@@ -997,7 +1030,8 @@ int gg_tsdf_mesh_emit(const int32_t *dims, const float *grid, const float *tsdf,
 #define GG_K_CLOUD_FRAMES 48  /* gg_cloud_frames: init, sort and the frames kernel */
 #define GG_K_ICP_STEP 49      /* gg_icp_step: the sort (unless reused), the step kernel and its finishing workgroup */
 #define GG_K_GRASP_CLEAR 50   /* gg_grasp_clearance: the pass and the per-grasp reduction */
-#define GG_K_IDS 51           /* ids are below this */
+#define GG_K_GRASP_NMS 51     /* gg_grasp_nms: gather, the pair matrix and the walk */
+#define GG_K_IDS 52           /* ids are below this */
 #define GG_PROF_NUM_KERNELS 32
 int gg_prof_enable(int on);
 int gg_prof_reset(void);
