@@ -1,7 +1,9 @@
 """What the command lines of grasp, grasp_propose, mesh and cluster share: the options that say which Gaussians are
 the object (the convex hull of --object-points, or the LERF relevancy of --positives against --negatives above
 --threshold; of that selection, with --instance, one DBSCAN instance), their cross-checks, the mask they select, and
-the per-grasp arrays of a --report file."""
+the per-grasp arrays of a --report file; and the options of the support plane (--support-plane fits or loads the
+table's plane, --remove-support takes the Gaussians that are not above it out of the selection, and the grasp command
+lines also hold the gripper above it)."""
 from __future__ import annotations
 
 import argparse
@@ -76,14 +78,82 @@ def check_nms_options(ap, a) -> None:
         a.nms_rotation = NMS_ROTATION_DEGREES
 
 
+def add_support_options(ap, grasp: bool = True) -> None:
+    """--support-plane, --support-dist and --remove-support (support.support_plane, support.above); with `grasp` also
+    --support-margin and --max-approach-tilt (grasp.plane_clear)."""
+    ap.add_argument("--support-plane", default=None, metavar="{fit,FILE.json}",
+                    help="the table's plane, scene frame: fitted to the Gaussians around the selection (fit; around "
+                         "all of them without a selection) or read from a file support.save_plane wrote"
+                         + ("; the whole gripper and its approach must stay above it (needs --gripper)" if grasp
+                            else ""))
+    ap.add_argument("--support-dist", type=float, default=None, metavar="METRES",
+                    help="with --support-plane fit: half thickness of the plane's slab (default 0.01)")
+    ap.add_argument("--remove-support", action="store_true",
+                    help="with --support-plane: keep only the selected Gaussians above the plane's slab")
+    if grasp:
+        ap.add_argument("--support-margin", type=float, default=None, metavar="METRES",
+                        help="with --support-plane: the gripper stays this far above the plane (default 0)")
+        ap.add_argument("--max-approach-tilt", type=float, default=None, metavar="DEGREES",
+                        help="with --support-plane: the approach axis is within this of the plane's inward normal")
+
+
+def check_support_options(ap, a, grasp: bool = True) -> None:
+    """ap.error unless the support options are complete and in range; a.support_margin None becomes 0."""
+    given = [("support_dist", a.support_dist is not None), ("remove_support", a.remove_support)]
+    if grasp:
+        given += [("support_margin", a.support_margin is not None),
+                  ("max_approach_tilt", a.max_approach_tilt is not None)]
+    if not a.support_plane:
+        for n, g in given:
+            if g:
+                ap.error("--" + n.replace("_", "-") + " needs --support-plane")
+    elif grasp and not a.gripper:
+        ap.error("--support-plane needs --gripper: the plane test has to know which boxes must stay above the plane")
+    if a.support_dist is not None:
+        if a.support_plane != "fit":
+            ap.error("--support-dist goes with --support-plane fit (a plane file holds its own)")
+        if not (math.isfinite(a.support_dist) and a.support_dist >= 0.0):
+            ap.error(f"--support-dist must be finite and >= 0, got {a.support_dist}")
+    if a.remove_support and not (getattr(a, "object_points", None) or a.positives):
+        ap.error("--remove-support needs a selection to remove the support from")
+    if grasp:
+        if a.support_margin is not None and not math.isfinite(a.support_margin):
+            ap.error(f"--support-margin must be finite, got {a.support_margin}")
+        if a.max_approach_tilt is not None and not 0.0 <= a.max_approach_tilt <= 180.0:        # NaN fails
+            ap.error(f"--max-approach-tilt must be in 0..180 degrees, got {a.max_approach_tilt}")
+        if a.support_margin is None:
+            a.support_margin = 0.0
+
+
+def support_option_plane(a, scene, mask, scale: float = 1.0, up=None):
+    """The support.SupportPlane the parsed --support-plane asks for, None without the option: fitted around `mask`
+    (support.support_plane; --support-dist metres, times scale; `up` orients the normal) or loaded and labelled
+    against the scene's Gaussians.  Made once per parsed `a` and kept on it, so that --remove-support and the grasp
+    layer see the same plane."""
+    if not getattr(a, "support_plane", None):
+        return None
+    if getattr(a, "_support_fitted", None) is None:
+        from . import support
+        if a.support_plane == "fit":
+            kw = {} if a.support_dist is None else {"dist": a.support_dist}
+            a._support_fitted = support.support_plane(scene, mask, scale=scale, up=up, **kw)
+        else:
+            a._support_fitted = support.label_model(scene, support.load_plane(a.support_plane))
+    return a._support_fitted
+
+
 def report_arrays(res) -> dict:
     """The per-grasp arrays of a --report file: REPORT_KEYS of a GraspContacts, CLEAR_KEYS of its .clearance when it
-    has one, and NMS_KEYS of its .nms, as nms_keep, nms_suppressor and nms_support, when it has one."""
+    has one, NMS_KEYS of its .nms, as nms_keep, nms_suppressor and nms_support, when it has one, and support_clear
+    and support_lowest when a support plane was applied."""
     out = {k: getattr(res, k).cpu().numpy() for k in REPORT_KEYS}
     if res.clearance is not None:
         out.update({k: getattr(res.clearance, k).cpu().numpy() for k in CLEAR_KEYS})
     if getattr(res, "nms", None) is not None:
         out.update({"nms_" + k: getattr(res.nms, k).cpu().numpy() for k in NMS_KEYS})
+    for k in ("support_clear", "support_lowest"):
+        if getattr(res, k, None) is not None:
+            out[k] = getattr(res, k).cpu().numpy()
     return out
 
 
@@ -153,8 +223,13 @@ def check_object_options(ap, a, hull: str) -> None:
 def object_mask(a, scene, mlp_state, matrix=None, scale: float = 1.0):
     """(N,) mask on the scene's device of the Gaussians the parsed options select, None without a selection.
     matrix, scale: the world -> scene map of the object points (None: identity).  With --instance largest or K,
-    that selection's instance of that rank (cluster.object_instances; --cluster-eps times scale)."""
+    that selection's instance of that rank (cluster.object_instances; --cluster-eps times scale).  With
+    --remove-support, the selection is first cut to support.above(selection, plane), the plane of
+    support_option_plane around the selection."""
     mask = selection_mask(a, scene, mlp_state, matrix, scale)
+    if mask is not None and getattr(a, "remove_support", False):
+        from . import support
+        mask = support.above(mask, support_option_plane(a, scene, mask, scale, getattr(a, "support_up", None)))
     inst = getattr(a, "instance", "all")
     if inst == "all" or mask is None:
         return mask

@@ -10,7 +10,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgg_raster.so")
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 _P, _I, _F, _I64, _SZ = C.c_void_p, C.c_int, C.c_float, C.c_int64, C.c_size_t
 
@@ -118,6 +118,11 @@ SIGNATURES = {
     "gg_grasp_clearance": (_I, [_I, _P, _P, _I, _P, _I, _P] + [C.c_double] * 4 + [_P] * 6 + [_P, _SZ, _P]),
     "gg_grasp_nms_workspace": (_SZ, [_I]),
     "gg_grasp_nms": (_I, [_I, _P, _I, _P, C.c_double, C.c_double, _I] + [_P] * 4 + [_P, _SZ, _P]),
+    "gg_plane_consensus_workspace": (_SZ, [_I, _I]),
+    "gg_plane_consensus": (_I, [_I, _P, _P, C.c_double, _I, _P, C.c_double, C.c_double, _P, C.c_double, _P, _P, _P,
+                                _P, _SZ, _P]),
+    "gg_plane_classify_workspace": (_SZ, [_I]),
+    "gg_plane_classify": (_I, [_I, _P, _P, C.c_double, _P, _P, C.c_double, _P, _P, _P, _P, _SZ, _P]),
     "gg_backproject_workspace": (_SZ, [_I, _I, _I]),
     "gg_backproject": (_I, [_I, _I, _I] + [_P] * 5 + [C.c_double] * 4 + [_P] * 4 + [_SZ, _P]),
     "gg_subsample_workspace": (_SZ, [_I64]),

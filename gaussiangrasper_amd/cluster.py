@@ -260,7 +260,8 @@ def report(instances: Instances) -> dict:
 # command line
 # ------------------------------------------------------------------------------------------------
 def main(argv: Optional[Sequence[str]] = None) -> int:
-    from ._cli import add_object_options, check_object_options, object_mask
+    from ._cli import (add_object_options, add_support_options, check_object_options, check_support_options,
+                       object_mask)
     from .frames import check_rotation, load_transform_json
     ap = argparse.ArgumentParser(prog="python -m gaussiangrasper_amd.cluster",
                                  description="Split the Gaussians a query selects into object instances (DBSCAN) and "
@@ -268,6 +269,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--ckpt", required=True, help="step-*.ckpt of a splatting model")
     ap.add_argument("--transform-json", default=None, help="JSON with transform_matrix and scale (world -> scene)")
     add_object_options(ap, "the query selects the Gaussians", "selects the Gaussians", instances=False)
+    add_support_options(ap, grasp=False)
     ap.add_argument("--eps", type=float, default=None, help="neighbour radius, world units (default: --eps-scale "
                                                             "times the selection's median 3rd-neighbour distance)")
     ap.add_argument("--eps-scale", type=float, default=EPS_SCALE, help="see --eps")
@@ -280,6 +282,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                                                    "(scene frame)")
     a = ap.parse_args(argv)
     check_object_options(ap, a, "required")
+    check_support_options(ap, a, grasp=False)
     if a.eps is not None and not (np.isfinite(a.eps) and a.eps > 0.0):
         ap.error(f"--eps must be finite and > 0, got {a.eps}")
     if not (np.isfinite(a.eps_scale) and a.eps_scale > 0.0):

@@ -125,6 +125,7 @@ extern "C" const char *gg_prof_name(int id) {
         case GG_K_ICP_STEP: return "gg_icp_step(all launches)";
         case GG_K_GRASP_CLEAR: return "gg_grasp_clearance(all launches)";
         case GG_K_GRASP_NMS: return "gg_grasp_nms(all launches)";
+        case GG_K_SUPPORT_PLANE: return "gg_support_plane(all launches)";
         default: break;
     }
     if (id >= GG_K_BLEND_FWD && id < GG_K_BLEND_FWD + 6) {

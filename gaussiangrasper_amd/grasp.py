@@ -16,6 +16,8 @@ every candidate against every oriented point in fp64; the contract is in include
                        (gg_grasp_clearance, csrc/grasp_clear.hip, PARITY.md "Gripper clearance"; GraspClearance)
     nms                distinct grasps: greedy pose-distance suppression of the active rows, best score first
                        (gg_grasp_nms, csrc/grasp_nms.hip, PARITY.md "Grasp NMS"; GraspNMS)
+    plane_clear        whether the whole gripper, at the final pose and at the start of its approach, stays above a
+                       support plane (support.SupportPlane, PARITY.md "Support plane")
     python -m gaussiangrasper_amd.grasp --ckpt IN --grasps grasps.npy [...] --out kept.npy
 
 Grasp candidates come from outside the project (AnyGrasp): this module only scores them."""
@@ -35,8 +37,9 @@ from torch import Tensor
 from . import _lib
 from ._call import (ArrayLike, f32_rows, host_ptr, nonneg, positive, ptr as _ptr, require_hip as _require_hip,
                     stream as _stream, workspace as _ws)
-from ._cli import (add_clearance_options, add_nms_options, add_object_options, check_clearance_options,
-                   check_nms_options, check_object_options, object_mask, report_arrays)
+from ._cli import (add_clearance_options, add_nms_options, add_object_options, add_support_options,
+                   check_clearance_options, check_nms_options, check_object_options, check_support_options, object_mask,
+                   report_arrays, support_option_plane)
 from .frames import ORTHO_TOL, load_transform_json, rigid_to_scene  # noqa: F401
 
 GRASP_COLS = 17
@@ -67,6 +70,8 @@ class GraspContacts:
     feasible: Tensor           # (M,) bool
     clearance: Optional["GraspClearance"] = None     # set by score_grasps / grasp_object when a gripper is given
     nms: Optional["GraspNMS"] = None                 # set by score_grasps / grasp_object with nms_translation
+    support_clear: Optional[Tensor] = None           # (M,) bool, set by score_grasps / grasp_object with support
+    support_lowest: Optional[Tensor] = None          # (M,) float64: the gripper's lowest height over the plane
 
 
 @dataclass
@@ -419,6 +424,65 @@ def apply_clearance(res: GraspContacts, scene_points: Tensor, scene_weights: Ten
     return res
 
 
+def plane_clear(rows: Tensor, gripper: ArrayLike, plane, approach: float = 0.0, margin: float = 0.0,
+                scale: float = 1.0):
+    """(clear bool (M,), lowest float64 (M,)): whether the whole gripper of every row stays above a support plane.
+    rows (M, 17) scene-frame GraspGroup rows on any device (plain torch fp64, CPU included); gripper: a check_gripper
+    model; plane: anything with .normal (3,) and .offset (support.SupportPlane), n.x + offset the height of x; the
+    gripper's constant terms, approach and margin are in grasp units and multiplied by `scale`.  Every part's bounds
+    follow check_gripper's affine rule; a part with lo > hi on an axis or a bound that is not finite is empty.  lowest
+    is the smallest height over the 8 corners of every part that is not empty, at the final pose t and at the approach
+    start t - approach a (+inf for a row without such a part); a box between the two lies between them, so the whole
+    approach stays above when both ends do.  clear = every entry of the row is finite and lowest >= margin."""
+    if rows.ndim != 2 or rows.shape[1] != GRASP_COLS:
+        raise ValueError(f"rows must be (M, {GRASP_COLS}) GraspGroup rows, got {tuple(rows.shape)}")
+    s = positive("scale", scale)
+    dev = rows.device
+    parts = torch.from_numpy(scale_gripper(gripper, s)).to(dev)                  # (P, 6, 4) float64
+    n = torch.as_tensor(np.asarray(plane.normal, dtype=np.float64).reshape(3)).to(dev)
+    ap, mg = nonneg("approach", approach) * s, float(margin) * s
+    if math.isnan(mg):
+        raise ValueError("margin must not be NaN")
+    g = rows.detach().double()
+    width, height, depth = g[:, 1, None, None], g[:, 2, None, None], g[:, 3, None, None]
+    c = parts[None]                                                               # (1, P, 6, 4)
+    b = ((c[..., 0] + c[..., 1] * width) + c[..., 2] * depth) + c[..., 3] * height           # (M, P, 6)
+    full = torch.isfinite(b).all(dim=2) & (b[..., 0] <= b[..., 1]) & (b[..., 2] <= b[..., 3]) & (b[..., 4] <= b[..., 5])
+    R, t = g[:, 4:13].reshape(-1, 3, 3), g[:, 13:16]
+    gn = (n[None, :, None] * R).sum(dim=1)                                        # (M, 3): n . (a, b, c)
+    base = (t * n[None]).sum(dim=1) + float(plane.offset)                         # (M,): height of t
+    lo, hi = b[..., 0::2], b[..., 1::2]                                           # (M, P, 3)
+    low = torch.minimum(gn[:, None] * lo, gn[:, None] * hi).sum(dim=2)            # (M, P): the lowest corner over t
+    low = torch.where(full, low, torch.full_like(low, math.inf)).min(dim=1).values
+    lowest = torch.minimum(base + low, (base - ap * gn[:, 0]) + low)
+    clear = torch.isfinite(g).all(dim=1) & (lowest >= mg)
+    return clear, lowest
+
+
+def apply_support(res: GraspContacts, rows: Tensor, gripper: Optional[ArrayLike], support, scale: float,
+                  approach: float, margin: float, max_approach_tilt: Optional[float]) -> GraspContacts:
+    """`res` with a support plane applied to scene-frame `rows`: res.support_clear / res.support_lowest =
+    plane_clear(...) and res.feasible &= clear; with max_approach_tilt (radians), also res.feasible &= a.(-n) >=
+    cos(max_approach_tilt), a the approach axis of the row (the gripper comes down onto the table, within that tilt of
+    its normal).  support None: nothing is done, and the other two must be at their defaults."""
+    if support is None:
+        if max_approach_tilt is not None or margin != 0.0:
+            raise ValueError("support_margin and max_approach_tilt need support: they are measured against the plane")
+        return res
+    if gripper is None:
+        raise ValueError("support needs gripper: the plane test has to know which boxes must stay above the plane")
+    res.support_clear, res.support_lowest = plane_clear(rows, gripper, support, approach, margin, scale)
+    res.feasible = res.feasible & res.support_clear
+    if max_approach_tilt is not None:
+        tilt = float(max_approach_tilt)
+        if not 0.0 <= tilt <= math.pi:
+            raise ValueError(f"max_approach_tilt must be in [0, pi] radians, got {max_approach_tilt}")
+        n = torch.as_tensor(np.asarray(support.normal, dtype=np.float64).reshape(3)).to(rows.device)
+        a = rows.detach().double()[:, [4, 7, 10]]
+        res.feasible = res.feasible & (-(a * n[None]).sum(dim=1) >= math.cos(tilt))
+    return res
+
+
 @torch.no_grad()
 def model_points(model_or_scene, mask: Optional[Tensor] = None):
     """(points, normals, weights) of a model or scene: the means, the smallest-axis normals as the renderer forms
@@ -446,15 +510,21 @@ def score_grasps(model_or_scene, grasps: ArrayLike, mask: Optional[Tensor] = Non
                  max_collision: Optional[float] = None, gripper: Optional[ArrayLike] = None, approach: float = 0.0,
                  max_body: Optional[float] = None, max_sweep: Optional[float] = None,
                  nms_translation: Optional[float] = None, nms_rotation: float = NMS_ROTATION,
-                 nms_symmetric: bool = True, top_k: Optional[int] = None) -> GraspContacts:
+                 nms_symmetric: bool = True, top_k: Optional[int] = None, support=None,
+                 support_margin: float = 0.0, max_approach_tilt: Optional[float] = None) -> GraspContacts:
     """Candidates in the grasp frame, scored against the model's Gaussians in one call: grasps_to_scene, then
     contacts on model_points.  depth_base, finger_width and band are in grasp units and scaled with the grasps.
     With a `gripper` (default_gripper(), or any check_gripper model; grasp units), also clearance of the whole
     gripper and its approach against the WHOLE scene's points (model_points(model, None), whatever `mask` is):
     feasible &= clear, and the record is returned as .clearance.  With `nms_translation` (grasp units), also nms of
     the feasible rows, returned as .nms; with top_k its .order is cut to the best top_k.  Without nms_translation
-    there is no NMS call and .nms is None."""
+    there is no NMS call and .nms is None.  With `support` (a support.SupportPlane of the scene frame; it needs
+    `gripper`), before the NMS also feasible &= plane_clear(rows, gripper, support, approach, support_margin, scale)
+    and, with max_approach_tilt (radians), feasible &= a.(-n) >= cos(max_approach_tilt); the plane test's outputs are
+    returned as .support_clear and .support_lowest.  Without `support` nothing of this runs."""
     top_k = check_top_k(nms_translation, top_k)
+    if support is not None and gripper is None:
+        raise ValueError("support needs gripper: the plane test has to know which boxes must stay above the plane")
     pts, nrm, w = model_points(model_or_scene, mask)
     g = grasps_to_scene(grasps, cam_to_world, matrix, scale)
     s = float(scale)
@@ -465,6 +535,7 @@ def score_grasps(model_or_scene, grasps: ArrayLike, mask: Optional[Tensor] = Non
     if gripper is not None:
         w_all = w if mask is None else model_points(model_or_scene, None)[2]
         apply_clearance(res, pts, w_all, rows, gripper, s, approach, min_weight, max_body, max_sweep)
+    apply_support(res, rows, gripper, support, s, approach, support_margin, max_approach_tilt)
     if nms_translation is not None:
         res.nms.order = apply_nms(res, rows, nms_translation, nms_rotation, nms_symmetric, s, top_k)
     return res
@@ -510,6 +581,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--max-collision", type=float, default=None, help="limit on the opacity inside the fingers")
     add_clearance_options(ap)
     add_nms_options(ap)
+    add_support_options(ap)
     ap.add_argument("--out", required=True, help="output .npy: feasible rows, input frame, by score")
     ap.add_argument("--report", default=None, help="output .npz: every per-grasp output, scene frame")
     a = ap.parse_args(argv)
@@ -522,6 +594,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         ap.error("--max-collision must not be NaN")
     check_clearance_options(ap, a)
     check_nms_options(ap, a)
+    check_support_options(ap, a)
     try:
         grasps = load_grasps(a.grasps)
         gripper = load_gripper_option(a.gripper)
@@ -531,11 +604,14 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         scene, mlp_state, _ = load_checkpoint(a.ckpt)
         scene = scene.to(torch.device("cuda"))
         mask = object_mask(a, scene, mlp_state, matrix, scale)
+        plane = support_option_plane(a, scene, mask, scale)
+        tilt = None if a.max_approach_tilt is None else math.radians(a.max_approach_tilt)
         res = score_grasps(scene, grasps, mask, cam, matrix, scale, band=a.band, mu=a.mu, min_weight=a.min_opacity,
                            max_collision=a.max_collision, gripper=gripper, approach=a.approach,
                            max_body=a.max_body_collision, max_sweep=a.max_sweep_collision,
                            nms_translation=a.nms_translation, nms_rotation=math.radians(a.nms_rotation),
-                           nms_symmetric=not a.nms_no_symmetry, top_k=a.top_k)
+                           nms_symmetric=not a.nms_no_symmetry, top_k=a.top_k, support=plane,
+                           support_margin=a.support_margin, max_approach_tilt=tilt)
     except (KeyError, ValueError, OSError) as exc:
         raise SystemExit(f"error: {exc}") from exc
     keep = (filter_grasps(grasps, res) if res.nms is None else res.nms.order).cpu().numpy()

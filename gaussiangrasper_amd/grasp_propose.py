@@ -27,11 +27,12 @@ from torch import Tensor
 from . import _lib
 from ._call import (f32_rows, host_ptr, nonneg, positive, ptr as _ptr, require_hip as _require_hip,
                     stream as _stream, workspace as _ws)
-from ._cli import (add_clearance_options, add_nms_options, add_object_options, check_clearance_options,
-                   check_nms_options, check_object_options, object_mask, report_arrays)
+from ._cli import (add_clearance_options, add_nms_options, add_object_options, add_support_options,
+                   check_clearance_options, check_nms_options, check_object_options, check_support_options, object_mask,
+                   report_arrays, support_option_plane)
 from .frames import check_rotation, load_transform_json
 from .grasp import (BAND, DEPTH_BASE, FINGER_WIDTH, GRASP_COLS, MIN_WEIGHT, MU, NMS_ROTATION, GraspContacts,
-                    apply_clearance, apply_nms, check_top_k, contacts, filter_grasps, grasps_from_scene,
+                    apply_clearance, apply_nms, apply_support, check_top_k, contacts, filter_grasps, grasps_from_scene,
                     load_gripper_option, model_points, nms_summary)
 
 # UNVERIFIED defaults (PARITY.md "Grasp proposals"), in grasp units (metres): max_width, depth and height are
@@ -179,6 +180,7 @@ def grasp_object(model_or_scene, mask: Optional[Tensor] = None, scale: float = 1
                  gripper=None, approach: float = 0.0, max_body: Optional[float] = None,
                  max_sweep: Optional[float] = None, nms_translation: Optional[float] = None,
                  nms_rotation: float = NMS_ROTATION, nms_symmetric: bool = True, top_k: Optional[int] = None,
+                 support=None, support_margin: float = 0.0, max_approach_tilt: Optional[float] = None,
                  **propose) -> Tuple[Tensor, GraspContacts, Tensor]:
     """From a model and an object mask to feasible grasps: (rows, contacts, keep), all on the device.  rows (M, 17):
     propose_grasps(model, mask, scale=scale, **propose), scene frame.  contacts: grasp.contacts of those rows, in two
@@ -195,8 +197,14 @@ def grasp_object(model_or_scene, mask: Optional[Tensor] = None, scale: float = 1
     scale), also grasp.nms of the feasible rows (near: within nms_translation and nms_rotation radians, with
     nms_symmetric also of the half turn about the approach axis): the record is contacts.nms and keep becomes its
     order[:top_k], the distinct grasps best first, a subsequence of what filter_grasps gives.  Without
-    nms_translation there is no NMS call and contacts.nms is None; top_k then is an error."""
+    nms_translation there is no NMS call and contacts.nms is None; top_k then is an error.  With `support` (a
+    support.SupportPlane of the scene frame; it needs `gripper`), before the NMS also feasible &=
+    grasp.plane_clear(rows, gripper, support, approach, support_margin, scale) and, with max_approach_tilt (radians),
+    feasible &= a.(-n) >= cos(max_approach_tilt); the plane test's outputs are contacts.support_clear and
+    contacts.support_lowest.  Without `support` nothing of this runs."""
     top_k = check_top_k(nms_translation, top_k)
+    if support is not None and gripper is None:
+        raise ValueError("support needs gripper: the plane test has to know which boxes must stay above the plane")
     rows = propose_grasps(model_or_scene, mask, scale=scale, min_weight=min_weight, **propose)
     s = float(scale)
     lengths = (nonneg("depth_base", depth_base) * s, nonneg("finger_width", finger_width) * s,
@@ -212,6 +220,7 @@ def grasp_object(model_or_scene, mask: Optional[Tensor] = None, scale: float = 1
     if gripper is not None:
         pts, _, w = model_points(model_or_scene, None)
         apply_clearance(res, pts, w, rows, gripper, s, approach, min_weight, max_body, max_sweep)
+    apply_support(res, rows, gripper, support, s, approach, support_margin, max_approach_tilt)
     if nms_translation is not None:
         return rows, res, apply_nms(res, rows, nms_translation, nms_rotation, nms_symmetric, s, top_k)
     return rows, res, filter_grasps(rows, res)
@@ -230,13 +239,15 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--max-seeds", type=int, default=MAX_SEEDS, help="seed points at most")
     ap.add_argument("--num-approach", type=int, default=NUM_APPROACH, help="approach directions per seed")
     ap.add_argument("--up", type=float, nargs=3, default=list(UP), metavar=("X", "Y", "Z"),
-                    help="up direction, world frame")
+                    help="up direction, world frame; with --support-plane it only orients the fitted plane, whose "
+                         "normal then is the proposer's up")
     ap.add_argument("--max-width", type=float, default=MAX_WIDTH, help="gripper opening, grasp units")
     ap.add_argument("--mu", type=float, default=MU, help="friction coefficient")
     ap.add_argument("--min-opacity", type=float, default=MIN_WEIGHT, help="a Gaussian takes part above it")
     ap.add_argument("--max-collision", type=float, default=None, help="limit on the opacity inside the fingers")
     add_clearance_options(ap)
     add_nms_options(ap)
+    add_support_options(ap)
     ap.add_argument("--out", required=True, help="output .npy: feasible rows by score, world frame (scene frame "
                                                  "without --transform-json: the two are the same then)")
     ap.add_argument("--report", default=None, help="output .npz: every candidate (scene frame) and its outputs")
@@ -250,6 +261,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         ap.error("--max-collision must not be NaN")
     check_clearance_options(ap, a)
     check_nms_options(ap, a)
+    check_support_options(ap, a)
     if a.max_seeds < 1:
         ap.error(f"--max-seeds must be >= 1, got {a.max_seeds}")
     try:
@@ -269,14 +281,20 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         from .interop import load_checkpoint
         scene, mlp_state, _ = load_checkpoint(a.ckpt)
         scene = scene.to(torch.device("cuda"))
+        a.support_up = up
         mask = object_mask(a, scene, mlp_state, matrix, scale)
+        plane = support_option_plane(a, scene, mask, scale, up)
+        if plane is not None:
+            up = plane.normal                # the table's own normal, not the command line's guess
+        tilt = None if a.max_approach_tilt is None else math.radians(a.max_approach_tilt)
         rows, res, keep = grasp_object(scene, mask, scale=scale, mu=a.mu, min_weight=a.min_opacity,
                                        max_collision=a.max_collision, gripper=gripper, approach=a.approach,
                                        max_body=a.max_body_collision, max_sweep=a.max_sweep_collision,
                                        nms_translation=a.nms_translation,
                                        nms_rotation=math.radians(a.nms_rotation),
                                        nms_symmetric=not a.nms_no_symmetry, top_k=a.top_k, max_seeds=a.max_seeds,
-                                       num_approach=a.num_approach, up=up, max_width=a.max_width)
+                                       num_approach=a.num_approach, up=up, max_width=a.max_width, support=plane,
+                                       support_margin=a.support_margin, max_approach_tilt=tilt)
     except (KeyError, ValueError, OSError) as exc:
         raise SystemExit(f"error: {exc}") from exc
     rows_np = rows.cpu().numpy()

@@ -31,7 +31,8 @@ from torch import Tensor
 from . import _lib
 from ._call import (ArrayLike, default_device, host_ptr, ptr as _ptr, require_hip as _require_hip, stream as _stream,
                     workspace as _ws)
-from ._cli import add_object_options, check_object_options, object_mask
+from ._cli import (add_object_options, add_support_options, check_object_options, check_support_options,
+                   object_mask)
 from .frames import c2w_to_scene, directions_from_scene, homogeneous, load_transform_json, points_from_scene
 
 RESOLUTION = 128                 # the reference exporter's defaults
@@ -416,6 +417,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--downscale", type=float, default=DOWNSCALE, help="render at 1 / K of each camera's size")
     ap.add_argument("--depth-units", type=float, default=1.0, help="with --scan: raw depth units per metre")
     add_object_options(ap, "mesh only the Gaussians the query selects")
+    add_support_options(ap, grasp=False)
     ap.add_argument("--out-points", help="also write the mesh vertices as an (N, 3) float64 .npy (object points)")
     a = ap.parse_args(argv)
     if a.ckpt and not a.transforms:
@@ -423,6 +425,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     if a.scan and (a.transforms or a.transform_json or a.positives):
         ap.error("--transforms, --transform-json and --positives go with --ckpt")
     check_object_options(ap, a, "none")
+    check_support_options(ap, a, grasp=False)
     if a.resolution < 2 or a.downscale <= 0:
         ap.error("--resolution must be >= 2 and --downscale > 0")
     bbox = BBOX if a.bbox is None else (tuple(a.bbox[:3]), tuple(a.bbox[3:]))

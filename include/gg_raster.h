@@ -768,6 +768,59 @@ int gg_grasp_nms(int num_grasps, const float *grasps, int num_order, const int32
                  double cos_rotation, int symmetric, uint8_t *keep, int32_t *suppressor, int32_t *kept,
                  int32_t *num_kept, void *ws, size_t ws_bytes, gg_stream_t stream);
 
+/* ---- support plane: RANSAC consensus and the labels of one plane (PARITY "Support plane") -------------
+ * gg_plane_consensus: every three-point plane hypothesis against every point, exact in fp64.
+ *   points: num_points x 3 fp32; weights: num_points fp32, or NULL for "all take part".  A point takes part iff p is
+ *           finite and (weights is NULL or (double)w > min_weight).
+ *   hyp:    num_hypotheses x 3 int32 point indices (a, b, c) on the device.
+ * Per hypothesis, in fp64 from the fp32 inputs, no contraction, in this order:
+ *   e1_k = (double)p_bk - (double)p_ak;  e2_k = (double)p_ck - (double)p_ak;
+ *   n = e1 x e2:  n0 = e1_1 e2_2 - e1_2 e2_1,  n1 = e1_2 e2_0 - e1_0 e2_2,  n2 = e1_0 e2_1 - e1_1 e2_0;
+ *   nn = (n0 n0 + n1 n1) + n2 n2;  ee1 = (e1_0 e1_0 + e1_1 e1_1) + e1_2 e1_2,  ee2 likewise;
+ *   VALID iff a, b, c are in [0, num_points) and distinct, all three points take part, nn is finite,
+ *             nn > min_sin2 (ee1 ee2)  (nn / (ee1 ee2) is the squared sine of the angle at p_a: a triple that is
+ *             collinear, or nearly so, defines no plane), and, with `up`,
+ *             g g >= cos2_tilt (nn uu)  with g = (n0 u0 + n1 u1) + n2 u2, uu = (u0 u0 + u1 u1) + u2 u2
+ *             (the plane's normal, either sign, is within the tilt limit of `up`).
+ *   Point j is an INLIER of a valid hypothesis iff it takes part and  s s <= (dist dist) nn  with
+ *             d_k = (double)p_jk - (double)p_ak,  s = (n0 d0 + n1 d1) + n2 d2.  The limit is inclusive.
+ * No square root or division decides anything: count, valid and best are exact.  Outputs, every element written:
+ *   count int32 [H]: the inliers (the hypothesis' own three points are among them); 0 when not valid;
+ *   valid uint8 [H];
+ *   best int32 [2]: the index of the valid hypothesis with the largest count, the smaller index on ties, and its
+ *           count; (-1, 0) when no hypothesis is valid.
+ * dist finite and >= 0; min_sin2 in [0, 1]; min_weight not NaN; up: HOST array of 3 doubles, finite and not zero, or
+ * NULL for no tilt limit; cos2_tilt in [0, 1] (read only with up).  num_hypotheses == 0 does nothing (every pointer
+ * may be null); num_points == 0 makes every hypothesis not valid.  Counts are integer sums: identical call to call.
+ * `ws`: gg_plane_consensus_workspace() bytes, 256-byte aligned (0 is returned for counts out of range: the limits are
+ * GG_GRASP_MAX_POINTS and GG_PLANE_MAX_HYPOTHESES).
+ *
+ * gg_plane_classify: one plane against every point.
+ *   plane:  HOST array of 4 doubles (n0, n1, n2, d), n finite and not zero, d finite.  Distances are in units of |n|:
+ *           the caller passes a unit normal.  origin: HOST array of 3 finite doubles, the point the moments are taken
+ *           about (a point near the plane's inliers keeps them small).
+ * Per point, in fp64, no contraction:  h = ((n0 x + n1 y) + n2 z) + d.
+ *   height fp32 [N] = (float)h, NaN for a point that is not finite;
+ *   side uint8 [N]: 3 = takes no part; 0 = h < -dist (below); 1 = -dist <= h <= dist (on); 2 = h > dist (above).
+ *   sums: device double [16] over the points that take part, w = (double)weight (1 with weights NULL):
+ *     [0] [1] [2]  the number of points on / above / below;
+ *     [3]          sum of h h over "on";
+ *     [4..6]       sum of q,  [7..12] sum of q q^T (xx, xy, xz, yy, yz, zz),  q_k = (double)p_k - origin_k, over "on";
+ *     [13] [14] [15]  sum of w on / above / below.
+ * The sums are formed in a fixed order that depends on num_points only, without floating-point atomics: the same
+ * inputs give the same bits, call to call.  num_points == 0 writes 16 zeros.  dist finite and >= 0; min_weight not
+ * NaN.  `ws`: gg_plane_classify_workspace() bytes, 256-byte aligned (0 is returned for num_points out of range). */
+#define GG_PLANE_MAX_HYPOTHESES 65536
+size_t gg_plane_consensus_workspace(int num_points, int num_hypotheses);
+int gg_plane_consensus(int num_points, const float *points, const float *weights, double min_weight,
+                       int num_hypotheses, const int32_t *hyp, double dist, double min_sin2, const double *up,
+                       double cos2_tilt, int32_t *count, uint8_t *valid, int32_t *best, void *ws, size_t ws_bytes,
+                       gg_stream_t stream);
+size_t gg_plane_classify_workspace(int num_points);
+int gg_plane_classify(int num_points, const float *points, const float *weights, double min_weight,
+                      const double *plane, const double *origin, double dist, float *height, uint8_t *side,
+                      double *sums, void *ws, size_t ws_bytes, gg_stream_t stream);
+
 /* ---- scene preparation from RGB-D frames (PARITY "Scene preparation") --------------------------------
  * gg_backproject: depth frames to a base-frame point cloud (generate_data.py depth_image_to_point_cloud +
  * merge_point_clouds).  Frames are F x H x W, frame-major then row-major:
@@ -1031,7 +1084,8 @@ int gg_tsdf_mesh_emit(const int32_t *dims, const float *grid, const float *tsdf,
 #define GG_K_ICP_STEP 49      /* gg_icp_step: the sort (unless reused), the step kernel and its finishing workgroup */
 #define GG_K_GRASP_CLEAR 50   /* gg_grasp_clearance: the pass and the per-grasp reduction */
 #define GG_K_GRASP_NMS 51     /* gg_grasp_nms: gather, the pair matrix and the walk */
-#define GG_K_IDS 52           /* ids are below this */
+#define GG_K_SUPPORT_PLANE 52 /* gg_plane_consensus and gg_plane_classify: all their launches */
+#define GG_K_IDS 53           /* ids are below this */
 #define GG_PROF_NUM_KERNELS 32
 int gg_prof_enable(int on);
 int gg_prof_reset(void);
