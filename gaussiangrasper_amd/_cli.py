@@ -17,8 +17,21 @@ NMS_KEYS = ("keep", "suppressor", "support")             # only with --nms-trans
 NMS_ROTATION_DEGREES = 30.0                              # grasp.NMS_ROTATION
 
 
-def add_clearance_options(ap) -> None:
-    """--gripper, --approach, --max-body-collision, --max-sweep-collision (grasp.clearance)."""
+def load_scene(ckpt: str):
+    """(scene, mlp_state) of a checkpoint, the scene on the device."""
+    from .interop import load_checkpoint
+    scene, mlp_state, _ = load_checkpoint(ckpt)
+    return scene.to("cuda"), mlp_state
+
+
+def add_grasp_options(ap) -> None:
+    """What the grasp and grasp_propose command lines share: --mu, --min-opacity, --max-collision (grasp.contacts);
+    --gripper, --approach, --max-body-collision, --max-sweep-collision (grasp.clearance); --nms-translation,
+    --nms-rotation, --nms-no-symmetry, --top-k (grasp.nms); and add_support_options."""
+    from .grasp import MIN_WEIGHT, MU
+    ap.add_argument("--mu", type=float, default=MU, help="friction coefficient")
+    ap.add_argument("--min-opacity", type=float, default=MIN_WEIGHT, help="a Gaussian takes part above it")
+    ap.add_argument("--max-collision", type=float, default=None, help="limit on the opacity inside the fingers")
     ap.add_argument("--gripper", default=None, metavar="{default,FILE.json}",
                     help="also test the whole gripper against the whole scene: graspnetAPI's drawing (default) or a "
                          "JSON list of parts (grasp.load_gripper)")
@@ -28,10 +41,28 @@ def add_clearance_options(ap) -> None:
                     help="with --gripper: limit on the opacity inside the gripper at the final pose")
     ap.add_argument("--max-sweep-collision", type=float, default=None,
                     help="with --gripper: limit on the opacity the gripper passes through on its approach")
+    ap.add_argument("--nms-translation", type=float, default=None, metavar="METRES",
+                    help="keep distinct grasps only: of the feasible rows, best first, drop one that is within this "
+                         "distance (grasp units) and --nms-rotation of a kept one")
+    ap.add_argument("--nms-rotation", type=float, default=None, metavar="DEGREES",
+                    help=f"with --nms-translation: the rotation that still counts as near (default "
+                         f"{NMS_ROTATION_DEGREES:g})")
+    ap.add_argument("--nms-no-symmetry", action="store_true",
+                    help="with --nms-translation: a pose and its half turn about the approach axis are two grasps")
+    ap.add_argument("--top-k", type=int, default=None, metavar="K",
+                    help="with --nms-translation: write the best K distinct grasps only")
+    add_support_options(ap)
 
 
-def check_clearance_options(ap, a) -> None:
-    """ap.error unless the clearance options are complete and in range; a.approach None becomes 0."""
+def check_grasp_options(ap, a, lengths=()) -> None:
+    """ap.error unless the options of add_grasp_options (and the caller's own `lengths`, checked like --mu) are complete
+    and in range; a.approach None becomes 0, a.nms_rotation None the default, a.support_margin None 0."""
+    for name in ("mu", *lengths, "min_opacity"):
+        v = getattr(a, name)
+        if not (math.isfinite(v) and v >= 0.0):
+            ap.error(f"--{name.replace('_', '-')} must be finite and >= 0, got {v}")
+    if a.max_collision is not None and math.isnan(a.max_collision):
+        ap.error("--max-collision must not be NaN")
     for n in ("approach", "max_body_collision", "max_sweep_collision"):
         v = getattr(a, n)
         if v is None:
@@ -45,24 +76,6 @@ def check_clearance_options(ap, a) -> None:
         ap.error(f"--approach must be finite and >= 0, got {a.approach}")
     if a.approach is None:
         a.approach = 0.0
-
-
-def add_nms_options(ap) -> None:
-    """--nms-translation, --nms-rotation, --nms-no-symmetry, --top-k (grasp.nms)."""
-    ap.add_argument("--nms-translation", type=float, default=None, metavar="METRES",
-                    help="keep distinct grasps only: of the feasible rows, best first, drop one that is within this "
-                         "distance (grasp units) and --nms-rotation of a kept one")
-    ap.add_argument("--nms-rotation", type=float, default=None, metavar="DEGREES",
-                    help=f"with --nms-translation: the rotation that still counts as near (default "
-                         f"{NMS_ROTATION_DEGREES:g})")
-    ap.add_argument("--nms-no-symmetry", action="store_true",
-                    help="with --nms-translation: a pose and its half turn about the approach axis are two grasps")
-    ap.add_argument("--top-k", type=int, default=None, metavar="K",
-                    help="with --nms-translation: write the best K distinct grasps only")
-
-
-def check_nms_options(ap, a) -> None:
-    """ap.error unless the NMS options are complete and in range; a.nms_rotation None becomes the default."""
     if a.nms_translation is None:
         for n, given in (("nms_rotation", a.nms_rotation is not None), ("nms_no_symmetry", a.nms_no_symmetry),
                          ("top_k", a.top_k is not None)):
@@ -76,6 +89,17 @@ def check_nms_options(ap, a) -> None:
         ap.error(f"--top-k must be >= 1, got {a.top_k}")
     if a.nms_rotation is None:
         a.nms_rotation = NMS_ROTATION_DEGREES
+    check_support_options(ap, a)
+
+
+def grasp_gate_kwargs(a, plane) -> dict:
+    """The keywords grasp.score_grasps and grasp_propose.grasp_object take from the checked options of add_grasp_options
+    (the gripper apart, which the command lines load first), degrees as radians; `plane`: support_option_plane's."""
+    return dict(mu=a.mu, min_weight=a.min_opacity, max_collision=a.max_collision, approach=a.approach,
+                max_body=a.max_body_collision, max_sweep=a.max_sweep_collision, nms_translation=a.nms_translation,
+                nms_rotation=math.radians(a.nms_rotation), nms_symmetric=not a.nms_no_symmetry, top_k=a.top_k,
+                support=plane, support_margin=a.support_margin,
+                max_approach_tilt=None if a.max_approach_tilt is None else math.radians(a.max_approach_tilt))
 
 
 def add_support_options(ap, grasp: bool = True) -> None:

@@ -261,7 +261,7 @@ def report(instances: Instances) -> dict:
 # ------------------------------------------------------------------------------------------------
 def main(argv: Optional[Sequence[str]] = None) -> int:
     from ._cli import (add_object_options, add_support_options, check_object_options, check_support_options,
-                       object_mask)
+                       load_scene, object_mask)
     from .frames import check_rotation, load_transform_json
     ap = argparse.ArgumentParser(prog="python -m gaussiangrasper_amd.cluster",
                                  description="Split the Gaussians a query selects into object instances (DBSCAN) and "
@@ -296,9 +296,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             if matrix.shape not in ((3, 4), (4, 4)):
                 raise ValueError(f"transform_matrix must be 3x4 or 4x4, got {matrix.shape}")
             check_rotation(matrix[:3, :3], "matrix rotation")
-        from .interop import load_checkpoint
-        scene, mlp_state, _ = load_checkpoint(a.ckpt)
-        scene = scene.to(torch.device("cuda"))
+        scene, mlp_state = load_scene(a.ckpt)
         mask = object_mask(a, scene, mlp_state, matrix, scale)
         inst = object_instances(scene, mask, None if a.eps is None else a.eps * nonneg("scale", scale),
                                 a.min_points, a.min_weight, a.min_count, a.eps_scale)

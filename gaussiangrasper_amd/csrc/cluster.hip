@@ -157,26 +157,21 @@ struct ClWs {
 };
 
 static size_t cl_layout(int n, const int32_t *dims, ClWs *w, char *base) {
-    size_t off = kn_layout(n, dims, w ? &w->sort : nullptr, base);
     const size_t tiles = ((size_t)n + PP_TILE - 1) / PP_TILE;
-    auto take = [&](size_t bytes) {
-        char *p = base ? base + off : nullptr;
-        off += gg_align_up(bytes, 256);
-        return p;
-    };
+    GgCarve cv{base, kn_layout(n, dims, w ? &w->sort : nullptr, base)};
     ClWs t;
-    t.totals = (int64_t *)take(16);
-    t.parent = (int32_t *)take((size_t)n * 4);
-    t.flags = (int32_t *)take((size_t)n * 4);
-    t.rank = (int32_t *)take((size_t)n * 4);
-    t.tile_sums = (int32_t *)take(tiles * 4);
-    t.tile_offs = (int32_t *)take(tiles * 4);
-    t.core_s = (uint8_t *)take((size_t)n);
+    t.totals = (int64_t *)cv.take(16);
+    t.parent = (int32_t *)cv.take((size_t)n * 4);
+    t.flags = (int32_t *)cv.take((size_t)n * 4);
+    t.rank = (int32_t *)cv.take((size_t)n * 4);
+    t.tile_sums = (int32_t *)cv.take(tiles * 4);
+    t.tile_offs = (int32_t *)cv.take(tiles * 4);
+    t.core_s = (uint8_t *)cv.take((size_t)n);
     if (w) {
         t.sort = w->sort;
         *w = t;
     }
-    return off;
+    return cv.off;
 }
 
 extern "C" size_t gg_cluster_workspace(int num_points, const int32_t *dims) {

@@ -36,6 +36,29 @@ static inline int gg_width_index(int w) {
 
 static inline size_t gg_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// Carves a workspace into 256-byte-aligned pieces.  With base null it only sizes: take() returns null and `off`
+// ends as the bytes needed.
+struct GgCarve {
+    char *base;
+    size_t off;
+    char *take(size_t bytes) {
+        char *p = base ? base + off : nullptr;
+        off += gg_align_up(bytes, 256);
+        return p;
+    }
+};
+
+// The caller's workspace: non-null, 256-byte aligned, at least `need` bytes.
+#define GG_REQUIRE_WS(ws, ws_bytes, need)                                                              \
+    do {                                                                                               \
+        GG_REQUIRE((ws) && ((uintptr_t)(ws) & 255) == 0, "ws must be non-null and 256-byte aligned");  \
+        if ((ws_bytes) < (need)) {                                                                     \
+            gg_set_error("%s: workspace too small: %zu < %zu bytes", __func__, (size_t)(ws_bytes),     \
+                         (size_t)(need));                                                              \
+            return GG_ERR_WORKSPACE;                                                                   \
+        }                                                                                              \
+    } while (0)
+
 // ---------------------------------------------------------------------------------------------
 // gg_fill_async: hipMemsetAsync as an ordinary kernel.  On this runtime a hipMemsetAsync between two kernels
 // of a stream leaves ~6 us of idle GPU on either side of it (rocprofv3 kernel trace of a bench view: four

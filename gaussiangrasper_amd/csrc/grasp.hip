@@ -6,7 +6,7 @@
 // Tiling: one lane per grasp, GC_TILE grasps per workgroup (grid.y), each lane holding its grasp's fp64 frame in
 // registers; grid.x splits the points into C chunks of `len` points, a multiple of GC_STAGE, staged through LDS
 // GC_STAGE at a time and read as broadcasts.  Every lane walks the staged points in increasing index order.
-// Cull: each grasp's region + finger boxes are bounded by a world-space fp32 box (gc_load: fp64 inverse of R,
+// Cull: each grasp's region + finger boxes are bounded by a world-space fp32 box (gc_cull_box: fp64 inverse of R,
 // half-extents widened by GC_MARGIN relative, bounds rounded outward), tested with six fp32 compares per pair;
 // only pairs inside it take the fp64 test.  A point that takes no part is staged as NaN and fails every compare.
 // Determinism: no atomics.  Each (chunk, grasp) writes its partial state; a per-grasp kernel combines the C
@@ -51,73 +51,10 @@ __device__ void gc_load(const float *row, const GcParams &P, GcGrasp &g) {
         g.hi[k] = -INFINITY;
     }
     if (!ok) return;
-    // p = t + Q u with Q = R^-T = cofactor(R) / det(R); the local box is u0 in [-d_base, depth], |u1| <= hi1,
-    // |u2| <= hh (region and both finger boxes)
-    const double *R = g.R;
-    double Q[9];
-    Q[0] = R[4] * R[8] - R[5] * R[7];
-    Q[1] = R[5] * R[6] - R[3] * R[8];
-    Q[2] = R[3] * R[7] - R[4] * R[6];
-    Q[3] = R[2] * R[7] - R[1] * R[8];
-    Q[4] = R[0] * R[8] - R[2] * R[6];
-    Q[5] = R[1] * R[6] - R[0] * R[7];
-    Q[6] = R[1] * R[5] - R[2] * R[4];
-    Q[7] = R[2] * R[3] - R[0] * R[5];
-    Q[8] = R[0] * R[4] - R[1] * R[3];
-    const double det = (R[0] * Q[0] + R[1] * Q[1]) + R[2] * Q[2];
-    double qmax = 0.0, rmax = 0.0;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-        Q[k] = Q[k] / det;
-        qmax = fmax(qmax, fabs(Q[k]));       // fmax drops a NaN: checked below
-        rmax = fmax(rmax, fabs(R[k]));
-    }
-    bool cull = det != 0.0 && qmax * rmax <= GC_MAX_COND;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) cull = cull && isfinite(Q[k]);
-    const double m0 = 0.5 * (g.depth - P.depth_base), h0 = 0.5 * (g.depth + P.depth_base);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        if (!cull) {
-            g.lo[i] = -INFINITY;
-            g.hi[i] = INFINITY;
-            continue;
-        }
-        const double c = g.t[i] + Q[i * 3] * m0;
-        const double e = fabs(Q[i * 3]) * h0 + fabs(Q[i * 3 + 1]) * g.hi1 + fabs(Q[i * 3 + 2]) * g.hh;
-        const double w = e + GC_MARGIN * (fabs(c) + e);
-        g.lo[i] = gc_down(c - w);
-        g.hi[i] = gc_up(c + w);
-    }
-}
-
-__device__ __forceinline__ bool gc_in_box(const GcGrasp &g, float4 a) {
-    return a.x >= g.lo[0] && a.x <= g.hi[0] && a.y >= g.lo[1] && a.y <= g.hi[1] && a.z >= g.lo[2] &&
-           a.z <= g.hi[2];
-}
-
-// u_j = (R[0][j] d0 + R[1][j] d1) + R[2][j] d2, d = (double)p - t: fp64, no contraction (-ffp-contract=off)
-__device__ __forceinline__ void gc_local(const GcGrasp &g, float4 a, double &u0, double &u1, double &u2) {
-    const double d0 = (double)a.x - g.t[0], d1 = (double)a.y - g.t[1], d2 = (double)a.z - g.t[2];
-    u0 = (g.R[0] * d0 + g.R[3] * d1) + g.R[6] * d2;
-    u1 = (g.R[1] * d0 + g.R[4] * d1) + g.R[7] * d2;
-    u2 = (g.R[2] * d0 + g.R[5] * d1) + g.R[8] * d2;
-}
-
-// Stage points [s0, s0 + ns) into LDS: (x, y, z, w), x/y/z NaN when the point takes no part.
-__device__ __forceinline__ void gc_stage(int s0, int ns, const float *__restrict__ points,
-                                         const float *__restrict__ normals, const float *__restrict__ weights,
-                                         double min_weight, float4 *s_p, float4 *s_n) {
-    for (int k = threadIdx.x; k < ns; k += blockDim.x) {
-        const size_t i = (size_t)(s0 + k);
-        const float px = points[i * 3], py = points[i * 3 + 1], pz = points[i * 3 + 2];
-        const float nx = normals[i * 3], ny = normals[i * 3 + 1], nz = normals[i * 3 + 2];
-        const float w = weights[i];
-        const bool part = isfinite(px) && isfinite(py) && isfinite(pz) && isfinite(nx) && isfinite(ny) &&
-                          isfinite(nz) && (double)w > min_weight;
-        s_p[k] = part ? make_float4(px, py, pz, w) : make_float4(NAN, NAN, NAN, 0.0f);
-        if (s_n) s_n[k] = make_float4(nx, ny, nz, 0.0f);
-    }
+    // the local box is u0 in [-d_base, depth], |u1| <= hi1, |u2| <= hh (region and both finger boxes)
+    const double m[3] = {0.5 * (g.depth - P.depth_base), 0.0, 0.0};
+    const double h[3] = {0.5 * (g.depth + P.depth_base), g.hi1, g.hh};
+    gc_cull_box(g.R, g.t, m, h, g.lo, g.hi);
 }
 
 struct GcWs {
@@ -147,9 +84,9 @@ __global__ __launch_bounds__(GC_TILE) void grasp_pass1_kernel(int N, const float
         __syncthreads();
         for (int k = 0; k < ns; ++k) {
             const float4 a = s_p[k];
-            if (!gc_in_box(G, a)) continue;
+            if (!gc_in_box(G.lo, G.hi, a)) continue;
             double u0, u1, u2;
-            gc_local(G, a, u0, u1, u2);
+            gc_local(G.R, G.t, a, u0, u1, u2);
             if (!(u0 >= nb && u0 <= G.depth && fabs(u2) <= G.hh)) continue;
             const double w = (double)a.w;
             if (fabs(u1) <= G.hw) {
@@ -239,9 +176,9 @@ __global__ __launch_bounds__(GC_TILE) void grasp_pass2_kernel(int N, const float
         __syncthreads();
         for (int k = 0; k < ns; ++k) {
             const float4 a = s_p[k];
-            if (!gc_in_box(G, a)) continue;
+            if (!gc_in_box(G.lo, G.hi, a)) continue;
             double u0, u1, u2;
-            gc_local(G, a, u0, u1, u2);
+            gc_local(G.R, G.t, a, u0, u1, u2);
             if (!(u0 >= nb && u0 <= G.depth && fabs(u2) <= G.hh && fabs(u1) <= G.hw)) continue;
             const bool left = u1 <= tl, right = u1 >= tr;
             if (!left && !right) continue;
@@ -328,27 +265,22 @@ static size_t gc_layout(int N, int M, GcWs *w, char *base) {
     int C, len;
     gc_chunks(N, M, &C, &len);
     const size_t cm = (size_t)C * M;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char *p = base ? base + off : nullptr;
-        off += gg_align_up(bytes, 256);
-        return p;
-    };
+    GgCarve cv{base, 0};
     GcWs t;
-    t.cnt = (int *)take(cm * 4);
-    t.il = (int *)take(cm * 4);
-    t.ir = (int *)take(cm * 4);
-    t.yl = (double *)take(cm * 8);
-    t.yr = (double *)take(cm * 8);
-    t.rw = (double *)take(cm * 8);
-    t.cw = (double *)take(cm * 8);
-    t.nrm = (double *)take(6 * cm * 8);
-    t.gcnt = (int *)take((size_t)M * 4);
-    t.gyl = (double *)take((size_t)M * 8);
-    t.gyr = (double *)take((size_t)M * 8);
-    t.gcw = (double *)take((size_t)M * 8);
+    t.cnt = (int *)cv.take(cm * 4);
+    t.il = (int *)cv.take(cm * 4);
+    t.ir = (int *)cv.take(cm * 4);
+    t.yl = (double *)cv.take(cm * 8);
+    t.yr = (double *)cv.take(cm * 8);
+    t.rw = (double *)cv.take(cm * 8);
+    t.cw = (double *)cv.take(cm * 8);
+    t.nrm = (double *)cv.take(6 * cm * 8);
+    t.gcnt = (int *)cv.take((size_t)M * 4);
+    t.gyl = (double *)cv.take((size_t)M * 8);
+    t.gyr = (double *)cv.take((size_t)M * 8);
+    t.gcw = (double *)cv.take((size_t)M * 8);
     if (w) *w = t;
-    return off;
+    return cv.off;
 }
 
 extern "C" size_t gg_grasp_contacts_workspace(int num_points, int num_grasps) {
@@ -382,11 +314,7 @@ extern "C" int gg_grasp_contacts(int num_points, const float *points, const floa
                    ((uintptr_t)grasps & 3) == 0,
                "points / normals / weights / grasps misaligned");
     const size_t need = gc_layout(num_points, num_grasps, nullptr, nullptr);
-    GG_REQUIRE(ws && ((uintptr_t)ws & 255) == 0, "ws must be non-null and 256-byte aligned");
-    if (ws_bytes < need) {
-        gg_set_error("%s: workspace too small: %zu < %zu bytes", __func__, ws_bytes, need);
-        return GG_ERR_WORKSPACE;
-    }
+    GG_REQUIRE_WS(ws, ws_bytes, need);
     GcWs w;
     gc_layout(num_points, num_grasps, &w, (char *)ws);
     int C, len;
@@ -394,17 +322,17 @@ extern "C" int gg_grasp_contacts(int num_points, const float *points, const floa
     const GcParams P{depth_base, finger_width, band, min_weight, max_collision, atan(mu)};
     hipStream_t s = (hipStream_t)stream;
     const int M = num_grasps;
-    const unsigned threads = (unsigned)min(GC_TILE, (M + GG_WAVE - 1) / GG_WAVE * GG_WAVE);
-    const dim3 grid((unsigned)C, (unsigned)((M + threads - 1) / threads));
+    dim3 grid, block;
+    gc_launch_shape(C, M, &grid, &block);
     const unsigned per_grasp = (unsigned)((M + 255) / 256);
     gg_prof_begin(GG_K_GRASP, s);
     if (C > 0)
-        hipLaunchKernelGGL(grasp_pass1_kernel, grid, dim3(threads), 0, s, num_points, points, normals, weights, M,
+        hipLaunchKernelGGL(grasp_pass1_kernel, grid, block, 0, s, num_points, points, normals, weights, M,
                            grasps, P, len, w);
     hipLaunchKernelGGL(grasp_reduce1_kernel, dim3(per_grasp), dim3(256), 0, s, M, C, w, contact_idx, region_count,
                        region_weight, collision_weight);
     if (C > 0)
-        hipLaunchKernelGGL(grasp_pass2_kernel, grid, dim3(threads), 0, s, num_points, points, normals, weights, M,
+        hipLaunchKernelGGL(grasp_pass2_kernel, grid, block, 0, s, num_points, points, normals, weights, M,
                            grasps, P, len, C, w);
     hipLaunchKernelGGL(grasp_finalize_kernel, dim3(per_grasp), dim3(256), 0, s, M, C, grasps, P, w, normals_out,
                        angles, feasible);

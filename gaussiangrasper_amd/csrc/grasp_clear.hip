@@ -8,9 +8,9 @@
 // every per-part array is indexed at compile time); grid.x splits the points into C chunks, staged through LDS
 // GC_STAGE at a time and read as broadcasts.
 // Cull: the union of every part's body and sweep volume is one box of the gripper frame; its world-space fp32
-// bounding box (fp64 inverse of R, half-extents widened by GC_MARGIN relative, rounded outward) is tested with six
-// fp32 compares per pair, and only pairs inside it take the fp64 test.  A point that takes no part is staged as NaN
-// and fails every compare.
+// bounding box (gc_cull_box: fp64 inverse of R, half-extents widened by GC_MARGIN relative, rounded outward) is
+// tested with six fp32 compares per pair, and only pairs inside it take the fp64 test.  A point that takes no part
+// is staged as NaN and fails every compare.
 // Determinism: no atomics.  Each (chunk, part, grasp) writes its partial counts and fp64 sums; a per-grasp kernel
 // adds them in chunk order, rounds, and decides `clear`.  C depends on (N, M) only.
 #include "grasp_common.h"
@@ -87,50 +87,13 @@ __device__ void cl_load(const float *row, const ClParts &parts, double approach,
         g.hi[k] = -INFINITY;
     }
     if (!(L[0] <= H[0])) return;                // not valid, or every part empty: nothing to count
-    // p = t + Q u with Q = R^-T = cofactor(R) / det(R); u in [L, H]
-    const double *R = g.R;
-    double Q[9];
-    Q[0] = R[4] * R[8] - R[5] * R[7];
-    Q[1] = R[5] * R[6] - R[3] * R[8];
-    Q[2] = R[3] * R[7] - R[4] * R[6];
-    Q[3] = R[2] * R[7] - R[1] * R[8];
-    Q[4] = R[0] * R[8] - R[2] * R[6];
-    Q[5] = R[1] * R[6] - R[0] * R[7];
-    Q[6] = R[1] * R[5] - R[2] * R[4];
-    Q[7] = R[2] * R[3] - R[0] * R[5];
-    Q[8] = R[0] * R[4] - R[1] * R[3];
-    const double det = (R[0] * Q[0] + R[1] * Q[1]) + R[2] * Q[2];
-    double qmax = 0.0, rmax = 0.0;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-        Q[k] = Q[k] / det;
-        qmax = fmax(qmax, fabs(Q[k]));       // fmax drops a NaN: checked below
-        rmax = fmax(rmax, fabs(R[k]));
-    }
-    bool cull = det != 0.0 && qmax * rmax <= GC_MAX_COND;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) cull = cull && isfinite(Q[k]);
     double m[3], h[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         m[k] = 0.5 * L[k] + 0.5 * H[k];
         h[k] = 0.5 * H[k] - 0.5 * L[k];
-        cull = cull && isfinite(m[k]) && isfinite(h[k]);
     }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        if (!cull) {
-            g.lo[i] = -INFINITY;
-            g.hi[i] = INFINITY;
-            continue;
-        }
-        const double c = g.t[i] + ((Q[i * 3] * m[0] + Q[i * 3 + 1] * m[1]) + Q[i * 3 + 2] * m[2]);
-        const double e = fabs(Q[i * 3]) * h[0] + fabs(Q[i * 3 + 1]) * h[1] + fabs(Q[i * 3 + 2]) * h[2];
-        const double w = e + GC_MARGIN * (((fabs(g.t[i]) + fabs(Q[i * 3] * m[0])) + fabs(Q[i * 3 + 1] * m[1])) +
-                                          fabs(Q[i * 3 + 2] * m[2]) + e);
-        g.lo[i] = gc_down(c - w);
-        g.hi[i] = gc_up(c + w);
-    }
+    gc_cull_box(g.R, g.t, m, h, g.lo, g.hi);
 }
 
 template <int NP>
@@ -155,25 +118,13 @@ __global__ __launch_bounds__(GC_TILE) void grasp_clear_pass_kernel(int N, const 
     const int i0 = blockIdx.x * len, i1 = min(N, i0 + len);
     for (int s0 = i0; s0 < i1; s0 += GC_STAGE) {
         const int ns = min(GC_STAGE, i1 - s0);
-        // (x, y, z, w), x/y/z NaN when the point takes no part
-        for (int k = threadIdx.x; k < ns; k += blockDim.x) {
-            const size_t i = (size_t)(s0 + k);
-            const float px = points[i * 3], py = points[i * 3 + 1], pz = points[i * 3 + 2];
-            const float w = weights[i];
-            const bool part = isfinite(px) && isfinite(py) && isfinite(pz) && (double)w > min_weight;
-            s_p[k] = part ? make_float4(px, py, pz, w) : make_float4(NAN, NAN, NAN, 0.0f);
-        }
+        gc_stage(s0, ns, points, nullptr, weights, min_weight, s_p, nullptr);
         __syncthreads();
         for (int k = 0; k < ns; ++k) {
             const float4 a = s_p[k];
-            if (!(a.x >= G.lo[0] && a.x <= G.hi[0] && a.y >= G.lo[1] && a.y <= G.hi[1] && a.z >= G.lo[2] &&
-                  a.z <= G.hi[2]))
-                continue;
-            // u_j = (R[0][j] d0 + R[1][j] d1) + R[2][j] d2, d = (double)p - t: fp64, no contraction
-            const double d0 = (double)a.x - G.t[0], d1 = (double)a.y - G.t[1], d2 = (double)a.z - G.t[2];
-            const double u0 = (G.R[0] * d0 + G.R[3] * d1) + G.R[6] * d2;
-            const double u1 = (G.R[1] * d0 + G.R[4] * d1) + G.R[7] * d2;
-            const double u2 = (G.R[2] * d0 + G.R[5] * d1) + G.R[8] * d2;
+            if (!gc_in_box(G.lo, G.hi, a)) continue;
+            double u0, u1, u2;
+            gc_local(G.R, G.t, a, u0, u1, u2);
             const double w = (double)a.w;
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
@@ -245,19 +196,14 @@ static size_t cl_layout(int N, int M, int P, ClWs *w, char *base) {
     int C, len;
     gc_chunks(N, M, &C, &len);
     const size_t n = (size_t)C * M * P;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char *p = base ? base + off : nullptr;
-        off += gg_align_up(bytes, 256);
-        return p;
-    };
+    GgCarve cv{base, 0};
     ClWs t;
-    t.bc = (int *)take(n * 4);
-    t.sc = (int *)take(n * 4);
-    t.bs = (double *)take(n * 8);
-    t.ss = (double *)take(n * 8);
+    t.bc = (int *)cv.take(n * 4);
+    t.sc = (int *)cv.take(n * 4);
+    t.bs = (double *)cv.take(n * 8);
+    t.ss = (double *)cv.take(n * 8);
     if (w) *w = t;
-    return off < 256 ? 256 : off;           // never 0 for counts in range: 0 says "out of range"
+    return cv.off < 256 ? 256 : cv.off;     // never 0 for counts in range: 0 says "out of range"
 }
 
 extern "C" size_t gg_grasp_clearance_workspace(int num_points, int num_grasps, int num_parts) {
@@ -304,19 +250,15 @@ extern "C" int gg_grasp_clearance(int num_points, const float *points, const flo
                    ((uintptr_t)sweep_count & 3) == 0 && ((uintptr_t)sweep_weight & 3) == 0,
                "points / weights / grasps / counts / sums misaligned");
     const size_t need = cl_layout(num_points, num_grasps, num_parts, nullptr, nullptr);
-    GG_REQUIRE(ws && ((uintptr_t)ws & 255) == 0, "ws must be non-null and 256-byte aligned");
-    if (ws_bytes < need) {
-        gg_set_error("%s: workspace too small: %zu < %zu bytes", __func__, ws_bytes, need);
-        return GG_ERR_WORKSPACE;
-    }
+    GG_REQUIRE_WS(ws, ws_bytes, need);
     ClWs w;
     cl_layout(num_points, num_grasps, num_parts, &w, (char *)ws);
     int C, len;
     gc_chunks(num_points, num_grasps, &C, &len);
     hipStream_t s = (hipStream_t)stream;
     const int M = num_grasps;
-    const unsigned threads = (unsigned)min(GC_TILE, (M + GG_WAVE - 1) / GG_WAVE * GG_WAVE);
-    const dim3 grid((unsigned)C, (unsigned)((M + threads - 1) / threads)), block(threads);
+    dim3 grid, block;
+    gc_launch_shape(C, M, &grid, &block);
     gg_prof_begin(GG_K_GRASP_CLEAR, s);
     if (C > 0) {
 #define CL_CASE(NP)                                                                                           \

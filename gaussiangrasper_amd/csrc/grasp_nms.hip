@@ -193,18 +193,13 @@ __global__ __launch_bounds__(256) void nms_empty_kernel(int M, uint8_t *__restri
 
 static size_t nms_layout(int A, NmsWs *w, char *base) {
     const size_t W = ((size_t)A + 63) / 64;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char *p = base ? base + off : nullptr;
-        off += gg_align_up(bytes, 256);
-        return p;
-    };
+    GgCarve cv{base, 0};
     NmsWs t;
-    t.pose = (float *)take((size_t)A * 12 * 4);
-    t.part = (uint64_t *)take(W * 8);
-    t.mat = (uint64_t *)take((size_t)A * W * 8);
+    t.pose = (float *)cv.take((size_t)A * 12 * 4);
+    t.part = (uint64_t *)cv.take(W * 8);
+    t.mat = (uint64_t *)cv.take((size_t)A * W * 8);
     if (w) *w = t;
-    return off < 256 ? 256 : off;           // never 0 for a count in range: 0 says "out of range"
+    return cv.off < 256 ? 256 : cv.off;     // never 0 for a count in range: 0 says "out of range"
 }
 
 extern "C" size_t gg_grasp_nms_workspace(int num_order) {
@@ -240,11 +235,7 @@ extern "C" int gg_grasp_nms(int num_grasps, const float *grasps, int num_order, 
         return GG_OK;
     }
     const size_t need = nms_layout(A, nullptr, nullptr);
-    GG_REQUIRE(ws && ((uintptr_t)ws & 255) == 0, "ws must be non-null and 256-byte aligned");
-    if (ws_bytes < need) {
-        gg_set_error("%s: workspace too small: %zu < %zu bytes", __func__, ws_bytes, need);
-        return GG_ERR_WORKSPACE;
-    }
+    GG_REQUIRE_WS(ws, ws_bytes, need);
     NmsWs w;
     nms_layout(A, &w, (char *)ws);
     const int W = (A + 63) / 64;

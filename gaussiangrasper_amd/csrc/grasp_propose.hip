@@ -10,26 +10,18 @@
 //   (s_lo, j_lo) / (s_hi, j_hi) the extremes of s over the tube (smallest index on a tie), tube_count their number;
 //   valid iff q = s_hi - s_lo has (w0 w0) nn <= q q <= ((W - 2c)(W - 2c)) nn and both contact normals pass
 //   g g >= (min_align min_align)(nn m), m > 0.  No square root and no division decides anything.
-// Tiling (grasp.hip's): one lane per seed, GP_TILE seeds per workgroup (grid.y), the seed's fp64 state in registers;
-// grid.x splits the points into C chunks of `len` points, a multiple of GP_STAGE, staged through LDS GP_STAGE at a
+// Tiling (grasp.hip's): one lane per seed, GC_TILE seeds per workgroup (grid.y), the seed's fp64 state in registers;
+// grid.x splits the points into C chunks of `len` points, a multiple of GC_STAGE, staged through LDS GC_STAGE at a
 // time and read as broadcasts, walked in increasing index order.
-// Cull: the tube lies in the fp32 box |x_k - p_k| <= W |b_k| + r, widened by GP_MARGIN (W + r + |p_k|) and rounded
+// Cull: the tube lies in the fp32 box |x_k - p_k| <= W |b_k| + r, widened by GC_MARGIN (W + r + |p_k|) and rounded
 // outward (gp_load); six fp32 compares per pair, only pairs inside take the fp64 test.  The widening is ~1e9 times
 // the fp64 test's rounding, so the cull never changes a decision.  A point that takes no part is staged as NaN.
 // Determinism: no atomics.  Each (chunk, seed) writes (count, s_lo, j_lo, s_hi, j_hi); propose_reduce_kernel
 // combines the C partials in chunk order with strict < / >: min, max, the smallest index reaching them and an
 // integer count are the same for every chunking, so the result does not depend on the launch geometry.
 // propose_rows_kernel then writes the K rows of each seed, one thread per row.
-#include <math.h>
+#include "grasp_common.h"
 
-#include "gg_common.h"
-
-#define GP_TILE 256              // seeds per workgroup (one per lane)
-#define GP_STAGE 256             // points per LDS stage
-#define GP_TARGET_BLOCKS 2048    // chunks x seed tiles aimed for: 8 workgroups per CU
-#define GP_MIN_CHUNK 512         // fewest points a chunk is given
-#define GP_MARGIN 1e-6           // relative widening of the cull box
-#define GP_ROW 17
 #define GP_FRAME 14              // per-seed frame in ws: m (3), b (3), a_0 (3), c_0 (3), width, score
 
 struct GpParams {
@@ -51,23 +43,6 @@ struct GpWs {
     double *frame;               // [S][GP_FRAME]
 };
 
-__device__ __forceinline__ float gp_down(double x) {
-    float f = (float)x;
-    return (double)f > x ? nextafterf(f, -INFINITY) : f;
-}
-__device__ __forceinline__ float gp_up(double x) {
-    float f = (float)x;
-    return (double)f < x ? nextafterf(f, INFINITY) : f;
-}
-
-__device__ __forceinline__ bool gp_part(int j, const float *__restrict__ points, const float *__restrict__ normals,
-                                        const float *__restrict__ weights, double min_weight) {
-    const size_t i = (size_t)j;
-    return isfinite(points[i * 3]) && isfinite(points[i * 3 + 1]) && isfinite(points[i * 3 + 2]) &&
-           isfinite(normals[i * 3]) && isfinite(normals[i * 3 + 1]) && isfinite(normals[i * 3 + 2]) &&
-           (double)weights[i] > min_weight;
-}
-
 // `idx` is the seed's point index, or any value outside [0, N) for a lane past the last seed.
 __device__ void gp_load(int idx, int N, const float *__restrict__ points, const float *__restrict__ normals,
                         const float *__restrict__ weights, const GpParams &P, bool box, GpSeed &g) {
@@ -80,11 +55,12 @@ __device__ void gp_load(int idx, int N, const float *__restrict__ points, const 
     }
     g.nn = g.rrnn = g.wwnn = 0.0;
     g.usable = false;
-    if (idx < 0 || idx >= N || !gp_part(idx, points, normals, weights, P.min_weight)) return;
+    const size_t i3 = (size_t)idx * 3;
+    if (idx < 0 || idx >= N || !gc_part(points + i3, normals + i3, weights[idx], P.min_weight)) return;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        g.p[k] = (double)points[(size_t)idx * 3 + k];
-        g.n[k] = (double)normals[(size_t)idx * 3 + k];
+        g.p[k] = (double)points[i3 + k];
+        g.n[k] = (double)normals[i3 + k];
     }
     g.nn = (g.n[0] * g.n[0] + g.n[1] * g.n[1]) + g.n[2] * g.n[2];
     if (!(g.nn > 0.0)) return;
@@ -96,39 +72,32 @@ __device__ void gp_load(int idx, int N, const float *__restrict__ points, const 
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const double e = P.W * (fabs(g.n[k]) / sq) + P.r;
-        const double w = e + GP_MARGIN * ((P.W + P.r) + fabs(g.p[k]));
+        const double w = e + GC_MARGIN * ((P.W + P.r) + fabs(g.p[k]));
         const bool fin = isfinite(w);
-        g.lo[k] = fin ? gp_down(g.p[k] - w) : -INFINITY;
-        g.hi[k] = fin ? gp_up(g.p[k] + w) : INFINITY;
+        g.lo[k] = fin ? gc_down(g.p[k] - w) : -INFINITY;
+        g.hi[k] = fin ? gc_up(g.p[k] + w) : INFINITY;
     }
 }
 
-__global__ __launch_bounds__(GP_TILE) void propose_search_kernel(int N, const float *__restrict__ points,
+__global__ __launch_bounds__(GC_TILE) void propose_search_kernel(int N, const float *__restrict__ points,
                                                                  const float *__restrict__ normals,
                                                                  const float *__restrict__ weights, int S,
                                                                  const int32_t *__restrict__ seeds, GpParams P,
                                                                  int len, GpWs ws) {
-    __shared__ float4 s_p[GP_STAGE];
+    __shared__ float4 s_p[GC_STAGE];
     const int g = blockIdx.y * blockDim.x + threadIdx.x;
     GpSeed G;
     gp_load(g < S ? seeds[g] : -1, N, points, normals, weights, P, true, G);
     int cnt = 0, jlo = -1, jhi = -1;
     double slo = INFINITY, shi = -INFINITY;
     const int i0 = blockIdx.x * len, i1 = min(N, i0 + len);
-    for (int s0 = i0; s0 < i1; s0 += GP_STAGE) {
-        const int ns = min(GP_STAGE, i1 - s0);
-        for (int k = threadIdx.x; k < ns; k += blockDim.x) {
-            const size_t i = (size_t)(s0 + k);
-            s_p[k] = gp_part(s0 + k, points, normals, weights, P.min_weight)
-                         ? make_float4(points[i * 3], points[i * 3 + 1], points[i * 3 + 2], 0.0f)
-                         : make_float4(NAN, NAN, NAN, 0.0f);
-        }
+    for (int s0 = i0; s0 < i1; s0 += GC_STAGE) {
+        const int ns = min(GC_STAGE, i1 - s0);
+        gc_stage(s0, ns, points, normals, weights, P.min_weight, s_p, nullptr);
         __syncthreads();
         for (int k = 0; k < ns; ++k) {
             const float4 a = s_p[k];
-            if (!(a.x >= G.lo[0] && a.x <= G.hi[0] && a.y >= G.lo[1] && a.y <= G.hi[1] && a.z >= G.lo[2] &&
-                  a.z <= G.hi[2]))
-                continue;
+            if (!gc_in_box(G.lo, G.hi, a)) continue;
             const double d0 = (double)a.x - G.p[0], d1 = (double)a.y - G.p[1], d2 = (double)a.z - G.p[2];
             const double s = (G.n[0] * d0 + G.n[1] * d1) + G.n[2] * d2;
             const double dd = (d0 * d0 + d1 * d1) + d2 * d2;
@@ -265,10 +234,10 @@ __global__ __launch_bounds__(256) void propose_rows_kernel(int S, GpParams P, co
     if (t >= (size_t)S * P.K) return;
     const size_t g = t / P.K;
     const int k = (int)(t % P.K);
-    float *o = rows + t * GP_ROW;
+    float *o = rows + t * GC_ROW;
     if (!valid[g]) {
 #pragma unroll
-        for (int i = 0; i < GP_ROW; ++i) o[i] = NAN;
+        for (int i = 0; i < GC_ROW; ++i) o[i] = NAN;
         return;
     }
     const double *f = frame + g * GP_FRAME;
@@ -297,39 +266,20 @@ __global__ __launch_bounds__(256) void propose_rows_kernel(int S, GpParams P, co
     o[16] = 0.0f;
 }
 
-// C chunks of len points (len a multiple of GP_STAGE), from (N, S) only.
-static void gp_chunks(int N, int S, int *C, int *len) {
-    *C = 0;
-    *len = 0;
-    if (N <= 0 || S <= 0) return;
-    const int tiles = (S + GP_TILE - 1) / GP_TILE;
-    int c = GP_TARGET_BLOCKS / tiles;
-    c = max(1, min(c, (N + GP_MIN_CHUNK - 1) / GP_MIN_CHUNK));
-    int l = (N + c - 1) / c;
-    l = (l + GP_STAGE - 1) / GP_STAGE * GP_STAGE;
-    *len = l;
-    *C = (N + l - 1) / l;
-}
-
 static size_t gp_layout(int N, int S, GpWs *w, char *base) {
     int C, len;
-    gp_chunks(N, S, &C, &len);
+    gc_chunks(N, S, &C, &len);
     const size_t cs = (size_t)C * S;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char *p = base ? base + off : nullptr;
-        off += gg_align_up(bytes, 256);
-        return p;
-    };
+    GgCarve cv{base, 0};
     GpWs t;
-    t.cnt = (int *)take(cs * 4);
-    t.jlo = (int *)take(cs * 4);
-    t.jhi = (int *)take(cs * 4);
-    t.slo = (double *)take(cs * 8);
-    t.shi = (double *)take(cs * 8);
-    t.frame = (double *)take((size_t)S * GP_FRAME * 8);
+    t.cnt = (int *)cv.take(cs * 4);
+    t.jlo = (int *)cv.take(cs * 4);
+    t.jhi = (int *)cv.take(cs * 4);
+    t.slo = (double *)cv.take(cs * 8);
+    t.shi = (double *)cv.take(cs * 8);
+    t.frame = (double *)cv.take((size_t)S * GP_FRAME * 8);
     if (w) *w = t;
-    return off;
+    return cv.off;
 }
 
 extern "C" size_t gg_grasp_propose_workspace(int num_points, int num_seeds) {
@@ -369,15 +319,11 @@ extern "C" int gg_grasp_propose(int num_points, const float *points, const float
                    ((uintptr_t)seeds & 3) == 0,
                "points / normals / weights / seeds misaligned");
     const size_t need = gp_layout(num_points, num_seeds, nullptr, nullptr);
-    GG_REQUIRE(ws && ((uintptr_t)ws & 255) == 0, "ws must be non-null and 256-byte aligned");
-    if (ws_bytes < need) {
-        gg_set_error("%s: workspace too small: %zu < %zu bytes", __func__, ws_bytes, need);
-        return GG_ERR_WORKSPACE;
-    }
+    GG_REQUIRE_WS(ws, ws_bytes, need);
     GpWs w;
     gp_layout(num_points, num_seeds, &w, (char *)ws);
     int C, len;
-    gp_chunks(num_points, num_seeds, &C, &len);
+    gc_chunks(num_points, num_seeds, &C, &len);
     GpParams P;
     P.r = tube_radius;
     P.W = max_width;
@@ -397,12 +343,12 @@ extern "C" int gg_grasp_propose(int num_points, const float *points, const float
     P.K = num_approach;
     hipStream_t s = (hipStream_t)stream;
     const int S = num_seeds;
-    const unsigned threads = (unsigned)min(GP_TILE, (S + GG_WAVE - 1) / GG_WAVE * GG_WAVE);
-    const dim3 grid((unsigned)C, (unsigned)((S + threads - 1) / threads));
+    dim3 grid, block;
+    gc_launch_shape(C, S, &grid, &block);
     const size_t nrows = (size_t)S * num_approach;
     gg_prof_begin(GG_K_GRASP_PROPOSE, s);
     if (C > 0)
-        hipLaunchKernelGGL(propose_search_kernel, grid, dim3(threads), 0, s, num_points, points, normals, weights, S,
+        hipLaunchKernelGGL(propose_search_kernel, grid, block, 0, s, num_points, points, normals, weights, S,
                            seeds, P, len, w);
     hipLaunchKernelGGL(propose_reduce_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, s, num_points, points,
                        normals, weights, S, seeds, P, C, w, pair_idx, tube_count, span, valid);

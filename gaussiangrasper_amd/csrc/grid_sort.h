@@ -118,21 +118,16 @@ static inline bool kn_dims_ok(const int32_t *dims) {
 static inline size_t kn_layout(int n, const int32_t *dims, KnWs *w, char *base) {
     const int64_t cells = (int64_t)dims[0] * dims[1] * dims[2];
     const int64_t tiles = (cells + PP_TILE - 1) / PP_TILE;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char *p = base ? base + off : nullptr;
-        off += gg_align_up(bytes, 256);
-        return p;
-    };
+    GgCarve cv{base, 0};
     KnWs t;
-    t.counts = (int32_t *)take((size_t)cells * 4);
-    t.cursor = (int32_t *)take((size_t)cells * 4);
-    t.start = (int32_t *)take((size_t)cells * 4);
-    t.tile_sums = (int32_t *)take((size_t)tiles * 4);
-    t.tile_offs = (int32_t *)take((size_t)tiles * 4);
-    t.sorted = (float4 *)take((size_t)n * 16);
+    t.counts = (int32_t *)cv.take((size_t)cells * 4);
+    t.cursor = (int32_t *)cv.take((size_t)cells * 4);
+    t.start = (int32_t *)cv.take((size_t)cells * 4);
+    t.tile_sums = (int32_t *)cv.take((size_t)tiles * 4);
+    t.tile_offs = (int32_t *)cv.take((size_t)tiles * 4);
+    t.sorted = (float4 *)cv.take((size_t)n * 16);
     if (w) *w = t;
-    return off;
+    return cv.off;
 }
 
 // counts, start and sorted of the points (FILTER: of those that take part) on stream s; hipSuccess unless a fill

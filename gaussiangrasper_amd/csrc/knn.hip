@@ -130,11 +130,7 @@ extern "C" int gg_knn(int num_points, const float *points, int k, const double *
     GG_REQUIRE(((uintptr_t)points & 3) == 0 && ((uintptr_t)dist & 3) == 0 && ((uintptr_t)idx & 7) == 0,
                "points / dist / idx misaligned");
     const size_t need = kn_layout(num_points, dims, nullptr, nullptr);
-    GG_REQUIRE(ws && ((uintptr_t)ws & 255) == 0, "ws must be non-null and 256-byte aligned");
-    if (ws_bytes < need) {
-        gg_set_error("%s: workspace too small: %zu < %zu bytes", __func__, ws_bytes, need);
-        return GG_ERR_WORKSPACE;
-    }
+    GG_REQUIRE_WS(ws, ws_bytes, need);
     KnWs w;
     kn_layout(num_points, dims, &w, (char *)ws);
     KnGrid G;

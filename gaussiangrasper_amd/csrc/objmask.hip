@@ -407,19 +407,14 @@ static bool om_shape_ok(int V, int max_rows) {
 
 static size_t om_layout(int V, int max_rows, OmLayout *L, char *base) {
     const size_t J = 2 * (size_t)V;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char *q = base ? base + off : nullptr;
-        off += gg_align_up(bytes, 256);
-        return q;
-    };
-    int32_t *jb = (int32_t *)take(J * JB_WORDS * 4);
-    int32_t *box_ws = (int32_t *)take((size_t)V * 12 * 4);
-    int32_t *status = (int32_t *)take(4);
-    int2 *rows = (int2 *)take(J * (size_t)max_rows * sizeof(int2));
-    uint16_t *chains = (uint16_t *)take(J * 2 * (size_t)max_rows * sizeof(uint16_t));
+    GgCarve cv{base, 0};
+    int32_t *jb = (int32_t *)cv.take(J * JB_WORDS * 4);
+    int32_t *box_ws = (int32_t *)cv.take((size_t)V * 12 * 4);
+    int32_t *status = (int32_t *)cv.take(4);
+    int2 *rows = (int2 *)cv.take(J * (size_t)max_rows * sizeof(int2));
+    uint16_t *chains = (uint16_t *)cv.take(J * 2 * (size_t)max_rows * sizeof(uint16_t));
     if (L) *L = OmLayout{jb, box_ws, status, rows, chains};
-    return off;
+    return cv.off;
 }
 
 extern "C" size_t gg_object_masks_workspace(int num_views, int max_rows) {
@@ -445,11 +440,7 @@ extern "C" int gg_object_masks(int num_points, const double *points, const doubl
                    ((uintptr_t)centres & 7) == 0 && ((uintptr_t)boxes & 3) == 0 && ((uintptr_t)dropped & 3) == 0,
                "points / intrinsics / w2c / centres / boxes / dropped misaligned");
     const size_t need = om_layout(num_views, max_rows, nullptr, nullptr);
-    GG_REQUIRE(ws && ((uintptr_t)ws & 255) == 0, "ws must be non-null and 256-byte aligned");
-    if (ws_bytes < need) {
-        gg_set_error("%s: workspace too small: %zu < %zu bytes", __func__, ws_bytes, need);
-        return GG_ERR_WORKSPACE;
-    }
+    GG_REQUIRE_WS(ws, ws_bytes, need);
     if (num_views == 0) return GG_OK;
     OmLayout L;
     om_layout(num_views, max_rows, &L, (char *)ws);

@@ -104,17 +104,12 @@ static int64_t bp_tiles(int F, int H, int W) { return ((int64_t)F * H * W + PP_T
 
 static size_t bp_layout(int F, int H, int W, int32_t **counts, int32_t **offsets, char *base) {
     const int64_t nb = bp_tiles(F, H, W);
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char *p = base ? base + off : nullptr;
-        off += gg_align_up(bytes, 256);
-        return p;
-    };
-    int32_t *c = (int32_t *)take((size_t)nb * 4);
-    int32_t *o = (int32_t *)take((size_t)nb * 4);
+    GgCarve cv{base, 0};
+    int32_t *c = (int32_t *)cv.take((size_t)nb * 4);
+    int32_t *o = (int32_t *)cv.take((size_t)nb * 4);
     if (counts) *counts = c;
     if (offsets) *offsets = o;
-    return off;
+    return cv.off;
 }
 
 static bool bp_shape_ok(int F, int H, int W) {
@@ -140,11 +135,7 @@ extern "C" int gg_backproject(int num_frames, int height, int width, const doubl
                    ((uintptr_t)points & 7) == 0 && ((uintptr_t)count & 7) == 0,
                "depth / intrinsics / c2w / points / count misaligned");
     const size_t need = bp_layout(num_frames, height, width, nullptr, nullptr, nullptr);
-    GG_REQUIRE(ws && ((uintptr_t)ws & 255) == 0, "ws must be non-null and 256-byte aligned");
-    if (ws_bytes < need) {
-        gg_set_error("%s: workspace too small: %zu < %zu bytes", __func__, ws_bytes, need);
-        return GG_ERR_WORKSPACE;
-    }
+    GG_REQUIRE_WS(ws, ws_bytes, need);
     int32_t *counts, *offsets;
     bp_layout(num_frames, height, width, &counts, &offsets, (char *)ws);
     hipStream_t s = (hipStream_t)stream;
@@ -279,23 +270,18 @@ __global__ __launch_bounds__(PP_THREADS) void subsample_emit_kernel(int64_t num,
 static size_t ss_layout(int64_t num, SelState **st, uint32_t **hist, int32_t **counts, int32_t **offsets,
                         int64_t **total, char *base) {
     const int64_t nb = (num + PP_TILE - 1) / PP_TILE;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char *p = base ? base + off : nullptr;
-        off += gg_align_up(bytes, 256);
-        return p;
-    };
-    SelState *a = (SelState *)take(sizeof(SelState));
-    uint32_t *h = (uint32_t *)take((size_t)PP_SEL_BINS * 4);
-    int32_t *c = (int32_t *)take((size_t)nb * 4);
-    int32_t *o = (int32_t *)take((size_t)nb * 4);
-    int64_t *t = (int64_t *)take(8);
+    GgCarve cv{base, 0};
+    SelState *a = (SelState *)cv.take(sizeof(SelState));
+    uint32_t *h = (uint32_t *)cv.take((size_t)PP_SEL_BINS * 4);
+    int32_t *c = (int32_t *)cv.take((size_t)nb * 4);
+    int32_t *o = (int32_t *)cv.take((size_t)nb * 4);
+    int64_t *t = (int64_t *)cv.take(8);
     if (st) *st = a;
     if (hist) *hist = h;
     if (counts) *counts = c;
     if (offsets) *offsets = o;
     if (total) *total = t;
-    return off;
+    return cv.off;
 }
 
 extern "C" size_t gg_subsample_workspace(int64_t num) {
@@ -316,11 +302,7 @@ extern "C" int gg_subsample(int64_t num, int64_t keep, uint64_t seed, const doub
     GG_REQUIRE(((uintptr_t)points & 7) == 0 && ((uintptr_t)out_points & 7) == 0 && ((uintptr_t)out_index & 7) == 0,
                "points / out_points / out_index misaligned");
     const size_t need = ss_layout(num, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-    GG_REQUIRE(ws && ((uintptr_t)ws & 255) == 0, "ws must be non-null and 256-byte aligned");
-    if (ws_bytes < need) {
-        gg_set_error("%s: workspace too small: %zu < %zu bytes", __func__, ws_bytes, need);
-        return GG_ERR_WORKSPACE;
-    }
+    GG_REQUIRE_WS(ws, ws_bytes, need);
     SelState *st;
     uint32_t *hist;
     int32_t *counts, *offsets;

@@ -153,11 +153,7 @@ extern "C" int gg_cloud_frames(int num_points, const float *points, const float 
                    ((uintptr_t)gradients & 3) == 0 && ((uintptr_t)count & 3) == 0,
                "points / intensity / normals / gradients / count misaligned");
     const size_t sort_bytes = kn_layout(num_points, dims, nullptr, nullptr);
-    GG_REQUIRE(ws && ((uintptr_t)ws & 255) == 0, "ws must be non-null and 256-byte aligned");
-    if (ws_bytes < sort_bytes + 256) {
-        gg_set_error("%s: workspace too small: %zu < %zu bytes", __func__, ws_bytes, sort_bytes + 256);
-        return GG_ERR_WORKSPACE;
-    }
+    GG_REQUIRE_WS(ws, ws_bytes, sort_bytes + 256);
     const KnGrid G = rg_grid(grid, dims, radius);
     GG_REQUIRE(isfinite(G.cell) && isfinite(radius * radius), "radius too large");
     KnWs w;
@@ -330,11 +326,7 @@ extern "C" int gg_icp_step(int num_source, const float *source, const float *sou
                "source / source_intensity / points / intensity / normals / gradients / corr / sums misaligned");
     size_t sort_bytes = 0;
     const size_t need = rg_step_layout(num_source, num_target, dims, &sort_bytes);
-    GG_REQUIRE(ws && ((uintptr_t)ws & 255) == 0, "ws must be non-null and 256-byte aligned");
-    if (ws_bytes < need) {
-        gg_set_error("%s: workspace too small: %zu < %zu bytes", __func__, ws_bytes, need);
-        return GG_ERR_WORKSPACE;
-    }
+    GG_REQUIRE_WS(ws, ws_bytes, need);
     const KnGrid G = rg_grid(grid, dims, max_dist);
     GG_REQUIRE(isfinite(G.cell), "max_dist too large for the grid");
     KnWs w;

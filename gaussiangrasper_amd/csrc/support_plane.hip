@@ -222,11 +222,7 @@ extern "C" int gg_plane_consensus(int num_points, const float *points, const flo
                    ((uintptr_t)count & 3) == 0 && ((uintptr_t)best & 3) == 0,
                "points / weights / hyp / count / best misaligned");
     const size_t need = sp_consensus_bytes(num_hypotheses);
-    GG_REQUIRE(ws && ((uintptr_t)ws & 255) == 0, "ws must be non-null and 256-byte aligned");
-    if (ws_bytes < need) {
-        gg_set_error("%s: workspace too small: %zu < %zu bytes", __func__, ws_bytes, need);
-        return GG_ERR_WORKSPACE;
-    }
+    GG_REQUIRE_WS(ws, ws_bytes, need);
     double *rec = (double *)ws;
     const int N = num_points, H = num_hypotheses;
     int C, len;
@@ -363,11 +359,7 @@ extern "C" int gg_plane_classify(int num_points, const float *points, const floa
                    ((uintptr_t)sums & 7) == 0,
                "points / weights / height / sums misaligned");
     const size_t need = sp_classify_bytes(num_points);
-    GG_REQUIRE(ws && ((uintptr_t)ws & 255) == 0, "ws must be non-null and 256-byte aligned");
-    if (ws_bytes < need) {
-        gg_set_error("%s: workspace too small: %zu < %zu bytes", __func__, ws_bytes, need);
-        return GG_ERR_WORKSPACE;
-    }
+    GG_REQUIRE_WS(ws, ws_bytes, need);
     double *slab = (double *)ws;
     const int blocks = sp_classify_blocks(num_points);
     hipStream_t s = (hipStream_t)stream;

@@ -465,21 +465,16 @@ struct TmLayout {
 static size_t tm_layout(int64_t P, TmLayout *L, char *base) {
     const int nb = (int)((P + TM_POINTS - 1) / TM_POINTS);
     const size_t sb = gg_scan_state_bytes(nb);
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char *q = base ? base + off : nullptr;
-        off += gg_align_up(bytes, 256);
-        return q;
-    };
-    uint32_t *masks = (uint32_t *)take(4 * (size_t)((P + 3) / 4));
-    ScanState *stv = (ScanState *)take(sb);
-    ScanState *stf = (ScanState *)take(sb);
-    const size_t reset = off;
-    uint8_t *fc = (uint8_t *)take((size_t)P);
-    uint32_t *voff = (uint32_t *)take(4 * (size_t)P);
-    uint32_t *foff = (uint32_t *)take(4 * (size_t)P);
+    GgCarve cv{base, 0};
+    uint32_t *masks = (uint32_t *)cv.take(4 * (size_t)((P + 3) / 4));
+    ScanState *stv = (ScanState *)cv.take(sb);
+    ScanState *stf = (ScanState *)cv.take(sb);
+    const size_t reset = cv.off;
+    uint8_t *fc = (uint8_t *)cv.take((size_t)P);
+    uint32_t *voff = (uint32_t *)cv.take(4 * (size_t)P);
+    uint32_t *foff = (uint32_t *)cv.take(4 * (size_t)P);
     if (L) *L = TmLayout{masks, fc, voff, foff, stv, stf, reset};
-    return off;
+    return cv.off;
 }
 
 static int64_t ts_points(const int32_t *dims) { return (int64_t)dims[0] * dims[1] * dims[2]; }
@@ -533,11 +528,7 @@ extern "C" int gg_tsdf_mesh_count(const int32_t *dims, const float *tsdf, const 
                "tsdf / weight / counts misaligned");
     const int64_t P = ts_points(dims);
     const size_t need = tm_layout(P, nullptr, nullptr);
-    GG_REQUIRE(ws && ((uintptr_t)ws & 255) == 0, "ws must be non-null and 256-byte aligned");
-    if (ws_bytes < need) {
-        gg_set_error("%s: workspace too small: %zu < %zu bytes", __func__, ws_bytes, need);
-        return GG_ERR_WORKSPACE;
-    }
+    GG_REQUIRE_WS(ws, ws_bytes, need);
     TmLayout L;
     tm_layout(P, &L, (char *)ws);
     TmParams pr{TsGrid{dims[0], dims[1], dims[2], {0.f, 0.f, 0.f}, {1.f, 1.f, 1.f}}, P,
@@ -574,11 +565,7 @@ extern "C" int gg_tsdf_mesh_emit(const int32_t *dims, const float *grid, const f
                "arrays must be 4-byte aligned");
     const int64_t P = ts_points(dims);
     const size_t need = tm_layout(P, nullptr, nullptr);
-    GG_REQUIRE(ws && ((uintptr_t)ws & 255) == 0, "ws must be non-null and 256-byte aligned");
-    if (ws_bytes < need) {
-        gg_set_error("%s: workspace too small: %zu < %zu bytes", __func__, ws_bytes, need);
-        return GG_ERR_WORKSPACE;
-    }
+    GG_REQUIRE_WS(ws, ws_bytes, need);
     TmLayout L;
     tm_layout(P, &L, (char *)const_cast<void *>(ws));
     TmParams pr{g, P, (int)((P + TM_POINTS - 1) / TM_POINTS)};

@@ -18,6 +18,7 @@ every candidate against every oriented point in fp64; the contract is in include
                        (gg_grasp_nms, csrc/grasp_nms.hip, PARITY.md "Grasp NMS"; GraspNMS)
     plane_clear        whether the whole gripper, at the final pose and at the start of its approach, stays above a
                        support plane (support.SupportPlane, PARITY.md "Support plane")
+    GraspGates         the gates after the contacts (clearance, support plane, NMS) as one record, run by apply_gates
     python -m gaussiangrasper_amd.grasp --ckpt IN --grasps grasps.npy [...] --out kept.npy
 
 Grasp candidates come from outside the project (AnyGrasp): this module only scores them."""
@@ -28,7 +29,7 @@ import json
 import math
 import sys
 from dataclasses import dataclass
-from typing import Optional, Sequence, Union
+from typing import Callable, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -37,9 +38,8 @@ from torch import Tensor
 from . import _lib
 from ._call import (ArrayLike, f32_rows, host_ptr, nonneg, positive, ptr as _ptr, require_hip as _require_hip,
                     stream as _stream, workspace as _ws)
-from ._cli import (add_clearance_options, add_nms_options, add_object_options, add_support_options,
-                   check_clearance_options, check_nms_options, check_object_options, check_support_options, object_mask,
-                   report_arrays, support_option_plane)
+from ._cli import (add_grasp_options, add_object_options, check_grasp_options, check_object_options,
+                   grasp_gate_kwargs, load_scene, object_mask, report_arrays, support_option_plane)
 from .frames import ORTHO_TOL, load_transform_json, rigid_to_scene  # noqa: F401
 
 GRASP_COLS = 17
@@ -278,7 +278,7 @@ def contacts(points: Tensor, normals: Tensor, weights: Tensor, grasps: Tensor, d
     return res
 
 
-def _limit(name: str, v: Optional[float]) -> float:
+def limit(name: str, v: Optional[float]) -> float:
     v = math.inf if v is None else float(v)
     if math.isnan(v):
         raise ValueError(f"{name} must not be NaN")
@@ -305,8 +305,8 @@ def clearance(points: Tensor, weights: Tensor, grasps: Tensor, gripper: ArrayLik
     p = parts.shape[0]
     if math.isnan(float(min_weight)):
         raise ValueError("min_weight must not be NaN")
-    args = (nonneg("approach", approach), float(min_weight), _limit("max_body", max_body),
-            _limit("max_sweep", max_sweep))
+    args = (nonneg("approach", approach), float(min_weight), limit("max_body", max_body),
+            limit("max_sweep", max_sweep))
     lib = _lib.load()
     res = GraspClearance(
         body_count=torch.empty(m, p, dtype=torch.int32, device=dev),
@@ -483,6 +483,52 @@ def apply_support(res: GraspContacts, rows: Tensor, gripper: Optional[ArrayLike]
     return res
 
 
+@dataclass
+class GraspGates:
+    """The gates score_grasps and grasp_propose.grasp_object put after the friction cone, by their keywords, in this
+    order; each is off at its default and then makes no call.  Lengths are in grasp units, times the call's `scale`.
+    Clearance, with a `gripper` (default_gripper(), or any check_gripper model): clearance of the whole gripper and of
+    its straight approach of length `approach` against the WHOLE scene's points (model_points(model, None), whatever
+    the mask is): feasible &= clear (body weight <= max_body, sweep weight <= max_sweep; None: no limit); the record
+    is .clearance.  Support, with `support` (a support.SupportPlane of the scene frame; it needs `gripper`): feasible
+    &= plane_clear(rows, gripper, support, approach, support_margin, scale) and, with max_approach_tilt (radians),
+    feasible &= a.(-n) >= cos(max_approach_tilt); the plane test's outputs are .support_clear and .support_lowest.
+    NMS, with `nms_translation`: nms of the feasible rows (near: within nms_translation and nms_rotation radians, with
+    nms_symmetric also of the half turn about the approach axis); the record is .nms and the kept rows its
+    order[:top_k], the distinct grasps best first, a subsequence of what filter_grasps gives.  Without nms_translation
+    there is no NMS call and .nms is None; top_k then is an error."""
+    gripper: Optional[ArrayLike] = None
+    approach: float = 0.0
+    max_body: Optional[float] = None
+    max_sweep: Optional[float] = None
+    nms_translation: Optional[float] = None
+    nms_rotation: float = NMS_ROTATION
+    nms_symmetric: bool = True
+    top_k: Optional[int] = None
+    support: object = None
+    support_margin: float = 0.0
+    max_approach_tilt: Optional[float] = None
+
+    def check(self) -> "GraspGates":
+        """The configuration errors that need no data, before anything runs; top_k becomes an int."""
+        self.top_k = check_top_k(self.nms_translation, self.top_k)
+        if self.support is not None and self.gripper is None:
+            raise ValueError("support needs gripper: the plane test has to know which boxes must stay above the plane")
+        return self
+
+
+def apply_gates(g: GraspGates, res: GraspContacts, rows: Tensor, scale: float, min_weight: float,
+                scene_points: Callable[[], Tuple[Tensor, Tensor]]) -> Tensor:
+    """The gates of a checked `g` on `res` and its scene-frame `rows`; returns the kept rows: res.nms.order[:top_k] with
+    NMS, else filter_grasps(rows, res).  scene_points(): whole-scene (points, weights), called only with a gripper."""
+    if g.gripper is not None:
+        apply_clearance(res, *scene_points(), rows, g.gripper, scale, g.approach, min_weight, g.max_body, g.max_sweep)
+    apply_support(res, rows, g.gripper, g.support, scale, g.approach, g.support_margin, g.max_approach_tilt)
+    if g.nms_translation is not None:
+        return apply_nms(res, rows, g.nms_translation, g.nms_rotation, g.nms_symmetric, scale, g.top_k)
+    return filter_grasps(rows, res)
+
+
 @torch.no_grad()
 def model_points(model_or_scene, mask: Optional[Tensor] = None):
     """(points, normals, weights) of a model or scene: the means, the smallest-axis normals as the renderer forms
@@ -514,30 +560,19 @@ def score_grasps(model_or_scene, grasps: ArrayLike, mask: Optional[Tensor] = Non
                  support_margin: float = 0.0, max_approach_tilt: Optional[float] = None) -> GraspContacts:
     """Candidates in the grasp frame, scored against the model's Gaussians in one call: grasps_to_scene, then
     contacts on model_points.  depth_base, finger_width and band are in grasp units and scaled with the grasps.
-    With a `gripper` (default_gripper(), or any check_gripper model; grasp units), also clearance of the whole
-    gripper and its approach against the WHOLE scene's points (model_points(model, None), whatever `mask` is):
-    feasible &= clear, and the record is returned as .clearance.  With `nms_translation` (grasp units), also nms of
-    the feasible rows, returned as .nms; with top_k its .order is cut to the best top_k.  Without nms_translation
-    there is no NMS call and .nms is None.  With `support` (a support.SupportPlane of the scene frame; it needs
-    `gripper`), before the NMS also feasible &= plane_clear(rows, gripper, support, approach, support_margin, scale)
-    and, with max_approach_tilt (radians), feasible &= a.(-n) >= cos(max_approach_tilt); the plane test's outputs are
-    returned as .support_clear and .support_lowest.  Without `support` nothing of this runs."""
-    top_k = check_top_k(nms_translation, top_k)
-    if support is not None and gripper is None:
-        raise ValueError("support needs gripper: the plane test has to know which boxes must stay above the plane")
+    The keywords from `gripper` on are the gates of GraspGates (clearance, support plane, NMS; its docstring says
+    what each does), run in that order after the contacts; with nms_translation .nms.order is cut to the best top_k."""
+    gates = GraspGates(gripper, approach, max_body, max_sweep, nms_translation, nms_rotation, nms_symmetric, top_k,
+                       support, support_margin, max_approach_tilt).check()
     pts, nrm, w = model_points(model_or_scene, mask)
-    g = grasps_to_scene(grasps, cam_to_world, matrix, scale)
+    rows = torch.from_numpy(grasps_to_scene(grasps, cam_to_world, matrix, scale)).to(pts.device)
     s = float(scale)
-    rows = torch.from_numpy(g).to(pts.device)
-    res = contacts(pts, nrm, w, rows, nonneg("depth_base", depth_base) * s,
-                   nonneg("finger_width", finger_width) * s, nonneg("band", band) * s, mu, min_weight,
-                   max_collision)
-    if gripper is not None:
-        w_all = w if mask is None else model_points(model_or_scene, None)[2]
-        apply_clearance(res, pts, w_all, rows, gripper, s, approach, min_weight, max_body, max_sweep)
-    apply_support(res, rows, gripper, support, s, approach, support_margin, max_approach_tilt)
-    if nms_translation is not None:
-        res.nms.order = apply_nms(res, rows, nms_translation, nms_rotation, nms_symmetric, s, top_k)
+    res = contacts(pts, nrm, w, rows, nonneg("depth_base", depth_base) * s, nonneg("finger_width", finger_width) * s,
+                   nonneg("band", band) * s, mu, min_weight, max_collision)
+    keep = apply_gates(gates, res, rows, s, min_weight,
+                       lambda: (pts, w if mask is None else model_points(model_or_scene, None)[2]))
+    if res.nms is not None:
+        res.nms.order = keep
     return res
 
 
@@ -575,43 +610,22 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--camera-pose", default=None, help=".npy 4x4, grasp frame -> world")
     ap.add_argument("--transform-json", default=None, help="JSON with transform_matrix and scale (world -> scene)")
     add_object_options(ap, "the query restricts the Gaussians", "restricts the Gaussians")
-    ap.add_argument("--mu", type=float, default=MU, help="friction coefficient")
     ap.add_argument("--band", type=float, default=BAND, help="contact patch depth, grasp units")
-    ap.add_argument("--min-opacity", type=float, default=MIN_WEIGHT, help="a Gaussian takes part above it")
-    ap.add_argument("--max-collision", type=float, default=None, help="limit on the opacity inside the fingers")
-    add_clearance_options(ap)
-    add_nms_options(ap)
-    add_support_options(ap)
+    add_grasp_options(ap)
     ap.add_argument("--out", required=True, help="output .npy: feasible rows, input frame, by score")
     ap.add_argument("--report", default=None, help="output .npz: every per-grasp output, scene frame")
     a = ap.parse_args(argv)
     check_object_options(ap, a, "optional")
-    for name in ("mu", "band", "min_opacity"):
-        v = getattr(a, name)
-        if not (math.isfinite(v) and v >= 0.0):
-            ap.error(f"--{name.replace('_', '-')} must be finite and >= 0, got {v}")
-    if a.max_collision is not None and math.isnan(a.max_collision):
-        ap.error("--max-collision must not be NaN")
-    check_clearance_options(ap, a)
-    check_nms_options(ap, a)
-    check_support_options(ap, a)
+    check_grasp_options(ap, a, ("band",))
     try:
         grasps = load_grasps(a.grasps)
         gripper = load_gripper_option(a.gripper)
         cam = _load_matrix(a.camera_pose, (4, 4), "camera pose") if a.camera_pose else None
         matrix, scale = load_transform_json(a.transform_json) if a.transform_json else (None, 1.0)
-        from .interop import load_checkpoint
-        scene, mlp_state, _ = load_checkpoint(a.ckpt)
-        scene = scene.to(torch.device("cuda"))
+        scene, mlp_state = load_scene(a.ckpt)
         mask = object_mask(a, scene, mlp_state, matrix, scale)
-        plane = support_option_plane(a, scene, mask, scale)
-        tilt = None if a.max_approach_tilt is None else math.radians(a.max_approach_tilt)
-        res = score_grasps(scene, grasps, mask, cam, matrix, scale, band=a.band, mu=a.mu, min_weight=a.min_opacity,
-                           max_collision=a.max_collision, gripper=gripper, approach=a.approach,
-                           max_body=a.max_body_collision, max_sweep=a.max_sweep_collision,
-                           nms_translation=a.nms_translation, nms_rotation=math.radians(a.nms_rotation),
-                           nms_symmetric=not a.nms_no_symmetry, top_k=a.top_k, support=plane,
-                           support_margin=a.support_margin, max_approach_tilt=tilt)
+        res = score_grasps(scene, grasps, mask, cam, matrix, scale, band=a.band, gripper=gripper,
+                           **grasp_gate_kwargs(a, support_option_plane(a, scene, mask, scale)))
     except (KeyError, ValueError, OSError) as exc:
         raise SystemExit(f"error: {exc}") from exc
     keep = (filter_grasps(grasps, res) if res.nms is None else res.nms.order).cpu().numpy()

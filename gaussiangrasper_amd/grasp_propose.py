@@ -27,13 +27,12 @@ from torch import Tensor
 from . import _lib
 from ._call import (f32_rows, host_ptr, nonneg, positive, ptr as _ptr, require_hip as _require_hip,
                     stream as _stream, workspace as _ws)
-from ._cli import (add_clearance_options, add_nms_options, add_object_options, add_support_options,
-                   check_clearance_options, check_nms_options, check_object_options, check_support_options, object_mask,
-                   report_arrays, support_option_plane)
+from ._cli import (add_grasp_options, add_object_options, check_grasp_options, check_object_options,
+                   grasp_gate_kwargs, load_scene, object_mask, report_arrays, support_option_plane)
 from .frames import check_rotation, load_transform_json
 from .grasp import (BAND, DEPTH_BASE, FINGER_WIDTH, GRASP_COLS, MIN_WEIGHT, MU, NMS_ROTATION, GraspContacts,
-                    apply_clearance, apply_nms, apply_support, check_top_k, contacts, filter_grasps, grasps_from_scene,
-                    load_gripper_option, model_points, nms_summary)
+                    GraspGates, apply_gates, contacts, grasps_from_scene, limit, load_gripper_option,
+                    model_points, nms_summary)
 
 # UNVERIFIED defaults (PARITY.md "Grasp proposals"), in grasp units (metres): max_width, depth and height are
 # recalled from graspnetAPI's gripper; tube_radius, min_width, clearance, min_align and num_approach are this
@@ -189,41 +188,24 @@ def grasp_object(model_or_scene, mask: Optional[Tensor] = None, scale: float = 1
     (weights times mask: the fingers close on the object, not on the table under it), and collision_weight from the
     WHOLE scene's points (model_points(model, None): what the fingers must not hit is everything, the object's own
     Gaussians beside the contacts included).  feasible = the object call's friction-cone result and the scene
-    call's collision_weight <= max_collision (None: no limit).  With a `gripper` (grasp.default_gripper(), or any
-    grasp.check_gripper model; grasp units, times scale), also grasp.clearance of the whole gripper and of its
-    straight approach of length `approach` against the WHOLE scene's points: feasible &= clear (body weight <=
-    max_body, sweep weight <= max_sweep; None: no limit), and the record is contacts.clearance.  keep:
-    filter_grasps(rows, contacts), indices of the feasible rows by score.  With `nms_translation` (grasp units, times
-    scale), also grasp.nms of the feasible rows (near: within nms_translation and nms_rotation radians, with
-    nms_symmetric also of the half turn about the approach axis): the record is contacts.nms and keep becomes its
-    order[:top_k], the distinct grasps best first, a subsequence of what filter_grasps gives.  Without
-    nms_translation there is no NMS call and contacts.nms is None; top_k then is an error.  With `support` (a
-    support.SupportPlane of the scene frame; it needs `gripper`), before the NMS also feasible &=
-    grasp.plane_clear(rows, gripper, support, approach, support_margin, scale) and, with max_approach_tilt (radians),
-    feasible &= a.(-n) >= cos(max_approach_tilt); the plane test's outputs are contacts.support_clear and
-    contacts.support_lowest.  Without `support` nothing of this runs."""
-    top_k = check_top_k(nms_translation, top_k)
-    if support is not None and gripper is None:
-        raise ValueError("support needs gripper: the plane test has to know which boxes must stay above the plane")
+    call's collision_weight <= max_collision (None: no limit).  keep: filter_grasps(rows, contacts), indices of the
+    feasible rows by score.  The keywords from `gripper` on are the gates of grasp.GraspGates (clearance, support
+    plane, NMS; its docstring says what each does), run in that order after the contacts: their records are
+    contacts.clearance, .support_clear / .support_lowest and .nms, and with NMS keep is its order[:top_k]."""
+    gates = GraspGates(gripper, approach, max_body, max_sweep, nms_translation, nms_rotation, nms_symmetric, top_k,
+                       support, support_margin, max_approach_tilt).check()
     rows = propose_grasps(model_or_scene, mask, scale=scale, min_weight=min_weight, **propose)
     s = float(scale)
     lengths = (nonneg("depth_base", depth_base) * s, nonneg("finger_width", finger_width) * s,
                nonneg("band", band) * s)
-    mc = math.inf if max_collision is None else float(max_collision)
-    if math.isnan(mc):
-        raise ValueError("max_collision must not be NaN")
-    res = contacts(*model_points(model_or_scene, mask), rows, *lengths, mu, min_weight, None)
+    mc = limit("max_collision", max_collision)
+    obj = model_points(model_or_scene, mask)
+    whole = obj if mask is None else model_points(model_or_scene, None)
+    res = contacts(*obj, rows, *lengths, mu, min_weight, None)
     if mask is not None:
-        whole = contacts(*model_points(model_or_scene, None), rows, *lengths, mu, min_weight, None)
-        res.collision_weight = whole.collision_weight
+        res.collision_weight = contacts(*whole, rows, *lengths, mu, min_weight, None).collision_weight
     res.feasible = res.feasible & (res.collision_weight.double() <= mc)
-    if gripper is not None:
-        pts, _, w = model_points(model_or_scene, None)
-        apply_clearance(res, pts, w, rows, gripper, s, approach, min_weight, max_body, max_sweep)
-    apply_support(res, rows, gripper, support, s, approach, support_margin, max_approach_tilt)
-    if nms_translation is not None:
-        return rows, res, apply_nms(res, rows, nms_translation, nms_rotation, nms_symmetric, s, top_k)
-    return rows, res, filter_grasps(rows, res)
+    return rows, res, apply_gates(gates, res, rows, s, min_weight, lambda: (whole[0], whole[2]))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -242,26 +224,13 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                     help="up direction, world frame; with --support-plane it only orients the fitted plane, whose "
                          "normal then is the proposer's up")
     ap.add_argument("--max-width", type=float, default=MAX_WIDTH, help="gripper opening, grasp units")
-    ap.add_argument("--mu", type=float, default=MU, help="friction coefficient")
-    ap.add_argument("--min-opacity", type=float, default=MIN_WEIGHT, help="a Gaussian takes part above it")
-    ap.add_argument("--max-collision", type=float, default=None, help="limit on the opacity inside the fingers")
-    add_clearance_options(ap)
-    add_nms_options(ap)
-    add_support_options(ap)
+    add_grasp_options(ap)
     ap.add_argument("--out", required=True, help="output .npy: feasible rows by score, world frame (scene frame "
                                                  "without --transform-json: the two are the same then)")
     ap.add_argument("--report", default=None, help="output .npz: every candidate (scene frame) and its outputs")
     a = ap.parse_args(argv)
     check_object_options(ap, a, "required")
-    for name in ("mu", "min_opacity"):
-        v = getattr(a, name)
-        if not (math.isfinite(v) and v >= 0.0):
-            ap.error(f"--{name.replace('_', '-')} must be finite and >= 0, got {v}")
-    if a.max_collision is not None and math.isnan(a.max_collision):
-        ap.error("--max-collision must not be NaN")
-    check_clearance_options(ap, a)
-    check_nms_options(ap, a)
-    check_support_options(ap, a)
+    check_grasp_options(ap, a)
     if a.max_seeds < 1:
         ap.error(f"--max-seeds must be >= 1, got {a.max_seeds}")
     try:
@@ -278,23 +247,15 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                 raise ValueError(f"transform_matrix must be 3x4 or 4x4, got {matrix.shape}")
             check_rotation(matrix[:3, :3], "matrix rotation")
         up = np.asarray(a.up, dtype=np.float64) if matrix is None else matrix[:3, :3] @ np.asarray(a.up)
-        from .interop import load_checkpoint
-        scene, mlp_state, _ = load_checkpoint(a.ckpt)
-        scene = scene.to(torch.device("cuda"))
+        scene, mlp_state = load_scene(a.ckpt)
         a.support_up = up
         mask = object_mask(a, scene, mlp_state, matrix, scale)
         plane = support_option_plane(a, scene, mask, scale, up)
         if plane is not None:
             up = plane.normal                # the table's own normal, not the command line's guess
-        tilt = None if a.max_approach_tilt is None else math.radians(a.max_approach_tilt)
-        rows, res, keep = grasp_object(scene, mask, scale=scale, mu=a.mu, min_weight=a.min_opacity,
-                                       max_collision=a.max_collision, gripper=gripper, approach=a.approach,
-                                       max_body=a.max_body_collision, max_sweep=a.max_sweep_collision,
-                                       nms_translation=a.nms_translation,
-                                       nms_rotation=math.radians(a.nms_rotation),
-                                       nms_symmetric=not a.nms_no_symmetry, top_k=a.top_k, max_seeds=a.max_seeds,
-                                       num_approach=a.num_approach, up=up, max_width=a.max_width, support=plane,
-                                       support_margin=a.support_margin, max_approach_tilt=tilt)
+        rows, res, keep = grasp_object(scene, mask, scale=scale, gripper=gripper, max_seeds=a.max_seeds,
+                                       num_approach=a.num_approach, up=up, max_width=a.max_width,
+                                       **grasp_gate_kwargs(a, plane))
     except (KeyError, ValueError, OSError) as exc:
         raise SystemExit(f"error: {exc}") from exc
     rows_np = rows.cpu().numpy()

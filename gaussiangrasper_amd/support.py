@@ -340,7 +340,7 @@ def label_model(model_or_scene, plane: SupportPlane, min_weight: float = 0.0) ->
 # command line
 # ------------------------------------------------------------------------------------------------
 def main(argv: Optional[Sequence[str]] = None) -> int:
-    from ._cli import add_object_options, check_object_options, object_mask
+    from ._cli import add_object_options, check_object_options, load_scene, object_mask
     from .frames import check_rotation, load_transform_json
     ap = argparse.ArgumentParser(prog="python -m gaussiangrasper_amd.support",
                                  description="Fit the support plane (the table) of a checkpoint's Gaussians, around "
@@ -380,9 +380,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         up = None
         if a.up is not None:
             up = np.asarray(a.up, dtype=np.float64) if matrix is None else matrix[:3, :3] @ np.asarray(a.up)
-        from .interop import load_checkpoint
-        scene, mlp_state, _ = load_checkpoint(a.ckpt)
-        scene = scene.to(torch.device("cuda"))
+        scene, mlp_state = load_scene(a.ckpt)
         mask = object_mask(a, scene, mlp_state, matrix, scale)
         plane = support_plane(scene, mask, dist=a.dist, scale=scale, num_hypotheses=a.hypotheses, up=up,
                               max_tilt=None if a.max_tilt is None else math.radians(a.max_tilt),

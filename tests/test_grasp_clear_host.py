@@ -295,7 +295,7 @@ def test_grasp_object_without_a_gripper_makes_no_clearance_call(monkeypatch):
     monkeypatch.setattr(grasp_propose, "propose_grasps", lambda *a, **k: rows)
     monkeypatch.setattr(grasp_propose, "model_points", lambda *a, **k: (torch.zeros(1, 3),) * 2 + (torch.zeros(1),))
     monkeypatch.setattr(grasp_propose, "contacts", lambda *a, **k: res)
-    monkeypatch.setattr(grasp_propose, "apply_clearance", refuse)
+    monkeypatch.setattr(grasp, "apply_clearance", refuse)
     monkeypatch.setattr(grasp, "clearance", refuse)
     got_rows, got, keep = grasp_propose.grasp_object(object(), None)
     assert got_rows is rows and got.clearance is None and keep.tolist() == [0, 2]

@@ -224,11 +224,10 @@ def _refuse(*a, **k):
 
 def _spy(monkeypatch):
     """every way to an NMS call raises _Called"""
-    from gaussiangrasper_amd import _lib, grasp, grasp_propose
+    from gaussiangrasper_amd import _lib, grasp
     monkeypatch.setattr(_lib.load(), "gg_grasp_nms", _refuse)
     monkeypatch.setattr(grasp, "nms", _refuse)
     monkeypatch.setattr(grasp, "apply_nms", _refuse)
-    monkeypatch.setattr(grasp_propose, "apply_nms", _refuse)
 
 
 def _contacts():
