@@ -93,13 +93,15 @@ def normals_literal(depth, fx, fy, c2w):
     return np.dot(c2w[:3, :3], nu.reshape(-1, 3).T).T.reshape((h, w, 3))
 
 
-def knn(points, k=3, chunk=512):
+def knn(points, k=3, chunk=512, index=False):
     """Brute force: per point the k smallest (sqrt(((dx dx + dy dy) + dz dz)) fp64, index) over j != i, the distance
-    rounded to fp32.  Returns (dist (N, k) float32, sorted fp64 squared distances (N, k))."""
+    rounded to fp32.  Returns (dist (N, k) float32, sorted fp64 squared distances (N, k)) and, with `index`, the
+    indices (N, k) int64 of the k smallest (squared distance, index) pairs in that order: gg_knn's tie rule."""
     x = np.asarray(points, dtype=np.float32).astype(np.float64)
     n = x.shape[0]
     d_out = np.empty((n, k), np.float32)
     s_out = np.empty((n, k))
+    i_out = np.empty((n, k), np.int64)
     for a in range(0, n, chunk):
         b = min(n, a + chunk)
         dx = x[a:b, None, 0] - x[None, :, 0]
@@ -110,7 +112,14 @@ def knn(points, k=3, chunk=512):
         part = np.sort(np.partition(s, k - 1, axis=1)[:, :k], axis=1)
         s_out[a:b] = part
         d_out[a:b] = np.sqrt(part).astype(np.float32)
-    return d_out, s_out
+        if index:
+            # every pair up to the k-th distance (all of its ties), sorted by (row, squared distance, index)
+            rr, cc = np.nonzero(s <= part[:, k - 1:k])
+            order = np.lexsort((cc, s[rr, cc], rr))
+            rr, cc = rr[order], cc[order]
+            first = np.searchsorted(rr, np.arange(b - a))
+            i_out[a:b] = cc[first[:, None] + np.arange(k)]
+    return (d_out, s_out, i_out) if index else (d_out, s_out)
 
 
 def qvec2rotmat(q):

@@ -109,3 +109,44 @@ def test_sh_constants_match_in_tree_magnitudes():
         0.9461746957575601, 0.6690465435572892, 0.10578554691520431, 0.47308734787878004,
         0.6258357354491761)})
     assert mags == in_tree
+
+
+def test_sizes_past_the_first_pass_follow_the_kernels_constants():
+    """The tests that cross a kernel's second pass (PARITY.md "Sizes past the first pass") took their sizes from these
+    constants of csrc/.  If one is retuned, the sizes named in the message turn back into first-pass sizes: derive
+    them again from the new value."""
+    csrc = os.path.join(ROOT, "gaussiangrasper_amd", "csrc")
+    read = lambda name: open(os.path.join(csrc, name)).read()
+
+    def define(src, name):
+        m = re.search(r"^#define\s+%s\s+(\d+)\b" % name, src, flags=re.M)
+        assert m, f"#define {name} not found"
+        return int(m.group(1))
+
+    losses, register, support = read("losses.hip"), read("register.hip"), read("support_plane.hip")
+    project, prep = read("project.hip"), read("prep_common.h")
+    # gg_mlp_bwd: tiles of MB_ROWS rows on a grid of at most 2048 workgroups
+    cap = re.search(r"ntiles < (\d+) \? ntiles : (\d+)", losses)
+    assert cap and cap.group(1) == cap.group(2), "gg_mlp_bwd's grid cap not found"
+    assert (define(losses, "MB_ROWS"), int(cap.group(1))) == (16, 2048), \
+        "tests/test_mlp_losses.py LATTICE_SHAPES: rows = MB_ROWS * cap + 1 and 2 * MB_ROWS * cap, MB_ROWS -/+ 1"
+    # gg_icp_step: rows of 256 source points, RG_FIN_THREADS / (2 RG_SUMS) chains
+    assert "blockIdx.x * 256 + threadIdx.x" in register
+    chains = define(register, "RG_FIN_THREADS") // (2 * define(read("register_math.h"), "RG_SUMS"))
+    assert chains == 16, \
+        "tests/test_register_gpu.py test_icp_step_past_one_row_per_chain: M = 256 chains, 256 chains + 1, > 512 chains"
+    # gg_plane_classify: rows of 256 SP_CL_ITEMS points, SP_FIN_THREADS / SP_SUMS chains
+    assert "blockIdx.x * (256 * SP_CL_ITEMS)" in support
+    assert "#define SP_FIN_CHAINS (SP_FIN_THREADS / SP_SUMS)" in support
+    chains = define(support, "SP_FIN_THREADS") // define(support, "SP_SUMS")
+    assert (chains, 256 * define(support, "SP_CL_ITEMS")) == (16, 1024), \
+        "tests/test_support_plane_gpu.py test_classify_is_exact_on_the_lattice: n = 1024 chains, + 1, 2048 chains + 1"
+    # pose_finish_kernel: rounds of 12 GG_POSE_FIN_ROWS rows of 256 Gaussians
+    unroll = re.search(r"r \+= (\d+) \* GG_POSE_FIN_ROWS", project)
+    assert unroll and f"float4 v[{unroll.group(1)}];" in project, "pose_finish_kernel's unroll not found"
+    assert int(unroll.group(1)) * define(project, "GG_POSE_FIN_ROWS") == 2016, \
+        "tests/test_pose_grad_gpu.py FIRST_ROUND, test_pose_finish_past_its_first_round: N = 256 rows per round + 3000"
+    # the grid sort's scan: tiles of PP_TILE cells, PP_TILE tile sums to a pass of pp_scan_single_kernel
+    assert "#define PP_TILE (PP_THREADS * PP_ITEMS)" in prep
+    assert define(prep, "PP_THREADS") * define(prep, "PP_ITEMS") == 1024, \
+        "tests/test_prepare_gpu.py HOSTILE_GRIDS 'scan carry': more than PP_TILE^2 cells"

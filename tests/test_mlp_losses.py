@@ -1,10 +1,14 @@
 """SURVEY 8f-2, second half: backward of the fea_up MLP and the cosine-similarity loss.  Both are
 pinnable: the reference code is plain torch (nerfstudio/models/gaussian_splatting.py:113-118,198-213),
 restated here in two lines each and differentiated by torch autograd."""
+import functools
+
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+import mlp_ref
 
 
 def ref_cosine_similarity_loss(e1, e2):          # gaussian_splatting.py:113-118
@@ -73,7 +77,12 @@ gpu = pytest.mark.gpu
 
 @gpu
 @pytest.mark.parametrize("p,in_dim,out_dim", [(1, 32, 512), (1000, 32, 512), (777, 8, 96), (4099, 64, 512),
-                                              (300, 128, 512)])
+                                              (300, 128, 512),
+                                              # output widths that clip the eight output groups (ob, o_hi): 1 and 7
+                                              # leave most groups empty, 37 is no multiple of 8 or 32; 1024 outputs
+                                              # with 128 inputs are the largest LDS request, 94 208 bytes
+                                              (300, 16, 1), (300, 32, 7), (300, 32, 37), (64, 64, 1024),
+                                              (64, 128, 1024)])
 def test_gpu_mlp_backward_vs_oracle_and_autograd(oracle, p, in_dim, out_dim):
     from gaussiangrasper_amd.mlp import mlp_forward
     x, w1, b1, w2, b2, g = (t.float() for t in _mlp_case(p, in_dim, out_dim, seed=3 * p))
@@ -88,6 +97,81 @@ def test_gpu_mlp_backward_vs_oracle_and_autograd(oracle, p, in_dim, out_dim):
         scale = max(1.0, np.abs(ref).max())
         assert np.abs(got - ref).max() <= 3e-5 * scale, name          # fp32 sums vs fp64 autograd
         assert np.abs(got - o).max() <= 3e-5 * scale, name            # and vs the oracle
+
+
+# The lattice cases (tests/mlp_ref.py): fp32 is exact on them, so gg_mlp_bwd must give the reference's bits whatever
+# the order of its tiles and atomics.  32769 rows are 2049 tiles of 16 on a grid capped at 2048 workgroups: workgroup 0
+# takes a second tile that holds one row.  65536 rows: every workgroup takes exactly two tiles (and in_dim 16, and 96
+# outputs in eighths of 12).  15 / 16 / 17 rows: a ragged tile, a full one, one row into a second workgroup.
+LATTICE_SHAPES = [(32769, 32, 512), (65536, 16, 96), (15, 8, 32), (16, 8, 32), (17, 8, 32)]
+
+
+@functools.lru_cache(maxsize=None)
+def _lattice_autograd(shape):
+    """The five gradients of the lattice case of `shape` by fp64 torch autograd, as read-only numpy arrays with +0
+    for every zero; computed once per process."""
+    (x, w1, b1, w2, b2, g), _ = mlp_ref.lattice_reference(*shape)
+    leaves = [torch.from_numpy(a.copy()).requires_grad_(True) for a in (x, w1, b1, w2, b2)]
+    ref_mlp(*leaves).backward(torch.from_numpy(g.copy()))
+    out = tuple(t.grad.numpy() + 0.0 for t in leaves)
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+@pytest.mark.parametrize("shape", LATTICE_SHAPES, ids=str)
+def test_mlp_backward_lattice_case_is_exact_in_fp32(shape):
+    """The condition under which the GPU test below may ask for bits: every term of every gradient element is a
+    multiple of a unit u, the absolute values of an element's terms sum to less than 2^24 u, and an fp32 evaluation
+    gives the same bits in two row orders, those of fp64 autograd."""
+    (x, w1, b1, w2, b2, g), grads = mlp_ref.lattice_reference(*shape)
+    cond, h = mlp_ref.condition(x, w1, b1, w2, g)
+    for name, (unit, abs_sum) in cond.items():
+        print(f"lattice {shape} {name}: unit {unit}, largest sum of |terms| {abs_sum / unit:.0f} units (2^24 = "
+              f"16777216)")
+        assert abs_sum < 2.0 ** 24 * unit, name
+    for name, a in zip(("v_x", "v_w1", "v_b1", "v_w2", "v_b2"), grads):
+        assert mlp_ref.is_multiple(a, cond[name][0]) and np.abs(a).max() <= cond[name][1], name
+        assert a.any(), name
+    # pre-activations exactly at 0, with a cotangent arriving there: relu'(0) = 0 (hp > 0) decides those gradients
+    at_zero = h == 0.0
+    arriving = (g @ w2)[at_zero]
+    print(f"lattice {shape}: {int(at_zero.sum())} of {h.size} pre-activations are 0, {int((arriving != 0).sum())} "
+          f"of them with a non-zero dL/dh")
+    assert at_zero.sum() >= h.size // 100 and (arriving != 0).sum() >= at_zero.sum() // 10
+    auto = _lattice_autograd(shape)
+    perm = np.random.default_rng(1).permutation(shape[0])
+    fwd = mlp_ref.backward(x, w1, b1, w2, g, dtype=np.float32)
+    rev = mlp_ref.backward(x[perm], w1, b1, w2, g[perm], dtype=np.float32)
+    rev = (rev[0][np.argsort(perm)],) + rev[1:]
+    for name, a, b, c, d in zip(("v_x", "v_w1", "v_b1", "v_w2", "v_b2"), fwd, rev, grads, auto):
+        assert a.dtype == np.float32 and a.tobytes() == b.tobytes(), name
+        assert a.tobytes() == c.astype(np.float32).tobytes() == d.astype(np.float32).tobytes(), name
+        assert np.array_equal(c, d), name
+
+
+@gpu
+@pytest.mark.parametrize("shape", LATTICE_SHAPES, ids=str)
+def test_gpu_mlp_backward_is_exact_on_the_lattice(monkeypatch, shape):
+    from gaussiangrasper_amd import _lib, mlp as M
+    (x, w1, b1, w2, b2, g), _ = mlp_ref.lattice_reference(*shape)
+    want = _lattice_autograd(shape)
+    lib, calls = _lib.load(), []
+    native = lib.gg_mlp_bwd
+
+    def spy(rows, *args):
+        calls.append(rows)
+        return native(rows, *args)
+    monkeypatch.setattr(lib, "gg_mlp_bwd", spy)
+    assert shape[0] <= M.NATIVE_BWD_MAX_ROWS
+    leaves = [torch.tensor(a, dtype=torch.float32, device=DEV).requires_grad_(True) for a in (x, w1, b1, w2, b2)]
+    M.mlp_forward(*leaves).backward(torch.tensor(g, dtype=torch.float32, device=DEV))
+    assert calls == [shape[0]]                                  # the native kernel ran, once
+    for name, t, r in zip(("v_x", "v_w1", "v_b1", "v_w2", "v_b2"), leaves, want):
+        got, ref = t.grad.cpu().numpy(), r.astype(np.float32)
+        wrong = int((got.view(np.uint32) != ref.view(np.uint32)).sum())
+        print(f"mlp_bwd lattice {shape} {name}: {wrong} of {ref.size} elements differ from fp64 autograd")
+        assert got.dtype == np.float32 and got.shape == ref.shape and wrong == 0, name
 
 
 @gpu

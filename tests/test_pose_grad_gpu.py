@@ -58,7 +58,7 @@ def _projmat(view):
 # ------------------------------------------------------------------------------------------------------------------
 # the kernels against the float64 reference
 # ------------------------------------------------------------------------------------------------------------------
-def _kernel_case(n, h, w, spread, smul, seed):
+def _kernel_case(n, h, w, spread, smul, seed, zero_rows=None):
     from gaussiangrasper_amd import _lib, ops as P
     lib = _lib.load()
     sc = make_scene(n, feature_dim=4, config_index=seed)
@@ -72,6 +72,8 @@ def _kernel_case(n, h, w, spread, smul, seed):
                                                                       v.cy, h, w, v.tile_bounds)
     g = torch.Generator(device="cpu").manual_seed(seed)
     rec = torch.randn(n, 16, generator=g).to(DEV)                 # the pair backward's 16-float records
+    if zero_rows is not None:
+        rec[zero_rows] = 0.0                                      # no cotangent: these Gaussians add 0 to every sum
     v_depth = rec[:, 9].contiguous()
     return lib, v, means, scales, quats, vm, pm, radii, conics, rec, v_depth
 
@@ -134,6 +136,51 @@ def test_pose_kernels_against_the_fp64_reference(n, h, w, spread, smul):
         err = (got.double() - want["v_" + key]).abs()
         bound = 1e-5 * want["abs_" + key] + 1e-30
         assert (err <= bound).all(), (key, err.max().item(), (err / bound).max().item())
+    assert (got_p.reshape(4, 4)[2] == 0).all()
+
+
+# pose_finish_kernel takes the slab's rows (256 Gaussians each) 12 x GG_POSE_FIN_ROWS = 2016 to a round
+FIRST_ROUND = 2016 * 256
+
+
+@pytest.mark.parametrize("planted", ["second round", "first round"])
+def test_pose_finish_past_its_first_round(planted):
+    """N = 516 096 + 3000 on the smallest image: 2028 slab rows, the last 12 of them in pose_finish_kernel's second
+    round.  1e-5 of the absolute sum would not notice a few lost rows among 2000, so the cotangents are planted: with
+    those of the first 516 096 Gaussians zero, every non-zero row is in the second round and the bound is 1e-5 of
+    those rows' own absolute sum; the complement (the last 3000 zero) pins the first round's 12-way unroll with all
+    twelve rows of every lane live."""
+    n, h, w, spread, smul = FIRST_ROUND + 3000, 16, 32, 1.0, 12.0
+    live = slice(FIRST_ROUND, n) if planted == "second round" else slice(0, FIRST_ROUND)
+    dead = slice(0, FIRST_ROUND) if planted == "second round" else slice(FIRST_ROUND, n)
+    lib, v, means, scales, quats, vm, pm, radii, conics, rec, v_depth = _kernel_case(n, h, w, spread, smul, seed=11,
+                                                                                     zero_rows=dead)
+    vis = radii > 0
+    rows = torch.zeros((n + 255) // 256 * 256, dtype=torch.bool, device=DEV)
+    rows[:n] = vis
+    rows[dead] = False
+    rows = rows.reshape(-1, 256).any(dim=1)                       # slab rows that hold a visible, live Gaussian
+    print(f"pose finish, {planted}: {int(vis[live].sum())} visible live Gaussians in {int(rows.sum())} slab rows of "
+          f"{rows.numel()}")
+    assert not rec[dead].any() and not v_depth[dead].any()
+    if planted == "second round":
+        assert int(vis[live].sum()) > 100 and not rows[:2016].any() and rows[2016:].any()
+    else:                                                         # each of the 12 loads of a lane has live rows
+        assert rows[:2016].reshape(12, 168).any(dim=1).all() and not rows[2016:].any()
+    got_v, got_p = _pose_bwd(lib, n, v, means, scales, quats, vm, pm, radii, conics, rec, v_depth)
+    again_v, again_p = _pose_bwd(lib, n, v, means, scales, quats, vm, pm, radii, conics, rec, v_depth)
+    _, gv, gp = _view_bwd(lib, True, n, v, means, scales, quats, vm, pm, radii, conics, rec)
+    torch.cuda.synchronize()
+    assert torch.equal(gv, got_v) and torch.equal(gp, got_p)                   # the two entries: the same bits
+    assert torch.equal(again_v, got_v) and torch.equal(again_p, got_p)         # two calls: the same bits
+    want = ref.pose_grads(means, scales, 1.0, quats, vm, pm, v.fx, v.fy, v.cx, v.cy, h, w, vis, rec[:, 0:2], v_depth,
+                          rec[:, 2:5])
+    for got, key in ((got_v.reshape(3, 4), "viewmat"), (got_p.reshape(4, 4), "projmat")):
+        err = (got.double() - want["v_" + key]).abs()
+        bound = 1e-5 * want["abs_" + key] + 1e-30
+        print(f"pose finish, {planted}, {key}: worst error {(err / bound).max().item():.3e} of its bound")
+        assert (err <= bound).all(), (key, err.max().item(), (err / bound).max().item())
+        assert want["abs_" + key].max() > 0
     assert (got_p.reshape(4, 4)[2] == 0).all()
 
 

@@ -4,6 +4,8 @@ pixels exactly on every window bound, in any batching; the subsample law; normal
 non-finite depths on non-square frames; kNN distances on uniform, clustered, tied, duplicated, outlier, identical,
 planar and minimal clouds, every index reproducing its distance; a worst-case time guard; the plugin's device kNN;
 and the command-line tool end to end, twice, byte for byte."""
+import ctypes
+import functools
 import os
 import time
 
@@ -153,26 +155,100 @@ def _clouds():
     return {k: v.astype(np.float32) for k, v in out.items()}
 
 
+@functools.lru_cache(maxsize=None)
+def _knn_ref(name):
+    """(cloud, fp32 distances, fp64 squared distances, indices by the tie rule) of a cloud of _clouds() for k = 8 (3
+    for N = 4), brute force, computed once per process and read-only; the first k columns are the answer for k."""
+    x = _clouds()[name]
+    out = (x,) + R.knn(x, 8 if x.shape[0] > 8 else 3, index=True)
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+def _check_knn(name, k, dist, idx, what):
+    """dist: the reference's bits.  idx: a neighbour set that reproduces its distances and, for every point without
+    a neighbour at distance 0, exactly the k smallest (squared distance, index) pairs."""
+    x, ref_d, ref_s, ref_i = _knn_ref(name)
+    n = x.shape[0]
+    assert dist.dtype == np.float32 and idx.dtype == np.int64 and dist.shape == idx.shape == (n, k)
+    assert np.array_equal(dist.view(np.uint32), ref_d[:, :k].view(np.uint32)), (name, k, what)
+    assert ((idx >= 0) & (idx < n)).all() and (idx != np.arange(n)[:, None]).all()
+    assert all(len(set(r)) == k for r in idx[:: max(1, n // 2000)])
+    xd = x.astype(np.float64)
+    d = xd[idx] - xd[:, None, :]
+    again = np.sqrt((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]).astype(np.float32)
+    assert np.array_equal(again.view(np.uint32), dist.view(np.uint32)), (name, k, what)
+    apart = ref_s[:, 0] > 0.0
+    assert np.array_equal(idx[apart], ref_i[apart, :k]), (name, k, what)
+    return int(apart.sum())
+
+
 @gpu
 @pytest.mark.parametrize("name", list(_clouds()))
 def test_knn_bit_exact(name):
     from gaussiangrasper_amd.prepare import knn_distances
     x = _clouds()[name]
     ks = (3, 1, 8) if x.shape[0] > 8 else (3,)
-    ref_all, _ = R.knn(x, max(ks))
     for k in ks:
         dist, idx = knn_distances(torch.from_numpy(x).cuda(), k)
-        dist, idx = dist.cpu().numpy(), idx.cpu().numpy()
-        ref = ref_all[:, :k]
-        assert dist.dtype == np.float32 and idx.dtype == np.int64 and dist.shape == (x.shape[0], k)
-        assert np.array_equal(dist.view(np.uint32), ref.view(np.uint32)), (name, k)
-        n = x.shape[0]
-        assert ((idx >= 0) & (idx < n)).all() and (idx != np.arange(n)[:, None]).all()
-        assert all(len(set(r)) == k for r in idx[:: max(1, n // 2000)])
-        xd = x.astype(np.float64)
-        d = xd[idx] - xd[:, None, :]
-        again = np.sqrt((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]).astype(np.float32)
-        assert np.array_equal(again.view(np.uint32), dist.view(np.uint32)), name
+        apart = _check_knn(name, k, dist.cpu().numpy(), idx.cpu().numpy(), "fitted grid")
+        if name == "lattice ties":                         # every neighbour shell is a tie: the rule decides them all
+            ref_s = _knn_ref(name)[2]
+            assert apart == x.shape[0] and (ref_s[:, 0] == ref_s[:, 1]).all()
+
+
+def _knn_on_grid(x, k, grid, dims):
+    """gg_knn on a caller's grid (lower corner and cell edge, cells per axis) -> (dist, idx) as numpy"""
+    from gaussiangrasper_amd import _lib
+    lib = _lib.load()
+    n = x.shape[0]
+    xd = torch.from_numpy(np.ascontiguousarray(x, np.float32)).cuda()
+    grid_c, dims_c = (ctypes.c_double * 4)(*grid), (ctypes.c_int32 * 3)(*dims)
+    need = lib.gg_knn_workspace(n, dims_c)
+    assert need > 0
+    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+    dist = torch.full((n, k), -1.0, dtype=torch.float32, device="cuda")
+    idx = torch.full((n, k), -1, dtype=torch.int64, device="cuda")
+    P = ctypes.c_void_p
+    st = lib.gg_knn(n, P(xd.data_ptr()), k, grid_c, dims_c, P(dist.data_ptr()), P(idx.data_ptr()), P(ws.data_ptr()),
+                    need, P(torch.cuda.current_stream().cuda_stream))
+    assert st == 0, lib.gg_last_error()
+    torch.cuda.synchronize()
+    return dist.cpu().numpy(), idx.cpu().numpy()
+
+
+# "any grid gives the same result" (include/gg_raster.h): cloud, (lower corner, cell edge), cells per axis
+HOSTILE_GRIDS = {
+    # every point of the 22^3 lattice lies exactly on a cell face: the search's face bound b is 0
+    "cell faces": ("lattice ties", (0.0, 0.0, 0.0, 0.25), (22, 22, 22)),
+    # one cell, and a grid that misses the cloud (everything clamped into one corner cell): the quadratic walk,
+    # 10 648^2 = 1.1e8 distances
+    "one cell": ("lattice ties", (0.0, 0.0, 0.0, 1.0), (1, 1, 1)),
+    "misses the cloud": ("lattice ties", (50.0, 50.0, 50.0, 0.001), (40, 30, 20)),
+    # flat: one column of 4096 thin cells, a lattice layer in every 128th of them
+    "flat": ("lattice ties", (0.0, 0.0, 0.0, 1.0 / 512.0), (1, 1, 4096)),
+    # 128 x 128 x 65 = 1 064 960 cells are 1040 tile sums: pp_scan_single_kernel carries across its first 1024;
+    # the upper half of the unit cube is clamped into the top layer
+    "scan carry": ("uniform", (0.0, 0.0, 0.0, 1.0 / 128.0), (128, 128, 65)),
+}
+
+
+@gpu
+@pytest.mark.parametrize("grid_name", list(HOSTILE_GRIDS))
+def test_knn_on_any_grid(grid_name):
+    from gaussiangrasper_amd.prepare import knn_distances
+    name, grid, dims = HOSTILE_GRIDS[grid_name]
+    x, _, ref_s, _ = _knn_ref(name)
+    assert (ref_s[:, 0] > 0.0).all()                           # no zero distances: the indices are pinned everywhere
+    if grid_name == "scan carry":
+        assert -(-dims[0] * dims[1] * dims[2] // 1024) > 1024 and (x[:, 2] > 65.0 / 128.0).sum() > 5000
+    for k in (1, 3, 8):
+        dist, idx = _knn_on_grid(x, k, grid, dims)
+        assert _check_knn(name, k, dist, idx, grid_name) == x.shape[0]
+        fit_d, fit_i = knn_distances(torch.from_numpy(x).cuda(), k)
+        assert np.array_equal(dist.view(np.uint32), fit_d.cpu().numpy().view(np.uint32))
+        assert np.array_equal(idx, fit_i.cpu().numpy())
 
 
 @gpu

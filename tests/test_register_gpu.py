@@ -27,17 +27,17 @@ def scene():
     return s
 
 
-def gpu_frames(P, I, radius):
+def gpu_frames(P, I, radius, grid=None):
     from gaussiangrasper_amd.register import cloud_frames
-    t = cloud_frames(dev32(P), dev32(I), radius)
+    t = cloud_frames(dev32(P), dev32(I), radius, grid=grid)
     torch.cuda.synchronize()
     return (t.normals.double().cpu().numpy(), t.gradients.double().cpu().numpy(), t.count.cpu().numpy(),
             t.valid.cpu().numpy().astype(bool))
 
 
-def check_frames(P, I, radius, ref=None, what="", max_excluded=0.0):
+def check_frames(P, I, radius, ref=None, what="", max_excluded=0.0, grid=None):
     P, I = R.f32(P), R.f32(I)
-    nrm, grad, count, valid = gpu_frames(P, I, radius)
+    nrm, grad, count, valid = gpu_frames(P, I, radius, grid)
     rn, rg, rc, rv, gap = ref if ref is not None else R.cloud_frames(P, I, radius)
     assert np.array_equal(count, rc) and np.array_equal(valid, rv)
     assert np.isnan(nrm[~rv]).all() and (grad[~rv] == 0).all()
@@ -156,6 +156,100 @@ def test_icp_step_against_one_point(m):
     n = np.array([0.6, 0.0, 0.8])
     check_step(S, rng.uniform(0, 1, m), [[0.001, -0.002, 0.003]], [0.4], [n], [[0.3, -0.2, 0.1]], [1],
                R.rigid([0.01, 0.02, -0.01], [0.001, 0.0, -0.001]), 0.03, 0.5, what="one target")
+
+
+@pytest.fixture(scope="module")
+def long_source():
+    """8449 source points (34 slab rows of 256) of the scene's surface, seen from the frame moved by the inverse of
+    TRUE_MOTION as R.scene()'s are; prefixes of it are the shorter sources."""
+    S0, Is = R.surface(8449, 3)
+    Gi = np.linalg.inv(R.TRUE_MOTION)
+    S = R.f32(S0 @ Gi[:3, :3].T + Gi[:3, 3])
+    S.setflags(write=False), Is.setflags(write=False)
+    return S, Is
+
+
+@pytest.mark.parametrize("m", [4096, 4097, 8449])
+def test_icp_step_past_one_row_per_chain(scene, long_source, m):
+    # rg_finish_kernel sums the slab's rows by 16 chains: 16, 17 and 34 rows give chain 0 one, two and three rows
+    S, Is = long_source[0][:m], long_source[1][:m]
+    sums, _, _ = check_step(S, Is, scene["P"], scene["I"], scene["nrm32"], scene["grad32"], scene["valid"],
+                            R.TRUE_MOTION @ START, 0.01, 0.968, what="scene, long source")
+    assert sums[27] > 0.9 * m                        # the rows past the first pass hold inliers
+
+
+@pytest.mark.parametrize("m", [1, 257, 3000, 8449])
+def test_icp_step_without_corr_and_abs_sums(scene, long_source, m):
+    # rg_step_kernel<false> / rg_finish_kernel<false> with corr == NULL is what colored_icp runs: the same terms
+    # summed in the same order, so the same bits
+    from gaussiangrasper_amd.register import icp_step
+    S, Is = dev32(long_source[0][:m]), dev32(long_source[1][:m])
+    target = make_target(scene["P"], scene["I"], scene["nrm32"], scene["grad32"], scene["valid"])
+    T = R.TRUE_MOTION @ START
+    full = icp_step(S, Is, target, T, 0.01, 0.968, corr=True, abs_sums=True)
+    lean = icp_step(S, Is, target, T, 0.01, 0.968, corr=False, abs_sums=False)
+    assert lean.corr is None and lean.abs_sums is None
+    assert full.sums[27] == (full.corr.cpu().numpy() >= 0).sum() > 0.9 * m
+    assert lean.sums.tobytes() == full.sums.tobytes()
+
+
+def test_icp_step_workspace_across_source_sizes(scene, long_source):
+    # one StepWorkspace, one target and max_dist: a shorter source reuses the sort, a longer one grows the workspace
+    # and sorts again; every step equals a fresh call's
+    from gaussiangrasper_amd.register import StepWorkspace
+    target = make_target(scene["P"], scene["I"], scene["nrm32"], scene["grad32"], scene["valid"])
+    T = R.TRUE_MOTION @ START
+    st = StepWorkspace()
+    sizes = []
+    for m in (3000, 257, 8449, 3000):
+        S, Is = long_source[0][:m], long_source[1][:m]
+        kept = gpu_step(S, Is, target, T, 0.01, 0.968, state=st)
+        fresh = gpu_step(S, Is, target, T, 0.01, 0.968)
+        assert fresh[0][27] > 0.9 * m
+        assert kept[0].tobytes() == fresh[0].tobytes() and kept[1].tobytes() == fresh[1].tobytes()
+        assert np.array_equal(kept[2], fresh[2])
+        sizes.append(st.ws.numel())
+    assert sizes[0] == sizes[1] < sizes[2] == sizes[3]           # kept, kept, grown, kept
+
+
+# "any grid gives the same result" (include/gg_raster.h): one cell, and a grid that misses the cloud, which clamps
+# every point into one corner cell; (lower corner and cell edge, cells per axis) as cluster.cluster_grid returns them
+HOSTILE_GRIDS = {"one cell": (np.array([0.0, 0.0, 0.0, 1.0]), np.array([1, 1, 1], np.int32)),
+                 "misses the cloud": (np.array([50.0, 50.0, 50.0, 0.001]), np.array([40, 30, 20], np.int32))}
+
+
+@pytest.fixture(scope="module")
+def small_target():
+    """A 3000-point target and the restatement's frames of it, computed once and never changed."""
+    P, I = R.surface(3000, 4)
+    ref = R.cloud_frames(P, I, 0.02)
+    for v in (P, I) + ref:
+        v.setflags(write=False)
+    return P, I, ref
+
+
+@pytest.mark.parametrize("grid", list(HOSTILE_GRIDS))
+def test_cloud_frames_on_any_grid(small_target, grid):
+    # count and valid equal the restatement's; the fp64 sums follow slot order, so normals and gradients keep
+    # check_frames' bounds rather than bits
+    P, I, ref = small_target
+    check_frames(P, I, 0.02, ref=ref, what=f"3000 points, {grid}", grid=HOSTILE_GRIDS[grid])
+    assert ref[3].all() and ref[2].min() >= 4
+
+
+@pytest.mark.parametrize("grid", list(HOSTILE_GRIDS))
+def test_icp_step_on_any_grid(small_target, long_source, grid):
+    # the correspondent is the smallest (distance, index) pair and the sums have a fixed order: nothing depends on
+    # the slot order, so a caller's grid gives the fitted grid's correspondences and bytes
+    P, I, (nrm, grad, _, valid, _) = small_target
+    target = make_target(P, I, R.f32(nrm), R.f32(grad), valid)
+    S, Is, T = long_source[0][:257], long_source[1][:257], R.TRUE_MOTION @ START
+    fit = gpu_step(S, Is, target, T, 0.01, 0.968)
+    got = gpu_step(S, Is, target, T, 0.01, 0.968, grid=HOSTILE_GRIDS[grid])
+    print(f"icp_step {grid}: {int(fit[0][27])} of 257 source points have a correspondent")
+    assert fit[0][27] > 128
+    assert np.array_equal(got[2], fit[2])
+    assert got[0].tobytes() == fit[0].tobytes() and got[1].tobytes() == fit[1].tobytes()
 
 
 def test_icp_step_is_independent_of_the_target_order(scene):

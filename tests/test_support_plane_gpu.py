@@ -194,10 +194,11 @@ def test_consensus_across_point_chunks_and_hypothesis_chunks():
 # 3. classify
 # ------------------------------------------------------------------------------------------------
 @gpu
-@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 1023, 1024, 1025, 4099])
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 1023, 1024, 1025, 4099, 16384, 16385, 32769])
 def test_classify_is_exact_on_the_lattice(n):
     """plane z = 0, dist 2^-5: a quarter of the points lie exactly at +-dist, and they are "on".  Every term is a
-    multiple of 2^-14 below 2: the sums are exact in any order."""
+    multiple of 2^-14 below 2: the sums are exact in any order.  16384, 16385 and 32769 points are 16, 17 and 33 slab
+    rows: sp_finish_kernel's 16 chains take one, two and three rows."""
     pts, w = PR.lattice_scene(n, seed=100 + n)
     if n > 10:
         pts[3], pts[7, 1] = (np.inf, 0.0, 0.0), np.nan
