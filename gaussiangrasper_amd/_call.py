@@ -1,5 +1,5 @@
 """Device-call plumbing shared by every module that calls libgg_raster.so: which device, tensors and host arrays
-as the pointers the C ABI takes, the stream, workspaces, and the argument checks several callers make alike.
+as the pointers the C ABI takes, the stream, workspaces, grids, and the argument checks several callers make alike.
 Imports nothing from the package."""
 from __future__ import annotations
 
@@ -69,6 +69,20 @@ def stream(dev: torch.device):
 
 def workspace(nbytes: int, dev: torch.device) -> Tensor:
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
+
+
+def sized_workspace(nbytes: int, what: str, dev: torch.device) -> Tensor:
+    """The workspace a gg_*_workspace query sized.  0 bytes is the query's "out of range": ValueError(what)."""
+    if nbytes == 0:
+        raise ValueError(what)
+    return workspace(nbytes, dev)
+
+
+def grid_args(grid):
+    """(grid, dims) as grid.knn_grid and grid.cluster_grid return them -> (c_double[4], c_int32[3]) for the C ABI."""
+    g, dims = grid
+    return ((C.c_double * 4)(*np.asarray(g, dtype=np.float64).tolist()),
+            (C.c_int32 * 3)(*np.asarray(dims, dtype=np.int32).tolist()))
 
 
 def f32_rows(t: Tensor, name: str, width: Optional[int]) -> Tensor:

@@ -3,7 +3,7 @@ not every mug in the room plus speckle.  Two HIP calls (`gg_cluster_dbscan` and 
 csrc/cluster.hip); the contract is in include/gg_raster.h and PARITY.md "Object instances".  Labels are a pure
 function of the inputs and equal sklearn.cluster.DBSCAN's wherever no pair sits within rounding of eps.
 
-    cluster_grid       the grid gg_cluster_dbscan sorts into: prepare.knn_grid with cells of at least eps
+    cluster_grid       the grid gg_cluster_dbscan sorts into (grid.py): knn_grid with cells of at least eps
     dbscan             labels, core flags, neighbour counts and the number of clusters of a point set (Clusters)
     cluster_stats      per cluster: count, weight, weighted centroid, bounding box (ClusterStats)
     rank_instances     clusters above min_count / min_weight by descending weight (Instances); any device
@@ -15,7 +15,6 @@ function of the inputs and equal sklearn.cluster.DBSCAN's wherever no pair sits 
 from __future__ import annotations
 
 import argparse
-import ctypes
 import json
 import sys
 from dataclasses import dataclass
@@ -26,8 +25,9 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._call import (f32_rows, host_ptr, nonneg, positive, ptr as _ptr, require_hip as _require_hip,
-                    stream as _stream, workspace as _ws)
+from ._call import (f32_rows, grid_args, host_ptr, nonneg, positive, ptr as _ptr, require_hip as _require_hip,
+                    sized_workspace, stream as _stream)
+from .grid import active as _active, cluster_grid
 
 # This project's choices (PARITY.md "Object instances"); nobody has measured good values on a real checkpoint
 EPS_SCALE = 3.0              # eps = EPS_SCALE x the median 3rd-nearest-neighbour distance of the selection
@@ -78,28 +78,6 @@ class Instances:
 # ------------------------------------------------------------------------------------------------
 # device side
 # ------------------------------------------------------------------------------------------------
-def _active(points: Tensor, mask: Optional[Tensor]) -> Tensor:
-    a = torch.isfinite(points).all(dim=1)
-    return a if mask is None else a & (mask != 0)
-
-
-def cluster_grid(points: Tensor, eps: float, mask: Optional[Tensor] = None) -> Tuple[np.ndarray, np.ndarray]:
-    """The grid gg_cluster_dbscan sorts into: prepare.knn_grid fitted to the active points, with the cell edge raised
-    to at least eps (fewer cells over the same box).  Points outside it go to its border cells: the grid sets the
-    speed, never the result.  Returns (grid float64 [lo x, y, z, cell], dims int32 [3])."""
-    from .prepare import knn_grid
-    eps = positive("eps", eps)
-    pts = points[_active(points, mask)]
-    if pts.shape[0] == 0:
-        return np.array([0.0, 0.0, 0.0, eps]), np.ones(3, dtype=np.int32)
-    grid, dims = knn_grid(pts)
-    if grid[3] < eps:
-        ext = dims.astype(np.float64) * grid[3]
-        dims = np.maximum(1, np.ceil(ext / eps)).astype(np.int32)
-        grid = np.array([grid[0], grid[1], grid[2], eps], dtype=np.float64)
-    return grid, dims
-
-
 def dbscan(points: Tensor, eps: float, min_points: int = MIN_POINTS, mask: Optional[Tensor] = None,
            grid: Optional[Tuple[np.ndarray, np.ndarray]] = None) -> Clusters:
     """DBSCAN of `points` (N, 3) float32 on the HIP device (no CPU path) with radius eps and sklearn's min_samples
@@ -126,14 +104,10 @@ def dbscan(points: Tensor, eps: float, min_points: int = MIN_POINTS, mask: Optio
                    core=torch.empty(n, dtype=torch.uint8, device=dev),
                    neighbor_count=torch.empty(n, dtype=torch.int32, device=dev), num_clusters=0)
     if n > 0:
-        g, dims = cluster_grid(points, eps, mask) if grid is None else grid
-        grid_c = (ctypes.c_double * 4)(*np.asarray(g, dtype=np.float64).tolist())
-        dims_c = (ctypes.c_int32 * 3)(*np.asarray(dims, dtype=np.int32).tolist())
+        grid_c, dims_c = grid_args(cluster_grid(points, eps, mask) if grid is None else grid)
         lib = _lib.load()
-        nbytes = lib.gg_cluster_workspace(n, dims_c)
-        if nbytes == 0:
-            raise ValueError(f"{n} points on a grid of {list(dims_c)} cells is beyond gg_cluster_dbscan's limits")
-        ws = _ws(nbytes, dev)
+        ws = sized_workspace(lib.gg_cluster_workspace(n, dims_c), f"{n} points on a grid of {list(dims_c)} cells is "
+                             f"beyond gg_cluster_dbscan's limits", dev)
         count = torch.empty(1, dtype=torch.int32, device=dev)
         _lib.check(lib.gg_cluster_dbscan(n, _ptr(points), _ptr(act), eps, k, host_ptr(grid_c), host_ptr(dims_c),
                                          _ptr(res.labels), _ptr(res.core), _ptr(res.neighbor_count), _ptr(count),

@@ -29,6 +29,7 @@
 
 #include "gg_common.h"
 #include "grid_sort.h"
+#include "ordered_sum.h"
 
 __device__ __forceinline__ int cl_load(const int32_t *p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -186,10 +187,7 @@ extern "C" int gg_cluster_dbscan(int num_points, const float *points, const uint
     GG_REQUIRE(num_points >= 0 && num_points <= GG_CLUSTER_MAX_POINTS, "need 0 <= num_points <= GG_CLUSTER_MAX_POINTS");
     GG_REQUIRE(isfinite(eps) && eps > 0.0, "eps must be finite and > 0");
     GG_REQUIRE(min_points >= 1, "min_points must be >= 1");
-    GG_REQUIRE(grid && isfinite(grid[0]) && isfinite(grid[1]) && isfinite(grid[2]) && isfinite(grid[3]) &&
-                   grid[3] > 0.0,
-               "grid: lower corner finite, cell edge finite and > 0");
-    GG_REQUIRE(kn_dims_ok(dims), "dims: each >= 1, product <= GG_KNN_MAX_CELLS");
+    GG_REQUIRE_GRID(grid, dims);
     if (num_points == 0) return GG_OK;
     GG_REQUIRE(points && labels && core && neighbor_count && num_clusters, "null pointer");
     GG_REQUIRE(((uintptr_t)points & 3) == 0 && ((uintptr_t)labels & 3) == 0 && ((uintptr_t)neighbor_count & 3) == 0 &&
@@ -203,37 +201,22 @@ extern "C" int gg_cluster_dbscan(int num_points, const float *points, const uint
     }
     ClWs w;
     cl_layout(num_points, dims, &w, (char *)ws);
-    KnGrid G;
-    for (int d = 0; d < 3; ++d) {
-        G.lo[d] = grid[d];
-        G.dims[d] = dims[d];
-    }
-    G.cell = kn_radius_cell(grid[3], eps);
+    const KnGrid G = kn_grid(grid, dims, eps);
     GG_REQUIRE(isfinite(G.cell), "eps too large for the grid");
     const double eps2 = eps * eps;
     const int n = num_points;
-    const int tiles = (n + PP_TILE - 1) / PP_TILE;
     const unsigned pb = (unsigned)((n + 255) / 256);
     hipStream_t s = (hipStream_t)stream;
     gg_prof_begin(GG_K_CLUSTER, s);
     hipLaunchKernelGGL(cl_init_kernel, dim3(pb), dim3(256), 0, s, n, labels, core, neighbor_count, w.parent, w.flags);
-    const hipError_t e = kn_sort<true>(n, points, active, G, w.sort, w.totals, s);
-    if (e != hipSuccess) {
-        gg_prof_end(GG_K_CLUSTER, s);
-        gg_set_error("%s: fill failed: %s", __func__, hipGetErrorString(e));
-        return GG_ERR_LAUNCH;
-    }
+    GG_REQUIRE_FILL(GG_K_CLUSTER, s, kn_sort<true>(n, points, active, G, w.sort, w.totals, s));
     hipLaunchKernelGGL(cl_core_kernel, dim3(pb), dim3(256), 0, s, n, w.totals, G, w.sort.start, w.sort.counts,
                        w.sort.sorted, eps2, min_points, neighbor_count, core, w.core_s);
     hipLaunchKernelGGL(cl_union_kernel, dim3(pb), dim3(256), 0, s, n, w.totals, G, w.sort.start, w.sort.counts,
                        w.sort.sorted, eps2, w.core_s, w.parent);
     hipLaunchKernelGGL(cl_root_kernel, dim3(pb), dim3(256), 0, s, n, w.totals, G, w.sort.start, w.sort.counts,
                        w.sort.sorted, eps2, w.core_s, w.parent, labels, w.flags);
-    hipLaunchKernelGGL(pp_scan_reduce_kernel, dim3((unsigned)tiles), dim3(PP_THREADS), 0, s, w.flags, n, w.tile_sums);
-    hipLaunchKernelGGL(pp_scan_single_kernel, dim3(1), dim3(PP_THREADS), 0, s, w.tile_sums, tiles, w.tile_offs,
-                       w.totals + 1);
-    hipLaunchKernelGGL(pp_scan_apply_kernel, dim3((unsigned)tiles), dim3(PP_THREADS), 0, s, w.flags, n, w.tile_offs,
-                       w.rank);
+    pp_scan_long(w.flags, n, w.tile_sums, w.tile_offs, w.rank, w.totals + 1, s);
     hipLaunchKernelGGL(cl_relabel_kernel, dim3(pb), dim3(256), 0, s, n, w.rank, w.totals + 1, labels, num_clusters);
     gg_prof_end(GG_K_CLUSTER, s);
     GG_CHECK_LAUNCH();
@@ -266,22 +249,6 @@ __global__ __launch_bounds__(256) void cl_stats_init_kernel(int k, unsigned long
     }
 }
 
-__device__ __forceinline__ double cl_wave_sum(double v) {
-#pragma unroll
-    for (int o = GG_WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, GG_WAVE);
-    return v;
-}
-__device__ __forceinline__ uint32_t cl_wave_min(uint32_t v) {
-#pragma unroll
-    for (int o = GG_WAVE / 2; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o, GG_WAVE));
-    return v;
-}
-__device__ __forceinline__ uint32_t cl_wave_max(uint32_t v) {
-#pragma unroll
-    for (int o = GG_WAVE / 2; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o, GG_WAVE));
-    return v;
-}
-
 // One lane per point.  A wave takes its labels one at a time (at most 64 rounds: every round retires the lanes of
 // one label), sums that label's lanes with a butterfly and lets one lane add the result, so the atomics per wave
 // are one set per distinct label, not one per point.
@@ -309,13 +276,13 @@ __global__ __launch_bounds__(256) void cl_stats_kernel(int n, int k, const float
         const int L = __shfl(lab, leader, GG_WAVE);
         const bool mine = lab == L;
         const unsigned long long m = __ballot(mine);
-        const double sw = cl_wave_sum(mine ? w : 0.0);
-        const double sx = cl_wave_sum(mine ? w * (double)x : 0.0);
-        const double sy = cl_wave_sum(mine ? w * (double)y : 0.0);
-        const double sz = cl_wave_sum(mine ? w * (double)z : 0.0);
-        const uint32_t lx = cl_wave_min(mine ? cl_encode(x) : 0xffffffffu), hx = cl_wave_max(mine ? cl_encode(x) : 0u);
-        const uint32_t ly = cl_wave_min(mine ? cl_encode(y) : 0xffffffffu), hy = cl_wave_max(mine ? cl_encode(y) : 0u);
-        const uint32_t lz = cl_wave_min(mine ? cl_encode(z) : 0xffffffffu), hz = cl_wave_max(mine ? cl_encode(z) : 0u);
+        const double sw = gg_wave_sum(mine ? w : 0.0);
+        const double sx = gg_wave_sum(mine ? w * (double)x : 0.0);
+        const double sy = gg_wave_sum(mine ? w * (double)y : 0.0);
+        const double sz = gg_wave_sum(mine ? w * (double)z : 0.0);
+        const uint32_t lx = gg_wave_min(mine ? cl_encode(x) : 0xffffffffu), hx = gg_wave_max(mine ? cl_encode(x) : 0u);
+        const uint32_t ly = gg_wave_min(mine ? cl_encode(y) : 0xffffffffu), hy = gg_wave_max(mine ? cl_encode(y) : 0u);
+        const uint32_t lz = gg_wave_min(mine ? cl_encode(z) : 0xffffffffu), hz = gg_wave_max(mine ? cl_encode(z) : 0u);
         if (lane == leader) {
             atomicAdd(&count[L], (unsigned long long)__popcll(m));
             atomicAdd(&weight[L], sw);

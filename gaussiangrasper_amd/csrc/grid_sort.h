@@ -1,4 +1,5 @@
-// grid_sort.h — the uniform-grid counting sort shared by csrc/knn.hip and csrc/cluster.hip.
+// grid_sort.h — the uniform-grid counting sort and its call path, shared by csrc/knn.hip, csrc/cluster.hip and
+// csrc/register.hip.
 //
 // The caller gives the grid (lower corner, cell edge, cells per axis); a point's cell is floor((p - lo) / cell) per
 // axis, clamped into the grid, so points outside the grid sit in its border cells.  Counts per cell (integer
@@ -7,6 +8,8 @@
 // int64) then holds how many were taken.  Slot order within a cell follows the atomics.
 // kn_ball walks the sorted points within a radius of a query point (csrc/cluster.hip, csrc/register.hip): with a
 // cell edge of kn_radius_cell the 27 cells around the query's cell hold them all.
+// A call checks its grid with GG_REQUIRE_GRID, fills a KnGrid with kn_grid, lays its workspace out with kn_layout and
+// sorts with kn_sort under GG_REQUIRE_FILL.
 #pragma once
 #include <math.h>
 
@@ -36,6 +39,31 @@ __device__ __forceinline__ int kn_cell(const KnGrid &G, float x, float y, float 
 // 1 / (1 + 2^-20) between neighbours.  Clamping into the grid is monotone and 1-Lipschitz in the cell index, so it
 // holds for points outside the grid too.
 static inline double kn_radius_cell(double cell, double radius) { return fmax(cell, radius) * (1.0 + 0x1p-20); }
+
+// The caller's grid (lower corner and cell edge) and dims, before anything reads them.
+#define GG_REQUIRE_GRID(grid, dims)                                                                            \
+    do {                                                                                                       \
+        GG_REQUIRE((grid) && isfinite((grid)[0]) && isfinite((grid)[1]) && isfinite((grid)[2]) &&              \
+                       isfinite((grid)[3]) && (grid)[3] > 0.0,                                                 \
+                   "grid: lower corner finite, cell edge finite and > 0");                                     \
+        GG_REQUIRE(kn_dims_ok(dims), "dims: each >= 1, product <= GG_KNN_MAX_CELLS");                          \
+    } while (0)
+
+// The grid as given (gg_knn: any cell edge is exact there), and the grid of a sort that is searched within `radius`.
+static inline KnGrid kn_grid(const double *grid, const int32_t *dims) {
+    KnGrid G;
+    for (int d = 0; d < 3; ++d) {
+        G.lo[d] = grid[d];
+        G.dims[d] = dims[d];
+    }
+    G.cell = grid[3];
+    return G;
+}
+static inline KnGrid kn_grid(const double *grid, const int32_t *dims, double radius) {
+    KnGrid G = kn_grid(grid, dims);
+    G.cell = kn_radius_cell(grid[3], radius);
+    return G;
+}
 
 // f(slot j, sorted[j], squared distance) for every sorted point o with (dx dx + dy dy) + dz dz <= r2 in fp64, dx the
 // fp64 difference o - q; q = (px, py, pz), fp64, need not be a sorted point.  The grid's cell edge
@@ -131,22 +159,18 @@ static inline size_t kn_layout(int n, const int32_t *dims, KnWs *w, char *base) 
 }
 
 // counts, start and sorted of the points (FILTER: of those that take part) on stream s; hipSuccess unless a fill
-// could not be launched.  Launch errors of the kernels are left for the caller's GG_CHECK_LAUNCH.
+// could not be launched (the caller's GG_REQUIRE_FILL).  Launch errors of the kernels are left for the caller's
+// GG_CHECK_LAUNCH.
 template <bool FILTER>
 static inline hipError_t kn_sort(int n, const float *points, const uint8_t *active, const KnGrid &G, const KnWs &w,
                                  int64_t *total, hipStream_t s) {
     const int cells = G.dims[0] * G.dims[1] * G.dims[2];
-    const int tiles = (cells + PP_TILE - 1) / PP_TILE;
     const unsigned pb = (unsigned)((n + 255) / 256);
     hipError_t e = gg_fill_async(w.counts, 0, (size_t)cells * 4, s);
     if (e == hipSuccess) e = gg_fill_async(w.cursor, 0, (size_t)cells * 4, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(knn_count_kernel<FILTER>, dim3(pb), dim3(256), 0, s, n, points, active, G, w.counts);
-    hipLaunchKernelGGL(pp_scan_reduce_kernel, dim3((unsigned)tiles), dim3(PP_THREADS), 0, s, w.counts, cells,
-                       w.tile_sums);
-    hipLaunchKernelGGL(pp_scan_single_kernel, dim3(1), dim3(PP_THREADS), 0, s, w.tile_sums, tiles, w.tile_offs, total);
-    hipLaunchKernelGGL(pp_scan_apply_kernel, dim3((unsigned)tiles), dim3(PP_THREADS), 0, s, w.counts, cells,
-                       w.tile_offs, w.start);
+    pp_scan_long(w.counts, cells, w.tile_sums, w.tile_offs, w.start, total, s);
     hipLaunchKernelGGL(knn_scatter_kernel<FILTER>, dim3(pb), dim3(256), 0, s, n, points, active, G, w.start, w.cursor,
                        w.sorted);
     return hipSuccess;

@@ -12,12 +12,14 @@
 // three partial-derivative maps of the SSIM (d/d mu_rgb, d/d E[rgb^2], d/d E[gt rgb]) for the backward, and the
 // backward is ONE pass that filters those maps back (transposed filter = the same symmetric window, zero outside)
 // and adds the L1 sign term.  HBM-bound stencil: 24 B/pixel read + 36 B/pixel of maps written (forward), 36 + 24
-// read + 12 written (backward); no atomics — per-workgroup partial sums, summed in a fixed order by one workgroup.
+// read + 12 written (backward); no atomics — per-workgroup partial sums (the block row of ordered_sum.h), summed by
+// one workgroup in that header's tree order.
 //
 // The arithmetic follows oracle/gg_oracle.c:image_loss_* operation for operation (filter rows first, then columns;
 // -ffp-contract=off), so the maps and the gradient image are bit-identical to the oracle; the two scalar sums are
 // double sums in a different order and agree to 1e-7.
 #include "gg_common.h"
+#include "ordered_sum.h"
 
 #define IL_WIN 11
 #define IL_T 16                  // tile edge
@@ -52,7 +54,7 @@ __global__ __launch_bounds__(256) void image_loss_fwd_kernel(int H, int W, const
                                                              float *__restrict__ maps) {
     __shared__ float sx[3][IL_IN][IL_IN + 1], sy[3][IL_IN][IL_IN + 1];     // gt, rgb (masked)
     __shared__ float hb[5][3][IL_IN][IL_T + 1];                            // row-filtered moments
-    __shared__ double red[3][4];
+    __shared__ double red[4][3];
     const int Ho = H - IL_WIN + 1, Wo = W - IL_WIN + 1;
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     const int x0 = blockIdx.x * IL_T, y0 = blockIdx.y * IL_T;
@@ -132,44 +134,18 @@ __global__ __launch_bounds__(256) void image_loss_fwd_kernel(int H, int W, const
             maps[(3 * ch + 2) * plane + o] = gxy;
         }
     }
-    // workgroup sums, fixed order: lanes of a wave by shuffle, the four waves through LDS
-    double v[3] = {ss, l1, cnt};
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-        for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_down(v[k], off, 64);
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) red[k][tid >> 6] = v[k];
-    }
-    __syncthreads();
-    if (tid == 0) {
-        const size_t blk = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) partials[3 * blk + k] = ((red[k][0] + red[k][1]) + red[k][2]) + red[k][3];
-    }
+    const double v[3] = {ss, l1, cnt};
+    gg_block_row<3>(v, red, partials + 3 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x));
 }
 
-// one workgroup: the partials in index order -> header sums and the three scalars
+// one workgroup: the partials by gg_tree_sum -> header sums and the three scalars
 __global__ __launch_bounds__(256) void image_loss_finish_kernel(int nblocks, int Ho, int Wo, float ssim_lambda,
                                                                 const double *__restrict__ partials,
                                                                 double *__restrict__ header,
                                                                 float *__restrict__ out3) {
     __shared__ double red[3][256];
-    const int tid = threadIdx.x;
-    double v[3] = {0.0, 0.0, 0.0};
-    for (int b = tid; b < nblocks; b += 256)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) v[k] += partials[3 * (size_t)b + k];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) red[k][tid] = v[k];
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s)
-#pragma unroll
-            for (int k = 0; k < 3; ++k) red[k][tid] += red[k][tid + s];
-        __syncthreads();
-    }
-    if (tid == 0) {
+    gg_tree_sum<3>(nblocks, partials, red);
+    if (threadIdx.x == 0) {
         header[0] = red[0][0];
         header[1] = red[1][0];
         header[2] = red[2][0];
@@ -329,7 +305,8 @@ extern "C" int gg_image_loss_bwd(int H, int W, const float *rgb, int rgb_pixel_s
 // The reference gathers the masked pixels with boolean indexing (a host round trip for the count and five gathered
 // copies of up to 1.9 M pixels each way), then runs ~15 elementwise / reduction launches.  One streaming pass each
 // way here: 37 B/pixel read forward, + 16 B/pixel written backward; per-workgroup partial sums in double, summed
-// in index order (reproducible).  The arithmetic follows oracle/gg_oracle.c:geom_loss_* (gradients bit-identical).
+// as the image loss's are (reproducible).  The arithmetic follows oracle/gg_oracle.c:geom_loss_* (gradients
+// bit-identical).
 // =============================================================================================
 struct GeomLossArgs {
     const float *depth, *gt_depth, *normal, *gt_normal;
@@ -360,40 +337,14 @@ __global__ __launch_bounds__(256) void geom_loss_fwd_kernel(long P, GeomLossArgs
         v[2] += (double)(dot / (fmaxf(n1, GL_EPS) * fmaxf(n2, GL_EPS)));
         v[3] += 1.0;
     }
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_down(v[k], off, 64);
-    const int tid = threadIdx.x;
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) red[k][tid >> 6] = v[k];
-    }
-    __syncthreads();
-    if (tid == 0) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            partials[4 * (size_t)blockIdx.x + k] = ((red[k][0] + red[k][1]) + red[k][2]) + red[k][3];
-    }
+    gg_block_row<4>(v, red, partials + 4 * (size_t)blockIdx.x);
 }
 __global__ __launch_bounds__(256) void geom_loss_finish_kernel(int nblocks, const double *__restrict__ partials,
                                                                double *__restrict__ header,
                                                                float *__restrict__ out3) {
     __shared__ double red[4][256];
-    const int tid = threadIdx.x;
-    double v[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int b = tid; b < nblocks; b += 256)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] += partials[4 * (size_t)b + k];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) red[k][tid] = v[k];
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) red[k][tid] += red[k][tid + s];
-        __syncthreads();
-    }
-    if (tid == 0) {
+    gg_tree_sum<4>(nblocks, partials, red);
+    if (threadIdx.x == 0) {
         const double cnt = red[3][0];
         header[0] = cnt;
         out3[0] = (float)(red[0][0] / cnt);

@@ -2,10 +2,9 @@
 // gaussian_splatting.py:315-331, whose distances set the first log-scales).  The contract is in
 // include/gg_raster.h (gg_knn) and PARITY.md "Scene preparation"; the design in DESIGN.md §3.13.
 //
-// Uniform grid, counting sort (grid_sort.h, shared with csrc/cluster.hip): the caller gives the grid (lower corner,
-// cell edge, cells per axis); a point's cell is floor((p - lo) / cell) per axis, clamped into the grid, so points
-// outside the grid sit in its border cells.  Counts per cell (integer atomics), exclusive offsets (prep_common.h
-// scans), a scatter of (x, y, z, index) into cell order.  One lane per sorted slot then searches Chebyshev shells of cells around its own cell, r = 0, 1, ...
+// Uniform grid, counting sort (grid_sort.h: the grid, the sort and the call path shared with csrc/cluster.hip and
+// csrc/register.hip).  Points outside the caller's grid sit in its border cells.  One lane per sorted slot then
+// searches Chebyshev shells of cells around its own cell, r = 0, 1, ...
 // and stops after shell r when its k-th squared distance is <= b^2, b a lower bound of the distance to every cell
 // outside the searched cube:
 //   b = min over the faces of the cube that have cells beyond them of the distance from p to that face plane,
@@ -122,10 +121,7 @@ extern "C" int gg_knn(int num_points, const float *points, int k, const double *
                       float *dist, int64_t *idx, void *ws, size_t ws_bytes, gg_stream_t stream) {
     GG_REQUIRE(k >= 1 && k <= GG_KNN_MAX_K, "need 1 <= k <= GG_KNN_MAX_K");
     GG_REQUIRE(num_points > k && num_points <= GG_KNN_MAX_POINTS, "need k < num_points <= GG_KNN_MAX_POINTS");
-    GG_REQUIRE(grid && isfinite(grid[0]) && isfinite(grid[1]) && isfinite(grid[2]) && isfinite(grid[3]) &&
-                   grid[3] > 0.0,
-               "grid: lower corner finite, cell edge finite and > 0");
-    GG_REQUIRE(kn_dims_ok(dims), "dims: each >= 1, product <= GG_KNN_MAX_CELLS");
+    GG_REQUIRE_GRID(grid, dims);
     GG_REQUIRE(points && dist && idx, "null pointer");
     GG_REQUIRE(((uintptr_t)points & 3) == 0 && ((uintptr_t)dist & 3) == 0 && ((uintptr_t)idx & 7) == 0,
                "points / dist / idx misaligned");
@@ -133,21 +129,11 @@ extern "C" int gg_knn(int num_points, const float *points, int k, const double *
     GG_REQUIRE_WS(ws, ws_bytes, need);
     KnWs w;
     kn_layout(num_points, dims, &w, (char *)ws);
-    KnGrid G;
-    for (int d = 0; d < 3; ++d) {
-        G.lo[d] = grid[d];
-        G.dims[d] = dims[d];
-    }
-    G.cell = grid[3];
+    const KnGrid G = kn_grid(grid, dims);
     const unsigned pb = (unsigned)((num_points + 255) / 256);
     hipStream_t s = (hipStream_t)stream;
     gg_prof_begin(GG_K_KNN, s);
-    const hipError_t e = kn_sort<false>(num_points, points, nullptr, G, w, nullptr, s);
-    if (e != hipSuccess) {
-        gg_prof_end(GG_K_KNN, s);
-        gg_set_error("%s: fill failed: %s", __func__, hipGetErrorString(e));
-        return GG_ERR_LAUNCH;
-    }
+    GG_REQUIRE_FILL(GG_K_KNN, s, kn_sort<false>(num_points, points, nullptr, G, w, nullptr, s));
     switch (k) {
 #define KN_CASE(KK)                                                                                                  \
     case KK:                                                                                                         \

@@ -12,6 +12,7 @@
 // would not be filled by such tiles and the whole problem is 0.3 GFLOP), weight and input gradients summed
 // across tiles with float atomics (the entry point clears them first).
 #include "gg_common.h"
+#include "ordered_sum.h"
 
 #define MB_HID 128
 #ifndef MB_ROWS
@@ -218,12 +219,6 @@ extern "C" int gg_mlp_bwd(int64_t num_rows, int in_dim, int hidden_dim, int out_
 // ---------------------------------------------------------------------------------------------
 #define CL_EPS 1e-12f    // F.normalize default eps
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // waves stride over the points and add ONE total per wave to sim_sum (a point-per-atomic form serialises on that
 // address: 140 ms for the 1.7 M masked pixels of the reference's normal loss, :879)
 __global__ __launch_bounds__(256) void cosine_fwd_kernel(long M, int C, const float *__restrict__ a,
@@ -241,9 +236,9 @@ __global__ __launch_bounds__(256) void cosine_fwd_kernel(long M, int C, const fl
             sa = __builtin_fmaf(u, u, sa);
             sb = __builtin_fmaf(v, v, sb);
         }
-        dot = wave_sum(dot);
-        sa = wave_sum(sa);
-        sb = wave_sum(sb);
+        dot = gg_wave_sum(dot);
+        sa = gg_wave_sum(sa);
+        sb = gg_wave_sum(sb);
         if (lane == 0) {
             const float n1 = sqrtf(sa), n2 = sqrtf(sb);
             const float s = dot / (fmaxf(n1, CL_EPS) * fmaxf(n2, CL_EPS));
@@ -281,7 +276,7 @@ __global__ __launch_bounds__(256) void cosine_fwd_small_kernel(long M, int C, co
         sim[m] = s;
         total += s;
     }
-    total = wave_sum(total);
+    total = gg_wave_sum(total);
     if ((threadIdx.x & 63) == 0) atomicAdd(sim_sum, total);
 }
 template <int CMAX>

@@ -23,6 +23,7 @@
 #include <math.h>
 
 #include "gg_common.h"
+#include "ordered_sum.h"
 
 #define OM_THREADS 256
 #define OM_VIEWS 8                // views per workgroup of the projection passes (each lane's point is read once)
@@ -66,17 +67,6 @@ __device__ __forceinline__ void om_points(const OmMotion &T, const double *__res
     for (int r = 0; r < 3; ++r) q[3 + r] = ((T.t[4 * r] * x + T.t[4 * r + 1] * y) + T.t[4 * r + 2] * z) + T.t[4 * r + 3];
 }
 
-__device__ __forceinline__ int om_wave_min(int v) {
-#pragma unroll
-    for (int o = 1; o < GG_WAVE; o <<= 1) v = min(v, __shfl_xor(v, o, GG_WAVE));
-    return v;
-}
-__device__ __forceinline__ int om_wave_max(int v) {
-#pragma unroll
-    for (int o = 1; o < GG_WAVE; o <<= 1) v = max(v, __shfl_xor(v, o, GG_WAVE));
-    return v;
-}
-
 __device__ __forceinline__ int64_t om_span(const int32_t *jb) {
     return jb[JB_YMIN] > jb[JB_YMAX] ? 0 : (int64_t)jb[JB_YMAX] - (int64_t)jb[JB_YMIN] + 1;
 }
@@ -100,8 +90,8 @@ __global__ __launch_bounds__(OM_THREADS) void om_bounds_kernel(OmParams p, OmMot
             const bool kept = live && om_project(w2c + 12 * (size_t)v, intr + 4 * (size_t)v, q[3 * pose],
                                                  q[3 * pose + 1], q[3 * pose + 2], ix, iy);
             const unsigned long long dropped = __ballot(live && !kept);
-            const int xmin = om_wave_min(kept ? ix : OM_EMPTY_LO), xmax = om_wave_max(kept ? ix : OM_EMPTY_HI);
-            const int ymin = om_wave_min(kept ? iy : OM_EMPTY_LO), ymax = om_wave_max(kept ? iy : OM_EMPTY_HI);
+            const int xmin = gg_wave_min(kept ? ix : OM_EMPTY_LO), xmax = gg_wave_max(kept ? ix : OM_EMPTY_HI);
+            const int ymin = gg_wave_min(kept ? iy : OM_EMPTY_LO), ymax = gg_wave_max(kept ? iy : OM_EMPTY_HI);
             if ((threadIdx.x & (GG_WAVE - 1)) == 0) {
                 int32_t *r = jb + JB_WORDS * (size_t)(2 * v + pose);
                 if (xmin != OM_EMPTY_LO) {

@@ -1,12 +1,25 @@
-// prep_common.h — ordered workgroup scans shared by csrc/prepare.hip, csrc/knn.hip and csrc/cluster.hip.
+// prep_common.h — ordered workgroup scans shared by csrc/prepare.hip and, through grid_sort.h, by csrc/knn.hip,
+// csrc/cluster.hip and csrc/register.hip; and GG_REQUIRE_FILL, the one way their calls give up on a failed fill.
 //
 // A workgroup of PP_THREADS lanes owns PP_TILE = PP_THREADS x PP_ITEMS consecutive items, PP_ITEMS consecutive
 // items per lane; pp_block_scan gives each lane the number of items before its own in the tile.  Exclusive
 // offsets of per-tile (or per-cell) int32 counts come from one workgroup walking them in order
-// (pp_scan_single_kernel) or, for long arrays, from per-tile sums + that walk + a per-tile apply.  Integer adds
-// only: every offset is exact and independent of scheduling.
+// (pp_scan_single_kernel) or, for long arrays, from per-tile sums + that walk + a per-tile apply (pp_scan_long).
+// Integer adds only: every offset is exact and independent of scheduling.
 #pragma once
 #include "gg_common.h"
+
+// e: the hipError_t of a gg_fill_async (or of a kn_sort, whose only failures are its fills), between gg_prof_begin
+// and gg_prof_end of kernel `id` on stream s.
+#define GG_REQUIRE_FILL(id, s, e)                                                    \
+    do {                                                                             \
+        const hipError_t e__ = (e);                                                  \
+        if (e__ != hipSuccess) {                                                     \
+            gg_prof_end(id, s);                                                      \
+            gg_set_error("%s: fill failed: %s", __func__, hipGetErrorString(e__));   \
+            return GG_ERR_LAUNCH;                                                    \
+        }                                                                            \
+    } while (0)
 
 #define PP_THREADS 256
 #define PP_ITEMS 4
@@ -94,4 +107,15 @@ static __global__ __launch_bounds__(PP_THREADS) void pp_scan_apply_kernel(const 
         if (i0 + j < n) offsets[i0 + j] = o;
         o += c[j];
     }
+}
+
+// The long form on stream s: offsets[i] = counts[0] + ... + counts[i-1] for i < n, *total = the sum.  tile_sums and
+// tile_offs hold one int32 per tile of PP_TILE items.
+static inline void pp_scan_long(const int32_t *counts, int n, int32_t *tile_sums, int32_t *tile_offs, int32_t *offsets,
+                                int64_t *total, hipStream_t s) {
+    const int tiles = (n + PP_TILE - 1) / PP_TILE;
+    hipLaunchKernelGGL(pp_scan_reduce_kernel, dim3((unsigned)tiles), dim3(PP_THREADS), 0, s, counts, n, tile_sums);
+    hipLaunchKernelGGL(pp_scan_single_kernel, dim3(1), dim3(PP_THREADS), 0, s, tile_sums, tiles, tile_offs, total);
+    hipLaunchKernelGGL(pp_scan_apply_kernel, dim3((unsigned)tiles), dim3(PP_THREADS), 0, s, counts, n, tile_offs,
+                       offsets);
 }

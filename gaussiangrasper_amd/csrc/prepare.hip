@@ -312,12 +312,7 @@ extern "C" int gg_subsample(int64_t num, int64_t keep, uint64_t seed, const doub
     const int64_t nb = (num + PP_TILE - 1) / PP_TILE;
     const unsigned rows_blocks = (unsigned)((num + PP_THREADS - 1) / PP_THREADS);
     gg_prof_begin(GG_K_SUBSAMPLE, s);
-    hipError_t e = gg_fill_async(hist, 0, (size_t)PP_SEL_BINS * 4, s);
-    if (e != hipSuccess) {
-        gg_prof_end(GG_K_SUBSAMPLE, s);
-        gg_set_error("%s: fill failed: %s", __func__, hipGetErrorString(e));
-        return GG_ERR_LAUNCH;
-    }
+    GG_REQUIRE_FILL(GG_K_SUBSAMPLE, s, gg_fill_async(hist, 0, (size_t)PP_SEL_BINS * 4, s));
     for (int pass = 0; pass < 4; ++pass) {
         hipLaunchKernelGGL(subsample_hist_kernel, dim3(rows_blocks), dim3(PP_THREADS), 0, s, num, (unsigned long long)seed,
                            pass, st, hist);

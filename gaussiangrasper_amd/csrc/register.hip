@@ -12,18 +12,17 @@
 //
 // gg_icp_step: one lane per source point.  The lane moves its point, finds the nearest sorted target (smallest
 // (distance, index) pair: no dependence on slot order) and forms the 32 terms of register_math.h.  The terms are
-// summed in a fixed order: a butterfly over the wave's 64 lanes (both partners add the same two numbers, so every
-// lane holds the same bits), the block's 4 waves in wave order by the first 32 (64 with abs_sums) threads, one slab
-// row per block; then one workgroup sums the rows, 16 interleaved chains per column, and the chains in order.  No
-// floating-point atomics: the same inputs give the same bits.
+// summed in the fixed orders of ordered_sum.h: one block row of 32 (64 with abs_sums) sums per workgroup of 256
+// source points into a slab, then the chains over the slab's rows.  The same inputs give the same bits.
 #include <limits.h>
 #include <math.h>
 
 #include "gg_common.h"
 #include "grid_sort.h"
+#include "ordered_sum.h"
 #include "register_math.h"
 
-#define RG_FIN_THREADS 1024
+#define RG_FIN_THREADS (GG_SUM_CHAINS * 2 * RG_SUMS)
 
 // ------------------------------------------------------------------------------------------------
 // surface frames
@@ -122,20 +121,6 @@ __global__ __launch_bounds__(256) void rg_frames_kernel(int n, const int64_t *__
     valid[id] = 1;
 }
 
-static bool rg_grid_ok(const double *grid) {
-    return grid && isfinite(grid[0]) && isfinite(grid[1]) && isfinite(grid[2]) && isfinite(grid[3]) && grid[3] > 0.0;
-}
-
-static KnGrid rg_grid(const double *grid, const int32_t *dims, double radius) {
-    KnGrid G;
-    for (int d = 0; d < 3; ++d) {
-        G.lo[d] = grid[d];
-        G.dims[d] = dims[d];
-    }
-    G.cell = kn_radius_cell(grid[3], radius);
-    return G;
-}
-
 extern "C" size_t gg_cloud_frames_workspace(int num_points, const int32_t *dims) {
     if (num_points < 1 || num_points > GG_REGISTER_MAX_POINTS || !kn_dims_ok(dims)) return 0;
     return kn_layout(num_points, dims, nullptr, nullptr) + 256;
@@ -146,15 +131,14 @@ extern "C" int gg_cloud_frames(int num_points, const float *points, const float 
                                int32_t *count, uint8_t *valid, void *ws, size_t ws_bytes, gg_stream_t stream) {
     GG_REQUIRE(num_points >= 1 && num_points <= GG_REGISTER_MAX_POINTS, "need 1 <= num_points <= GG_REGISTER_MAX_POINTS");
     GG_REQUIRE(isfinite(radius) && radius > 0.0, "radius must be finite and > 0");
-    GG_REQUIRE(rg_grid_ok(grid), "grid: lower corner finite, cell edge finite and > 0");
-    GG_REQUIRE(kn_dims_ok(dims), "dims: each >= 1, product <= GG_KNN_MAX_CELLS");
+    GG_REQUIRE_GRID(grid, dims);
     GG_REQUIRE(points && intensity && normals && gradients && count && valid, "null pointer");
     GG_REQUIRE(((uintptr_t)points & 3) == 0 && ((uintptr_t)intensity & 3) == 0 && ((uintptr_t)normals & 3) == 0 &&
                    ((uintptr_t)gradients & 3) == 0 && ((uintptr_t)count & 3) == 0,
                "points / intensity / normals / gradients / count misaligned");
     const size_t sort_bytes = kn_layout(num_points, dims, nullptr, nullptr);
     GG_REQUIRE_WS(ws, ws_bytes, sort_bytes + 256);
-    const KnGrid G = rg_grid(grid, dims, radius);
+    const KnGrid G = kn_grid(grid, dims, radius);
     GG_REQUIRE(isfinite(G.cell) && isfinite(radius * radius), "radius too large");
     KnWs w;
     kn_layout(num_points, dims, &w, (char *)ws);
@@ -163,12 +147,7 @@ extern "C" int gg_cloud_frames(int num_points, const float *points, const float 
     hipStream_t s = (hipStream_t)stream;
     gg_prof_begin(GG_K_CLOUD_FRAMES, s);
     hipLaunchKernelGGL(rg_frames_init_kernel, dim3(pb), dim3(256), 0, s, num_points, normals, gradients, count, valid);
-    const hipError_t e = kn_sort<true>(num_points, points, nullptr, G, w, total, s);
-    if (e != hipSuccess) {
-        gg_prof_end(GG_K_CLOUD_FRAMES, s);
-        gg_set_error("%s: fill failed: %s", __func__, hipGetErrorString(e));
-        return GG_ERR_LAUNCH;
-    }
+    GG_REQUIRE_FILL(GG_K_CLOUD_FRAMES, s, kn_sort<true>(num_points, points, nullptr, G, w, total, s));
     hipLaunchKernelGGL(rg_frames_kernel, dim3(pb), dim3(256), 0, s, num_points, total, G, w.start, w.counts, w.sorted,
                        intensity, radius * radius, normals, gradients, count, valid);
     gg_prof_end(GG_K_CLOUD_FRAMES, s);
@@ -183,13 +162,7 @@ struct RgPose {
     double m[12];
 };
 
-__device__ __forceinline__ double rg_wave_sum(double v) {
-#pragma unroll
-    for (int o = GG_WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, GG_WAVE);
-    return v;
-}
-
-// slab row of this block: W = 32 sums, or 64 with the sums of absolute values behind them
+// slab row of this block (gg_block_row): W = 32 sums, or 64 with the sums of absolute values behind them
 template <bool ABS>
 __global__ __launch_bounds__(256) void rg_step_kernel(int m, const float *__restrict__ source,
                                                       const float *__restrict__ source_intensity, RgPose T, KnGrid G,
@@ -204,13 +177,9 @@ __global__ __launch_bounds__(256) void rg_step_kernel(int m, const float *__rest
     constexpr int W = ABS ? 2 * RG_SUMS : RG_SUMS;
     __shared__ double s_w[4][W];
     const int i = blockIdx.x * 256 + threadIdx.x;
-    double v[RG_SUMS], va[ABS ? RG_SUMS : 1];
+    double v[W];
 #pragma unroll
-    for (int k = 0; k < RG_SUMS; ++k) v[k] = 0.0;
-    if constexpr (ABS) {
-#pragma unroll
-        for (int k = 0; k < RG_SUMS; ++k) va[k] = 0.0;
-    }
+    for (int k = 0; k < W; ++k) v[k] = 0.0;
     if (i < m) {
         const double x = (double)source[3 * (size_t)i], y = (double)source[3 * (size_t)i + 1],
                      z = (double)source[3 * (size_t)i + 2];
@@ -241,53 +210,24 @@ __global__ __launch_bounds__(256) void rg_step_kernel(int m, const float *__rest
                 d[k] = (double)gradients[3 * (size_t)bi + k];
             }
             rg_terms(s, q, n, d, (double)source_intensity[i], (double)intensity[bi], best, wg, wp, v,
-                     ABS ? va : nullptr);
+                     ABS ? v + RG_SUMS : nullptr);
         }
     }
-    const int lane = threadIdx.x & (GG_WAVE - 1), wave = threadIdx.x / GG_WAVE;
-#pragma unroll
-    for (int k = 0; k < RG_SUMS; ++k) {
-        const double t = rg_wave_sum(v[k]);
-        if (lane == 0) s_w[wave][k] = t;
-    }
-    if constexpr (ABS) {
-#pragma unroll
-        for (int k = 0; k < RG_SUMS; ++k) {
-            const double t = rg_wave_sum(va[k]);
-            if (lane == 0) s_w[wave][RG_SUMS + k] = t;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < W) {
-        const int k = threadIdx.x;
-        slab[(size_t)W * blockIdx.x + k] = ((s_w[0][k] + s_w[1][k]) + s_w[2][k]) + s_w[3][k];
-    }
+    gg_block_row<W>(v, s_w, slab + (size_t)W * blockIdx.x);
 }
 
-// One workgroup: column k of the slab is summed by 16 chains (chain c takes rows c, c + 16, ... in order), then the
-// chains in order.
+// One workgroup: the slab's columns by gg_chain_sum.  RG_FIN_THREADS lanes for either W: 2 RG_SUMS lanes per chain.
 template <bool ABS>
 __global__ __launch_bounds__(RG_FIN_THREADS) void rg_finish_kernel(int nrows, const double *__restrict__ slab,
                                                                    double *__restrict__ sums,
                                                                    double *__restrict__ abs_sums) {
     constexpr int W = ABS ? 2 * RG_SUMS : RG_SUMS;
-    constexpr int CHAINS = RG_FIN_THREADS / (2 * RG_SUMS);
-    __shared__ double s_c[CHAINS][W];
-    const int k = threadIdx.x % (2 * RG_SUMS), c = threadIdx.x / (2 * RG_SUMS);
-    if (k < W) {
-        double a = 0.0;
-        for (int r = c; r < nrows; r += CHAINS) a += slab[(size_t)W * r + k];
-        s_c[c][k] = a;
-    }
-    __syncthreads();
-    if (threadIdx.x < W) {
-        double a = s_c[0][threadIdx.x];
-        for (int cc = 1; cc < CHAINS; ++cc) a += s_c[cc][threadIdx.x];
-        if (threadIdx.x < RG_SUMS)
-            sums[threadIdx.x] = a;
-        else
-            abs_sums[threadIdx.x - RG_SUMS] = a;
-    }
+    __shared__ double s_c[GG_SUM_CHAINS][W];
+    const double a = gg_chain_sum<W, GG_SUM_CHAINS, 2 * RG_SUMS>(nrows, slab, s_c);
+    if (threadIdx.x < RG_SUMS)
+        sums[threadIdx.x] = a;
+    else if (threadIdx.x < W)
+        abs_sums[threadIdx.x - RG_SUMS] = a;
 }
 
 static size_t rg_step_layout(int num_source, int num_target, const int32_t *dims, size_t *sort_bytes) {
@@ -314,8 +254,7 @@ extern "C" int gg_icp_step(int num_source, const float *source, const float *sou
     GG_REQUIRE(isfinite(max_dist) && max_dist > 0.0 && isfinite(max_dist * max_dist),
                "max_dist must be finite and > 0");
     GG_REQUIRE(lambda_geometric >= 0.0 && lambda_geometric <= 1.0, "lambda_geometric must be in [0, 1]");
-    GG_REQUIRE(rg_grid_ok(grid), "grid: lower corner finite, cell edge finite and > 0");
-    GG_REQUIRE(kn_dims_ok(dims), "dims: each >= 1, product <= GG_KNN_MAX_CELLS");
+    GG_REQUIRE_GRID(grid, dims);
     GG_REQUIRE(source && source_intensity && points && intensity && normals && gradients && valid && transform && sums,
                "null pointer");
     for (int k = 0; k < 12; ++k) GG_REQUIRE(isfinite(transform[k]), "transform must be finite");
@@ -327,7 +266,7 @@ extern "C" int gg_icp_step(int num_source, const float *source, const float *sou
     size_t sort_bytes = 0;
     const size_t need = rg_step_layout(num_source, num_target, dims, &sort_bytes);
     GG_REQUIRE_WS(ws, ws_bytes, need);
-    const KnGrid G = rg_grid(grid, dims, max_dist);
+    const KnGrid G = kn_grid(grid, dims, max_dist);
     GG_REQUIRE(isfinite(G.cell), "max_dist too large for the grid");
     KnWs w;
     kn_layout(num_target, dims, &w, (char *)ws);
@@ -339,14 +278,7 @@ extern "C" int gg_icp_step(int num_source, const float *source, const float *sou
     const int blocks = (num_source + 255) / 256;
     hipStream_t s = (hipStream_t)stream;
     gg_prof_begin(GG_K_ICP_STEP, s);
-    if (!reuse_sort) {
-        const hipError_t e = kn_sort<true>(num_target, points, valid, G, w, total, s);
-        if (e != hipSuccess) {
-            gg_prof_end(GG_K_ICP_STEP, s);
-            gg_set_error("%s: fill failed: %s", __func__, hipGetErrorString(e));
-            return GG_ERR_LAUNCH;
-        }
-    }
+    if (!reuse_sort) GG_REQUIRE_FILL(GG_K_ICP_STEP, s, kn_sort<true>(num_target, points, valid, G, w, total, s));
     if (abs_sums) {
         hipLaunchKernelGGL(rg_step_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, num_source, source,
                            source_intensity, T, G, w.start, w.counts, w.sorted, intensity, normals, gradients,

@@ -100,10 +100,11 @@ __host__ __device__ inline bool rg_gradient_singular(double det, double k, doubl
 
 // The sums' terms of one correspondence (include/gg_raster.h gg_icp_step): s the moved source point, q, n, d, iq
 // the target's point, normal, colour gradient and intensity, is the source's intensity, d2 the squared distance,
-// wg = sqrt(lambda), wp = sqrt(1 - lambda).  ab (may be null): the same terms with every product's absolute value.
+// wg = sqrt(lambda), wp = sqrt(1 - lambda).  out: RG_SUMS doubles.  ab (may be null): RG_SUMS doubles, the same terms
+// with every product's absolute value.
 __host__ __device__ inline void rg_terms(const double (&s)[3], const double (&q)[3], const double (&n)[3],
                                          const double (&d)[3], double is, double iq, double d2, double wg, double wp,
-                                         double (&out)[RG_SUMS], double *ab) {
+                                         double *out, double *ab) {
     const double e[3] = {s[0] - q[0], s[1] - q[1], s[2] - q[2]};
     const double rg = rg_dot(e, n);
     double jg[6], jp[6], cr[3];

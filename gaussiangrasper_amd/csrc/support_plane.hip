@@ -14,12 +14,13 @@
 //   sp_best_kernel     one workgroup: the valid hypothesis with the largest count, the smaller index on ties.
 // There is no fp32 cull: the fp64 test is 10 operations a pair, and a conservative fp32 bound on |s| needs most of them.
 //
-// Classify, two launches, the pattern of gg_icp_step: sp_classify_kernel writes height and side and one slab row of 16
-// sums per workgroup (a lane's SP_CL_ITEMS points in index order, the wave by xor butterfly, the 4 waves in wave
-// order); sp_finish_kernel, one workgroup, sums the rows by 16 chains and the chains in order.  No atomics.
+// Classify, two launches, the fixed orders of ordered_sum.h: sp_classify_kernel writes height and side and one slab
+// row of 16 sums per workgroup (a lane's SP_CL_ITEMS points in index order, then the block row); sp_finish_kernel,
+// one workgroup, sums the slab's rows by the chains.  No atomics.
 #include <math.h>
 
 #include "gg_common.h"
+#include "ordered_sum.h"
 
 #define SP_TILE 256              // points per pass of a workgroup (one per lane)
 #define SP_HCHUNK 256            // hypothesis records per workgroup: 16 KB of LDS
@@ -28,8 +29,7 @@
 #define SP_MIN_CHUNK 1024        // fewest points a chunk is given
 #define SP_SUMS 16
 #define SP_CL_ITEMS 4            // points per lane of the classify kernel
-#define SP_FIN_THREADS 256
-#define SP_FIN_CHAINS (SP_FIN_THREADS / SP_SUMS)
+#define SP_FIN_THREADS (GG_SUM_CHAINS * SP_SUMS)
 
 struct SpUp {
     double u[3], uu, cos2;
@@ -243,12 +243,6 @@ extern "C" int gg_plane_consensus(int num_points, const float *points, const flo
 // ------------------------------------------------------------------------------------------------
 // one plane against every point: labels, heights and the 16 sums
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double sp_wave_sum(double v) {
-#pragma unroll
-    for (int o = GG_WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, GG_WAVE);
-    return v;
-}
-
 __global__ __launch_bounds__(256) void sp_classify_kernel(int N, const float *__restrict__ points,
                                                           const float *__restrict__ weights, double min_weight,
                                                           SpPlane P, float *__restrict__ height,
@@ -293,34 +287,15 @@ __global__ __launch_bounds__(256) void sp_classify_kernel(int N, const float *__
             v[15] += w;
         }
     }
-    const int lane = threadIdx.x & (GG_WAVE - 1), wave = threadIdx.x / GG_WAVE;
-#pragma unroll
-    for (int k = 0; k < SP_SUMS; ++k) {
-        const double t = sp_wave_sum(v[k]);
-        if (lane == 0) s_w[wave][k] = t;
-    }
-    __syncthreads();
-    if (threadIdx.x < SP_SUMS) {
-        const int k = threadIdx.x;
-        slab[(size_t)SP_SUMS * blockIdx.x + k] = ((s_w[0][k] + s_w[1][k]) + s_w[2][k]) + s_w[3][k];
-    }
+    gg_block_row<SP_SUMS>(v, s_w, slab + (size_t)SP_SUMS * blockIdx.x);
 }
 
-// One workgroup: column k of the slab is summed by 16 chains (chain c takes rows c, c + 16, ... in order), then the
-// chains in order.
+// One workgroup: the slab's columns by gg_chain_sum.
 __global__ __launch_bounds__(SP_FIN_THREADS) void sp_finish_kernel(int nrows, const double *__restrict__ slab,
                                                                    double *__restrict__ sums) {
-    __shared__ double s_c[SP_FIN_CHAINS][SP_SUMS];
-    const int k = threadIdx.x % SP_SUMS, c = threadIdx.x / SP_SUMS;
-    double a = 0.0;
-    for (int r = c; r < nrows; r += SP_FIN_CHAINS) a += slab[(size_t)SP_SUMS * r + k];
-    s_c[c][k] = a;
-    __syncthreads();
-    if (threadIdx.x < SP_SUMS) {
-        double t = s_c[0][threadIdx.x];
-        for (int cc = 1; cc < SP_FIN_CHAINS; ++cc) t += s_c[cc][threadIdx.x];
-        sums[threadIdx.x] = t;
-    }
+    __shared__ double s_c[GG_SUM_CHAINS][SP_SUMS];
+    const double t = gg_chain_sum<SP_SUMS, GG_SUM_CHAINS>(nrows, slab, s_c);
+    if (threadIdx.x < SP_SUMS) sums[threadIdx.x] = t;
 }
 
 static int sp_classify_blocks(int N) { return (int)(((long long)N + 256 * SP_CL_ITEMS - 1) / (256 * SP_CL_ITEMS)); }

@@ -19,7 +19,6 @@ No GPU work falls back to the host: a missing device is an error."""
 from __future__ import annotations
 
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -32,8 +31,9 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._call import (ArrayLike, default_device, ptr as _ptr, require_hip as _require_hip, stream as _stream, to_device,
-                    workspace as _ws)
+from ._call import (ArrayLike, default_device, grid_args, ptr as _ptr, require_hip as _require_hip, stream as _stream,
+                    to_device, workspace as _ws)
+from .grid import knn_grid
 
 DEPTH_RANGE = (0.001, 1.2)       # depth_image_to_point_cloud :22
 Z_RANGE = (-0.3, -0.1)           # merge_point_clouds :39
@@ -179,41 +179,6 @@ def depth_normals(depth: ArrayLike, intrinsics: ArrayLike, c2w: ArrayLike) -> Te
     return out
 
 
-def knn_grid(points: Tensor, target_cells_per_point: float = 2.0, sample: int = 65536):
-    """The grid gg_knn sorts into: fitted to the bulk of the cloud (per axis the 0.1 %-99.9 % quantiles of a strided
-    sample of at most `sample` rows, within the quartiles -/+ 3 IQR) so that far outliers, up to a quarter of the
-    points on one side, do not stretch it; about `target_cells_per_point` cells per point.  Points outside it go to its border cells: the grid only sets the speed, never the result.
-    Returns (grid float64 [lo x, y, z, cell], dims int32 [3])."""
-    n = points.shape[0]
-    step = max(1, n // sample)
-    s = points[::step].detach().to("cpu", torch.float64).numpy()
-    # per axis: the 0.1 %-99.9 % quantiles, narrowed to Tukey's far fences (quartiles -/+ 3 IQR) so that a few per
-    # cent of far points cannot stretch the grid over the dense part
-    q = np.quantile(s, [0.001, 0.25, 0.75, 0.999], axis=0)
-    iqr = q[2] - q[1]
-    lo = np.maximum(q[0], q[1] - 3.0 * iqr)
-    hi = np.minimum(q[3], q[2] + 3.0 * iqr)
-    ext = hi - lo
-    emax = float(ext.max())
-    cap = 1 << 26
-    target = int(min(max(1.0, target_cells_per_point * n), cap // 2))
-    if not emax > 0.0:
-        return np.array([lo[0], lo[1], lo[2], 1.0]), np.ones(3, dtype=np.int32)
-
-    def cells(cell):
-        return np.maximum(1, np.ceil(ext / cell)).astype(np.int64)
-
-    a, b = emax / target, emax    # cells(a) >= target, cells(b) == 1 per axis
-    for _ in range(60):
-        mid = (a * b) ** 0.5
-        if np.prod(cells(mid)) > target:
-            a = mid
-        else:
-            b = mid
-    dims = cells(b)
-    return np.array([lo[0], lo[1], lo[2], b], dtype=np.float64), dims.astype(np.int32)
-
-
 def knn_distances(points: ArrayLike, k: int = 3) -> Tuple[Tensor, Tensor]:
     """k_nearest_sklearn without the KD-tree: for every point the k smallest distances to the other points (exact:
     fp64 from the fp32 coordinates, rounded to fp32) and a neighbour set attaining them.  Returns (dist (N, k)
@@ -234,9 +199,7 @@ def knn_distances(points: ArrayLike, k: int = 3) -> Tuple[Tensor, Tensor]:
         raise ValueError("Input X contains NaN or infinity")
     x = (x if x.device.type == "cuda" else x.to(default_device("prepare"))).contiguous()
     dev = x.device
-    grid, dims = knn_grid(x)
-    grid_c = (ctypes.c_double * 4)(*grid.tolist())
-    dims_c = (ctypes.c_int32 * 3)(*dims.tolist())
+    grid_c, dims_c = grid_args(knn_grid(x))
     lib = _lib.load()
     ws = _ws(lib.gg_knn_workspace(n, dims_c), dev)
     dist = torch.empty((n, k), dtype=torch.float32, device=dev)

@@ -15,7 +15,6 @@ No GPU work falls back to the host: a missing device is an error."""
 from __future__ import annotations
 
 import argparse
-import ctypes
 import json
 import math
 import sys
@@ -27,9 +26,10 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._call import (ArrayLike, default_device, f32_rows, host_ptr, positive, ptr as _ptr, require_hip as _require_hip,
-                    stream as _stream, to_device, workspace as _ws)
+from ._call import (ArrayLike, default_device, f32_rows, grid_args, host_ptr, positive, ptr as _ptr,
+                    require_hip as _require_hip, sized_workspace, stream as _stream, to_device)
 from .frames import homogeneous, rigid_rows
+from .grid import cluster_grid
 
 VOXEL_RADIUS = (0.02, 0.01, 0.005)     # coloricp :62
 MAX_ITER = (30, 20, 10)                # coloricp :63
@@ -135,12 +135,6 @@ class StepWorkspace:
         self.grid = None
 
 
-def _grid_c(grid):
-    g, dims = grid
-    return ((ctypes.c_double * 4)(*np.asarray(g, dtype=np.float64).tolist()),
-            (ctypes.c_int32 * 3)(*np.asarray(dims, dtype=np.int32).tolist()))
-
-
 def cloud_frames(points: Tensor, intensity: Tensor, radius: float, grid=None) -> IcpTarget:
     """Surface frames of `points` (N, 3) float32 with `intensity` (N,) float32 on the HIP device (gg_cloud_frames):
     per point the neighbours within `radius`, the normal of their covariance and the colour gradient in the tangent
@@ -152,18 +146,15 @@ def cloud_frames(points: Tensor, intensity: Tensor, radius: float, grid=None) ->
     n = points.shape[0]
     if intensity.shape[0] != n or not 1 <= n <= MAX_POINTS:
         raise ValueError(f"points has {n} rows (1 .. 2^30 wanted), intensity {intensity.shape[0]}")
-    from .cluster import cluster_grid
-    grid_c, dims_c = _grid_c(cluster_grid(points, radius) if grid is None else grid)
+    grid_c, dims_c = grid_args(cluster_grid(points, radius) if grid is None else grid)
     res = IcpTarget(points=points, intensity=intensity,
                     normals=torch.empty((n, 3), dtype=torch.float32, device=dev),
                     gradients=torch.empty((n, 3), dtype=torch.float32, device=dev),
                     count=torch.empty(n, dtype=torch.int32, device=dev),
                     valid=torch.empty(n, dtype=torch.uint8, device=dev), radius=radius)
     lib = _lib.load()
-    nbytes = lib.gg_cloud_frames_workspace(n, dims_c)
-    if nbytes == 0:
-        raise ValueError(f"{n} points on a grid of {list(dims_c)} cells is beyond gg_cloud_frames' limits")
-    ws = _ws(nbytes, dev)
+    ws = sized_workspace(lib.gg_cloud_frames_workspace(n, dims_c), f"{n} points on a grid of {list(dims_c)} cells is "
+                         f"beyond gg_cloud_frames' limits", dev)
     _lib.check(lib.gg_cloud_frames(n, _ptr(points), _ptr(intensity), radius, host_ptr(grid_c), host_ptr(dims_c),
                                    _ptr(res.normals), _ptr(res.gradients), _ptr(res.count), _ptr(res.valid), _ptr(ws),
                                    ws.numel(), _stream(dev)), "gg_cloud_frames")
@@ -196,17 +187,11 @@ def icp_step(source: Tensor, source_intensity: Tensor, target: IcpTarget, transf
     if reuse:
         grid_c, dims_c = state.grid
     else:
-        from .cluster import cluster_grid
-        grid_c, dims_c = _grid_c(cluster_grid(target.points, max_dist, target.valid) if grid is None else grid)
+        grid_c, dims_c = grid_args(cluster_grid(target.points, max_dist, target.valid) if grid is None else grid)
     nbytes = lib.gg_icp_step_workspace(m, n, dims_c)
-    if nbytes == 0:
-        raise ValueError(f"{m} source and {n} target points on a grid of {list(dims_c)} cells is beyond "
-                         f"gg_icp_step's limits")
-    if reuse and state.ws.numel() >= nbytes:
-        ws = state.ws
-    else:
-        reuse = False
-        ws = _ws(nbytes, dev)
+    reuse = reuse and 0 < nbytes <= state.ws.numel()
+    ws = state.ws if reuse else sized_workspace(nbytes, f"{m} source and {n} target points on a grid of "
+                                                f"{list(dims_c)} cells is beyond gg_icp_step's limits", dev)
     out = torch.empty((2 if abs_sums else 1, NUM_SUMS), dtype=torch.float64, device=dev)
     cor = torch.empty(m, dtype=torch.int32, device=dev) if corr else None
     _lib.check(lib.gg_icp_step(m, _ptr(source), _ptr(source_intensity), n, _ptr(target.points),

@@ -124,22 +124,27 @@ def test_sizes_past_the_first_pass_follow_the_kernels_constants():
         return int(m.group(1))
 
     losses, register, support = read("losses.hip"), read("register.hip"), read("support_plane.hip")
-    project, prep = read("project.hip"), read("prep_common.h")
+    project, prep, ordered = read("project.hip"), read("prep_common.h"), read("ordered_sum.h")
     # gg_mlp_bwd: tiles of MB_ROWS rows on a grid of at most 2048 workgroups
     cap = re.search(r"ntiles < (\d+) \? ntiles : (\d+)", losses)
     assert cap and cap.group(1) == cap.group(2), "gg_mlp_bwd's grid cap not found"
     assert (define(losses, "MB_ROWS"), int(cap.group(1))) == (16, 2048), \
         "tests/test_mlp_losses.py LATTICE_SHAPES: rows = MB_ROWS * cap + 1 and 2 * MB_ROWS * cap, MB_ROWS -/+ 1"
-    # gg_icp_step: rows of 256 source points, RG_FIN_THREADS / (2 RG_SUMS) chains
+    # both finishes are ordered_sum.h's gg_chain_sum over GG_SUM_CHAINS chains: chain c takes rows c, c + CHAINS, ...
+    chains = define(ordered, "GG_SUM_CHAINS")
+    assert "const int k = threadIdx.x % LANES, c = threadIdx.x / LANES;" in ordered
+    assert "for (int r = c; r < nrows; r += CHAINS) a += slab[(size_t)W * r + k];" in ordered
+    # gg_icp_step: rows of 256 source points, GG_SUM_CHAINS chains of 32 or 64 columns
     assert "blockIdx.x * 256 + threadIdx.x" in register
-    chains = define(register, "RG_FIN_THREADS") // (2 * define(read("register_math.h"), "RG_SUMS"))
-    assert chains == 16, \
+    assert "gg_chain_sum<W, GG_SUM_CHAINS, 2 * RG_SUMS>(nrows, slab, s_c)" in register
+    assert "#define RG_FIN_THREADS (GG_SUM_CHAINS * 2 * RG_SUMS)" in register
+    assert (chains, chains * 2 * define(read("register_math.h"), "RG_SUMS")) == (16, 1024), \
         "tests/test_register_gpu.py test_icp_step_past_one_row_per_chain: M = 256 chains, 256 chains + 1, > 512 chains"
-    # gg_plane_classify: rows of 256 SP_CL_ITEMS points, SP_FIN_THREADS / SP_SUMS chains
+    # gg_plane_classify: rows of 256 SP_CL_ITEMS points, GG_SUM_CHAINS chains of SP_SUMS columns
     assert "blockIdx.x * (256 * SP_CL_ITEMS)" in support
-    assert "#define SP_FIN_CHAINS (SP_FIN_THREADS / SP_SUMS)" in support
-    chains = define(support, "SP_FIN_THREADS") // define(support, "SP_SUMS")
-    assert (chains, 256 * define(support, "SP_CL_ITEMS")) == (16, 1024), \
+    assert "gg_chain_sum<SP_SUMS, GG_SUM_CHAINS>(nrows, slab, s_c)" in support
+    assert "#define SP_FIN_THREADS (GG_SUM_CHAINS * SP_SUMS)" in support
+    assert (chains, chains * define(support, "SP_SUMS"), 256 * define(support, "SP_CL_ITEMS")) == (16, 256, 1024), \
         "tests/test_support_plane_gpu.py test_classify_is_exact_on_the_lattice: n = 1024 chains, + 1, 2048 chains + 1"
     # pose_finish_kernel: rounds of 12 GG_POSE_FIN_ROWS rows of 256 Gaussians
     unroll = re.search(r"r \+= (\d+) \* GG_POSE_FIN_ROWS", project)
