@@ -106,6 +106,7 @@ SIGNATURES = {
     "gg_cull_mask": (_I, [_I, _P, _P, _P, _F, _F, _F, _I, _I, _P, _P]),
     "gg_adam_step": (_I, [_I, C.POINTER(AdamGroup), _I, _P]),
     "gg_hull_edit": (_I, [_I, _P, _P, _I, _P, C.c_double, _P, _P, _P, _P]),
+    "gg_sh_rotate": (_I, [_I, _I, _P, _P, _P, _P]),
     "gg_object_masks_workspace": (_SZ, [_I, _I]),
     "gg_object_masks": (_I, [_I, _P, _P, _I, _P, _P, _I, _I, _I, _I] + [_P] * 7 + [_SZ, _P]),
     "gg_clip_query_workspace": (_SZ, [_I, _I, _I, _I]),

@@ -6,6 +6,7 @@ gripper's pose change — on one HIP kernel (`gg_hull_edit`, csrc/edit.hip) inst
     points_inside_convex_hull :293-328         filter_object_points -> hull_planes -> select_and_move (mask)
     prepare_transform :342-355, main :141-158  rotvec_to_matrix, compose_transform, object_points_to_scene
     transformed_gs :217-240                    select_and_move (in place) / edit_model
+    (not in the reference)                     sh= / rotate_sh= / --rotate-sh: the moved Gaussians' SH lobes turn too
     save_checkpoint :257-286                   python -m gaussiangrasper_amd.edit ... --out step-000000000.ckpt
 
 The fine-tune that follows is the existing training path.  Two deliberate differences from the reference
@@ -25,7 +26,7 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _lib, sh_rotation
 from ._call import ArrayLike, host_ptr, ptr as _ptr, require_hip as _require_hip, stream as _stream
 from .frames import load_transform_json, points_to_scene as object_points_to_scene, rigid_rows
 from .interop import MODEL_PREFIX
@@ -92,15 +93,21 @@ def compose_transform(matrix: ArrayLike, scale: float, pose_from: ArrayLike, pos
 # device side: one launch of gg_hull_edit
 # ------------------------------------------------------------------------------------------------
 def select_and_move(means: Tensor, quats: Optional[Tensor], planes: ArrayLike,
-                    transform: Optional[ArrayLike] = None, tol: float = 0.0) -> Tuple[Tensor, Tensor]:
+                    transform: Optional[ArrayLike] = None, tol: float = 0.0,
+                    sh: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
     """Select the Gaussians whose mean is inside the hull (every plane n.x + d <= tol) and, with a transform, move
     them in place: means' = R x + t, quats' = quaternion of R quat_to_rotmat(q) (Shepperd, w >= 0).  Rows not
     selected are not written.  One launch; nothing waits on the host.
 
     means (N, 3) and quats (N, 4): fp32, contiguous, on the HIP device (no CPU path); quats may be None without a
     transform.  planes: (F >= 4, 4) half-spaces (hull_planes).  Returns (mask (N,) uint8, count () int64), both on
-    the device."""
-    dev = _require_hip(means) if quats is None else _require_hip(means, quats)
+    the device.
+
+    sh: the SH colour coefficients (N, K, 3), fp32, contiguous, same device.  With it the selected rows' lobes are
+    turned by R as well (gg_sh_rotate, a second launch on the same stream that reads the mask the first one wrote; no
+    read-back).  R is the float32 [R | t] actually applied to the means, widened to fp64 (sh_rotation.rotation_bands);
+    when it is exactly the identity, a translation only, the second launch is skipped.  Needs a transform."""
+    dev = _require_hip(*[t for t in (means, quats, sh) if t is not None])
     for name, t, w in (("means", means, 3), ("quats", quats, 4)):
         if t is None:
             continue
@@ -113,6 +120,16 @@ def select_and_move(means: Tensor, quats: Optional[Tensor], planes: ArrayLike,
     rt = None if transform is None else rigid_rows(transform, np.float32)
     if rt is not None and quats is None:
         raise ValueError("a transform moves means and quats: pass quats")
+    packed = None
+    if sh is not None:
+        if rt is None:
+            raise ValueError("sh is rotated with the moved Gaussians: pass a transform")
+        k = sh_rotation.check_coefficients(sh)
+        if sh.shape[0] != n:
+            raise ValueError(f"means has {n} rows, sh {sh.shape[0]}")
+        R = rt.reshape(3, 4)[:, :3].astype(np.float64)
+        if k > 1 and not np.array_equal(R, np.eye(3)):      # built before anything is moved: a bad R moves nothing
+            packed = sh_rotation.pack_bands(sh_rotation.rotation_bands(R, sh_rotation.NUM_BASES.index(k)), k)
     pl = torch.as_tensor(planes.detach() if isinstance(planes, Tensor) else np.asarray(planes))
     pl = pl.to(device=dev, dtype=torch.float64).contiguous()
     if pl.ndim != 2 or pl.shape[1] != 4 or pl.shape[0] < 4:
@@ -121,21 +138,31 @@ def select_and_move(means: Tensor, quats: Optional[Tensor], planes: ArrayLike,
     count = torch.empty((), dtype=torch.int64, device=dev)
     _lib.check(_lib.load().gg_hull_edit(n, _ptr(means), _ptr(quats), pl.shape[0], _ptr(pl), float(tol), host_ptr(rt),
                                         _ptr(mask), _ptr(count), _stream(dev)), "gg_hull_edit")
+    if packed is not None:
+        sh_rotation.launch(sh, mask, packed, dev)
     return mask, count
 
 
 @torch.no_grad()
-def edit_model(model, planes: ArrayLike, transform: Optional[ArrayLike], tol: float = 0.0) -> int:
+def edit_model(model, planes: ArrayLike, transform: Optional[ArrayLike], tol: float = 0.0,
+               rotate_sh: bool = False) -> int:
     """update.py transformed_gs (:217-240) on a model holding `means` / `quats` Parameters (the plugin's fused model,
     stub.StubGaussianSplattingModel): the same Parameter objects are edited in place, so an optimizer keeps
     referencing them and its Adam moments stay as they are (the reference keeps them too: it saves the original
     checkpoint's `optimizers`).  The version counters are bumped after the raw-pointer write, so nothing keyed on
     (data_ptr, _version) serves the unedited scene.  Returns the number of Gaussians selected; raises if none are
-    (the reference asserts the same)."""
+    (the reference asserts the same).
+
+    rotate_sh: also turn the selected rows of `model.colors_all` (select_and_move's sh=), in place on the same
+    Parameter.  Its Adam moments are left as they are, like those of means and quats: they are not rotated."""
     means, quats = model.means, model.quats
-    mask, count = select_and_move(means.detach(), quats.detach(), planes, transform, tol)
+    colors = model.colors_all if rotate_sh else None
+    mask, count = select_and_move(means.detach(), quats.detach(), planes, transform, tol,
+                                  sh=None if colors is None else colors.detach())
     torch.autograd.graph.increment_version(means)
     torch.autograd.graph.increment_version(quats)
+    if colors is not None:
+        torch.autograd.graph.increment_version(colors)
     selected = int(count.item())
     if selected == 0:
         raise ValueError("no Gaussian lies inside the object's hull")
@@ -156,13 +183,15 @@ def load_object_points(path: str) -> np.ndarray:
 
 def edit_checkpoint(ckpt: str, object_points: np.ndarray, matrix: ArrayLike, scale: float, pose_from: ArrayLike,
                     pose_to: ArrayLike, out: str, tol: float = 0.0, outlier_factor: float = 1.0,
-                    device: str = "cuda") -> int:
+                    device: str = "cuda", rotate_sh: bool = False) -> int:
     """Load `ckpt`, move the Gaussians inside the object's hull, write `out` with `step` 0.  Only
-    `pipeline["_model.means"]` and `pipeline["_model.quats"]` change; every other entry, `optimizers` included, is
-    saved as loaded (update.py save_checkpoint :257-286).  Returns the selected count."""
+    `pipeline["_model.means"]` and `pipeline["_model.quats"]` change — with rotate_sh also
+    `pipeline["_model.colors_all"]`, the moved Gaussians' SH coefficients turned with them and written back in their
+    stored dtype; every other entry, `optimizers` included (Adam moments are not rotated), is saved as loaded
+    (update.py save_checkpoint :257-286).  Returns the selected count."""
     blob = torch.load(ckpt, map_location="cpu", weights_only=True)
     pipe = blob.get("pipeline") if isinstance(blob, dict) else None
-    keys = (MODEL_PREFIX + "means", MODEL_PREFIX + "quats")
+    keys = (MODEL_PREFIX + "means", MODEL_PREFIX + "quats") + ((MODEL_PREFIX + "colors_all",) if rotate_sh else ())
     if not isinstance(pipe, dict) or any(k not in pipe for k in keys):
         raise KeyError(f"{ckpt}: not a splatting checkpoint (no pipeline entries {', '.join(keys)})")
     pts = filter_object_points(object_points_to_scene(object_points, matrix, scale), outlier_factor)
@@ -171,13 +200,16 @@ def edit_checkpoint(ckpt: str, object_points: np.ndarray, matrix: ArrayLike, sca
     m0, q0 = pipe[keys[0]], pipe[keys[1]]
     means = m0.detach().to(device=device, dtype=torch.float32).contiguous()
     quats = q0.detach().to(device=device, dtype=torch.float32).contiguous()
-    _, count = select_and_move(means, quats, planes, rt, tol)
+    sh = pipe[keys[2]].detach().to(device=device, dtype=torch.float32).contiguous() if rotate_sh else None
+    _, count = select_and_move(means, quats, planes, rt, tol, sh=sh)
     selected = int(count.item())
     if selected == 0:
         raise ValueError("no Gaussian lies inside the object's hull")
     new_pipe = dict(pipe)
     new_pipe[keys[0]] = means.cpu().to(m0.dtype)
     new_pipe[keys[1]] = quats.cpu().to(q0.dtype)
+    if rotate_sh:
+        new_pipe[keys[2]] = sh.cpu().to(pipe[keys[2]].dtype)
     new_blob = dict(blob)
     new_blob["pipeline"] = new_pipe
     new_blob["step"] = 0
@@ -199,12 +231,14 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--out", required=True, help="output checkpoint, e.g. .../step-000000000.ckpt")
     ap.add_argument("--tol", type=float, default=0.0, help="a mean is inside when every n.x + d <= tol")
     ap.add_argument("--outlier-factor", type=float, default=1.0)
+    ap.add_argument("--rotate-sh", action="store_true",
+                    help="also rotate the moved Gaussians' SH colour coefficients (_model.colors_all)")
     a = ap.parse_args(argv)
     with open(a.transform_json) as f:
         tj = json.load(f)
     try:
         n = edit_checkpoint(a.ckpt, load_object_points(a.object_points), *load_transform_json(tj), a.pose_from,
-                            a.pose_to, a.out, a.tol, a.outlier_factor)
+                            a.pose_to, a.out, a.tol, a.outlier_factor, rotate_sh=a.rotate_sh)
     except (KeyError, ValueError) as exc:
         raise SystemExit(f"error: {exc}") from exc
     print(f"selected {n} Gaussians; wrote {a.out}")

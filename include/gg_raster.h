@@ -560,6 +560,22 @@ int gg_adam_step(int num_groups, const gg_adam_group_t *groups, int zero_grad, g
 int gg_hull_edit(int num_points, float *means, float *quats, int num_planes, const double *planes, double tol,
                  const float *rt, uint8_t *mask, int64_t *count_out, gg_stream_t stream);
 
+/* ---- the moved Gaussians' colour lobes (PARITY "Scene update") ---------------------------------------
+ * Rotates the spherical-harmonic coefficients of the selected rows, in place: band l (coefficients lo = l^2 ..
+ * hi - 1, hi = (l + 1)^2) of every channel is multiplied by that band's (2l+1) x (2l+1) matrix D_l.
+ *   coeffs: (num_points, num_bases, 3) fp32, 4-byte aligned.  num_bases in {1, 4, 9, 16, 25}; with 1 (band 0 only)
+ *           the call returns without launching.
+ *   mask:   (num_points) uint8 on the device, non-zero = selected (gg_hull_edit's mask as it is), or NULL: every row.
+ *   bands:  HOST array, D_1, D_2, ... of the bands num_bases has, each row-major, concatenated: 9, 34, 83 or 164
+ *           floats (sh_rotation.pack_bands).
+ *   For a selected row, band l >= 1, output a and channel ch, in fp32, every product and every sum rounded, b
+ *   ascending, no contraction:
+ *           out[a][ch] = ((D[a][lo] c[lo][ch] + D[a][lo+1] c[lo+1][ch]) + ...) + D[a][hi-1] c[hi-1][ch]
+ *   with every c the row's value before the call.  Band 0 and rows not selected are neither read nor written.
+ * One launch, no workspace, nothing waits on the host. */
+int gg_sh_rotate(int num_points, int num_bases, float *coeffs, const uint8_t *mask, const float *bands,
+                 gg_stream_t stream);
+
 /* ---- per-view masks of the moved object (reference scripts/project_hull.py :83-121; DESIGN 3.14, PARITY "Scene
  * update") -----------------------------------------------------------------------------------------------------------
  * For every view v and pose (0 = before, 1 = after) — a job — in fp64, no contraction:
