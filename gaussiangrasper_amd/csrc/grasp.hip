@@ -313,6 +313,9 @@ extern "C" int gg_grasp_contacts(int num_points, const float *points, const floa
     GG_REQUIRE(((uintptr_t)points & 3) == 0 && ((uintptr_t)normals & 3) == 0 && ((uintptr_t)weights & 3) == 0 &&
                    ((uintptr_t)grasps & 3) == 0,
                "points / normals / weights / grasps misaligned");
+    GG_REQUIRE((((uintptr_t)contact_idx | (uintptr_t)normals_out | (uintptr_t)angles | (uintptr_t)region_count |
+                 (uintptr_t)region_weight | (uintptr_t)collision_weight) & 3) == 0,
+               "contact_idx / normals_out / angles / region_count / region_weight / collision_weight misaligned");
     const size_t need = gc_layout(num_points, num_grasps, nullptr, nullptr);
     GG_REQUIRE_WS(ws, ws_bytes, need);
     GcWs w;

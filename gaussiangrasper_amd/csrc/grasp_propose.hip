@@ -318,6 +318,8 @@ extern "C" int gg_grasp_propose(int num_points, const float *points, const float
     GG_REQUIRE(((uintptr_t)points & 3) == 0 && ((uintptr_t)normals & 3) == 0 && ((uintptr_t)weights & 3) == 0 &&
                    ((uintptr_t)seeds & 3) == 0,
                "points / normals / weights / seeds misaligned");
+    GG_REQUIRE((((uintptr_t)pair_idx | (uintptr_t)tube_count | (uintptr_t)span | (uintptr_t)rows) & 3) == 0,
+               "pair_idx / tube_count / span / rows misaligned");
     const size_t need = gp_layout(num_points, num_seeds, nullptr, nullptr);
     GG_REQUIRE_WS(ws, ws_bytes, need);
     GpWs w;

@@ -261,10 +261,8 @@ extern "C" int gg_image_loss_fwd(int H, int W, const float *rgb, int rgb_pixel_s
     GG_REQUIRE(H >= IL_WIN && W >= IL_WIN, "image smaller than the 11 x 11 SSIM window");
     GG_REQUIRE(rgb_pixel_stride >= 3, "rgb pixels hold 3 values");
     GG_REQUIRE(rgb && gt && out3, "null pointer");
-    if (ws == nullptr || ws_bytes < gg_image_loss_workspace(H, W)) {
-        gg_set_error("gg_image_loss_fwd: workspace too small");
-        return GG_ERR_WORKSPACE;
-    }
+    GG_REQUIRE((((uintptr_t)rgb | (uintptr_t)gt | (uintptr_t)out3) & 3) == 0, "rgb / gt / out3 misaligned");
+    GG_REQUIRE_WS(ws, ws_bytes, gg_image_loss_workspace(H, W));
     hipStream_t s = (hipStream_t)stream;
     double *header = (double *)ws;
     double *partials = header + IL_HEADER;
@@ -285,10 +283,9 @@ extern "C" int gg_image_loss_bwd(int H, int W, const float *rgb, int rgb_pixel_s
     GG_REQUIRE(H >= IL_WIN && W >= IL_WIN, "image smaller than the 11 x 11 SSIM window");
     GG_REQUIRE(rgb_pixel_stride >= 3, "rgb pixels hold 3 values");
     GG_REQUIRE(rgb && gt && v_main && v_rgb, "null pointer");
-    if (ws == nullptr || ws_bytes < gg_image_loss_workspace(H, W)) {
-        gg_set_error("gg_image_loss_bwd: workspace too small (it must be the forward's)");
-        return GG_ERR_WORKSPACE;
-    }
+    GG_REQUIRE((((uintptr_t)rgb | (uintptr_t)gt | (uintptr_t)v_main | (uintptr_t)v_rgb) & 3) == 0,
+               "rgb / gt / v_main / v_rgb misaligned");
+    GG_REQUIRE_WS(ws, ws_bytes, gg_image_loss_workspace(H, W));          // the forward's
     const double *header = (const double *)ws;
     const size_t nblk = il_blocks(H, W);
     const float *maps = (const float *)((const char *)ws + gg_align_up(sizeof(double) * (IL_HEADER + 3 * nblk), 256));
@@ -411,10 +408,10 @@ extern "C" int gg_geom_loss_fwd(int64_t num_pixels, const float *depth, int dept
                                 size_t ws_bytes, gg_stream_t stream) {
     GG_REQUIRE(num_pixels >= 1, "num_pixels < 1");
     GG_REQUIRE(depth && gt_depth && normal && gt_normal && out3, "null pointer");
-    if (ws == nullptr || ws_bytes < gg_geom_loss_workspace()) {
-        gg_set_error("gg_geom_loss_fwd: workspace too small");
-        return GG_ERR_WORKSPACE;
-    }
+    GG_REQUIRE((((uintptr_t)depth | (uintptr_t)gt_depth | (uintptr_t)normal | (uintptr_t)gt_normal | (uintptr_t)out3) &
+                3) == 0,
+               "depth / gt_depth / normal / gt_normal / out3 misaligned");
+    GG_REQUIRE_WS(ws, ws_bytes, gg_geom_loss_workspace());
     hipStream_t s = (hipStream_t)stream;
     double *header = (double *)ws, *partials = header + IL_HEADER;
     const int nb = (int)((num_pixels + 255) / 256 < GL_BLOCKS ? (num_pixels + 255) / 256 : GL_BLOCKS);
@@ -436,10 +433,11 @@ extern "C" int gg_geom_loss_bwd(int64_t num_pixels, const float *depth, int dept
     GG_REQUIRE(num_pixels >= 1, "num_pixels < 1");
     GG_REQUIRE(depth && gt_depth && normal && gt_normal && v_depth_loss && v_normal_loss && v_depth && v_normal,
                "null pointer");
-    if (ws == nullptr || ws_bytes < gg_geom_loss_workspace()) {
-        gg_set_error("gg_geom_loss_bwd: workspace too small (it must be the forward's)");
-        return GG_ERR_WORKSPACE;
-    }
+    GG_REQUIRE((((uintptr_t)depth | (uintptr_t)gt_depth | (uintptr_t)normal | (uintptr_t)gt_normal |
+                 (uintptr_t)v_depth_loss | (uintptr_t)v_normal_loss | (uintptr_t)v_depth | (uintptr_t)v_normal) &
+                3) == 0,
+               "depth / gt_depth / normal / gt_normal / v_depth_loss / v_normal_loss / v_depth / v_normal misaligned");
+    GG_REQUIRE_WS(ws, ws_bytes, gg_geom_loss_workspace());               // the forward's
     const GeomLossArgs a = geom_args(depth, depth_stride, gt_depth, gt_depth_stride, normal, normal_pixel_stride,
                                      normal_channel_stride, gt_normal, gt_normal_pixel_stride,
                                      gt_normal_channel_stride, mask);

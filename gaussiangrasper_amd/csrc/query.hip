@@ -343,6 +343,8 @@ extern "C" int gg_clip_query(int64_t num_rows, int in_dim, int hidden_dim, int o
     GG_REQUIRE(sims || relevancy, "both outputs are NULL: nothing to compute");
     GG_REQUIRE(x && w1 && b1 && w2 && b2 && queries, "null pointer");
     GG_REQUIRE(((uintptr_t)x & 15) == 0, "x must be 16-byte aligned");
+    GG_REQUIRE((((uintptr_t)w1 | (uintptr_t)b1 | (uintptr_t)w2 | (uintptr_t)b2) & 3) == 0,
+               "w1, b1, w2 and b2 must be 4-byte aligned");
     GG_REQUIRE((((uintptr_t)queries | (uintptr_t)sims | (uintptr_t)relevancy) & 3) == 0,
                "queries, sims and relevancy must be 4-byte aligned");
     if (ws == nullptr || ws_bytes < gg_clip_query_workspace(in_dim, hidden_dim, out_dim, num_queries) ||

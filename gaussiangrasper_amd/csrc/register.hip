@@ -262,7 +262,8 @@ extern "C" int gg_icp_step(int num_source, const float *source, const float *sou
                    ((uintptr_t)intensity & 3) == 0 && ((uintptr_t)normals & 3) == 0 &&
                    ((uintptr_t)gradients & 3) == 0 && ((uintptr_t)corr & 3) == 0 && ((uintptr_t)sums & 7) == 0 &&
                    ((uintptr_t)abs_sums & 7) == 0,
-               "source / source_intensity / points / intensity / normals / gradients / corr / sums misaligned");
+               "source / source_intensity / points / intensity / normals / gradients / corr / sums / abs_sums "
+               "misaligned");
     size_t sort_bytes = 0;
     const size_t need = rg_step_layout(num_source, num_target, dims, &sort_bytes);
     GG_REQUIRE_WS(ws, ws_bytes, need);

@@ -497,7 +497,7 @@ extern "C" int gg_tsdf_integrate(const int32_t *dims, const float *grid, float t
                "color and color_weight are given exactly when rgb is");
     GG_REQUIRE((((uintptr_t)depth | (uintptr_t)rgb | (uintptr_t)intrinsics | (uintptr_t)w2c | (uintptr_t)tsdf |
                  (uintptr_t)weight | (uintptr_t)color | (uintptr_t)color_weight) & 3) == 0,
-               "arrays must be 4-byte aligned");
+               "depth / rgb / intrinsics / w2c / tsdf / weight / color / color_weight must be 4-byte aligned");
     if (num_views == 0) return GG_OK;
     TsParams p{g, trunc, num_views, height, width, (g.Y + TS_BY - 1) / TS_BY, (g.Z + TS_BZ - 1) / TS_BZ};
     const int64_t nbx = (g.X + TS_BX - 1) / TS_BX;
@@ -562,7 +562,7 @@ extern "C" int gg_tsdf_mesh_emit(const int32_t *dims, const float *grid, const f
     GG_REQUIRE(num_faces == 0 || faces, "null pointer: faces");
     GG_REQUIRE((((uintptr_t)tsdf | (uintptr_t)color | (uintptr_t)vertices | (uintptr_t)normals | (uintptr_t)colors |
                  (uintptr_t)faces) & 3) == 0,
-               "arrays must be 4-byte aligned");
+               "tsdf / color / vertices / normals / colors / faces must be 4-byte aligned");
     const int64_t P = ts_points(dims);
     const size_t need = tm_layout(P, nullptr, nullptr);
     GG_REQUIRE_WS(ws, ws_bytes, need);

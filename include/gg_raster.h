@@ -439,7 +439,9 @@ int gg_cosine_loss_bwd(int64_t num_points, int channels, const float *a, const f
  * is read in place); valid (H, W) bytes or NULL (all valid).  out3 = {main_loss, Ll1, ssim} (device).
  * The forward leaves what the backward needs (three derivative maps per channel, the valid count) in `ws`
  * (gg_image_loss_workspace bytes); the backward takes the SAME workspace, untouched, and v_main (1 float, device)
- * and writes v_rgb (H, W, 3) = v_main * d main_loss / d rgb, zero at invalid pixels.  H, W >= 11. */
+ * and writes v_rgb (H, W, 3) = v_main * d main_loss / d rgb, zero at invalid pixels.  H, W >= 11.
+ * rgb, gt, out3, v_main and v_rgb 4-byte aligned, valid any address; ws 256-byte aligned, of any content on entry of
+ * the forward; the backward only reads it. */
 size_t gg_image_loss_workspace(int img_height, int img_width);
 int gg_image_loss_fwd(int img_height, int img_width, const float *rgb, int rgb_pixel_stride, const float *gt,
                       const uint8_t *valid, float ssim_lambda, float *out3, void *ws, size_t ws_bytes,
@@ -455,7 +457,9 @@ int gg_image_loss_bwd(int img_height, int img_width, const float *rgb, int rgb_p
  * base[p * pixel_stride + c * channel_stride] (the model's images are pixel-major, the reference's ground truth
  * channel-major).  out3 = {depth_loss, normal_loss, number of masked pixels} (device).  The backward takes the
  * forward's workspace (gg_geom_loss_workspace bytes), the two loss cotangents from device memory (1 float each) and
- * writes dense v_depth (num_pixels,), v_normal (num_pixels, 3), zero outside the mask. */
+ * writes dense v_depth (num_pixels,), v_normal (num_pixels, 3), zero outside the mask.
+ * Every fp32 array 4-byte aligned, mask any address; ws 256-byte aligned, of any content on entry of the forward; the
+ * backward only reads it. */
 size_t gg_geom_loss_workspace(void);
 int gg_geom_loss_fwd(int64_t num_pixels, const float *depth, int depth_stride, const float *gt_depth,
                      int gt_depth_stride, const float *normal, int normal_pixel_stride, int normal_channel_stride,
@@ -556,7 +560,7 @@ int gg_adam_step(int num_groups, const gg_adam_group_t *groups, int zero_grad, g
  *           renormalised.  Rows not selected are never written.
  *   mask:      (num_points) uint8, 1 = selected, fully written.
  *   count_out: DEVICE int64, the number of selected rows (zeroed by the call, so num_points == 0 leaves 0).
- * quats 16-byte aligned.  No workspace. */
+ * means 4-byte, planes and count_out 8-byte, quats 16-byte aligned; mask any address.  No workspace. */
 int gg_hull_edit(int num_points, float *means, float *quats, int num_planes, const double *planes, double tol,
                  const float *rt, uint8_t *mask, int64_t *count_out, gg_stream_t stream);
 
@@ -600,7 +604,9 @@ int gg_sh_rotate(int num_points, int num_bases, float *coeffs, const uint8_t *ma
  * makes the call return GG_ERR_UNSUPPORTED naming the smallest such view, with nothing written to the outputs.  The
  * call reads one status word back and synchronises the stream once, at its end.  Deterministic: integer work only.
  * `ws`: gg_object_masks_workspace(V, max_rows) bytes (about 12 max_rows bytes per job), 256-byte aligned; 0 is
- * returned for counts out of range. */
+ * returned for counts out of range.  points, intrinsics, w2c and centres 8-byte aligned, boxes and dropped 4-byte; the
+ * three masks any address (when all three are 4-byte aligned and width % 4 == 0 they are written a word at a time: the
+ * same bytes).  num_views == 0 writes nothing. */
 #define GG_OBJMASK_MAX_VIEWS 16384
 #define GG_OBJMASK_MAX_ROWS 65536
 #define GG_OBJMASK_MAX_SIDE 32768
@@ -621,8 +627,9 @@ int gg_object_masks(int num_points, const double *points, const double *transfor
  *   sims:      num_rows x num_queries, or NULL;  relevancy: num_rows x num_positives, or NULL (needs 1 <= num_positives
  *              < num_queries).  At least one of the two.  y = 0 gives s = 0, r = 1/2; a NaN feature makes that row's
  *              outputs NaN; num_rows = 0 does nothing.  Fixed summation orders, no atomics: identical run to run.
- * x 16-byte aligned; `ws`: gg_clip_query_workspace() bytes (0 = shape not supported), 16-byte aligned, rewritten by
- * every call (the packed weights of gg_mlp_fwd_fast). */
+ * x 16-byte aligned; w1, b1, w2, b2, queries, sims and relevancy 4-byte aligned; `ws`: gg_clip_query_workspace() bytes
+ * (0 = shape not supported), 16-byte aligned, of any content on entry, rewritten by every call (the packed weights of
+ * gg_mlp_fwd_fast). */
 #define GG_QUERY_MAX 8
 size_t gg_clip_query_workspace(int in_dim, int hidden_dim, int out_dim, int num_queries);
 int gg_clip_query(int64_t num_rows, int in_dim, int hidden_dim, int out_dim, const float *x, const float *w1,
@@ -657,7 +664,8 @@ int gg_clip_query(int64_t num_rows, int in_dim, int hidden_dim, int out_dim, con
  * depth_base, finger_width, band and mu finite and >= 0; min_weight and max_collision not NaN (+inf: no collision
  * limit).  num_grasps == 0 does nothing; num_points == 0 marks every grasp not valid.  No atomics: per-chunk
  * partials combined in a fixed order, identical run to run.  `ws`: gg_grasp_contacts_workspace() bytes, 256-byte
- * aligned (0 bytes for num_grasps == 0; 0 is also returned for counts out of range). */
+ * aligned (0 bytes for num_grasps == 0; 0 is also returned for counts out of range).  Every fp32 / int32 array, inputs
+ * and outputs, 4-byte aligned; feasible any address. */
 #define GG_GRASP_MAX (1 << 20)
 #define GG_GRASP_MAX_POINTS (1 << 30)
 size_t gg_grasp_contacts_workspace(int num_points, int num_grasps);
@@ -699,7 +707,8 @@ int gg_grasp_contacts(int num_points, const float *points, const float *normals,
  * max_width; min_weight not NaN; min_align in [0, 1]; up: HOST array of 3 doubles, finite, not zero; num_approach in
  * 1..GG_PROPOSE_MAX_APPROACH.  num_seeds == 0 does nothing; num_points == 0 makes every seed not usable.  No atomics:
  * per-chunk extremes combined in a fixed order; the result does not depend on the launch geometry and is identical run
- * to run.  `ws`: gg_grasp_propose_workspace() bytes, 256-byte aligned (0 is returned for counts out of range). */
+ * to run.  `ws`: gg_grasp_propose_workspace() bytes, 256-byte aligned (0 is returned for counts out of range).  Every
+ * fp32 / int32 array, inputs and outputs, 4-byte aligned; valid any address. */
 #define GG_PROPOSE_MAX_SEEDS (1 << 20)
 #define GG_PROPOSE_MAX_APPROACH 64
 size_t gg_grasp_propose_workspace(int num_points, int num_seeds);
@@ -848,7 +857,9 @@ int gg_plane_classify(int num_points, const float *points, const float *weights,
  * and kept iff z_lo < p_2 < z_hi.  Kept points go to points fp64 [.][3] / colors uint8 [.][3] in pixel order (the
  * reference's boolean-index order); *count (device int64) = how many.  points / colors need room for F*H*W rows.
  * No atomics decide a position: identical output call to call, and the same rows whatever frames share a call.
- * `ws`: gg_backproject_workspace() bytes, 256-byte aligned (0 is returned for shapes out of range). */
+ * `ws`: gg_backproject_workspace() bytes, 256-byte aligned (0 is returned for shapes out of range).  depth, intrinsics,
+ * c2w, points and count 8-byte aligned; mask, rgb and colors any address.  Rows of points / colors past *count are not
+ * written.  num_frames == 0 writes *count = 0 and nothing else. */
 #define GG_PREP_MAX_ROWS (1 << 30)
 size_t gg_backproject_workspace(int num_frames, int height, int width);
 int gg_backproject(int num_frames, int height, int width, const double *depth, const uint8_t *mask, const uint8_t *rgb,
@@ -860,7 +871,7 @@ int gg_backproject(int num_frames, int height, int width, const double *depth, c
  * (the SplitMix64 output function; all keys distinct); the m rows with the smallest keys are written in ascending
  * index order: out_index int64 [m], and, when given, out_points fp64 [m][3] / out_colors uint8 [m][3] gathered from
  * points fp64 [num][3] / colors uint8 [num][3].  m == 0 does nothing.  `ws`: gg_subsample_workspace(num) bytes,
- * 256-byte aligned. */
+ * 256-byte aligned.  points, out_points and out_index 8-byte aligned; colors and out_colors any address. */
 size_t gg_subsample_workspace(int64_t num);
 int gg_subsample(int64_t num, int64_t keep, uint64_t seed, const double *points, const uint8_t *colors,
                  double *out_points, uint8_t *out_colors, int64_t *out_index, void *ws, size_t ws_bytes,
@@ -871,7 +882,7 @@ int gg_subsample(int64_t num, int64_t keep, uint64_t seed, const double *points,
  *   d' = d < 0.01 ? 1e-5 : d;  du, dv = np.gradient(d') along columns / rows (interior (f[i+1] - f[i-1]) / 2, edges
  *   one-sided);  a = -(du * (fx / d')), b = -(dv * (fy / d')), c = 1;  n = (a, b, c) / sqrt((a a + b b) + c c);
  *   a row with a non-finite component becomes (0, 0, 1);  out_k = (R[k][0] n0 + R[k][1] n1) + R[k][2] n2, R = c2w[:3,:3].
- * normals fp64 [F][H][W][3]. */
+ * normals fp64 [F][H][W][3].  Every array 8-byte aligned.  num_frames == 0 does nothing. */
 int gg_depth_normals(int num_frames, int height, int width, const double *depth, const double *intrinsics,
                      const double *c2w, double *normals, gg_stream_t stream);
 
@@ -884,7 +895,8 @@ int gg_depth_normals(int num_frames, int height, int width, const double *depth,
  * gives it fast (gaussiangrasper_amd.prepare.knn_grid).  Cost: O(N x max points per cell) plus the cells walked;
  * worst case per point one walk of every cell and point, O(N^2) in all when the grid crowds the cloud into a few
  * cells.
- * `ws`: gg_knn_workspace(N, dims) bytes, 256-byte aligned (0 for sizes out of range). */
+ * `ws`: gg_knn_workspace(N, dims) bytes, 256-byte aligned (0 for sizes out of range).  points and dist 4-byte aligned,
+ * idx 8-byte. */
 #define GG_KNN_MAX_K 8
 #define GG_KNN_MAX_POINTS (1 << 30)
 #define GG_KNN_MAX_CELLS (1 << 26)
@@ -915,14 +927,15 @@ int gg_knn(int num_points, const float *points, int k, const double *grid, const
  * (32-bit device-scope atomicCAS / atomicMin, parents only decrease); no thread waits on another.
  * Everything runs on `stream`; nothing is read back.  num_points == 0 returns GG_OK and launches nothing.
  * `ws`: gg_cluster_workspace(N, dims) bytes, 256-byte aligned (0 for sizes out of range); a short or NULL workspace
- * is GG_ERR_INVALID_ARG.
+ * is GG_ERR_INVALID_ARG.  points, labels, neighbor_count and num_clusters 4-byte aligned; active and core any address.
  *
  * gg_cluster_stats: per cluster c in [0, num_clusters), over the points with labels[i] == c (labels outside that
  * range are skipped):  count int64 [K] (exact);  weight fp64 [K] = sum of (double)weights[i];  centroid fp64 [K][3] =
  * (sum of (double)w_i (double)p_i) / weight (each product exact; NaN for weight 0);  bbox fp32 [K][6] = min x, y, z
  * then max x, y, z (exact; NaN for a cluster without members).  Integer atomics for count and, through an
  * order-preserving encoding, for bbox; fp64 atomic sums for weight and centroid, whose last bits may differ from
- * call to call.  points must be finite where a label is in range.  num_clusters == 0 does nothing. */
+ * call to call.  points must be finite where a label is in range.  num_clusters == 0 does nothing.  points, weights,
+ * labels and bbox 4-byte aligned; count, weight and centroid 8-byte. */
 #define GG_CLUSTER_MAX_POINTS (1 << 30)
 size_t gg_cluster_workspace(int num_points, const int32_t *dims);
 int gg_cluster_dbscan(int num_points, const float *points, const uint8_t *active, double eps, int min_points,
@@ -955,7 +968,8 @@ int gg_cluster_stats(int num_points, const float *points, const float *weights, 
  * the fp64 sums run in the sort's slot order, which follows integer atomics, so normals and gradients may differ in
  * their last bits from call to call.  Every neighbour within the radius is used (Open3D's hybrid search stops at the
  * 30 nearest).  Cost: N x (points within the 27 cells around each) x 3 passes.
- * `ws`: gg_cloud_frames_workspace(N, dims) bytes, 256-byte aligned (0 for sizes out of range).
+ * `ws`: gg_cloud_frames_workspace(N, dims) bytes, 256-byte aligned (0 for sizes out of range).  points, intensity,
+ * normals, gradients and count 4-byte aligned; valid any address.  num_points >= 1.
  *
  * gg_icp_step: one Gauss-Newton linearisation of the coloured-ICP objective.  source fp32 [M][3], source_intensity
  * fp32 [M]; the target's points fp32 [N][3], intensity fp32 [N] and gg_cloud_frames' normals, gradients and valid;
@@ -978,7 +992,8 @@ int gg_cluster_stats(int num_points, const float *points, const float *weights, 
  * and a correspondent never depends on the sort's slot order: the same inputs give the same bits.
  * reuse_sort != 0: `ws` still holds the sort a previous call made for the same points, valid, grid, dims and
  * max_dist, and it is not made again.
- * `ws`: gg_icp_step_workspace(M, N, dims) bytes, 256-byte aligned (0 for sizes out of range). */
+ * `ws`: gg_icp_step_workspace(M, N, dims) bytes, 256-byte aligned (0 for sizes out of range).  Every fp32 array and
+ * corr 4-byte aligned, sums and abs_sums 8-byte, valid any address.  num_source, num_target >= 1. */
 #define GG_REGISTER_MAX_POINTS (1 << 30)
 size_t gg_cloud_frames_workspace(int num_points, const int32_t *dims);
 int gg_cloud_frames(int num_points, const float *points, const float *intensity, double radius, const double *grid,
@@ -1038,7 +1053,9 @@ int gg_icp_step(int num_source, const float *source, const float *source_intensi
  * and writes vertices / normals [num_vertices][3], colors [num_vertices][3] (only when both color and colors are
  * not NULL) and faces [num_faces][3]; num_vertices / num_faces are the capacities of those arrays (the counts read
  * back): nothing is written past them.  A count of -1 means the prefix scan gave up (never expected).
- * `ws`: gg_tsdf_mesh_workspace(dims) bytes (about 10 per point), 256-byte aligned; 0 for dims out of range. */
+ * `ws`: gg_tsdf_mesh_workspace(dims) bytes (about 10 per point), 256-byte aligned, of any content on entry of
+ * gg_tsdf_mesh_count, read only by gg_tsdf_mesh_emit; 0 for dims out of range.  Every fp32 array of the three calls and
+ * faces 4-byte aligned, counts 8-byte.  gg_tsdf_integrate with num_views == 0 writes nothing. */
 #define GG_TSDF_MAX_POINTS (1 << 27)
 #define GG_TSDF_MAX_DIM 4096
 #define GG_TSDF_MAX_VIEWS (1 << 20)
