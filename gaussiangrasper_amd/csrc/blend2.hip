@@ -391,26 +391,35 @@ void blend2_fwd_kernel(
 // The exact-order pair forward above contracts over TWO Gaussians per v_mfma_f32_32x32x2_f32 (64 cycles each: a quarter
 // of the kernel's issue budget, r03 counters), spends 5.5 issue slots per pair on the v_permlane32_swap that builds its A
 // operand and 8 fma per (pixel, Gaussian) on the second array.  Here the survivors of the quadrant cull are QUEUED
-// (ascending list order) until 32 are there; the walk — the same sigma / exp / alpha / T arithmetic, operation for
+// (ascending list order) until 16 are there; the walk — the same sigma / exp / alpha / T arithmetic, operation for
 // operation, so final_T, final_idx and every pass / stop decision keep their bits — only writes vis = alpha T into a
 // slab [pixel][slot]; the batch then ends with ONE product
-//     OUT[64 pixels x 48 channels] += VIS[64 x 32 slots] * COL[32 x 48]        (32 feature channels | <= 8 of the second
-// array | padding) as 4 x 3 tiles of v_mfma_f32_16x16x32_f16 on fp16 TWO-PIECE operands (gg_common.h: x s = hi + lo,
-// four piece products per tile, fp32 accumulation): 48 MFMAs of 16 cycles per 32 Gaussians instead of 32 of 64 cycles
-// plus 256 fma.  Scales (powers of two, exact): vis x 2^15 (alpha T lies in [3.9e-7, 1)); the colours of a batch one
-// scale per CHANNEL (largest |colour| of the 32 slots into [2^14, 2^15)), taken out of the tile's result before it is
+//     OUT[64 pixels x 48 channels] += VIS[64 x 16 slots] * COL[16 x 48]        (32 feature channels | <= 8 of the second
+// array | padding) as 4 x 3 tiles of v_mfma_f32_16x16x32_f16 on fp16 TWO-PIECE operands (gg_common.h: x s = hi + lo).
+// The two pieces are concatenated along K: a lane's A operand is [hi x 4 | lo x 4] of its four slots, B is [Bh x 4 | Bh x 4]
+// for one instruction and [Bl x 4 | Bl x 4] for the other, so two instructions per tile give all four piece products
+// (hi Bh + lo Bh, hi Bl + lo Bl; fp32 accumulation): 24 MFMAs of 16 cycles per 16 Gaussians instead of 16 of 64 cycles
+// plus 128 fma.  Scales (powers of two, exact): vis x 2^15 (alpha T lies in [3.9e-7, 1)); the colours of a batch one
+// scale per CHANNEL (largest |colour| of the 16 slots into [2^14, 2^15)), taken out of the tile's result before it is
 // added to the fp32 accumulators.  Images therefore equal the exact-order kernel's to fp32 rounding, not bit for bit:
 // per channel the error is <= ~2^-22 of (largest |colour| of the batch) x (sum of vis) — elements more than 2^12 below
 // their channel's largest colour of the batch keep an ABSOLUTE error of 2^-40 of that colour (fp16 denormals) —
 // against the exact kernel's own ~n 2^-24 of the sequential fp32 sum.  tests/test_fast_forward.py holds the images to
 // 1e-6 (1 + |value|) of the oracle's and final_T / final_idx to its bits.
-// LDS per wave: queue 3.2 KB + slab 8 KB (16-byte chunks of a pixel's 32 slots XOR-swizzled by the pixel: the walk's
-// ds_write_b128 and the product's ds_read_b128 both spread over the banks).  One quadrant per 64-thread workgroup
-// (as the wide backward): 14 waves per CU by LDS.
-#define FB_SLOTS 32
-#define FB_QCAP 100     // <= 31 left over + 64 staged + 4 null records behind the last survivor
+// LDS per wave: queue 2.7 KB + slab 4 KB.  The slab is [pixel][4 chunks of 16 bytes], chunk c of pixel P stored at
+// c ^ ((P >> 1) & 3): the walk's ds_write_b128 (banks modulo 32, 8 consecutive lanes a group: bank slot 4 (P & 1) + chunk)
+// and the product's ds_read_b128 (banks modulo 64, the four 16-lane groups: bank slot 4 (P & 3) + chunk) both touch every
+// bank slot once per group.  One quadrant per 64-thread workgroup (as the wide backward); LDS allows 24 workgroups per
+// CU, so the 128 registers decide: four waves per SIMD (32-slot batches: 11.4 KB, 14 workgroups per CU, 0.384-0.388 ms
+// against 0.362 now; GG_FB_WAVES=5 reaches 96 registers only by spilling 56 values: 0.455 ms —
+// profiles/pair_forward_16slot.txt).
+#define FB_SLOTS 16
+#define FB_QCAP 84      // <= 15 left over + 64 staged + 4 null records behind the last survivor
 #ifndef GG_FB_WAVES
-#define GG_FB_WAVES 3
+#define GG_FB_WAVES 4
+#endif
+#ifndef GG_FB_ALWAYS_EXCHANGE   // measurement switch: form every batch's channel maximum across the lanes (see run_batch)
+#define GG_FB_ALWAYS_EXCHANGE 0
 #endif
 struct __attribute__((aligned(16))) FwdQueue {
     float4 a[FB_QCAP];   // x, y, opacity, list position + 1 (int bits)
@@ -426,6 +435,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GG_FB_WAVES)
     int32_t *__restrict__ final_idx, Seg2 seg2, unsigned bytes1, unsigned bytes2) {
     __shared__ FwdQueue s_q;
     __shared__ __attribute__((aligned(16))) float s_vis[64 * FB_SLOTS];
+#ifdef GG_FB_LDS_PAD   // measurement builds: dead LDS, fewer workgroups per CU (profiles/pair_forward_16slot.txt)
+    __shared__ char s_pad[GG_FB_LDS_PAD];
+    asm volatile("" ::"v"(&s_pad[threadIdx.x]));
+#endif
     int wave;
     const int tile = blend_tile_wave<1>(blockIdx.x, threadIdx.x, ntiles, wave);
     if (tile < 0) return;
@@ -466,15 +479,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GG_FB_WAVES)
     const unsigned rowb1 = 4u * (unsigned)C, rowb2 = 4u * (unsigned)seg2.C2;
     const unsigned lane_off1 = 4u * (unsigned)sl, lane_off2 = ch2_ok ? 4u * (unsigned)sl : 0u;
 
-    // one batch: queue entries [base, base + n), n <= 32, null records behind the last one up to a multiple of GRP
+    // one batch: queue entries [base, base + n), n <= 16, null records behind the last one up to a multiple of GRP
     auto run_batch = [&](const int base, const int n) {
-        // B operands COL[slot 8 q4 + t][channel 16 nb + sl]: requested here, used after the walk
+        // B operands COL[slot 4 q4 + t][channel 16 nb + sl]: requested here, used after the walk
         // (buffer loads: row offset = id x row bytes as ONE 24-bit multiply-add per load instead of 64-bit address
         //  arithmetic — the launcher takes this kernel only for arrays below 4 GB and ids below 2^24)
-        float cb[3][8];
+        float cb[3][4];
 #pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            const int s_ = min(8 * q4 + t, n - 1);          // slots past the batch repeat its last Gaussian (vis = 0 there)
+        for (int t = 0; t < 4; ++t) {
+            const int s_ = min(4 * q4 + t, n - 1);          // slots past the batch repeat its last Gaussian (vis = 0 there)
             const unsigned gid = (unsigned)__builtin_bit_cast(int, Q.b[base + s_].w);
             const unsigned o1 = __umul24(gid, rowb1) + lane_off1;
             cb[0][t] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs1, (int)o1, 0, 0));
@@ -506,67 +519,59 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GG_FB_WAVES)
                 done = done || stop;
                 if (q == 1) __builtin_amdgcn_sched_barrier(0);   // two Gaussians' records in flight at a time
             }
-            *reinterpret_cast<float4 *>(vis_w + lane * FB_SLOTS + ((((g >> 2) ^ lane) & 7) << 2)) =
+            *reinterpret_cast<float4 *>(vis_w + lane * FB_SLOTS + ((((g >> 2) ^ (lane >> 1)) & 3) << 2)) =
                 make_float4(vis[0], vis[1], vis[2], vis[3]);
             nw = g + GRP;
         }
         for (int g = nw; g < FB_SLOTS; g += GRP)
-            *reinterpret_cast<float4 *>(vis_w + lane * FB_SLOTS + ((((g >> 2) ^ lane) & 7) << 2)) =
+            *reinterpret_cast<float4 *>(vis_w + lane * FB_SLOTS + ((((g >> 2) ^ (lane >> 1)) & 3) << 2)) =
                 make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         __builtin_amdgcn_wave_barrier();
-        // B: two fp16 pieces of colour x csc (the channel's running scale); a batch with a larger colour shrinks the
-        // scale and rescales the channel's accumulators first (rare after a wave's first batches: wave-uniform branch)
+        // B: two fp16 pieces of colour x csc (the channel's running scale), each piece twice along K.  A batch with a
+        // larger colour shrinks the scale and rescales the channel's accumulators first.  The new scale is
+        // min(csc, pow2_scale(largest |colour| of the channel's 16 slots)), and pow2_scale only falls as its argument
+        // grows, so the scale stays csc unless some lane's OWN four slots ask for less: the exchange across the four
+        // lanes of a channel (two v_permlane*_swap per channel block) and the rescale run only then — rare after a
+        // wave's first batches, wave-uniform branch, same bits as the unconditional exchange (GG_FB_ALWAYS_EXCHANGE).
         h16x8 Bh[3], Bl[3];
-        float fac[3];
-        bool shrink = false;
 #pragma unroll
         for (int nb = 0; nb < 3; ++nb) {
-            float m = fmaxf(fmaxf(fabsf(cb[nb][0]), fabsf(cb[nb][1])), fabsf(cb[nb][2]));
-            m = fmaxf(fmaxf(m, fabsf(cb[nb][3])), fabsf(cb[nb][4]));
-            m = fmaxf(fmaxf(m, fabsf(cb[nb][5])), fmaxf(fabsf(cb[nb][6]), fabsf(cb[nb][7])));
-            {
+            float m = fmaxf(fmaxf(fabsf(cb[nb][0]), fabsf(cb[nb][1])), fmaxf(fabsf(cb[nb][2]), fabsf(cb[nb][3])));
+            if (GG_FB_ALWAYS_EXCHANGE || __ballot(pow2_scale(m) < csc[nb]) != 0ull) {
                 auto r16 = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, m), __builtin_bit_cast(unsigned, m), false, false);
                 m = fmaxf(__builtin_bit_cast(float, (unsigned)r16[0]), __builtin_bit_cast(float, (unsigned)r16[1]));
                 auto r32 = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, m), __builtin_bit_cast(unsigned, m), false, false);
                 m = fmaxf(__builtin_bit_cast(float, (unsigned)r32[0]), __builtin_bit_cast(float, (unsigned)r32[1]));
+                const float sb = fminf(csc[nb], pow2_scale(m));
+                if (__ballot(sb != csc[nb]) != 0ull) {
+                    const float fac = sb * pow2_inv(csc[nb]);      // 1, or the power of two < 1 the accumulators shrink by
+#pragma unroll
+                    for (int blk = 0; blk < 4; ++blk)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) acc[blk][nb][r] *= fac;
+                }
+                csc[nb] = sb;
             }
-            const float sb = fminf(csc[nb], pow2_scale(m));
-            fac[nb] = sb * pow2_inv(csc[nb]);      // 1, or the power of two < 1 the accumulators shrink by
-            shrink = shrink || sb != csc[nb];
-            csc[nb] = sb;
-            unsigned h_[4], l_[4];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) split2h(cb[nb][2 * t] * sb, cb[nb][2 * t + 1] * sb, h_[t], l_[t]);
-            Bh[nb] = H8(h_[0], h_[1], h_[2], h_[3]);
-            Bl[nb] = H8(l_[0], l_[1], l_[2], l_[3]);
-        }
-        if (__ballot(shrink) != 0ull) {
-#pragma unroll
-            for (int blk = 0; blk < 4; ++blk)
-#pragma unroll
-                for (int nb = 0; nb < 3; ++nb)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) acc[blk][nb][r] *= fac[nb];
+            const float sb = csc[nb];
+            unsigned h0, l0, h1, l1;
+            split2h(cb[nb][0] * sb, cb[nb][1] * sb, h0, l0);
+            split2h(cb[nb][2] * sb, cb[nb][3] * sb, h1, l1);
+            Bh[nb] = H8(h0, h1, h0, h1);
+            Bl[nb] = H8(l0, l1, l0, l1);
         }
 #pragma unroll
         for (int blk = 0; blk < 4; ++blk) {
-            // A: 2^15 VIS[pixel 16 blk + sl][slot 8 q4 + 0..7]
+            // A: 2^15 VIS[pixel 16 blk + sl][slot 4 q4 + 0..3] as [hi x 4 | lo x 4]
             const int P = 16 * blk + sl;
-            const float4 v0 = *reinterpret_cast<const float4 *>(vis_w + P * FB_SLOTS + ((((2 * q4) ^ P) & 7) << 2));
-            const float4 v1 = *reinterpret_cast<const float4 *>(vis_w + P * FB_SLOTS + ((((2 * q4 + 1) ^ P) & 7) << 2));
-            unsigned ah[4], al[4];
-            split2h(v0.x, v0.y, ah[0], al[0]);
-            split2h(v0.z, v0.w, ah[1], al[1]);
-            split2h(v1.x, v1.y, ah[2], al[2]);
-            split2h(v1.z, v1.w, ah[3], al[3]);
-            const h16x8 Ah = H8(ah[0], ah[1], ah[2], ah[3]), Al = H8(al[0], al[1], al[2], al[3]);
+            const float4 v = *reinterpret_cast<const float4 *>(vis_w + P * FB_SLOTS + (((q4 ^ (sl >> 1)) & 3) << 2));
+            unsigned ah0, al0, ah1, al1;
+            split2h(v.x, v.y, ah0, al0);
+            split2h(v.z, v.w, ah1, al1);
+            const h16x8 A = H8(ah0, ah1, al0, al1);
 #pragma unroll
-            for (int nb = 0; nb < 3; ++nb) {
-                acc[blk][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al, Bl[nb], acc[blk][nb], 0, 0, 0);
-                acc[blk][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al, Bh[nb], acc[blk][nb], 0, 0, 0);
-                acc[blk][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah, Bl[nb], acc[blk][nb], 0, 0, 0);
-                acc[blk][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah, Bh[nb], acc[blk][nb], 0, 0, 0);
-            }
+            for (int nb = 0; nb < 3; ++nb) acc[blk][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A, Bl[nb], acc[blk][nb], 0, 0, 0);
+#pragma unroll
+            for (int nb = 0; nb < 3; ++nb) acc[blk][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A, Bh[nb], acc[blk][nb], 0, 0, 0);
         }
         __builtin_amdgcn_wave_barrier();   // the slab is rewritten by the next batch's walk
     };
@@ -601,7 +606,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GG_FB_WAVES)
             done_n += FB_SLOTS;
         }
         if (!alive) break;
-        if (done_n > 0) {   // bring the left-over (< 32) to the front; source and destination do not overlap
+        if (done_n > 0) {   // bring the left-over (< 16) to the front; source and destination do not overlap
             const int left = qn - done_n;
             if (lane < left) { const float4 ta = Q.a[done_n + lane]; __builtin_amdgcn_wave_barrier(); Q.a[lane] = ta; }
             __builtin_amdgcn_wave_barrier();
@@ -610,7 +615,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GG_FB_WAVES)
             __builtin_amdgcn_wave_barrier();
         }
     }
-    if (alive && qn > 0) {   // what is left at the end of the list (< 32): null records behind it, one last batch
+    if (alive && qn > 0) {   // what is left at the end of the list (< 16): null records behind it, one last batch
         if (lane < GRP) {
             Q.a[qn + lane] = make_float4(0.f, 0.f, 0.f, 0.f);                                 // opacity 0: never passes
             Q.b[qn + lane] = make_float4(0.f, 0.f, 0.f, Q.b[qn - 1].w);
@@ -633,30 +638,33 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GG_FB_WAVES)
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[blk][nb][r] *= un;
     }
-    // first array: the accumulators go through the slab ([pixel][32 channels]) and leave as float4, one image row of the
-    // quadrant (1 KB) per store instruction
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int blk = 0; blk < 4; ++blk)
-#pragma unroll
-        for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) vis_w[(16 * blk + 4 * q4 + r) * 32 + 16 * nb + sl] = acc[blk][nb][r];
-    __builtin_amdgcn_wave_barrier();
+    // first array: the accumulators go through the slab ([pixel][32 channels], 32 pixels = two pixel blocks at a time) and
+    // leave as float4, one image row of the quadrant (1 KB) per store instruction
     {
         const int chunk = lane & 7;
         const float4 bg4 = *reinterpret_cast<const float4 *>(background + 4 * chunk);
 #pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            const int pq = (lane >> 3) + 8 * t;
-            const float4 v = *reinterpret_cast<const float4 *>(vis_w + pq * 32 + 4 * chunk);
-            const float Tp = __shfl(T, pq, 64);
-            const int pj = qx0 + (pq & 7), pi = qy0 + (pq >> 3);
-            if (pi < img_h && pj < img_w) {
-                typedef float f4v __attribute__((ext_vector_type(4)));
-                const f4v o = {__builtin_fmaf(Tp, bg4.x, v.x), __builtin_fmaf(Tp, bg4.y, v.y),
-                               __builtin_fmaf(Tp, bg4.z, v.z), __builtin_fmaf(Tp, bg4.w, v.w)};
-                *reinterpret_cast<f4v *>(out_img + ((size_t)pi * img_w + pj) * C + 4 * chunk) = o;
+        for (int half = 0; half < 2; ++half) {
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int b2 = 0; b2 < 2; ++b2)
+#pragma unroll
+                for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) vis_w[(16 * b2 + 4 * q4 + r) * 32 + 16 * nb + sl] = acc[2 * half + b2][nb][r];
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const int pl = (lane >> 3) + 8 * t, pq = 32 * half + pl;
+                const float4 v = *reinterpret_cast<const float4 *>(vis_w + pl * 32 + 4 * chunk);
+                const float Tp = __shfl(T, pq, 64);
+                const int pj = qx0 + (pq & 7), pi = qy0 + (pq >> 3);
+                if (pi < img_h && pj < img_w) {
+                    typedef float f4v __attribute__((ext_vector_type(4)));
+                    const f4v o = {__builtin_fmaf(Tp, bg4.x, v.x), __builtin_fmaf(Tp, bg4.y, v.y),
+                                   __builtin_fmaf(Tp, bg4.z, v.z), __builtin_fmaf(Tp, bg4.w, v.w)};
+                    *reinterpret_cast<f4v *>(out_img + ((size_t)pi * img_w + pj) * C + 4 * chunk) = o;
+                }
             }
         }
     }

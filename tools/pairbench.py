@@ -5,7 +5,9 @@ and cross-device variance that looks like a kernel property):
 
     python tools/pairbench.py [--libs product variants/libA.so variants/libB.so] [--rounds 3] [--reps 6]
 
-prints one JSON line per library: label, per-kernel ms (median over the rounds, and the minimum)."""
+prints one JSON line per library: label, per-kernel ms (median over the rounds, and the minimum), and whether its two
+forward images equal the first library's bit for bit (how a measurement switch that must not change a result is held
+to that: -DGG_FB_ALWAYS_EXCHANGE=1 beside the product)."""
 import argparse
 import ctypes
 import json
@@ -74,12 +76,15 @@ def main():
             torch.autograd.backward(imgs, vo)
         torch.cuda.synchronize()
         lib.gg_prof_enable(0)
-        return prof(lib) if timed else None
+        return prof(lib) if timed else [i.detach().clone() for i in imgs]
 
     res = {p: [] for p, _ in libs}
     try:
+        first, same = None, {}
         for p, lib in libs:
-            run(lib, 2, False)
+            imgs = run(lib, 2, False)
+            first = first or imgs
+            same[p] = all(torch.equal(a, b) for a, b in zip(imgs, first))
         for _ in range(args.rounds):
             for p, lib in libs:
                 res[p].append(run(lib, args.reps, True))
@@ -89,7 +94,7 @@ def main():
         names = sorted({k for r in res[p] for k in r if any(s in k for s in keys)})
         med = {k: round(statistics.median(r[k] for r in res[p] if k in r), 4) for k in names}
         mn = {k: round(min(r[k] for r in res[p] if k in r), 4) for k in names}
-        print(json.dumps({"label": p, "median_ms": med, "min_ms": mn}), flush=True)
+        print(json.dumps({"label": p, "median_ms": med, "min_ms": mn, "images_equal_first": same[p]}), flush=True)
 
 
 if __name__ == "__main__":
