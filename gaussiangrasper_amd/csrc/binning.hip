@@ -285,7 +285,9 @@ __global__ __launch_bounds__(RS_THREADS) void radix_scatter_kernel(
 //   db_offsets  exclusive scan of the bucket sums (one workgroup).
 // emit_kernel adds a Gaussian's in-bucket offset to its bucket's and reads nothing by Gaussian id.  7 launches instead of
 // 15; same order bit for bit
-// (tests/test_gpu_parity.py binning tests, incl. depth ties and runs beyond 512).
+// (tests/test_gpu_parity.py binning tests, incl. depth ties and runs beyond 512; tests/test_binning_constructed.py: a run
+// of every length either side of 64 / 128 / 192 / 256 / 512 / 1 024, tile grids up to 1023 x 1023 with one to three tile
+// passes, list lengths around the 16-keys-per-thread switch, handed-over range parts, 16 384 and 32 768 buckets).
 // ---------------------------------------------------------------------------------------------
 typedef unsigned long long u64;
 #define DB_BLOCKS 64

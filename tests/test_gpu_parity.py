@@ -249,6 +249,19 @@ def test_binning_truncated_capacity_stays_in_bounds(oracle):
     assert np.all(got_ids[cap:] == -7), "written past the capacity"
     ids_in = got_ids[:cap]
     assert ids_in.min() >= 0 and ids_in.max() < n
+    # what holds for any design that truncates in bounds: well-formed ranges that do not overlap, and in every tile
+    # some of the oracle's entries for that tile, in the oracle's order
+    assert np.all(got_bins[:, 0] <= got_bins[:, 1]), "a range ends before it starts"
+    filled = got_bins[got_bins[:, 0] < got_bins[:, 1]]
+    assert np.all(filled[1:, 0] >= filled[:-1, 1]), "non-empty ranges overlap or do not ascend with the tile id"
+    ref_bins, ref_ids = np.asarray(ref["tile_bins"]).reshape(-1, 2), np.asarray(ref["gaussian_ids_sorted"])
+    place = np.full(n, -1, np.int64)
+    for tile, ((s, e), (rs, re)) in enumerate(zip(got_bins, ref_bins)):
+        place[:] = -1
+        place[ref_ids[rs:re]] = np.arange(re - rs)          # (a Gaussian is in a tile's list once)
+        at = place[ids_in[s:e]]
+        assert np.all(at >= 0), f"tile {tile}: an entry that is not in the oracle's list for this tile"
+        assert np.all(np.diff(at) > 0), f"tile {tile}: entries repeated or out of the oracle's order"
 
 
 def _blend_inputs(oracle, n, h, w, ch, seed=0, cfg=1):
