@@ -1,6 +1,7 @@
 """What the command lines of grasp, grasp_propose, mesh and cluster share: the options that say which Gaussians are
 the object (the convex hull of --object-points, or the LERF relevancy of --positives against --negatives above
---threshold; of that selection, with --instance, one DBSCAN instance), their cross-checks, the mask they select, and
+--threshold — per Gaussian, or with --views in rendered views and lifted — or the 2-D masks of --object-masks lifted
+over --views; of that selection, with --instance, one DBSCAN instance), their cross-checks, the mask they select, and
 the per-grasp arrays of a --report file; and the options of the support plane (--support-plane fits or loads the
 table's plane, --remove-support takes the Gaussians that are not above it out of the selection, and the grasp command
 lines also hold the gripper above it)."""
@@ -138,7 +139,7 @@ def check_support_options(ap, a, grasp: bool = True) -> None:
             ap.error("--support-dist goes with --support-plane fit (a plane file holds its own)")
         if not (math.isfinite(a.support_dist) and a.support_dist >= 0.0):
             ap.error(f"--support-dist must be finite and >= 0, got {a.support_dist}")
-    if a.remove_support and not (getattr(a, "object_points", None) or a.positives):
+    if a.remove_support and not (getattr(a, "object_points", None) or a.positives or getattr(a, "object_masks", None)):
         ap.error("--remove-support needs a selection to remove the support from")
     if grasp:
         if a.support_margin is not None and not math.isfinite(a.support_margin):
@@ -204,6 +205,13 @@ def add_object_options(ap, query_does: str, hull_does: str = None, instances: bo
     ap.add_argument("--positives", default=None, help=".npy text embeddings: " + query_does)
     ap.add_argument("--negatives", default=None, help=".npy canonical negatives (LERF relevancy)")
     ap.add_argument("--threshold", type=float, default=None, help="relevancy threshold for --positives")
+    ap.add_argument("--views", default=None, metavar="T.json",
+                    help="a scan's transforms.json (OpenCV c2w, raw frame; --transform-json maps it): with --positives "
+                         "the relevancy is thresholded in these rendered views and lifted onto the Gaussians "
+                         "(query.select_gaussians_in_views) instead of being taken per Gaussian")
+    ap.add_argument("--object-masks", default=None, metavar="DIR",
+                    help="with --views: one 2-D mask per frame, named by the frame's file stem; the Gaussians that "
+                         "carry label 1 are the object (lift.lift_labels)")
     if instances:
         ap.add_argument("--instance", type=instance_choice, default="all", metavar="{all,largest,K}",
                         help="of the selection, keep one DBSCAN instance (cluster.object_instances): the heaviest, or "
@@ -220,7 +228,14 @@ def check_object_options(ap, a, hull: str) -> None:
     """ap.error unless the selection is complete.  hull "optional": --object-points or --positives or neither;
     "required": exactly one of them; "none": the parser has no --object-points, and stray --negatives / --threshold
     pass."""
-    if hull == "required" and bool(a.object_points) == bool(a.positives):
+    views, masks = getattr(a, "views", None), getattr(a, "object_masks", None)
+    if masks and not views:
+        ap.error("--object-masks needs --views (the cameras the masks belong to)")
+    if masks and (a.positives or getattr(a, "object_points", None)):
+        ap.error("--object-masks is an alternative to --positives" + ("" if hull == "none" else " and --object-points"))
+    if views and not (masks or a.positives):
+        ap.error("--views needs --positives or --object-masks")
+    if hull == "required" and bool(a.object_points) == bool(a.positives) and not masks:
         ap.error("one of --object-points and --positives is needed (they are alternatives)")
     if hull == "optional" and a.object_points and a.positives:
         ap.error("--object-points and --positives are alternatives")
@@ -232,7 +247,7 @@ def check_object_options(ap, a, hull: str) -> None:
     given = [n for n in ("cluster_eps", "cluster_eps_scale", "cluster_min_points") if getattr(a, n, None) is not None]
     if given and inst == "all":
         ap.error("--" + given[0].replace("_", "-") + " needs --instance largest or --instance K")
-    if inst != "all" and not (getattr(a, "object_points", None) or a.positives):
+    if inst != "all" and not (getattr(a, "object_points", None) or a.positives or masks):
         ap.error("--instance needs a selection (--positives" + (")" if hull == "none" else " or --object-points)"))
     for n in ("cluster_eps", "cluster_eps_scale"):
         v = getattr(a, n, None)
@@ -278,10 +293,21 @@ def selection_mask(a, scene, mlp_state, matrix=None, scale: float = 1.0):
         pts = edit.filter_object_points(edit.object_points_to_scene(
             edit.load_object_points(a.object_points), np.eye(4) if matrix is None else matrix, scale))
         return edit.select_and_move(scene.means.contiguous(), None, edit.hull_planes(pts))[0]
+    if getattr(a, "object_masks", None):
+        from . import lift
+        cams, _ = lift.scene_cameras(a.views, getattr(a, "transform_json", None))
+        labs = [lift.read_label_image(lift.find_mask(a.object_masks, st)) for st in lift.frame_stems(a.views)]
+        top = max(int(m[m != lift.IGNORE].max(initial=0)) for m in labs)
+        return lift.select(lift.lift_labels(scene, cams, labs, max(top, 1) + 1).votes, 1)
     if a.positives:
         from . import query
         from .interop import fea_up_weights
         w = fea_up_weights(mlp_state, scene.means.device, a.ckpt, "for --positives")
+        if getattr(a, "views", None):
+            from . import lift
+            cams, _ = lift.scene_cameras(a.views, getattr(a, "transform_json", None))
+            return query.select_gaussians_in_views(scene, w, cams, query.load_embeddings(a.positives, "positives"),
+                                                   query.load_embeddings(a.negatives, "negatives"), a.threshold)
         return query.select_gaussians(scene, w, query.load_embeddings(a.positives, "positives"),
                                       query.load_embeddings(a.negatives, "negatives"), a.threshold)
     return None

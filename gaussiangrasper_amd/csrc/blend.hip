@@ -235,6 +235,28 @@ extern "C" int gg_blend_fwd_pair_packed(int C, int C2, int N, int img_h, int img
                                out_img2, fast != 0, true);
 }
 
+// gg_blend_votes: the per-Gaussian sums of the forward walk's blend weights by pixel label (kernel: votes.hip)
+extern "C" int gg_blend_votes(int num_labels, int N, int img_h, int img_w, const int32_t *ids, const int32_t *tile_bins,
+                              const float *xys, const float *conics, const float *opacity, const uint8_t *labels,
+                              int64_t *votes, void *ws, size_t ws_bytes, int ws_packed, gg_stream_t stream) {
+    GG_REQUIRE(num_labels >= 1 && num_labels <= 255, "num_labels must be 1..255");
+    GG_REQUIRE(labels != nullptr, "labels is null");
+    GG_REQUIRE(N == 0 || votes != nullptr, "votes is null");
+    GG_REQUIRE((reinterpret_cast<uintptr_t>(votes) & 7) == 0, "votes must be 8-byte aligned");
+    GG_REQUIRE(N <= 0 || ids != nullptr, "gaussian_ids_sorted is null");
+    GG_REQUIRE(tile_bins != nullptr, "tile_bins is null");
+    GG_REQUIRE(N <= 0 || ws_packed != 0 || (xys && conics && opacity), "xys, conics or opacity is null");
+    BlendWalk w;
+    const int rc = blend_begin(__func__, {N, img_h, img_w, ids, tile_bins, xys, conics, opacity, ws, ws_bytes, stream},
+                               false, true, true, ws_packed != 0, w);
+    if (rc != GG_OK || N == 0) return rc;
+    gg_prof_begin(GG_K_BLEND_VOTES, w.s);
+    gg_launch_blend_votes(w, num_labels, N, labels, votes);
+    gg_prof_end(GG_K_BLEND_VOTES, w.s);
+    GG_CHECK_LAUNCH();
+    return GG_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // deterministic backward: slab of per-(list entry, quadrant) totals + ordered per-Gaussian sums
 // ---------------------------------------------------------------------------------------------

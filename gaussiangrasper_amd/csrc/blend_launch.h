@@ -53,6 +53,8 @@ void gg_launch_blend2_bwd(const BlendWalk &w, const BlendColors &src, const Blen
                           const BlendGradOut &g, const DetSlab &det);
 void gg_launch_blend2_bwd_pair(const BlendWalk &w, const BlendColors &src, const BlendBwdIn &in, const BlendGradOut &g,
                                const BlendColors &src2, const BlendGrad2 &g2);
+// votes.hip: the vote walk of gg_blend_votes (labels (H, W) bytes, votes (N, L) int64, added to)
+void gg_launch_blend_votes(const BlendWalk &w, int L, int N, const uint8_t *labels, int64_t *votes);
 #ifdef GG_ABLATION
 void gg_launch_blend2_bwd_ablate(int abl, const BlendWalk &w, const BlendColors &src, const BlendChunk &ch,
                                  const BlendBwdIn &in, const BlendGradOut &g);

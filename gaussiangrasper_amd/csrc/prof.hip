@@ -126,6 +126,7 @@ extern "C" const char *gg_prof_name(int id) {
         case GG_K_GRASP_CLEAR: return "gg_grasp_clearance(all launches)";
         case GG_K_GRASP_NMS: return "gg_grasp_nms(all launches)";
         case GG_K_SUPPORT_PLANE: return "gg_support_plane(all launches)";
+        case GG_K_BLEND_VOTES: return "blend_votes_kernel";
         default: break;
     }
     if (id >= GG_K_BLEND_FWD && id < GG_K_BLEND_FWD + 6) {

@@ -541,6 +541,60 @@ def _blend_with_lists(bins: Binning, launch) -> bool:
     return bins.num_intersects >= 1
 
 
+@torch.no_grad()
+def blend_votes(xys: Tensor, depths: Tensor, radii: Tensor, conics: Tensor, num_tiles_hit: Tensor, opacity: Tensor,
+                img_height: int, img_width: int, labels: Tensor, votes: Tensor) -> bool:
+    """The transpose of the blend (`gg_blend_votes`): votes[g, l] += sum over the pixels of label l of
+    trunc(alpha T 2^24), alpha T being the weight with which the exact forward walk blends Gaussian g there.
+    labels (H, W) uint8, a label >= votes.shape[1] (255: ignore) votes for nobody; votes (N, L) int64, contiguous,
+    ADDED to.  The lists are those of a render of the same view (one binning, cached).  False: nothing is visible,
+    votes is untouched."""
+    if xys.ndimension() != 2 or xys.size(1) != 2:
+        raise ValueError("xys must have dimensions (N, 2)")
+    n = xys.size(0)
+    img_height, img_width = int(img_height), int(img_width)
+    if labels.dtype != torch.uint8 or tuple(labels.shape) != (img_height, img_width):
+        raise ValueError(f"labels must be a uint8 ({img_height}, {img_width}) tensor, got {labels.dtype} "
+                         f"{tuple(labels.shape)}")
+    if votes.dtype != torch.int64 or votes.ndimension() != 2 or votes.size(0) != n or not votes.is_contiguous():
+        raise ValueError(f"votes must be a contiguous int64 ({n}, L) tensor, got {votes.dtype} {tuple(votes.shape)}")
+    num_labels = votes.size(1)
+    if not 1 <= num_labels <= 255:
+        raise ValueError(f"votes must have 1..255 label columns, got {num_labels}")
+    if opacity.numel() != n:
+        raise ValueError(f"opacity must have {n} entries, got {tuple(opacity.shape)}")
+    dev = _require_hip(xys, depths, radii, conics, num_tiles_hit, opacity, labels, votes)
+    if n == 0:
+        return False
+    xys_c, conics_c, opacity_c = _f32(xys.detach()), _f32(conics.detach()), _f32(opacity.detach())
+    labels_c = labels.contiguous()
+    bins = bin_and_sort_gaussians(xys, depths, radii, num_tiles_hit, img_height, img_width, speculative=True)
+    lib = _lib.load()
+    ws = _workspace(lib.gg_blend_workspace(n), dev)
+    # The call adds, so a walk over lists that turn out truncated (speculative capacity too small: rare) must not
+    # reach `votes`: while the lists' length is unknown the walk adds to a zeroed scratch array instead, which is
+    # added to `votes` once the lists are known to be whole (integer adds: the same bits either way).
+    scratch = []
+
+    def launch():
+        out = votes
+        if bins.num_intersects is None:
+            out = torch.zeros_like(votes)
+            scratch[:] = [out]
+        else:
+            scratch.clear()
+        _lib.check(lib.gg_blend_votes(num_labels, n, img_height, img_width, _ptr(bins.gaussian_ids_sorted),
+                                      _ptr(bins.tile_bins), _ptr(xys_c), _ptr(conics_c), _ptr(opacity_c),
+                                      _ptr(labels_c), _ptr(out), _ptr(ws), ws.numel(), 0, _stream(dev)),
+                   "gg_blend_votes")
+
+    if not _blend_with_lists(bins, launch):
+        return False
+    if scratch:
+        votes.add_(scratch[0])
+    return True
+
+
 def _rasterize_forward(ctx, xys, depths, radii, conics, num_tiles_hit, colors, opacity,
                        img_height, img_width, background, three_channel_only):
     if colors.dtype == torch.uint8:

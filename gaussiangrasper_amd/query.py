@@ -11,6 +11,9 @@ One HIP kernel (`gg_clip_query`, csrc/query.hip) computes both without writing t
     relevancy_view(model, camera, positives, negatives)        {"relevancy": (H, W, P)[, "similarity": (H, W, Q)]}
     relevancy_gaussians(model_or_scene, fea_up, pos, neg)      (N, P) over the Gaussians' own features
     select_gaussians(model_or_scene, fea_up, pos, neg, t)      (N,) bool: semantic selection
+    select_gaussians_in_views(model_or_scene, fea_up, cameras, pos, neg, t)
+                                                               (N,) bool: the selection made in rendered views and
+                                                               lifted onto the Gaussians (lift.py)
     python -m gaussiangrasper_amd.query --ckpt ... --positives pos.npy [--negatives neg.npy] --out scores.npy
 
 `fea_up` is any module with Linear `layers[0]` / `layers[2]` (mlp.MLP, stub.MLP, the reference's MLP) or a tuple
@@ -224,6 +227,51 @@ def select_gaussians(model_or_scene, fea_up, positives: ArrayLike, negatives: Ar
                      temperature: float = DEFAULT_TEMPERATURE) -> Tensor:
     """Semantic selection: (N,) bool, True where the relevancy to any positive exceeds `threshold`."""
     return (relevancy_gaussians(model_or_scene, fea_up, positives, negatives, temperature) > float(threshold)).any(dim=-1)
+
+
+@torch.no_grad()
+def lift_relevancy(model_or_scene, fea_up, cameras, positives: ArrayLike, negatives: ArrayLike, threshold: float,
+                   temperature: float = DEFAULT_TEMPERATURE):
+    """lift.Votes with two labels over `cameras` (as mesh.mesh_model takes them): per camera the feature image is
+    rendered (lift.project_view, ops.rasterize_segments with a second segment of ones for the alpha sum), a pixel is
+    labelled 1 where any positive's relevancy exceeds `threshold` and the alpha sum is >= mesh.ALPHA_MIN, 0
+    otherwise, and the labels are lifted through the same view's tile lists (ops.blend_votes)."""
+    from . import lift, ops
+    from .mesh import ALPHA_MIN
+    fea_up = getattr(model_or_scene, "fea_up", None) if fea_up is None else fea_up
+    feat = _gaussian_features(model_or_scene)
+    dev = _require_hip(feat)
+    feat = feat.float().contiguous()
+    n = feat.shape[0]
+    votes = torch.zeros(n, 2, dtype=torch.int64, device=dev)
+    counts = np.zeros(2, np.int64)
+    ones = torch.ones(n, 1, device=dev)
+    views = 0
+    for c2w, K, h, w in cameras:
+        h, w = int(h), int(w)
+        views += 1
+        if n == 0:
+            continue
+        proj = lift.project_view(model_or_scene, c2w, K, h, w)
+        img, alpha = ops.rasterize_segments(*proj, h, w, [(feat, torch.zeros(feat.shape[1], device=dev)),
+                                                           (ones, torch.zeros(1, device=dev))])
+        rel = relevancy(img, fea_up, positives, negatives, temperature)
+        lab = ((rel > float(threshold)).any(dim=-1) & (alpha[..., 0] >= ALPHA_MIN)).to(torch.uint8)
+        ones_px = int(lab.sum())
+        counts += np.asarray([h * w - ones_px, ones_px], np.int64)
+        ops.blend_votes(*proj, h, w, lab, votes)
+    return lift.Votes(votes, views, counts)
+
+
+def select_gaussians_in_views(model_or_scene, fea_up, cameras, positives: ArrayLike, negatives: ArrayLike,
+                              threshold: float, min_ratio: float = 0.5,
+                              temperature: float = DEFAULT_TEMPERATURE) -> Tensor:
+    """Semantic selection made where the features were supervised — in rendered pixels — and lifted onto the
+    Gaussians: (N,) bool, True where label 1 of lift_relevancy holds at least `min_ratio` of the Gaussian's blend
+    weight over `cameras`.  select_gaussians thresholds each Gaussian's own feature instead."""
+    from . import lift
+    res = lift_relevancy(model_or_scene, fea_up, cameras, positives, negatives, threshold, temperature)
+    return lift.select(res.votes, 1, min_ratio)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -381,6 +381,33 @@ int gg_blend_bwd_deterministic(int channels, int num_points, int img_height, int
                                int flags, int64_t num_intersects, void *det_ws, size_t det_ws_bytes,
                                gg_stream_t stream);
 
+/* gg_blend_votes: the transpose of the blend.  For every Gaussian, the blend weight with which the forward walk
+ * blended it into the pixels of each label, as an integer sum: what lifts a 2-D label image (a segmenter's mask, a
+ * thresholded relevancy image) onto the Gaussians, occlusion included (a hidden Gaussian has no weight).
+ *
+ *   vis(p, g)    the value by which the exact forward walk (gg_blend_fwd) multiplies g's colour at pixel p, for g in
+ *                the list of p's tile: alpha T when g is blended — the same sigma, gg_exp, alpha, T operations in
+ *                fp32 in the same order — and 0 when sigma < 0, when alpha < 1/255, and once the walk has stopped
+ *                (the Gaussian that would take T to <= 1e-4 is not blended and gets no vote);
+ *   q(p, g)      (int64) trunc(vis 2^24).  The product is exact in fp32; vis <= 0.999, so q < 2^24, and a blended
+ *                pair has vis >= ~3.9e-7 (alpha >= 1/255, T > 1e-4), so q >= 6;
+ *   votes[g, l] += sum over the pixels p inside the image with labels[p] == l of q(p, g).
+ *
+ * The call ADDS to votes (N, num_labels) int64, 8-byte aligned: the caller zeroes it once and accumulates view after
+ * view.  labels (H, W) bytes, any alignment; a pixel whose label is >= num_labels (255: "ignore") takes part in no
+ * sum.  Integer additions commute, so the result is a pure function of the inputs: identical bits from run to run,
+ * whatever the schedule.  A vote is exact as a double below 2^53, i.e. ~5e8 fully opaque pixel hits.
+ * num_labels: 1..255.  ws: gg_blend_workspace(num_points) bytes; ws_packed != 0: ws already holds these Gaussians'
+ * packed records (the workspace of a gg_blend_fwd over the same xys / conics / opacity, or gg_view_fwd's `records`),
+ * as GG_BWD_WS_FROM_FORWARD says for the backward — xys, conics and opacity are then not read.  Null or invalid
+ * arguments: GG_ERR_INVALID_ARG with the argument's name in gg_last_error(), before any launch.  num_points == 0
+ * or empty tile lists: GG_OK, nothing is written. */
+int gg_blend_votes(int num_labels, int num_points, int img_height, int img_width,
+                   const int32_t *gaussian_ids_sorted, const int32_t *tile_bins, const float *xys,
+                   const float *conics, const float *opacity, const uint8_t *labels /* (H, W) */,
+                   int64_t *votes /* (N, num_labels) */, void *ws, size_t ws_bytes, int ws_packed,
+                   gg_stream_t stream);
+
 /* ---- feature up-projection MLP ------------------------------------------------
  * Replaces the forward of the reference's `MLP(32, 512, hidden_list=[128])` module
  * (nerfstudio/models/gaussian_splatting.py:198-213; `self.fea_up`, called on every pixel of the
@@ -1087,6 +1114,7 @@ int gg_tsdf_mesh_emit(const int32_t *dims, const float *grid, const float *tsdf,
 #define GG_K_MLP_BWD 9
 #define GG_K_BLEND_FWD 10 /* + width index: template widths {1,3,4,8,16,32} -> 0..5 */
 #define GG_K_BLEND_BWD 20 /* + width index */
+#define GG_K_BLEND_VOTES 14 /* gg_blend_votes' walk: in the forward's range, the slot of the 16-wide build that no chunk plan uses */
 #define GG_K_BLEND_FWD_PAIR 16 /* 32 channels + a second array of <= 8 in one walk */
 #define GG_K_BLEND_BWD_PAIR 17
 #define GG_K_COMPACT 26
