@@ -91,6 +91,7 @@ SIGNATURES = {
     "gg_geom_loss_fwd": (_I, [_I64, _P, _I, _P, _I, _P, _I, _I, _P, _I, _I, _P, _P, _P, _SZ, _P]),
     "gg_geom_loss_bwd": (_I, [_I64, _P, _I, _P, _I, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _SZ, _P, _P, _P]),
     "gg_shade_tail_fwd": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "gg_shade_tail_fwd_ex": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
     "gg_shade_tail_bwd": (_I, [_I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P]),
     "gg_blend_bwd_pair": (_I, [_I, _I, _I, _I, _I] + [_P] * 12 + [C.POINTER(_P), C.POINTER(_I), _I] + [_P] * 5
                           + [_I, _I, _I, _P, _SZ, _I, _P]),

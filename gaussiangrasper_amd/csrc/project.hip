@@ -609,8 +609,12 @@ __host__ __device__ static inline int sh_nbases(int deg) {
 // clamp(sh + 0.5, 0, 1) (reference gaussian_splatting.py:731) written to columns 0..2 of a (N, 7) row, depth to
 // column 3, the normal to 4..6, and one byte per Gaussian saying which of the three clamps let the gradient
 // through (torch.clamp: min <= x <= max) for the backward.
-template <int K, bool TAIL = false>
-__global__ __launch_bounds__(256) void sh_fwd_kernel(int N, int deg,
+// WAVES: waves per workgroup (they share nothing: each wave stages and evaluates its own rows).  1 = a one-wave
+// workgroup with a quarter of the LDS (9.6 KB at K = 25), which is placed where one blend workgroup of another stream
+// has just finished; the four-wave workgroup (38 KB) is not placed beside a blend kernel until that kernel drains, and
+// everything behind it in its stream waits (profiles/forward_chain_overlap.txt).  Same rows per wave, same bits.
+template <int K, bool TAIL = false, int WAVES = 4>
+__global__ __launch_bounds__(64 * WAVES) void sh_fwd_kernel(int N, int deg,
                                                      const float *__restrict__ viewdirs,
                                                      const float *__restrict__ coeffs,
                                                      float *__restrict__ colors,
@@ -621,9 +625,9 @@ __global__ __launch_bounds__(256) void sh_fwd_kernel(int N, int deg,
     // the resident waves and with them the loads in flight — the kernel only moves bytes
     // (K = 25, N = 1 M: 0.112 -> 0.092 ms = 3.4 TB/s; 16 rows per wave: no further change)
     constexpr int ROW = 3 * K, SH_ROWS = (K >= 16) ? 32 : 64;
-    __shared__ float stage[4][SH_ROWS * ROW];
+    __shared__ float stage[WAVES][SH_ROWS * ROW];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int base = (blockIdx.x * 4 + wave) * SH_ROWS;  // first Gaussian of this wave
+    const int base = (blockIdx.x * WAVES + wave) * SH_ROWS;  // first Gaussian of this wave
     if (base >= N) return;
     const int nrows = min(SH_ROWS, N - base);
     const float *src = coeffs + (size_t)base * ROW;
@@ -998,10 +1002,13 @@ extern "C" int gg_sh_bwd_multi(int N, int K, int deg, int num_views, const float
 template <int K>
 static void launch_tail(bool fwd, bool acc, int N, int deg, const float *viewdirs, const float *in, float *out,
                         const float *depths, const float *normals, uint8_t *mask, int vstride, float *v_depths,
-                        float *v_normals, hipStream_t s) {
+                        float *v_normals, hipStream_t s, bool one_wave = false) {
     dim3 grid((N + 255) / 256), block(256);
     const int rows_fwd = 4 * ((K >= 16) ? 32 : 64);
-    if (fwd)
+    if (fwd && one_wave)
+        hipLaunchKernelGGL((sh_fwd_kernel<K, true, 1>), dim3((N + rows_fwd / 4 - 1) / (rows_fwd / 4)), dim3(64), 0, s, N,
+                           deg, viewdirs, in, out, depths, normals, mask);
+    else if (fwd)
         hipLaunchKernelGGL((sh_fwd_kernel<K, true>), dim3((N + rows_fwd - 1) / rows_fwd), block, 0, s, N, deg,
                            viewdirs, in, out, depths, normals, mask);
     else if (acc)
@@ -1013,7 +1020,7 @@ static void launch_tail(bool fwd, bool acc, int N, int deg, const float *viewdir
 }
 static int tail_dispatch(bool fwd, bool acc, int N, int K, int deg, const float *viewdirs, const float *in,
                          float *out, const float *depths, const float *normals, uint8_t *mask, int vstride,
-                         float *v_depths, float *v_normals, gg_stream_t stream) {
+                         float *v_depths, float *v_normals, gg_stream_t stream, bool one_wave = false) {
     GG_REQUIRE(N >= 0, "num_points < 0");
     GG_REQUIRE(K == 1 || K == 4 || K == 9 || K == 16 || K == 25, "num_bases must be 1,4,9,16,25");
     GG_REQUIRE(deg >= 0 && sh_nbases(deg) <= K, "degrees_to_use exceeds stored bases");
@@ -1022,11 +1029,11 @@ static int tail_dispatch(bool fwd, bool acc, int N, int K, int deg, const float 
     hipStream_t s = (hipStream_t)stream;
     gg_prof_begin(fwd ? GG_K_SH_FWD : GG_K_SH_BWD, s);
     switch (K) {
-        case 1: launch_tail<1>(fwd, acc, N, deg, viewdirs, in, out, depths, normals, mask, vstride, v_depths, v_normals, s); break;
-        case 4: launch_tail<4>(fwd, acc, N, deg, viewdirs, in, out, depths, normals, mask, vstride, v_depths, v_normals, s); break;
-        case 9: launch_tail<9>(fwd, acc, N, deg, viewdirs, in, out, depths, normals, mask, vstride, v_depths, v_normals, s); break;
-        case 16: launch_tail<16>(fwd, acc, N, deg, viewdirs, in, out, depths, normals, mask, vstride, v_depths, v_normals, s); break;
-        default: launch_tail<25>(fwd, acc, N, deg, viewdirs, in, out, depths, normals, mask, vstride, v_depths, v_normals, s); break;
+        case 1: launch_tail<1>(fwd, acc, N, deg, viewdirs, in, out, depths, normals, mask, vstride, v_depths, v_normals, s, one_wave); break;
+        case 4: launch_tail<4>(fwd, acc, N, deg, viewdirs, in, out, depths, normals, mask, vstride, v_depths, v_normals, s, one_wave); break;
+        case 9: launch_tail<9>(fwd, acc, N, deg, viewdirs, in, out, depths, normals, mask, vstride, v_depths, v_normals, s, one_wave); break;
+        case 16: launch_tail<16>(fwd, acc, N, deg, viewdirs, in, out, depths, normals, mask, vstride, v_depths, v_normals, s, one_wave); break;
+        default: launch_tail<25>(fwd, acc, N, deg, viewdirs, in, out, depths, normals, mask, vstride, v_depths, v_normals, s, one_wave); break;
     }
     gg_prof_end(fwd ? GG_K_SH_FWD : GG_K_SH_BWD, s);
     GG_CHECK_LAUNCH();
@@ -1038,6 +1045,13 @@ extern "C" int gg_shade_tail_fwd(int N, int K, int deg, const float *viewdirs, c
     GG_REQUIRE(N == 0 || (depths && normals), "null pointer");
     return tail_dispatch(true, false, N, K, deg, viewdirs, coeffs, tail, depths, normals, clamp_mask, 7, nullptr,
                          nullptr, stream);
+}
+extern "C" int gg_shade_tail_fwd_ex(int N, int K, int deg, const float *viewdirs, const float *coeffs,
+                                    const float *depths, const float *normals, float *tail, uint8_t *clamp_mask,
+                                    int one_wave, gg_stream_t stream) {
+    GG_REQUIRE(N == 0 || (depths && normals), "null pointer");
+    return tail_dispatch(true, false, N, K, deg, viewdirs, coeffs, tail, depths, normals, clamp_mask, 7, nullptr,
+                         nullptr, stream, one_wave != 0);
 }
 extern "C" int gg_shade_tail_bwd(int N, int K, int deg, const float *viewdirs, const float *v_tail,
                                  int v_tail_stride, const uint8_t *clamp_mask, float *v_coeffs, int accumulate,

@@ -331,10 +331,18 @@ class ShadeTail(Function):
     [ clamp(SphericalHarmonics(...) + 0.5, 0, 1) | depth | normal ]: the 7-channel colour array of the plugin
     route's rasterize operator in one kernel each way (reference :730-731 clamp, :765 depth, :779 normal colours).
     The backward reads the cotangent rows in place (the blend backward's interleaved gradient record, any row
-    stride) and adds the SH gradient into a registered gradient sink like SphericalHarmonics does."""
+    stride) and adds the SH gradient into a registered gradient sink like SphericalHarmonics does.
+
+    one_wave (optional sixth argument): launch the forward in one-wave workgroups (gg_shade_tail_fwd_ex: the same bits).
+    For a forward that runs beside a blend kernel of another stream — forward(k + 1) beside backward(k) in
+    dist.train_step_pipelined: the blend kernels refill every slot they free, so the default 256-thread workgroups with
+    38 KB of LDS are not placed until the backward drains (620 us instead of 65) and binning and the pair forward wait
+    behind them; one-wave workgroups are placed slot by slot (profiles/forward_chain_overlap.txt).  Alone on the GPU the
+    default launch is no slower."""
 
     @staticmethod
-    def forward(ctx, degrees_to_use: int, viewdirs: Tensor, coeffs: Tensor, depths: Tensor, normals: Tensor):
+    def forward(ctx, degrees_to_use: int, viewdirs: Tensor, coeffs: Tensor, depths: Tensor, normals: Tensor,
+                one_wave: bool = False):
         n, k = coeffs.shape[0], coeffs.shape[-2]
         assert k >= num_sh_bases(degrees_to_use), "not enough SH bases for degrees_to_use"
         deg_from_sh(k)
@@ -346,9 +354,14 @@ class ShadeTail(Function):
         viewdirs, coeffs, depths_c, normals_c = _f32(viewdirs), _f32(coeffs), _f32(depths), _f32(normals)
         tail = torch.empty(n, 7, dtype=torch.float32, device=dev)
         mask = torch.empty(n, dtype=torch.uint8, device=dev)
-        _lib.check(_lib.load().gg_shade_tail_fwd(n, k, int(degrees_to_use), _ptr(viewdirs), _ptr(coeffs),
-                                                 _ptr(depths_c), _ptr(normals_c), _ptr(tail), _ptr(mask),
-                                                 _stream(dev)), "gg_shade_tail_fwd")
+        if one_wave:
+            _lib.check(_lib.load().gg_shade_tail_fwd_ex(n, k, int(degrees_to_use), _ptr(viewdirs), _ptr(coeffs),
+                                                        _ptr(depths_c), _ptr(normals_c), _ptr(tail), _ptr(mask), 1,
+                                                        _stream(dev)), "gg_shade_tail_fwd_ex")
+        else:
+            _lib.check(_lib.load().gg_shade_tail_fwd(n, k, int(degrees_to_use), _ptr(viewdirs), _ptr(coeffs),
+                                                     _ptr(depths_c), _ptr(normals_c), _ptr(tail), _ptr(mask),
+                                                     _stream(dev)), "gg_shade_tail_fwd")
         ctx.degrees_to_use, ctx.num_bases = int(degrees_to_use), k
         ctx.save_for_backward(viewdirs, mask)
         ctx.sink = _sink_for(coeffs, coeffs.dtype == torch.float32)
@@ -371,7 +384,7 @@ class ShadeTail(Function):
                                                    _ptr(v_depths), _ptr(v_normals), _stream(dev)),
                        "gg_shade_tail_bwd_split")
             sink.keep_sh(ctx.degrees_to_use, ctx.num_bases, viewdirs, v_rgb)
-            return None, None, None, v_depths, v_normals
+            return None, None, None, v_depths, v_normals, None
         v_coeffs = sink.buffer if sink is not None \
             else torch.empty(n, ctx.num_bases, 3, dtype=torch.float32, device=dev)
         _lib.check(lib.gg_shade_tail_bwd(n, ctx.num_bases, ctx.degrees_to_use, _ptr(viewdirs), _ptr(v_tail), stride,
@@ -380,7 +393,7 @@ class ShadeTail(Function):
         if sink is not None:
             sink.done()
             v_coeffs = None
-        return None, None, v_coeffs, v_depths, v_normals
+        return None, None, v_coeffs, v_depths, v_normals, None
 
 
 # ------------------------------------------------------------------------------------------------
@@ -855,7 +868,7 @@ def _is_record_view(t: Optional[Tensor], base: int, offset: int, width: int, str
 
 class ViewGeometry(Function):
     """apply(means, log_scales, quats, opacities, colors_all, cam_pos, viewmat, full_proj, fx, fy, cx, cy,
-             img_height, img_width, tile_bounds, degrees_to_use)
+             img_height, img_width, tile_bounds, degrees_to_use[, one_wave_sh = False: ShadeTail's `one_wave`])
        -> (xys, depths, radii, conics, num_tiles_hit, opac, tail (N, 7), normals, packed)
 
     `packed`: a blend workspace already holding these Gaussians' packed records (pass it to rasterize_segments(...,
@@ -870,13 +883,13 @@ class ViewGeometry(Function):
 
     @staticmethod
     def forward(ctx, means, log_scales, quats, opacities, colors_all, cam_pos, viewmat, full_proj, fx, fy, cx, cy,
-                img_height, img_width, tile_bounds, degrees_to_use):
+                img_height, img_width, tile_bounds, degrees_to_use, one_wave_sh=False):
         ctx.set_materialize_grads(False)
         a, p, t = _PartCtx(), _PartCtx(), _PartCtx()
         scales_e, quats_n, opac, viewdirs, normals, xys, depths, radii, conics, num_tiles_hit, packed = \
             ViewGeometry._activate_and_project(a, p, means, log_scales, quats, opacities, cam_pos, viewmat, full_proj,
                                                fx, fy, cx, cy, img_height, img_width, tile_bounds)
-        tail = ShadeTail.forward(t, degrees_to_use, viewdirs, colors_all, depths, normals)
+        tail = ShadeTail.forward(t, degrees_to_use, viewdirs, colors_all, depths, normals, bool(one_wave_sh))
         ctx.parts = (a, p, t)
         ctx.pose_meta = (viewmat.shape, viewmat.dtype, full_proj.shape, full_proj.dtype)
         ctx.counts = tuple(len(c.saved_tensors) for c in ctx.parts)
@@ -957,14 +970,14 @@ class ViewGeometry(Function):
                 # frozen Gaussians (pose.refine_camera): only the depth cotangent of the chain reaches the camera
                 vd = torch.zeros(n, device=dev) if v_tail is None else v_tail[:, 3].float()
                 vd = vd if v_depths is None else vd + _f32(v_depths)
-                return (None,) * 6 + ViewGeometry._pose_only(ctx, p, v_xys, vd, v_conics) + (None,) * 8
+                return (None,) * 6 + ViewGeometry._pose_only(ctx, p, v_xys, vd, v_conics) + (None,) * 9
             g_t = ShadeTail.backward(t, v_tail if v_tail is not None else torch.zeros(n, 7, device=dev))
             vd = g_t[3] if v_depths is None else g_t[3] + _f32(v_depths)
             vn = g_t[4] if v_normals is None else g_t[4] + _f32(v_normals)
             g_p = ProjectGaussians.backward(p, v_xys, vd, None, v_conics, None, None)
             g_a = ActivateGaussians.backward(a, g_p[1], g_p[3], v_opac, None, vn)
             g_cam = ViewGeometry._pose_only(ctx, p, v_xys, vd, v_conics) if pose else (None, None)
-            return (g_p[0], g_a[1], g_a[2], g_a[3], g_t[2], None) + g_cam + (None,) * 8
+            return (g_p[0], g_a[1], g_a[2], g_a[3], g_t[2], None) + g_cam + (None,) * 9
         lib = _lib.load()
         glob_scale, fx, fy, _cx, _cy, img_height, img_width = p.scalars
         v_rgb = torch.empty(n, 3, dtype=torch.float32, device=dev)
@@ -984,7 +997,7 @@ class ViewGeometry(Function):
         t.sink.keep_sh(t.degrees_to_use, t.num_bases, viewdirs, v_rgb)
         for sink in (p.sink, *a.sinks):
             sink.done()
-        return (None,) * 6 + g_cam + (None,) * 8
+        return (None,) * 6 + g_cam + (None,) * 9
 
     @staticmethod
     def _pose_only(ctx, p, v_xys, v_depths, v_conics):

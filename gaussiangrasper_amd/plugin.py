@@ -48,9 +48,13 @@ def fused_view(model, means, log_scales, quats, opacities, colors_all, feature, 
         if full_proj is None:
             full_proj = projmat @ viewmat                                # :707
         model._gg_last_view = (viewmat, full_proj)
+        # training views: the SH forward in one-wave workgroups (ops.ShadeTail's `one_wave`) — the training step runs this
+        # forward beside the previous view's backward on another stream (dist.train_step_pipelined); render-only views
+        # have the GPU to themselves and keep the 256-thread launch
+        extra = (True,) if (model.training and ops is _ops) else ()
         model.xys, depths, model.radii, conics, num_tiles_hit, opac, tail, model.normals, packed = ops.ViewGeometry.apply(
             means, log_scales, quats, opacities, colors_all, cam_pos.reshape(-1)[:3], viewmat[:3, :], full_proj,
-            fx, fy, cx, cy, H, W, tile_bounds, sh_degree_to_use)
+            fx, fy, cx, cy, H, W, tile_bounds, sh_degree_to_use, *extra)
         if model.training:
             model.xys.retain_grad()                                    # :724-725
         feat_im, rgb, depth_im, normal_im = fused_images(ops, model.xys, depths, model.radii, conics, num_tiles_hit,

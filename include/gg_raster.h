@@ -113,6 +113,13 @@ int gg_sh_bwd_accumulate(int num_points, int num_bases, int degrees_to_use, cons
 int gg_shade_tail_fwd(int num_points, int num_bases, int degrees_to_use, const float *viewdirs,
                       const float *coeffs, const float *depths, const float *normals, float *tail,
                       uint8_t *clamp_mask, gg_stream_t stream);
+/* gg_shade_tail_fwd_ex: the same; one_wave != 0 launches the kernel's build with 64-thread workgroups and a quarter of
+ * the LDS per workgroup — the same bits.  For a launch that runs beside a blend kernel of another stream (forward of
+ * view k + 1 beside backward of view k): a one-wave workgroup is placed where one blend workgroup has finished, the
+ * four-wave one only once that kernel drains.  Alone on the GPU the four-wave build is no slower: keep it there. */
+int gg_shade_tail_fwd_ex(int num_points, int num_bases, int degrees_to_use, const float *viewdirs,
+                         const float *coeffs, const float *depths, const float *normals, float *tail,
+                         uint8_t *clamp_mask, int one_wave, gg_stream_t stream);
 int gg_shade_tail_bwd(int num_points, int num_bases, int degrees_to_use, const float *viewdirs,
                       const float *v_tail, int v_tail_stride, const uint8_t *clamp_mask, float *v_coeffs,
                       int accumulate, float *v_depths, float *v_normals, gg_stream_t stream);
