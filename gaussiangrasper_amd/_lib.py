@@ -144,6 +144,10 @@ SIGNATURES = {
     "gg_tsdf_mesh_workspace": (_SZ, [_P]),
     "gg_tsdf_mesh_count": (_I, [_P, _P, _P, _P, _P, _SZ, _P]),
     "gg_tsdf_mesh_emit": (_I, [_P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P, _P, _SZ, _P]),
+    "gg_field_splat": (_I, [_P, _P, _I, _P, _P, _P, _P, C.c_double, _I, C.c_double, _I, _P, _P, _P, _P]),
+    "gg_field_distance_workspace": (_SZ, [_P]),
+    "gg_field_distance": (_I, [_P, _P, _I64, _P, _P, _SZ, _P]),
+    "gg_field_paths": (_I, [_P, _P, _P, _I, _I, _P, _I, _P, _P, _I, _P, _P, _P]),
     "gg_prof_enable": (_I, [_I]),
     "gg_prof_reset": (_I, []),
     "gg_prof_get": (_I, [_I, C.POINTER(C.c_int), C.POINTER(C.c_double)]),

@@ -1,0 +1,409 @@
+// field.hip — the scene as a distance field: Gaussians splatted into integer occupancy mass, the exact squared
+// Euclidean distance transform of the occupied cells, and many gripper paths tested against it.  The contract is in
+// include/gg_raster.h (gg_field_*) and PARITY.md "Distance field"; the design in DESIGN.md §3.25.
+//
+// gg_field_splat      one launch, a thread per row.  A row whose reach is at most FS_THREAD_REACH cells walks its own
+//                     box (at most 125 cells).  The rows of a wave that reach further are then taken one at a time
+//                     by the whole wave (ballot, wave-uniform row index): the 64 lanes stride over the flattened box,
+//                     z fastest, so that a wave's atomics fall on runs of neighbouring cells.  Votes are int64 and
+//                     added with 64-bit integer atomics: no order of the adds changes a bit of `mass`.
+// gg_field_distance   three launches of one kernel, z then y then x: a workgroup stages FD_TILE whole lines in LDS,
+//                     and every thread finds its cell's minimum by an outward search that ends at delta^2 >= best.
+//                     A pass reads and writes only its own lines, so y runs in place on the workspace.
+// gg_field_paths      a thread per pose with the spheres in LDS, then a thread per path for first_hit.  No atomics.
+#include <math.h>
+
+#include "gg_common.h"
+
+#define FS_THREADS 256
+#define FS_THREAD_REACH 2          // rows that reach further are walked by their whole wave
+#define FD_THREADS 256
+#define FD_TILE 8                  // lines per workgroup of a distance pass
+#define FP_THREADS 256
+#define FIELD_CELL_CLAMP 1073741824.0   // 2^30: a cell index beyond it is outside every volume and every reach
+
+struct FieldGrid {
+    int X, Y, Z;
+    double lo[3], h;
+};
+
+// The cell along one axis of d = p - lo: floor(d / h), corrected by one so that c h <= d < (c + 1) h holds in fp64.
+// d finite.  Clamped to +-2^30 (outside every volume, and further from it than any reach).
+__device__ __forceinline__ int field_cell(double d, double h) {
+    double c = floor(d / h);
+    c = c < -FIELD_CELL_CLAMP ? -FIELD_CELL_CLAMP : (c > FIELD_CELL_CLAMP ? FIELD_CELL_CLAMP : c);
+    if (c * h > d)
+        c -= 1.0;
+    else if ((c + 1.0) * h <= d)
+        c += 1.0;
+    return (int)c;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// splat
+// ---------------------------------------------------------------------------------------------------------------
+struct FsRow {
+    double m[3], R[9], A[3], rhs;
+    int c[3];                      // the mean's cell, per axis, inside the volume or not
+    int reach;
+    long long q;
+    bool ok, cut;
+};
+
+// Row i as every lane that works on it needs it; i >= N gives a row that takes no part (and is not counted).
+__device__ __forceinline__ void fs_row(const FieldGrid &g, int i, int N, const float *__restrict__ means,
+                                       const float *__restrict__ rot, const float *__restrict__ scales,
+                                       const float *__restrict__ weights, double k, int max_reach, double min_weight,
+                                       FsRow &r) {
+    r.ok = false;
+    r.cut = false;
+    r.reach = 0;
+    r.q = 0;
+    r.rhs = 0.0;
+    r.c[0] = r.c[1] = r.c[2] = 0;
+    if (i >= N) return;
+    bool fin = true;
+    float smax = 0.0f;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float m = means[(size_t)i * 3 + a], s = scales[(size_t)i * 3 + a];
+        fin = fin && isfinite(m) && isfinite(s) && s > 0.0f;
+        r.m[a] = (double)m;
+        r.A[a] = (double)s * (double)s;
+        smax = fmaxf(smax, s);
+    }
+#pragma unroll
+    for (int a = 0; a < 9; ++a) {
+        const float v = rot[(size_t)i * 9 + a];
+        fin = fin && isfinite(v);
+        r.R[a] = (double)v;
+    }
+    const float wf = weights[i];
+    const double w = (double)wf;
+    if (!(fin && isfinite(wf) && min_weight < w && w < 32768.0)) return;
+    r.ok = true;
+    r.q = (long long)(w * 65536.0);            // exact product, truncated: |q| < 2^31
+    r.rhs = (k * k) * ((r.A[0] * r.A[1]) * r.A[2]);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) r.c[a] = field_cell(r.m[a] - g.lo[a], g.h);
+    // n: the smallest integer >= 0 with n h >= k smax, followed as far as GG_FIELD_MAX_REACH + 1: the division
+    // proposes, the comparisons decide
+    const double rad = k * (double)smax;
+    const double e = ceil(rad / g.h);
+    int n = e >= (double)(GG_FIELD_MAX_REACH + 1) ? GG_FIELD_MAX_REACH + 1 : (int)e;
+    while (n > 0 && (double)(n - 1) * g.h >= rad) --n;
+    while (n <= GG_FIELD_MAX_REACH && (double)n * g.h < rad) ++n;
+    r.cut = n + 1 > max_reach;
+    r.reach = r.cut ? max_reach : n + 1;
+}
+
+// Cell (x, y, z) of the volume: the mean's cell votes always, another one when its centre is in the closed ellipsoid.
+__device__ __forceinline__ void fs_cell(const FieldGrid &g, const FsRow &r, int x, int y, int z,
+                                        unsigned long long vote, unsigned long long *__restrict__ mass) {
+    bool hit = x == r.c[0] && y == r.c[1] && z == r.c[2];
+    if (!hit) {
+        const double d0 = (g.lo[0] + ((double)x + 0.5) * g.h) - r.m[0];
+        const double d1 = (g.lo[1] + ((double)y + 0.5) * g.h) - r.m[1];
+        const double d2 = (g.lo[2] + ((double)z + 0.5) * g.h) - r.m[2];
+        const double u0 = (r.R[0] * d0 + r.R[3] * d1) + r.R[6] * d2;
+        const double u1 = (r.R[1] * d0 + r.R[4] * d1) + r.R[7] * d2;
+        const double u2 = (r.R[2] * d0 + r.R[5] * d1) + r.R[8] * d2;
+        const double lhs =
+            ((u0 * u0) * (r.A[1] * r.A[2]) + (u1 * u1) * (r.A[0] * r.A[2])) + (u2 * u2) * (r.A[0] * r.A[1]);
+        hit = lhs <= r.rhs;
+    }
+    if (hit) atomicAdd(mass + ((size_t)x * g.Y + y) * g.Z + z, vote);
+}
+
+// The row's box cut to the volume: lo[a] <= hi[a] on every axis, or false.  c is within +-2^30 and reach <= 64.
+__device__ __forceinline__ bool fs_box(const FieldGrid &g, const FsRow &r, int *lo, int *hi) {
+    const int dim[3] = {g.X, g.Y, g.Z};
+    bool any = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = max(r.c[a] - r.reach, 0);
+        hi[a] = min(r.c[a] + r.reach, dim[a] - 1);
+        any = any && lo[a] <= hi[a];
+    }
+    return any;
+}
+
+__global__ __launch_bounds__(FS_THREADS) void field_splat_kernel(FieldGrid g, int N, const float *__restrict__ means,
+                                                                 const float *__restrict__ rot,
+                                                                 const float *__restrict__ scales,
+                                                                 const float *__restrict__ weights, double k,
+                                                                 int max_reach, double min_weight, int sign,
+                                                                 unsigned long long *__restrict__ mass,
+                                                                 unsigned long long *__restrict__ skipped,
+                                                                 unsigned long long *__restrict__ truncated) {
+    const int i = blockIdx.x * FS_THREADS + threadIdx.x;      // N <= 2^30 and the grid covers N: no overflow
+    const int lane = threadIdx.x & 63;
+    FsRow r;
+    fs_row(g, i, N, means, rot, scales, weights, k, max_reach, min_weight, r);
+    const uint64_t skip = __ballot(i < N && !r.ok), cut = __ballot(r.ok && r.cut);
+    if (lane == 0) {
+        if (skip) atomicAdd(skipped, (unsigned long long)__builtin_popcountll(skip));
+        if (cut) atomicAdd(truncated, (unsigned long long)__builtin_popcountll(cut));
+    }
+    int lo[3], hi[3];
+    const bool wide = r.ok && r.reach > FS_THREAD_REACH;
+    if (r.ok && !wide && fs_box(g, r, lo, hi)) {
+        const unsigned long long vote = sign > 0 ? (unsigned long long)r.q : 0ull - (unsigned long long)r.q;
+        for (int x = lo[0]; x <= hi[0]; ++x)
+            for (int y = lo[1]; y <= hi[1]; ++y)
+                for (int z = lo[2]; z <= hi[2]; ++z) fs_cell(g, r, x, y, z, vote, mass);
+    }
+    // the wave's wide rows, one at a time, by all of its lanes
+    const int wave_first = i - lane;
+    for (uint64_t rem = __ballot(wide); rem != 0ull; rem &= rem - 1ull) {
+        const int src = __builtin_amdgcn_readfirstlane(wave_first + (int)__builtin_ctzll(rem));
+        FsRow b;
+        fs_row(g, src, N, means, rot, scales, weights, k, max_reach, min_weight, b);
+        if (!fs_box(g, b, lo, hi)) continue;
+        const unsigned long long vote = sign > 0 ? (unsigned long long)b.q : 0ull - (unsigned long long)b.q;
+        const int ny = hi[1] - lo[1] + 1, nz = hi[2] - lo[2] + 1;
+        const int total = (hi[0] - lo[0] + 1) * ny * nz;      // <= 129^3
+        for (int t = lane; t < total; t += 64) {
+            const int xy = t / nz, z = t - xy * nz;
+            const int x = xy / ny, y = xy - x * ny;
+            fs_cell(g, b, lo[0] + x, lo[1] + y, lo[2] + z, vote, mass);
+        }
+    }
+}
+
+__global__ void field_zero2_kernel(unsigned long long *a, unsigned long long *b) {
+    *a = 0ull;
+    *b = 0ull;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// distance transform
+// ---------------------------------------------------------------------------------------------------------------
+// One min-plus pass along an axis of length L and element stride B: line n (of cells / L) starts at
+// (n / B) L B + n % B.  z: B = 1; y: B = Z; x: B = Y Z.  A workgroup owns FD_TILE consecutive lines and keeps them in
+// LDS as tile[l][t], or tile[t][l] (one int of padding per line) when the lines themselves are contiguous (UNIT:
+// B == 1), so that in both cases neighbouring threads read neighbouring addresses of memory and of LDS.
+// FIRST: the input is the mass (f = mass >= threshold ? 0 : FAR).  LAST: the output is clamped to FAR.
+template <bool UNIT, bool FIRST, bool LAST>
+__global__ __launch_bounds__(FD_THREADS) void field_distance_kernel(int L, long long B, long long lines,
+                                                                    const long long *__restrict__ mass,
+                                                                    long long threshold, const int *src, int *dst) {
+    extern __shared__ int fd_tile[];
+    const long long line0 = (long long)blockIdx.x * FD_TILE;
+    const int nt = (int)min((long long)FD_TILE, lines - line0);
+    const int work = nt * L;
+    for (int idx = threadIdx.x; idx < work; idx += FD_THREADS) {
+        const int t = UNIT ? idx / L : idx % nt, l = UNIT ? idx - t * L : idx / nt;
+        const long long n = line0 + t;
+        const long long at = (n / B) * ((long long)L * B) + n % B + (long long)l * B;
+        int f;
+        if (FIRST)
+            f = mass[at] >= threshold ? 0 : GG_FIELD_FAR;
+        else
+            f = src[at];
+        fd_tile[UNIT ? t * (L + 1) + l : l * FD_TILE + t] = f;
+    }
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < work; idx += FD_THREADS) {
+        const int t = UNIT ? idx / L : idx % nt, l = UNIT ? idx - t * L : idx / nt;
+        const int *col = fd_tile + (UNIT ? t * (L + 1) : t);
+        const int step = UNIT ? 1 : FD_TILE;
+        int best = col[l * step];
+        // outward: a candidate at distance d is at least d^2, so the search ends once d^2 >= best
+        for (int d = 1; d < L; ++d) {
+            const int dd = d * d;
+            if (dd >= best) break;
+            const bool below = l - d >= 0, above = l + d < L;
+            if (!below && !above) break;
+            if (below) best = min(best, col[(l - d) * step] + dd);
+            if (above) best = min(best, col[(l + d) * step] + dd);
+        }
+        if (LAST) best = min(best, GG_FIELD_FAR);
+        const long long n = line0 + t;
+        dst[(n / B) * ((long long)L * B) + n % B + (long long)l * B] = best;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// paths
+// ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(FP_THREADS) void field_paths_kernel(FieldGrid g, const int *__restrict__ dist2,
+                                                                 int poses_total, const float *__restrict__ poses,
+                                                                 int S, const float *__restrict__ spheres,
+                                                                 const int *__restrict__ need2, int outside,
+                                                                 int *__restrict__ slack) {
+    __shared__ float s_c[GG_FIELD_MAX_SPHERES * 3];
+    __shared__ int s_need[GG_FIELD_MAX_SPHERES];
+    for (int k = threadIdx.x; k < S; k += FP_THREADS) {
+        s_c[3 * k] = spheres[3 * k];
+        s_c[3 * k + 1] = spheres[3 * k + 1];
+        s_c[3 * k + 2] = spheres[3 * k + 2];
+        s_need[k] = need2[k];
+    }
+    __syncthreads();
+    const int i = blockIdx.x * FP_THREADS + threadIdx.x;      // poses_total <= 2^26
+    if (i >= poses_total) return;
+    double T[12];
+    bool fin = true;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+        const float v = poses[(size_t)i * 12 + k];
+        fin = fin && isfinite(v);
+        T[k] = (double)v;
+    }
+    if (!fin) {
+        slack[i] = INT32_MIN;
+        return;
+    }
+    const int dim[3] = {g.X, g.Y, g.Z};
+    int m = GG_FIELD_FAR;
+    for (int s = 0; s < S; ++s) {
+        const double x = (double)s_c[3 * s], y = (double)s_c[3 * s + 1], z = (double)s_c[3 * s + 2];
+        int cell[3];
+        bool in = true;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const double c = ((T[3 * a] * x + T[3 * a + 1] * y) + T[3 * a + 2] * z) + T[9 + a];
+            const bool ok = isfinite(c);          // a centre that is not finite is outside
+            cell[a] = ok ? field_cell(c - g.lo[a], g.h) : -1;
+            in = in && cell[a] >= 0 && cell[a] < dim[a];
+        }
+        const int d = in ? dist2[((size_t)cell[0] * g.Y + cell[1]) * g.Z + cell[2]] : outside;
+        m = min(m, d - s_need[s]);
+    }
+    slack[i] = m;
+}
+
+__global__ __launch_bounds__(FP_THREADS) void field_first_hit_kernel(int P, int W, const int *__restrict__ slack,
+                                                                     int *__restrict__ first_hit) {
+    const int p = blockIdx.x * FP_THREADS + threadIdx.x;
+    if (p >= P) return;
+    int w = 0;
+    while (w < W && slack[(size_t)p * W + w] >= 0) ++w;
+    first_hit[p] = w;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// C ABI
+// ---------------------------------------------------------------------------------------------------------------
+static bool field_dims_ok(const int32_t *dims) {
+    if (!dims) return false;
+    int64_t cells = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (dims[a] < 1 || dims[a] > GG_FIELD_MAX_DIM) return false;
+        cells *= dims[a];
+    }
+    return cells <= GG_FIELD_MAX_CELLS;
+}
+
+static bool field_grid(const int32_t *dims, const double *grid, FieldGrid *g) {
+    for (int a = 0; a < 4; ++a)
+        if (!isfinite(grid[a])) return false;
+    if (!(grid[3] > 0.0)) return false;
+    *g = FieldGrid{dims[0], dims[1], dims[2], {grid[0], grid[1], grid[2]}, grid[3]};
+    return true;
+}
+
+static int64_t field_cells(const int32_t *dims) { return (int64_t)dims[0] * dims[1] * dims[2]; }
+
+#define FIELD_DIMS_MSG "need 1 <= dims[a] <= GG_FIELD_MAX_DIM and dims[0] dims[1] dims[2] <= GG_FIELD_MAX_CELLS"
+#define FIELD_GRID_MSG "grid: the corner must be finite and the cell edge h finite and > 0"
+
+extern "C" int gg_field_splat(const int32_t *dims, const double *grid, int num_rows, const float *means,
+                              const float *rot, const float *scales, const float *weights, double extent,
+                              int max_reach, double min_weight, int sign, int64_t *mass, int64_t *skipped,
+                              int64_t *truncated, gg_stream_t stream) {
+    GG_REQUIRE(field_dims_ok(dims), FIELD_DIMS_MSG);
+    GG_REQUIRE(grid, "null pointer: grid (a host array of 4 doubles)");
+    FieldGrid g;
+    GG_REQUIRE(field_grid(dims, grid, &g), FIELD_GRID_MSG);
+    GG_REQUIRE(num_rows >= 0 && num_rows <= GG_FIELD_MAX_ROWS, "need 0 <= num_rows <= GG_FIELD_MAX_ROWS");
+    GG_REQUIRE(isfinite(extent) && extent >= 0.0, "extent must be finite and >= 0");
+    GG_REQUIRE(max_reach >= 0 && max_reach <= GG_FIELD_MAX_REACH, "max_reach must be in 0..GG_FIELD_MAX_REACH");
+    GG_REQUIRE(!isnan(min_weight), "min_weight is NaN");
+    GG_REQUIRE(sign == 1 || sign == -1, "sign must be +1 or -1");
+    if (num_rows == 0) return GG_OK;
+    GG_REQUIRE(means && rot && scales && weights, "null pointer: means / rot / scales / weights");
+    GG_REQUIRE(mass && skipped && truncated, "null pointer: mass / skipped / truncated");
+    GG_REQUIRE((((uintptr_t)means | (uintptr_t)rot | (uintptr_t)scales | (uintptr_t)weights) & 3) == 0 &&
+                   (((uintptr_t)mass | (uintptr_t)skipped | (uintptr_t)truncated) & 7) == 0,
+               "means / rot / scales / weights / mass / skipped / truncated misaligned");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(field_zero2_kernel, dim3(1), dim3(1), 0, s, reinterpret_cast<unsigned long long *>(skipped),
+                       reinterpret_cast<unsigned long long *>(truncated));
+    hipLaunchKernelGGL(field_splat_kernel, dim3((unsigned)((num_rows + FS_THREADS - 1) / FS_THREADS)),
+                       dim3(FS_THREADS), 0, s, g, num_rows, means, rot, scales, weights, extent, max_reach, min_weight,
+                       sign, reinterpret_cast<unsigned long long *>(mass),
+                       reinterpret_cast<unsigned long long *>(skipped),
+                       reinterpret_cast<unsigned long long *>(truncated));
+    GG_CHECK_LAUNCH();
+    return GG_OK;
+}
+
+extern "C" size_t gg_field_distance_workspace(const int32_t *dims) {
+    if (!field_dims_ok(dims)) return 0;
+    return gg_align_up((size_t)field_cells(dims) * 4, 256);
+}
+
+template <bool UNIT, bool FIRST, bool LAST>
+static void field_distance_pass(hipStream_t s, int L, int64_t B, int64_t cells, const int64_t *mass, int64_t threshold,
+                                const int *src, int *dst) {
+    const int64_t lines = cells / L;
+    hipLaunchKernelGGL((field_distance_kernel<UNIT, FIRST, LAST>), dim3((unsigned)((lines + FD_TILE - 1) / FD_TILE)),
+                       dim3(FD_THREADS), (size_t)FD_TILE * (L + 1) * sizeof(int), s, L, (long long)B, (long long)lines,
+                       reinterpret_cast<const long long *>(mass), (long long)threshold, src, dst);
+}
+
+extern "C" int gg_field_distance(const int32_t *dims, const int64_t *mass, int64_t threshold, int32_t *dist2, void *ws,
+                                 size_t ws_bytes, gg_stream_t stream) {
+    GG_REQUIRE(field_dims_ok(dims), FIELD_DIMS_MSG);
+    GG_REQUIRE(threshold >= 1, "threshold must be >= 1");
+    GG_REQUIRE(mass && dist2, "null pointer: mass / dist2");
+    GG_REQUIRE(((uintptr_t)mass & 7) == 0 && ((uintptr_t)dist2 & 3) == 0, "mass / dist2 misaligned");
+    GG_REQUIRE_WS(ws, ws_bytes, gg_field_distance_workspace(dims));
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t cells = field_cells(dims);
+    const int Y = dims[1], Z = dims[2];
+    int *f = (int *)ws;
+    field_distance_pass<true, true, false>(s, Z, 1, cells, mass, threshold, nullptr, f);
+    if (Z == 1)
+        field_distance_pass<true, false, false>(s, Y, 1, cells, nullptr, 0, f, f);
+    else
+        field_distance_pass<false, false, false>(s, Y, Z, cells, nullptr, 0, f, f);
+    if ((int64_t)Y * Z == 1)
+        field_distance_pass<true, false, true>(s, dims[0], 1, cells, nullptr, 0, f, dist2);
+    else
+        field_distance_pass<false, false, true>(s, dims[0], (int64_t)Y * Z, cells, nullptr, 0, f, dist2);
+    GG_CHECK_LAUNCH();
+    return GG_OK;
+}
+
+extern "C" int gg_field_paths(const int32_t *dims, const double *grid, const int32_t *dist2, int num_paths,
+                              int num_waypoints, const float *poses, int num_spheres, const float *spheres,
+                              const int32_t *need2, int32_t outside, int32_t *slack, int32_t *first_hit,
+                              gg_stream_t stream) {
+    GG_REQUIRE(field_dims_ok(dims), FIELD_DIMS_MSG);
+    GG_REQUIRE(grid, "null pointer: grid (a host array of 4 doubles)");
+    FieldGrid g;
+    GG_REQUIRE(field_grid(dims, grid, &g), FIELD_GRID_MSG);
+    GG_REQUIRE(num_paths >= 0 && num_waypoints >= 0, "num_paths / num_waypoints < 0");
+    GG_REQUIRE((int64_t)num_paths * num_waypoints <= GG_FIELD_MAX_POSES,
+               "num_paths num_waypoints > GG_FIELD_MAX_POSES");
+    GG_REQUIRE(num_spheres >= 0 && num_spheres <= GG_FIELD_MAX_SPHERES,
+               "num_spheres must be in 0..GG_FIELD_MAX_SPHERES");
+    GG_REQUIRE(outside >= 0 && outside <= GG_FIELD_FAR, "outside must be in 0..GG_FIELD_FAR");
+    if (num_paths == 0 || num_waypoints == 0) return GG_OK;
+    GG_REQUIRE(dist2 && poses && slack && first_hit, "null pointer: dist2 / poses / slack / first_hit");
+    GG_REQUIRE(num_spheres == 0 || (spheres && need2), "null pointer: spheres / need2");
+    GG_REQUIRE((((uintptr_t)dist2 | (uintptr_t)poses | (uintptr_t)spheres | (uintptr_t)need2 | (uintptr_t)slack |
+                 (uintptr_t)first_hit) & 3) == 0,
+               "dist2 / poses / spheres / need2 / slack / first_hit misaligned");
+    hipStream_t s = (hipStream_t)stream;
+    const int total = num_paths * num_waypoints;
+    hipLaunchKernelGGL(field_paths_kernel, dim3((unsigned)((total + FP_THREADS - 1) / FP_THREADS)), dim3(FP_THREADS), 0,
+                       s, g, dist2, total, poses, num_spheres, spheres, need2, outside, slack);
+    hipLaunchKernelGGL(field_first_hit_kernel, dim3((unsigned)((num_paths + FP_THREADS - 1) / FP_THREADS)),
+                       dim3(FP_THREADS), 0, s, num_paths, num_waypoints, slack, first_hit);
+    GG_CHECK_LAUNCH();
+    return GG_OK;
+}

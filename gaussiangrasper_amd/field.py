@@ -1,0 +1,473 @@
+"""The scene as a distance field, for the transit of the gripper: the Gaussians splatted into integer occupancy mass
+(`gg_field_splat`), the exact squared Euclidean distance transform of the occupied cells (`gg_field_distance`), and
+many gripper paths tested against it (`gg_field_paths`), csrc/field.hip.  The contract is in include/gg_raster.h and
+PARITY.md "Distance field"; the design in DESIGN.md §3.25.
+
+    DistanceField      the volume: .add / .remove Gaussians (a moved object: remove it, add it at the moved pose; no
+                       rebuild), .update the distances, .distance() in scene units, .save / .load
+    need2              the squared cell distance a sphere of `radius` plus `margin` needs: conservative
+    gripper_spheres    a grasp gripper model (grasp.default_gripper, ...) at given sizes, covered by spheres
+    grasp_poses        (M, 17) grasp rows as (M, 1, 12) poses
+    approach_paths     the straight approach of every row from a standoff, as (M, steps, 12) poses
+    interpolate        slerp plus lerp between two poses, on the host
+    path_clear         slack per waypoint, first hit and clear per path
+    python -m gaussiangrasper_amd.field --ckpt IN --bbox x0 y0 z0 x1 y1 z1 --voxel H --out field.npz [...]
+
+The field is for the transit.  At the grasp pose the fingers touch the object, where a cell-conservative sphere test
+rejects everything: there grasp.contacts' and grasp.clearance's exact box tests stay in charge."""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import math
+import sys
+from dataclasses import dataclass
+from typing import Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+from torch import Tensor
+
+from . import _lib
+from ._call import (ArrayLike, default_device, f32_rows, grid_args, nonneg, positive, ptr as _ptr,
+                    require_hip as _require_hip, sized_workspace, stream as _stream, to_device)
+from .grasp import MIN_WEIGHT, check_gripper
+
+FAR = 1 << 30                  # GG_FIELD_FAR
+MAX_DIM = 1024                 # GG_FIELD_MAX_DIM
+MAX_CELLS = 1 << 27            # GG_FIELD_MAX_CELLS
+MAX_REACH_LIMIT = 64           # GG_FIELD_MAX_REACH
+MAX_SPHERES = 1024             # GG_FIELD_MAX_SPHERES
+MAX_POSES = 1 << 26            # GG_FIELD_MAX_POSES
+VOTE_ONE = 1 << 16             # a weight of 1 as a vote
+# UNVERIFIED defaults (PARITY.md "Distance field"): this project's choices, not checked on a real checkpoint
+EXTENT = 1.0
+MAX_REACH = 8
+THRESHOLD = VOTE_ONE // 2      # trunc(0.5 2^16)
+VOXEL = 0.01
+
+
+@dataclass
+class SplatCounts:
+    """Of one gg_field_splat call: the rows that took no part and the rows max_reach cut (0-dim int64 tensors)."""
+    skipped: Tensor
+    truncated: Tensor
+
+
+@dataclass
+class PathClearance:
+    slack: Tensor          # (P, W) int32: min over the spheres of dist2 - need2; < 0: too near
+    first_hit: Tensor      # (P,) int32: the first waypoint with slack < 0, W when there is none
+    clear: Tensor          # (P,) bool: first_hit == W
+
+
+# ------------------------------------------------------------------------------------------------
+# host side
+# ------------------------------------------------------------------------------------------------
+def field_grid(bbox_min: Sequence[float], bbox_max: Sequence[float], voxel: float = VOXEL):
+    """(grid, dims): the lower corner and cell edge as float64 (4,), and the cells per axis that cover the box,
+    int32 (3,).  ValueError beyond GG_FIELD_MAX_DIM per axis or GG_FIELD_MAX_CELLS in all."""
+    lo, hi = np.asarray(bbox_min, np.float64).reshape(-1), np.asarray(bbox_max, np.float64).reshape(-1)
+    h = positive("voxel", voxel)
+    if lo.shape != (3,) or hi.shape != (3,) or not (np.isfinite(lo).all() and np.isfinite(hi).all()
+                                                    and (hi > lo).all()):
+        raise ValueError(f"bbox_min / bbox_max must be finite (3,) with min < max, got {lo} / {hi}")
+    dims = np.maximum(1, np.ceil((hi - lo) / h)).astype(np.int64)
+    if (dims > MAX_DIM).any() or int(dims.prod()) > MAX_CELLS:
+        raise ValueError(f"{tuple(int(d) for d in dims)} cells: at most {MAX_DIM} per axis and {MAX_CELLS} in all; "
+                         "use a larger voxel or a smaller box")
+    return np.array([*lo, h], np.float64), dims.astype(np.int32)
+
+
+def need2(radius: Union[float, ArrayLike], margin: float, h: float) -> np.ndarray:
+    """floor(((radius + margin) / h + sqrt(3))^2) + 1, at most FAR, int32 (shaped like radius).  Conservative: with p
+    in cell c and dist2[c] >= need2, the centres of c and of any occupied cell are further apart than radius + margin
+    + sqrt(3) h, p is within sqrt(3)/2 h of the one and every point of the occupied cell's cube within sqrt(3)/2 h of
+    the other, so no occupied cube meets the ball around p.  The square is nudged up by four ulps before the floor,
+    so that fp64 rounding cannot land it below an integer the exact value reaches (radius + margin = 0 gives 4, not
+    floor(2.9999999999999996) + 1)."""
+    r = np.asarray(radius, np.float64) + float(margin)
+    if not (np.isfinite(r).all() and (r >= 0).all()):
+        raise ValueError("radius + margin must be finite and >= 0")
+    v = np.floor((r / positive("h", h) + math.sqrt(3.0)) ** 2 * (1.0 + 2.0 ** -50)) + 1.0
+    return np.minimum(v, float(FAR)).astype(np.int32)
+
+
+def gripper_boxes(parts: ArrayLike, width: float, depth: float, height: float) -> np.ndarray:
+    """(P, 6) bounds x_lo, x_hi, y_lo, y_hi, z_lo, z_hi of a gripper model at these sizes (gg_grasp_clearance's form:
+    ((c0 + cw width) + cd depth) + ch height)."""
+    g = check_gripper(parts)
+    return ((g[:, :, 0] + g[:, :, 1] * float(width)) + g[:, :, 2] * float(depth)) + g[:, :, 3] * float(height)
+
+
+def gripper_spheres(parts: ArrayLike, width: float, depth: float, height: float, radius: float) -> np.ndarray:
+    """(S, 3) float32 sphere centres, gripper frame, whose balls of `radius` cover every box of the model that is not
+    empty: each box is cut into the fewest equal sub-boxes of edge <= 2 radius / sqrt(3) per axis (half diagonal <=
+    radius) and every sub-box's centre is a sphere.  The edge is taken 1e-4 shorter, which is far more than the
+    centres lose when they are rounded to float32.  ValueError when that takes more than GG_FIELD_MAX_SPHERES."""
+    edge = 2.0 * positive("radius", radius) / math.sqrt(3.0) * (1.0 - 1e-4)
+    out = []
+    for b in gripper_boxes(parts, width, depth, height):
+        if not (b[0] <= b[1] and b[2] <= b[3] and b[4] <= b[5]):
+            continue
+        axes = []
+        for a in range(3):
+            lo, hi = b[2 * a], b[2 * a + 1]
+            n = max(1, int(math.ceil((hi - lo) / edge)))
+            while (hi - lo) / n > edge:             # the division rounded the count down
+                n += 1
+            axes.append(lo + (np.arange(n) + 0.5) * ((hi - lo) / n))
+        out.append(np.stack(np.meshgrid(*axes, indexing="ij"), -1).reshape(-1, 3))
+    if not out:
+        raise ValueError("the gripper has no part that is not empty at these sizes")
+    c = np.concatenate(out)
+    if len(c) > MAX_SPHERES:
+        raise ValueError(f"{len(c)} spheres of radius {radius} are more than {MAX_SPHERES}: use a larger radius")
+    return c.astype(np.float32)
+
+
+def grasp_poses(rows: ArrayLike) -> np.ndarray:
+    """(M, 17) grasp rows (grasp.load_grasps) as (M, 1, 12) float32 poses: R row-major, then t."""
+    g = np.asarray(rows.cpu() if isinstance(rows, Tensor) else rows, np.float32)
+    if g.ndim != 2 or g.shape[1] != 17:
+        raise ValueError(f"grasp rows are (M, 17), got {g.shape}")
+    return np.ascontiguousarray(g[:, None, 4:16])
+
+
+def approach_paths(rows: ArrayLike, standoff: float, steps: int) -> np.ndarray:
+    """(M, steps, 12) float32: every row's straight approach, from `standoff` back along its approach axis (the first
+    column of R) at waypoint 0 to the grasp pose at the last one, orientation fixed."""
+    p = grasp_poses(rows)[:, 0].astype(np.float64)
+    back, steps = nonneg("standoff", standoff), int(steps)
+    if steps < 2:
+        raise ValueError(f"steps must be >= 2, got {steps}")
+    s = back * (1.0 - np.arange(steps) / (steps - 1.0))                     # standoff .. 0
+    out = np.repeat(p[:, None, :], steps, 1)
+    out[:, :, 9:12] = p[:, None, 9:12] - s[None, :, None] * p[:, None, 0:9:3]
+    return np.ascontiguousarray(out.astype(np.float32))
+
+
+def _quat(R: np.ndarray) -> np.ndarray:
+    """wxyz unit quaternion of a rotation matrix (Shepperd: the largest of the four squares is the pivot)."""
+    t = np.trace(R)
+    d = [t, R[0, 0], R[1, 1], R[2, 2]]
+    k = int(np.argmax(d))
+    if k == 0:
+        q = np.array([1.0 + t, R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    else:
+        i, j, l = k - 1, k % 3, (k + 1) % 3
+        q = np.zeros(4)
+        q[0] = R[l, j] - R[j, l]
+        q[1 + i] = 1.0 + R[i, i] - R[j, j] - R[l, l]
+        q[1 + j] = R[j, i] + R[i, j]
+        q[1 + l] = R[l, i] + R[i, l]
+    return q / np.linalg.norm(q)
+
+
+def _rotmat(q: np.ndarray) -> np.ndarray:
+    w, x, y, z = q
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+
+
+def interpolate(pose_a: ArrayLike, pose_b: ArrayLike, steps: int) -> np.ndarray:
+    """(steps, 12) float32 poses from pose_a to pose_b (12 numbers each: R row-major, then t), both included: the
+    rotation by slerp along the shorter arc, the translation by lerp.  fp64 on the host."""
+    a, b = (np.asarray(p, np.float64).reshape(-1) for p in (pose_a, pose_b))
+    steps = int(steps)
+    if a.shape != (12,) or b.shape != (12,) or not (np.isfinite(a).all() and np.isfinite(b).all()):
+        raise ValueError("a pose is 12 finite numbers: R row-major, then t")
+    if steps < 2:
+        raise ValueError(f"steps must be >= 2, got {steps}")
+    qa, qb = _quat(a[:9].reshape(3, 3)), _quat(b[:9].reshape(3, 3))
+    dot = float(qa @ qb)
+    if dot < 0.0:
+        qb, dot = -qb, -dot
+    theta = math.acos(min(1.0, dot))
+    out = np.empty((steps, 12))
+    for i, s in enumerate(np.arange(steps) / (steps - 1.0)):
+        if theta < 1e-9:
+            q = (1.0 - s) * qa + s * qb
+        else:
+            q = (math.sin((1.0 - s) * theta) * qa + math.sin(s * theta) * qb) / math.sin(theta)
+        out[i, :9] = _rotmat(q / np.linalg.norm(q)).reshape(-1)
+        out[i, 9:] = (1.0 - s) * a[9:] + s * b[9:]
+    out[0], out[-1] = a, b
+    return out.astype(np.float32)
+
+
+# ------------------------------------------------------------------------------------------------
+# device side: the three calls
+# ------------------------------------------------------------------------------------------------
+def _volume(grid, dims):
+    g = np.asarray(grid, np.float64).reshape(-1)
+    d = np.asarray(dims, np.int64).reshape(-1)
+    if g.shape != (4,) or d.shape != (3,):
+        raise ValueError("grid is (4,) lower corner and cell edge, dims (3,) cells")
+    return grid_args((g, d)), tuple(int(v) for v in d)
+
+
+def splat(mass: Tensor, grid, dims, means: Tensor, rot: Tensor, scales: Tensor, weights: Tensor,
+          extent: float = EXTENT, max_reach: int = MAX_REACH, min_weight: float = MIN_WEIGHT,
+          sign: int = 1) -> SplatCounts:
+    """One gg_field_splat call: adds sign times every row's vote into `mass` (int64 [X][Y][Z] on the HIP device, in
+    place).  means (N, 3), rot (N, 9) or (N, 3, 3), scales (N, 3) activated, weights (N,): float32 on the same device
+    (no CPU path).  Nothing waits on the host."""
+    dev = _require_hip(mass, means, rot, scales, weights)
+    (g, d), shape = _volume(grid, dims)
+    if mass.dtype != torch.int64 or tuple(mass.shape) != shape or not mass.is_contiguous():
+        raise ValueError(f"mass must be a contiguous int64 {shape} tensor, got {mass.dtype} {tuple(mass.shape)}")
+    means = f32_rows(means, "means", 3)
+    n = means.shape[0]
+    rot = f32_rows(rot.reshape(rot.shape[0], 9) if rot.ndim == 3 else rot, "rot", 9)
+    scales = f32_rows(scales, "scales", 3)
+    weights = f32_rows(weights, "weights", None)
+    if not (rot.shape[0] == scales.shape[0] == weights.shape[0] == n):
+        raise ValueError(f"means has {n} rows, rot {rot.shape[0]}, scales {scales.shape[0]}, "
+                         f"weights {weights.shape[0]}")
+    if math.isnan(float(min_weight)):
+        raise ValueError("min_weight must not be NaN")
+    if int(sign) not in (1, -1):
+        raise ValueError(f"sign must be +1 or -1, got {sign}")
+    if not 0 <= int(max_reach) <= MAX_REACH_LIMIT:
+        raise ValueError(f"max_reach must be in 0..{MAX_REACH_LIMIT}, got {max_reach}")
+    counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    _lib.check(_lib.load().gg_field_splat(d, g, n, _ptr(means), _ptr(rot), _ptr(scales), _ptr(weights),
+                                          nonneg("extent", extent), int(max_reach), float(min_weight), int(sign),
+                                          _ptr(mass), _ptr(counts[0:]), _ptr(counts[1:]), _stream(dev)),
+               "gg_field_splat")
+    return SplatCounts(counts[0], counts[1])
+
+
+def distance(mass: Tensor, dims, threshold: int = THRESHOLD, out: Optional[Tensor] = None) -> Tensor:
+    """dist2 int32 [X][Y][Z] of `mass` (gg_field_distance): the squared distance, in cells, to the nearest cell with
+    mass >= threshold; FAR everywhere when there is none."""
+    dev = _require_hip(mass)
+    shape = tuple(int(v) for v in np.asarray(dims).reshape(-1))
+    if mass.dtype != torch.int64 or tuple(mass.shape) != shape or not mass.is_contiguous():
+        raise ValueError(f"mass must be a contiguous int64 {shape} tensor, got {mass.dtype} {tuple(mass.shape)}")
+    if int(threshold) < 1:
+        raise ValueError(f"threshold must be >= 1, got {threshold}")
+    d = (C.c_int32 * 3)(*shape)
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty(shape, dtype=torch.int32, device=dev)
+    elif out.dtype != torch.int32 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"out must be a contiguous int32 {shape} tensor on {dev}")
+    ws = sized_workspace(lib.gg_field_distance_workspace(d), f"{shape} cells are beyond gg_field_distance's limits",
+                         dev)
+    _lib.check(lib.gg_field_distance(d, _ptr(mass), int(threshold), _ptr(out), _ptr(ws), ws.numel(), _stream(dev)),
+               "gg_field_distance")
+    return out
+
+
+def paths(dist2: Tensor, grid, dims, poses: Tensor, spheres: Tensor, need: Tensor,
+          outside: int = FAR) -> Tuple[Tensor, Tensor]:
+    """(slack (P, W) int32, first_hit (P,) int32) of one gg_field_paths call.  poses (P, W, 12) and spheres (S, 3)
+    float32, need (S,) int32 in 0..FAR, dist2 int32 [X][Y][Z]: on the HIP device (no CPU path)."""
+    dev = _require_hip(dist2, poses, spheres, need)
+    (g, d), shape = _volume(grid, dims)
+    if dist2.dtype != torch.int32 or tuple(dist2.shape) != shape or not dist2.is_contiguous():
+        raise ValueError(f"dist2 must be a contiguous int32 {shape} tensor, got {dist2.dtype} {tuple(dist2.shape)}")
+    if poses.dtype != torch.float32 or poses.ndim != 3 or poses.shape[2] != 12:
+        raise ValueError(f"poses must be a float32 (P, W, 12) tensor, got {poses.dtype} {tuple(poses.shape)}")
+    spheres = f32_rows(spheres, "spheres", 3)
+    s = spheres.shape[0]
+    if need.dtype != torch.int32 or tuple(need.shape) != (s,):
+        raise ValueError(f"need must be an int32 ({s},) tensor, got {need.dtype} {tuple(need.shape)}")
+    p, w = poses.shape[:2]
+    if p * w > MAX_POSES or s > MAX_SPHERES:
+        raise ValueError(f"{p} x {w} poses and {s} spheres: at most {MAX_POSES} poses and {MAX_SPHERES} spheres")
+    if not 0 <= int(outside) <= FAR:
+        raise ValueError(f"outside must be in 0..{FAR}, got {outside}")
+    poses, need = poses.contiguous(), need.contiguous()
+    slack = torch.empty(p, w, dtype=torch.int32, device=dev)
+    first = torch.empty(p, dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().gg_field_paths(d, g, _ptr(dist2), p, w, _ptr(poses), s, _ptr(spheres), _ptr(need),
+                                          int(outside), _ptr(slack), _ptr(first), _stream(dev)), "gg_field_paths")
+    return slack, first
+
+
+# ------------------------------------------------------------------------------------------------
+# the volume
+# ------------------------------------------------------------------------------------------------
+@torch.no_grad()
+def model_gaussians(model_or_scene, mask: Optional[Tensor] = None):
+    """(means, rot, scales, weights) of a model or scene as gg_field_splat takes them, built the way
+    grasp.model_points builds its inputs: ops.quat_to_rotmat, exp(scales), sigmoid(opacities) times `mask`."""
+    from . import ops
+    means, quats = model_or_scene.means.detach(), model_or_scene.quats.detach()
+    scales, opac = model_or_scene.scales.detach(), model_or_scene.opacities.detach()
+    _require_hip(means, quats, scales, opac)
+    rot = ops.quat_to_rotmat(quats.float()).reshape(-1, 9).contiguous()
+    weights = torch.sigmoid(opac.float()).reshape(-1)
+    if mask is not None:
+        mask = mask.reshape(-1)
+        if mask.shape[0] != weights.shape[0]:
+            raise ValueError(f"mask has {mask.shape[0]} entries for {weights.shape[0]} Gaussians")
+        weights = weights * mask.to(device=weights.device, dtype=torch.float32)
+    return means.float().contiguous(), rot, torch.exp(scales.float()).contiguous(), weights.contiguous()
+
+
+class DistanceField:
+    """Occupancy mass and squared distances of the scene inside a box: `mass` int64 and `dist2` int32 [X][Y][Z] on
+    the HIP device, `grid` (4,) float64 lower corner and cell edge, `dims` (3,) int32.  add / remove change the mass
+    (integer votes: removing what was added restores it bit for bit), update() recomputes dist2 from it."""
+
+    def __init__(self, bbox_min: Sequence[float], bbox_max: Sequence[float], voxel: float = VOXEL, device=None):
+        self.grid, self.dims = field_grid(bbox_min, bbox_max, voxel)
+        dev = default_device("field") if device is None else torch.device(device)
+        shape = tuple(int(d) for d in self.dims)
+        self.mass = torch.zeros(shape, dtype=torch.int64, device=dev)
+        self.dist2 = torch.full(shape, FAR, dtype=torch.int32, device=dev)
+        self.threshold = THRESHOLD
+
+    @property
+    def h(self) -> float:
+        return float(self.grid[3])
+
+    def add(self, source, mask: Optional[Tensor] = None, extent: float = EXTENT, max_reach: int = MAX_REACH,
+            min_weight: float = MIN_WEIGHT, sign: int = 1) -> SplatCounts:
+        """Adds the votes of a model or scene (model_gaussians, times `mask`), or of a tuple (means, rot, scales,
+        weights) of device tensors, to the mass.  dist2 is stale until update()."""
+        if isinstance(source, (tuple, list)):
+            means, rot, scales, weights = source
+            if mask is not None:
+                weights = weights * mask.reshape(-1).to(device=weights.device, dtype=torch.float32)
+        else:
+            means, rot, scales, weights = model_gaussians(source, mask)
+        return splat(self.mass, self.grid, self.dims, means, rot, scales, weights, extent, max_reach, min_weight, sign)
+
+    def remove(self, source, mask: Optional[Tensor] = None, extent: float = EXTENT, max_reach: int = MAX_REACH,
+               min_weight: float = MIN_WEIGHT) -> SplatCounts:
+        """add with sign -1: takes out exactly what the same call of add put in."""
+        return self.add(source, mask, extent, max_reach, min_weight, sign=-1)
+
+    def update(self, threshold: Optional[int] = None) -> "DistanceField":
+        if threshold is not None:
+            self.threshold = int(threshold)
+        distance(self.mass, self.dims, self.threshold, out=self.dist2)
+        return self
+
+    def distance(self) -> Tensor:
+        """sqrt(dist2) h as float32, in scene units between cell centres; inf where dist2 is FAR."""
+        d = torch.sqrt(self.dist2.to(torch.float64)) * self.h
+        return torch.where(self.dist2 >= FAR, torch.full_like(d, math.inf), d).float()
+
+    def save(self, path: str) -> None:
+        np.savez_compressed(path, mass=self.mass.cpu().numpy(), dist2=self.dist2.cpu().numpy(), grid=self.grid,
+                            dims=self.dims, threshold=np.int64(self.threshold))
+
+    @classmethod
+    def load(cls, path: str, device=None) -> "DistanceField":
+        with np.load(path) as z:
+            grid, dims = np.asarray(z["grid"], np.float64), np.asarray(z["dims"], np.int32)
+            mass, dist2, thr = z["mass"], z["dist2"], int(z["threshold"])
+        shape = tuple(int(d) for d in dims)
+        if grid.shape != (4,) or dims.shape != (3,) or mass.shape != shape or dist2.shape != shape:
+            raise ValueError(f"{path}: not a distance field (grid {grid.shape}, dims {dims.shape}, mass {mass.shape})")
+        f = cls.__new__(cls)
+        dev = default_device("field") if device is None else torch.device(device)
+        f.grid, f.dims, f.threshold = grid, dims, thr
+        f.mass = torch.from_numpy(mass.astype(np.int64)).to(dev)
+        f.dist2 = torch.from_numpy(dist2.astype(np.int32)).to(dev)
+        return f
+
+
+def path_clear(field: DistanceField, poses: ArrayLike, spheres: ArrayLike, radius: Union[float, ArrayLike],
+               margin: float = 0.0, outside: str = "free") -> PathClearance:
+    """Every path's waypoints against field.dist2 (update() first): poses (P, W, 12), spheres (S, 3) gripper-frame
+    centres of `radius` (one number or (S,)), kept `margin` away from every occupied cell (need2).  outside: what a
+    sphere centre outside the volume counts as, "free" or "blocked"."""
+    if outside not in ("free", "blocked"):
+        raise ValueError(f"outside must be 'free' or 'blocked', got {outside!r}")
+    dev = field.dist2.device
+    sp = to_device(spheres, torch.float32, dev).reshape(-1, 3)
+    need = need2(np.broadcast_to(np.asarray(radius, np.float64), (sp.shape[0],)), margin, field.h)
+    p = to_device(poses, torch.float32, dev)
+    slack, first = paths(field.dist2, field.grid, field.dims, p, sp, torch.from_numpy(need).to(dev),
+                         FAR if outside == "free" else 0)
+    return PathClearance(slack, first, first == p.shape[1])
+
+
+# ------------------------------------------------------------------------------------------------
+# command line
+# ------------------------------------------------------------------------------------------------
+def main(argv: Optional[Sequence[str]] = None) -> int:
+    from ._cli import add_object_options, check_object_options, load_scene, object_mask
+    from .frames import load_transform_json
+    from .grasp import load_gripper_option
+    ap = argparse.ArgumentParser(prog="python -m gaussiangrasper_amd.field",
+                                 description="Distance field of a checkpoint's Gaussians inside a box and, with "
+                                             "--paths, the clearance of gripper paths through it.")
+    ap.add_argument("--ckpt", required=True, help="step-*.ckpt of a splatting model")
+    ap.add_argument("--bbox", type=float, nargs=6, required=True, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
+                    help="the box, scene frame")
+    ap.add_argument("--voxel", type=float, default=VOXEL, help="cell edge, scene units")
+    ap.add_argument("--extent", type=float, default=EXTENT, help="a Gaussian occupies its k-sigma ellipsoid")
+    ap.add_argument("--max-reach", type=int, default=MAX_REACH, help="cells a Gaussian may reach from its mean's cell")
+    ap.add_argument("--min-opacity", type=float, default=MIN_WEIGHT, help="a Gaussian takes part above it")
+    ap.add_argument("--occupied", type=float, default=THRESHOLD / VOTE_ONE,
+                    help="a cell is occupied from this much opacity mass on")
+    ap.add_argument("--transform-json", default=None, help="JSON with transform_matrix and scale (world -> scene)")
+    add_object_options(ap, "the selected Gaussians are LEFT OUT of the field (the object being carried)",
+                       "selects the Gaussians that are left out of the field (the object being carried)")
+    ap.add_argument("--out", required=True, help="output .npz: mass, dist2, grid, dims, threshold")
+    ap.add_argument("--paths", default=None, help=".npy (P, W, 12) gripper poses, scene frame: R row-major, then t")
+    ap.add_argument("--gripper", default=None, metavar="{default,FILE.json}", help="with --paths: the gripper model")
+    ap.add_argument("--width", type=float, default=0.08, help="with --paths: the gripper's opening, scene units")
+    ap.add_argument("--depth", type=float, default=0.02, help="with --paths: the fingers' depth")
+    ap.add_argument("--height", type=float, default=0.02, help="with --paths: the fingers' height")
+    ap.add_argument("--radius", type=float, default=0.005, help="with --paths: radius of the covering spheres")
+    ap.add_argument("--margin", type=float, default=0.0, help="with --paths: clearance kept beyond the spheres")
+    ap.add_argument("--outside", choices=("free", "blocked"), default="free",
+                    help="with --paths: what space outside the box counts as")
+    ap.add_argument("--report", default=None, help="with --paths: output .npz slack, first_hit, clear, spheres")
+    a = ap.parse_args(argv)
+    check_object_options(ap, a, "optional")
+    if bool(a.paths) != bool(a.gripper) or bool(a.paths) != bool(a.report):
+        ap.error("--paths, --gripper and --report go together")
+    for n in ("voxel", "radius", "width"):
+        if not (math.isfinite(getattr(a, n)) and getattr(a, n) > 0.0):
+            ap.error(f"--{n} must be finite and > 0, got {getattr(a, n)}")
+    for n in ("extent", "margin", "depth", "height"):
+        if not (math.isfinite(getattr(a, n)) and getattr(a, n) >= 0.0):
+            ap.error(f"--{n} must be finite and >= 0, got {getattr(a, n)}")
+    if not 0 <= a.max_reach <= MAX_REACH_LIMIT:
+        ap.error(f"--max-reach must be in 0..{MAX_REACH_LIMIT}, got {a.max_reach}")
+    if math.isnan(a.min_opacity):
+        ap.error("--min-opacity must not be NaN")
+    if not (math.isfinite(a.occupied) and 1 <= math.trunc(a.occupied * VOTE_ONE) < 2 ** 62):
+        ap.error(f"--occupied must be at least 2^-16, got {a.occupied}")
+    try:
+        grid, dims = field_grid(a.bbox[:3], a.bbox[3:], a.voxel)
+        spheres = poses = None
+        if a.paths:
+            spheres = gripper_spheres(load_gripper_option(a.gripper), a.width, a.depth, a.height, a.radius)
+            poses = np.asarray(np.load(a.paths), np.float32)
+            if poses.ndim != 3 or poses.shape[2] != 12:
+                raise ValueError(f"{a.paths}: expected (P, W, 12) poses, got {poses.shape}")
+        matrix, scale = load_transform_json(a.transform_json) if a.transform_json else (None, 1.0)
+        scene, mlp_state = load_scene(a.ckpt)
+        carried = object_mask(a, scene, mlp_state, matrix, scale)
+        field = DistanceField(a.bbox[:3], a.bbox[3:], a.voxel)
+        counts = field.add(scene, None if carried is None else ~carried.bool(), a.extent, a.max_reach, a.min_opacity)
+        field.update(math.trunc(a.occupied * VOTE_ONE))
+        field.save(a.out)
+        line = (f"{tuple(int(d) for d in dims)} cells, {int((field.dist2 == 0).sum())} occupied; "
+                f"{int(counts.skipped)} Gaussians took no part, {int(counts.truncated)} were cut by --max-reach; "
+                f"wrote {a.out}")
+        if a.paths:
+            res = path_clear(field, poses, spheres, a.radius, a.margin, a.outside)
+            np.savez(a.report, slack=res.slack.cpu().numpy(), first_hit=res.first_hit.cpu().numpy(),
+                     clear=res.clear.cpu().numpy(), spheres=spheres)
+            line += f"; {int(res.clear.sum())} of {poses.shape[0]} paths clear, wrote {a.report}"
+    except (KeyError, ValueError, OSError) as exc:
+        raise SystemExit(f"error: {exc}") from exc
+    print(line)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1104,6 +1104,62 @@ int gg_tsdf_mesh_emit(const int32_t *dims, const float *grid, const float *tsdf,
                       int64_t num_faces, float *vertices, float *normals, float *colors, int32_t *faces,
                       const void *ws, size_t ws_bytes, gg_stream_t stream);
 
+/* ---- distance field of the scene (PARITY "Distance field") -----------------------------------------
+ * The volume: dims (host, 3 ints) X, Y, Z cells, 1 <= each <= GG_FIELD_MAX_DIM, X Y Z <= GG_FIELD_MAX_CELLS; grid
+ * (host, 4 doubles) the lower corner lo and ONE cubic cell edge h > 0, all finite.  Cell (i, j, k) has index
+ * (i Y + j) Z + k (C order [X][Y][Z], z fastest, the TSDF volume's layout).  Along axis a, cell c contains the
+ * coordinate p iff (double)c h <= d < (double)(c + 1) h with d = (double)p - lo_a: fp64 products and comparisons (a
+ * division may propose c, the comparisons decide).  A cell's centre is x_a = lo_a + ((double)c + 0.5) h.
+ *
+ * gg_field_splat: Gaussians to integer occupancy mass.  means [N][3], rot [N][9] (row-major, the columns are the
+ * axes: ops.quat_to_rotmat), scales [N][3] (activated), weights [N]: fp32.  extent k: finite, >= 0; max_reach in
+ * 0..GG_FIELD_MAX_REACH; min_weight not NaN; sign +1 or -1.  A row takes part iff all 16 of its inputs are finite,
+ * every scale is > 0 and min_weight < (double)w < 2^15; its vote is q = trunc((double)w 2^16) (an exact product) as
+ * int64.  mass int64 [X][Y][Z], in / out: the row adds sign q to
+ *   (a) the cell that contains its mean, if there is one;
+ *   (b) every other cell within Chebyshev distance `reach` of that cell (found per axis by the rule above even when
+ *       it lies outside the volume; cells outside the volume are dropped) whose centre x is in the closed k-sigma
+ *       ellipsoid: with d = x - (double)m, u_j = (R[0][j] d_0 + R[1][j] d_1) + R[2][j] d_2, A_j = (double)s_j (double)s_j:
+ *       ((u_0 u_0)(A_1 A_2) + (u_1 u_1)(A_0 A_2)) + (u_2 u_2)(A_0 A_1) <= (k k)((A_0 A_1) A_2)
+ *       in fp64 with exactly this parenthesisation and no contraction.
+ * reach = min(max_reach, n + 1), n the smallest integer >= 0 with (double)n h >= k (double)max_j s_j.  The box is a
+ * cull; a row it cuts (n + 1 > max_reach) is data, not an error.  skipped / truncated (device, one int64 each) are
+ * WRITTEN: the rows of this call that took no part / that max_reach cut.  Integer sums commute: mass is the same from
+ * run to run, and a +1 call followed by a -1 call on the same rows restores it bit for bit (-1 adds the two's
+ * complement).  num_rows == 0 writes nothing.  fp32 arrays 4-byte aligned, int64 arrays 8-byte.
+ *
+ * gg_field_distance: the exact squared Euclidean distance transform.  A cell is occupied iff mass >= threshold
+ * (>= 1).  dist2 int32 [X][Y][Z] (written whole) = min over occupied cells of di^2 + dj^2 + dk^2 in cell units: 0 on
+ * occupied cells, exactly GG_FIELD_FAR everywhere when no cell is occupied.  Three separable integer min-plus passes,
+ * z then y then x, from f = occupied ? 0 : FAR, f'[c] = min_c' f[c'] + (c - c')^2 (values stay below 2^31: FAR +
+ * 2 1023^2 < 2^31), and a final clamp to FAR.  ws: gg_field_distance_workspace(dims) bytes (0 for dims out of
+ * range), 256-byte aligned, of any content.
+ *
+ * gg_field_paths: gripper paths against the field.  poses fp32 [P][W][12]: R row-major (9), then t (3); spheres fp32
+ * [S][3]: centres in the gripper frame; need2 int32 [S], each in 0..GG_FIELD_FAR; outside in 0..GG_FIELD_FAR: the
+ * dist2 taken for a centre outside the volume (FAR: free, 0: blocked).  Per pose with 12 finite entries and per
+ * sphere: c_k = ((R[k][0] x + R[k][1] y) + R[k][2] z) + t_k in fp64, its cell by the rule above (a centre that is
+ * not finite is outside), d = dist2[cell].  slack int32 [P][W] = min_s (d - need2[s]); GG_FIELD_FAR when S == 0;
+ * INT32_MIN for a pose that is not finite.  first_hit int32 [P] = the smallest w with slack < 0, or W.  No atomics
+ * and no floating-point decision beyond the cell rule.  P W <= GG_FIELD_MAX_POSES, S <= GG_FIELD_MAX_SPHERES; with
+ * P == 0 or W == 0 nothing is written.  Every array 4-byte aligned. */
+#define GG_FIELD_MAX_DIM 1024
+#define GG_FIELD_MAX_CELLS (1 << 27)
+#define GG_FIELD_FAR (1 << 30)
+#define GG_FIELD_MAX_REACH 64
+#define GG_FIELD_MAX_ROWS (1 << 30)
+#define GG_FIELD_MAX_POSES (1 << 26)
+#define GG_FIELD_MAX_SPHERES 1024
+int gg_field_splat(const int32_t *dims, const double *grid, int num_rows, const float *means, const float *rot,
+                   const float *scales, const float *weights, double extent, int max_reach, double min_weight,
+                   int sign, int64_t *mass, int64_t *skipped, int64_t *truncated, gg_stream_t stream);
+size_t gg_field_distance_workspace(const int32_t *dims);
+int gg_field_distance(const int32_t *dims, const int64_t *mass, int64_t threshold, int32_t *dist2, void *ws,
+                      size_t ws_bytes, gg_stream_t stream);
+int gg_field_paths(const int32_t *dims, const double *grid, const int32_t *dist2, int num_paths, int num_waypoints,
+                   const float *poses, int num_spheres, const float *spheres, const int32_t *need2, int32_t outside,
+                   int32_t *slack, int32_t *first_hit, gg_stream_t stream);
+
 /* ---- in-library kernel timing (measurement only; off by default) --------------------------------
  * When enabled, every launch of the kernels below is bracketed by a hipEvent pair recorded on the
  * launch stream, so bench.py can report the average duration of exactly that kernel over its
