@@ -76,6 +76,7 @@ SIGNATURES = {
     "gg_blend_fwd_pair_fast": (_I, [_I, _I, _I, _I, _I] + [_P] * 14 + [_SZ, _P]),
     "gg_blend_bwd": (_I, [_I, _I, _I, _I] + [_P] * 14 + [_I, _I, _P, _SZ, _I, _P]),
     "gg_blend_votes": (_I, [_I, _I, _I, _I] + [_P] * 7 + [_P, _SZ, _I, _P]),
+    "gg_blend_hits": (_I, [_I, _I, _I] + [_P] * 5 + [_F] + [_P] * 4 + [_P, _SZ, _I, _P]),
     "gg_shade_tail_bwd_split": (_I, [_I, _P, _I, _P, _P, _P, _P, _P]),
     "gg_view_bwd": (_I, [_I, _P, _I, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _F, _F, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gg_pose_grad_workspace": (_SZ, [_I]),

@@ -257,6 +257,35 @@ extern "C" int gg_blend_votes(int num_labels, int N, int img_h, int img_w, const
     return GG_OK;
 }
 
+// gg_blend_hits: what the forward walk finds under every pixel (kernel: hits.hip).  No profiling id: the ids of the
+// forward's range are taken, so tools/hits_bench.py times the call with device events.
+extern "C" int gg_blend_hits(int N, int img_h, int img_w, const int32_t *ids, const int32_t *tile_bins, const float *xys,
+                             const float *conics, const float *opacity, float t_hit, int32_t *hit_idx, int32_t *top_idx,
+                             float *top_vis, int32_t *count, void *ws, size_t ws_bytes, int ws_packed,
+                             gg_stream_t stream) {
+    auto misaligned = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3) != 0; };
+    GG_REQUIRE(N >= 0, "num_points < 0");
+    GG_REQUIRE(img_h > 0 && img_w > 0, "img_height and img_width must be > 0");
+    GG_REQUIRE(t_hit > GG_T_EPS && t_hit < 1.0f, "t_hit must be in (1e-4, 1)");   // NaN fails
+    GG_REQUIRE(hit_idx != nullptr, "hit_idx is null");
+    GG_REQUIRE((top_idx != nullptr) == (top_vis != nullptr) && (top_idx != nullptr) == (count != nullptr),
+               "top_idx, top_vis and count are given together or not at all");
+    GG_REQUIRE(!misaligned(hit_idx), "hit_idx must be 4-byte aligned");
+    GG_REQUIRE(!misaligned(top_idx), "top_idx must be 4-byte aligned");
+    GG_REQUIRE(!misaligned(top_vis), "top_vis must be 4-byte aligned");
+    GG_REQUIRE(!misaligned(count), "count must be 4-byte aligned");
+    GG_REQUIRE(N == 0 || ids != nullptr, "gaussian_ids_sorted is null");
+    GG_REQUIRE(tile_bins != nullptr, "tile_bins is null");
+    GG_REQUIRE(N == 0 || ws_packed != 0 || (xys && conics && opacity), "xys, conics or opacity is null");
+    BlendWalk w;
+    const int rc = blend_begin(__func__, {N, img_h, img_w, ids, tile_bins, xys, conics, opacity, ws, ws_bytes, stream},
+                               false, true, true, ws_packed != 0, w);
+    if (rc != GG_OK) return rc;
+    gg_launch_blend_hits(w, N, t_hit, hit_idx, top_idx, top_vis, count);
+    GG_CHECK_LAUNCH();
+    return GG_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // deterministic backward: slab of per-(list entry, quadrant) totals + ordered per-Gaussian sums
 // ---------------------------------------------------------------------------------------------

@@ -55,6 +55,9 @@ void gg_launch_blend2_bwd_pair(const BlendWalk &w, const BlendColors &src, const
                                const BlendColors &src2, const BlendGrad2 &g2);
 // votes.hip: the vote walk of gg_blend_votes (labels (H, W) bytes, votes (N, L) int64, added to)
 void gg_launch_blend_votes(const BlendWalk &w, int L, int N, const uint8_t *labels, int64_t *votes);
+// hits.hip: the walk of gg_blend_hits ((H, W) outputs, overwritten; top_idx == nullptr: the hit-only build)
+void gg_launch_blend_hits(const BlendWalk &w, int N, float t_hit, int32_t *hit_idx, int32_t *top_idx, float *top_vis,
+                          int32_t *count);
 #ifdef GG_ABLATION
 void gg_launch_blend2_bwd_ablate(int abl, const BlendWalk &w, const BlendColors &src, const BlendChunk &ch,
                                  const BlendBwdIn &in, const BlendGradOut &g);

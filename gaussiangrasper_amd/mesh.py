@@ -9,7 +9,8 @@ csrc/tsdf.hip).  The contract is in include/gg_raster.h, the deliberate differen
     reference (nerfstudio)                           here
     TSDF.from_aabb (tsdf_utils.py)                   TSDFVolume(bbox_min, bbox_max, resolution)
     TSDF.integrate_tsdf                              TSDFVolume.integrate (projective z, plain running mean)
-    render_trajectory (exporter_utils.py)            render_depth (the library's own operators, depth = D / A)
+    render_trajectory (exporter_utils.py)            render_depth (the library's own operators, depth = D / A, or
+                                                     depth_mode="median": the median Gaussian's, surface.py)
     TSDF.get_mesh (skimage marching cubes)           TSDFVolume.extract (marching tetrahedra, observed cells)
     export_tsdf_mesh + pymeshlab save                mesh_model / mesh_scan + write_ply_mesh
     ns-export tsdf --resolution 128 --downscale 2    python -m gaussiangrasper_amd.mesh --ckpt ... | --scan ...
@@ -179,16 +180,30 @@ class TSDFVolume:
 # ------------------------------------------------------------------------------------------------
 # depth of the Gaussian field
 # ------------------------------------------------------------------------------------------------
+DEPTH_MODES = ("expected", "median")
+
+
+def check_depth_mode(depth_mode: str) -> str:
+    if depth_mode not in DEPTH_MODES:
+        raise ValueError(f"depth_mode must be one of {', '.join(DEPTH_MODES)}, got {depth_mode!r}")
+    return depth_mode
+
+
 @torch.no_grad()
 def render_depth(model_or_scene, c2w: ArrayLike, intrinsics: ArrayLike, height: int, width: int,
-                 mask: Optional[Tensor] = None, alpha_min: float = ALPHA_MIN) -> Tuple[Tensor, Tensor, Tensor]:
+                 mask: Optional[Tensor] = None, alpha_min: float = ALPHA_MIN,
+                 depth_mode: str = "expected") -> Tuple[Tensor, Tensor, Tensor]:
     """(depth (H, W), rgb (H, W, 3), alpha (H, W)) of a model or Scene from one nerfstudio / OpenGL c2w, through the
     library's operators with eval semantics (the full SH degree).  One extra segment of colour (z, 1) over a (0, 0)
     background gives D = sum w z and A = sum w; depth = D / A where A >= alpha_min, +inf (free space) elsewhere;
-    rgb = the rendered colour / A.  mask (N,) bool renders only the selected Gaussians."""
+    rgb = the rendered colour / A.  mask (N,) bool renders only the selected Gaussians.
+    depth_mode "median": depth is the depth of the Gaussian at which the transmittance falls to <= 0.5
+    (ops.blend_hits on the same tile lists), +inf where it never does — always the depth of a real Gaussian, where D / A
+    lies between two surfaces that share a pixel; t_hit = 0.5 plays the role of alpha_min, which is then not used."""
     from . import ops
     from .camera import view_from_c2w
     from .constants import deg_from_sh
+    check_depth_mode(depth_mode)
     src = model_or_scene
     means, scales, quats = src.means.detach(), src.scales.detach(), src.quats.detach()
     opac, sh = src.opacities.detach(), src.colors_all.detach()
@@ -224,6 +239,9 @@ def render_depth(model_or_scene, c2w: ArrayLike, intrinsics: ArrayLike, height: 
     D, A = za[..., 0], za[..., 1]
     hit = A >= float(alpha_min)
     depth = torch.where(hit, D / A, torch.full_like(D, float("inf")))
+    if depth_mode == "median":       # what surface.view_hits(full=False).depth holds, on this call's projection
+        from .surface import hit_depth
+        depth = hit_depth(depths, ops.blend_hits(xys, depths, radii, conics, num_tiles_hit, op, h, w, full=False)[0])
     rgb = torch.where(A[..., None] > 0, rgb / A[..., None].clamp_min(1e-12), torch.zeros_like(rgb)).clamp(0.0, 1.0)
     return depth, rgb, A
 
@@ -236,9 +254,11 @@ def _scaled_intrinsics(K: np.ndarray, h: int, w: int, downscale: float) -> Tuple
 def mesh_model(model_or_scene, cameras: Sequence[Tuple[ArrayLike, ArrayLike, int, int]], bbox=BBOX,
                resolution=RESOLUTION, downscale: float = DOWNSCALE, mask: Optional[Tensor] = None,
                truncation: Optional[float] = None, alpha_min: float = ALPHA_MIN, batch: int = 16,
-               color: bool = True) -> Mesh:
+               color: bool = True, depth_mode: str = "expected") -> Mesh:
     """Mesh of a model or Scene (of the Gaussians `mask` selects): every camera (c2w OpenGL (3|4, 4), intrinsics
-    fx, fy, cx, cy, height, width) rendered at 1 / downscale of its size, fused in batches of `batch` frames."""
+    fx, fy, cx, cy, height, width) rendered at 1 / downscale of its size, fused in batches of `batch` frames.
+    depth_mode: render_depth's ("median": no skirt where a front object and the background share a pixel)."""
+    check_depth_mode(depth_mode)
     if downscale <= 0:
         raise ValueError(f"downscale must be > 0, got {downscale}")
     vol = TSDFVolume(bbox[0], bbox[1], resolution, truncation, device=model_or_scene.means.device)
@@ -252,7 +272,7 @@ def mesh_model(model_or_scene, cameras: Sequence[Tuple[ArrayLike, ArrayLike, int
     for (hs, ws), group in by_size.items():
         for b0 in range(0, len(group), batch):
             part = group[b0:b0 + batch]
-            rendered = [render_depth(model_or_scene, c2w, K, hs, ws, mask, alpha_min) for c2w, K, _, _ in part]
+            rendered = [render_depth(model_or_scene, c2w, K, hs, ws, mask, alpha_min, depth_mode) for c2w, K, _, _ in part]
             depth = torch.stack([r[0] for r in rendered])
             rgb = torch.stack([r[1] for r in rendered]) if color else None
             vol.integrate(depth, np.stack([p[1] for p in part]), np.stack([homogeneous(p[0]) for p in part]), rgb)
@@ -395,7 +415,7 @@ def _checkpoint_mesh(a, bbox) -> Tuple[Mesh, Optional[Tuple[np.ndarray, float]]]
     mask = object_mask(a, scene, mlp_state)
     if mask is not None and not bool(mask.any()):
         raise ValueError("the query selects no Gaussian")
-    mesh = mesh_model(scene, cams, bbox, a.resolution, a.downscale, mask)
+    mesh = mesh_model(scene, cams, bbox, a.resolution, a.downscale, mask, depth_mode=a.depth_mode)
     return mesh, tf
 
 
@@ -415,6 +435,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                     help="volume box (checkpoint frame for --ckpt, default [-1, 1]^3)")
     ap.add_argument("--resolution", type=int, default=RESOLUTION, help="lattice points per axis")
     ap.add_argument("--downscale", type=float, default=DOWNSCALE, help="render at 1 / K of each camera's size")
+    ap.add_argument("--depth-mode", choices=DEPTH_MODES, default="expected",
+                    help="with --ckpt: the depth fused per pixel: the expected depth D / A, or the depth of the median "
+                         "Gaussian (transmittance 0.5)")
     ap.add_argument("--depth-units", type=float, default=1.0, help="with --scan: raw depth units per metre")
     add_object_options(ap, "mesh only the Gaussians the query selects")
     add_support_options(ap, grasp=False)
@@ -424,6 +447,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         ap.error("--ckpt needs --transforms")
     if a.scan and (a.transforms or a.transform_json or a.positives):
         ap.error("--transforms, --transform-json and --positives go with --ckpt")
+    if a.scan and a.depth_mode != "expected":
+        ap.error("--depth-mode goes with --ckpt")
     check_object_options(ap, a, "none")
     check_support_options(ap, a, grasp=False)
     if a.resolution < 2 or a.downscale <= 0:

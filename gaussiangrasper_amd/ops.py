@@ -608,6 +608,68 @@ def blend_votes(xys: Tensor, depths: Tensor, radii: Tensor, conics: Tensor, num_
     return True
 
 
+def check_t_hit(t_hit: float) -> float:
+    """t_hit as gg_blend_hits takes it: a float32 strictly between GG_T_EPS (1e-4) and 1."""
+    t = C.c_float(float(t_hit)).value
+    if not C.c_float(1e-4).value < t < 1.0:                      # NaN fails
+        raise ValueError(f"t_hit must be in (1e-4, 1), got {t_hit}")
+    return t
+
+
+@torch.no_grad()
+def blend_hits(xys: Tensor, depths: Tensor, radii: Tensor, conics: Tensor, num_tiles_hit: Tensor, opacity: Tensor,
+               img_height: int, img_width: int, t_hit: float = 0.5, full: bool = True):
+    """What the exact forward walk finds under every pixel (`gg_blend_hits`): (hit_idx, top_idx, top_vis, count),
+    each (H, W).  hit_idx int32: the Gaussian at which the transmittance falls to <= t_hit (the median Gaussian for
+    0.5), -1 where it never does; top_idx int32 / top_vis float32: the Gaussian with the largest blend weight alpha T
+    and that weight (-1 / 0: nothing blended); count int32: the number of blended Gaussians.  full=False returns
+    (hit_idx, None, None, None) from a walk that leaves every pixel at its hit.  The lists are those of a render of
+    the same view (one binning, cached).  Nothing visible: the defaults everywhere."""
+    if xys.ndimension() != 2 or xys.size(1) != 2:
+        raise ValueError("xys must have dimensions (N, 2)")
+    n = xys.size(0)
+    img_height, img_width = int(img_height), int(img_width)
+    if img_height < 1 or img_width < 1:
+        raise ValueError(f"the image must have at least one pixel, got ({img_height}, {img_width})")
+    t_hit = check_t_hit(t_hit)
+    if conics.ndimension() != 2 or tuple(conics.shape) != (n, 3):
+        raise ValueError(f"conics must have dimensions ({n}, 3), got {tuple(conics.shape)}")
+    if opacity.numel() != n:
+        raise ValueError(f"opacity must have {n} entries, got {tuple(opacity.shape)}")
+    dev = _require_hip(xys, depths, radii, conics, num_tiles_hit, opacity)
+    shape = (img_height, img_width)
+    hit_idx = torch.empty(shape, dtype=torch.int32, device=dev)
+    outs = [hit_idx, None, None, None]
+    if full:
+        outs[1:] = [torch.empty(shape, dtype=torch.int32, device=dev), torch.empty(shape, dtype=torch.float32, device=dev),
+                    torch.empty(shape, dtype=torch.int32, device=dev)]
+
+    def defaults():
+        hit_idx.fill_(-1)
+        if full:
+            outs[1].fill_(-1)
+            outs[2].zero_()
+            outs[3].zero_()
+        return tuple(outs)
+
+    if n == 0:
+        return defaults()
+    xys_c, conics_c, opacity_c = _f32(xys.detach()), _f32(conics.detach()), _f32(opacity.detach())
+    bins = bin_and_sort_gaussians(xys, depths, radii, num_tiles_hit, img_height, img_width, speculative=True)
+    lib = _lib.load()
+    ws = _workspace(lib.gg_blend_workspace(n), dev)
+
+    # the call overwrites every pixel, so a walk over lists that turn out truncated is simply walked again
+    def launch():
+        _lib.check(lib.gg_blend_hits(n, img_height, img_width, _ptr(bins.gaussian_ids_sorted), _ptr(bins.tile_bins),
+                                     _ptr(xys_c), _ptr(conics_c), _ptr(opacity_c), t_hit, *(_ptr(t) for t in outs),
+                                     _ptr(ws), ws.numel(), 0, _stream(dev)), "gg_blend_hits")
+
+    if not _blend_with_lists(bins, launch):
+        return defaults()
+    return tuple(outs)
+
+
 def _rasterize_forward(ctx, xys, depths, radii, conics, num_tiles_hit, colors, opacity,
                        img_height, img_width, background, three_channel_only):
     if colors.dtype == torch.uint8:

@@ -415,6 +415,30 @@ int gg_blend_votes(int num_labels, int num_points, int img_height, int img_width
                    int64_t *votes /* (N, num_labels) */, void *ws, size_t ws_bytes, int ws_packed,
                    gg_stream_t stream);
 
+/* gg_blend_hits: what is under a pixel.  For every pixel p inside the image the list of p's tile is walked exactly
+ * as gg_blend_fwd walks it — the same sigma, gg_exp, alpha, T operations in fp32 in the same order, the same
+ * sigma < 0 and alpha < 1/255 rules, the same stop (the entry that would take T to <= 1e-4 is not blended and ends
+ * the walk).  With vis = alpha T of a blended entry and T_after = T (1 - alpha):
+ *
+ *   hit_idx[p]   (int32) the Gaussian id of the first blended entry with T_after <= t_hit (fp32 comparison), -1 if
+ *                there is none: the "median" Gaussian of the pixel for t_hit = 0.5;
+ *   top_idx[p]   (int32) the id of the blended entry with the largest vis, the earliest in list order on equal
+ *                values (strict >); -1 if nothing was blended;
+ *   top_vis[p]   (float) that vis, or 0;
+ *   count[p]     (int32) the number of blended entries.
+ *
+ * Every output is a pure function of the inputs: identical bits from run to run.  A pixel has a hit iff the
+ * forward's final_T there is <= t_hit.  GG_T_EPS (1e-4) < t_hit < 1.  hit_idx is required; top_idx, top_vis and
+ * count are given together or all NULL (the walk then leaves a pixel at its hit).  Each output (H, W), 4-byte
+ * aligned.  The call OVERWRITES: every pixel inside the image is written exactly once, pixels of tiles with empty
+ * lists included (-1, -1, 0, 0); with num_points == 0 every pixel gets these defaults and the lists are not read.
+ * ws, ws_packed: as in gg_blend_votes.  Null, misaligned or out-of-range arguments: GG_ERR_INVALID_ARG with the
+ * argument's name in gg_last_error(), before any launch. */
+int gg_blend_hits(int num_points, int img_height, int img_width, const int32_t *gaussian_ids_sorted,
+                  const int32_t *tile_bins, const float *xys, const float *conics, const float *opacity, float t_hit,
+                  int32_t *hit_idx, int32_t *top_idx, float *top_vis, int32_t *count, void *ws, size_t ws_bytes,
+                  int ws_packed, gg_stream_t stream);
+
 /* ---- feature up-projection MLP ------------------------------------------------
  * Replaces the forward of the reference's `MLP(32, 512, hidden_list=[128])` module
  * (nerfstudio/models/gaussian_splatting.py:198-213; `self.fea_up`, called on every pixel of the
