@@ -110,6 +110,9 @@ SIGNATURES = {
     "gg_adam_step": (_I, [_I, C.POINTER(AdamGroup), _I, _P]),
     "gg_hull_edit": (_I, [_I, _P, _P, _I, _P, C.c_double, _P, _P, _P, _P]),
     "gg_sh_rotate": (_I, [_I, _I, _P, _P, _P, _P]),
+    "gg_rigid_bwd_workspace": (_SZ, [_I]),
+    "gg_rigid_fwd": (_I, [_I] + [_P] * 7 + [_P]),
+    "gg_rigid_bwd": (_I, [_I] + [_P] * 11 + [_P, _SZ, _P]),
     "gg_object_masks_workspace": (_SZ, [_I, _I]),
     "gg_object_masks": (_I, [_I, _P, _P, _I, _P, _P, _I, _I, _I, _I] + [_P] * 7 + [_SZ, _P]),
     "gg_clip_query_workspace": (_SZ, [_I, _I, _I, _I]),

@@ -7,6 +7,8 @@ gripper's pose change — on one HIP kernel (`gg_hull_edit`, csrc/edit.hip) inst
     prepare_transform :342-355, main :141-158  rotvec_to_matrix, compose_transform, object_points_to_scene
     transformed_gs :217-240                    select_and_move (in place) / edit_model
     (not in the reference)                     sh= / rotate_sh= / --rotate-sh: the moved Gaussians' SH lobes turn too
+    (not in the reference)                     refine= / --refine-transforms: the pose change is first corrected against
+                                               frames captured after the object was put down (pose.refine_object)
     save_checkpoint :257-286                   python -m gaussiangrasper_amd.edit ... --out step-000000000.ckpt
 
 The fine-tune that follows is the existing training path.  Two deliberate differences from the reference
@@ -143,9 +145,26 @@ def select_and_move(means: Tensor, quats: Optional[Tensor], planes: ArrayLike,
     return mask, count
 
 
-@torch.no_grad()
+def refine_transform(model, planes: ArrayLike, transform: Optional[ArrayLike], refine: dict, tol: float = 0.0
+                     ) -> np.ndarray:
+    """The object's motion re-localised against observed frames before it is applied (pose.refine_object): select
+    the hull's Gaussians (nothing is moved), fit the six-number correction on the left of `transform` with every
+    Gaussian frozen, and return the composed [R | t], (3, 4) float32 — what select_and_move takes.
+    refine: pose.refine_object's keywords — cameras, rgbs, and optionally depths, valids, steps, depth_weight, mode."""
+    from . import pose
+    mask, count = select_and_move(model.means.detach(), None, planes, None, tol)
+    if int(count.item()) == 0:
+        raise ValueError("no Gaussian lies inside the object's hull")
+    base = None
+    if transform is not None:
+        base = torch.eye(4, dtype=torch.float64)
+        base[:3, :] = torch.from_numpy(rigid_rows(transform, np.float64).reshape(3, 4))
+    T, _ = pose.refine_object(model, mask, base=base, **refine)
+    return T[:3, :].detach().cpu().numpy().astype(np.float32)
+
+
 def edit_model(model, planes: ArrayLike, transform: Optional[ArrayLike], tol: float = 0.0,
-               rotate_sh: bool = False) -> int:
+               rotate_sh: bool = False, refine: Optional[dict] = None) -> int:
     """update.py transformed_gs (:217-240) on a model holding `means` / `quats` Parameters (the plugin's fused model,
     stub.StubGaussianSplattingModel): the same Parameter objects are edited in place, so an optimizer keeps
     referencing them and its Adam moments stay as they are (the reference keeps them too: it saves the original
@@ -154,7 +173,19 @@ def edit_model(model, planes: ArrayLike, transform: Optional[ArrayLike], tol: fl
     (the reference asserts the same).
 
     rotate_sh: also turn the selected rows of `model.colors_all` (select_and_move's sh=), in place on the same
-    Parameter.  Its Adam moments are left as they are, like those of means and quats: they are not rotated."""
+    Parameter.  Its Adam moments are left as they are, like those of means and quats: they are not rotated.
+
+    refine: None, or refine_transform's dictionary (cameras, rgbs, depths, valids, steps, ...): the transform is
+    first corrected against the observed frames with the Gaussians frozen, then applied by the same exact path
+    (Shepperd's quaternion rule, rotate_sh as given)."""
+    if refine is not None:
+        with torch.enable_grad():
+            transform = refine_transform(model, planes, transform, refine, tol)
+    with torch.no_grad():
+        return _edit_model(model, planes, transform, tol, rotate_sh)
+
+
+def _edit_model(model, planes, transform, tol, rotate_sh) -> int:
     means, quats = model.means, model.quats
     colors = model.colors_all if rotate_sh else None
     mask, count = select_and_move(means.detach(), quats.detach(), planes, transform, tol,
@@ -181,9 +212,65 @@ def load_object_points(path: str) -> np.ndarray:
     return pts[:, :3]
 
 
+def read_refine_frames(transforms_json: str, transform_json: Optional[str], scale: float,
+                       depth_dir: Optional[str] = None):
+    """The observed frames pose.refine_object fits against, from a scan's transforms.json (OpenCV c2w, raw frame):
+    (cameras as lift.scene_cameras gives them, in the checkpoint's frame; rgbs (H, W, 3) float32 in [0, 1], read with
+    PIL from images/<stem>.png next to the json, as prepare reads them; depths (H, W) float32 or None, <stem>.npy of
+    depth_dir in the scan's metres times `scale`; valids (H, W) bool, depth > 0, or None)."""
+    from PIL import Image
+    from .lift import frame_stems, scene_cameras
+    cams, _ = scene_cameras(transforms_json, transform_json)
+    root = os.path.dirname(os.path.abspath(transforms_json))
+    rgbs, depths, valids = [], [], []
+    for stem, (_, _, h, w) in zip(frame_stems(transforms_json), cams):
+        path = os.path.join(root, "images", stem + ".png")
+        if not os.path.exists(path):
+            raise ValueError(f"missing file: {path}")
+        rgb = np.asarray(Image.open(path).convert("RGB"))
+        if rgb.shape[:2] != (h, w):
+            raise ValueError(f"{path} is {rgb.shape[0]} x {rgb.shape[1]}, transforms.json gives h x w = {h} x {w}")
+        rgbs.append(torch.from_numpy(rgb.astype(np.float32) / 255.0))
+        if depth_dir:
+            dpath = os.path.join(depth_dir, stem + ".npy")
+            if not os.path.exists(dpath):
+                raise ValueError(f"missing file: {dpath}")
+            d = np.load(dpath).astype(np.float64).reshape(h, w) * float(scale)
+            depths.append(torch.from_numpy(d.astype(np.float32)))
+            valids.append(torch.from_numpy(np.isfinite(d) & (d > 0)))
+    return cams, rgbs, (depths or None), (valids or None)
+
+
+def refine_scene_transform(scene, mask: Tensor, rt: np.ndarray, cams, rgbs, depths=None, valids=None,
+                           steps: int = 100) -> np.ndarray:
+    """pose.refine_object on a Scene (a checkpoint's tensors) through the differentiable operator sequence
+    (pipeline.render_view), cameras as lift.scene_cameras gives them: the corrected [R | t], (3, 4) float32."""
+    from . import ops, pose
+    from .camera import view_from_c2w
+    from .constants import deg_from_sh
+    from .frames import homogeneous
+    from .pipeline import render_view
+    from .scene import Scene
+    dev = scene.means.device
+    views = [view_from_c2w(torch.as_tensor(homogeneous(c2w)), *[float(v) for v in K], int(h), int(w), dev)
+             for c2w, K, h, w in cams]
+    deg = deg_from_sh(scene.colors_all.shape[1])
+    fixed = [t.detach() for t in (scene.scales, scene.opacities, scene.colors_all, scene.feature)]
+
+    def render(means, quats, k):
+        ops.clear_bin_cache()
+        s = Scene(means, fixed[0], quats, fixed[1], fixed[2], fixed[3])
+        return render_view(s, views[k], ops, sh_degree_to_use=deg, channels=("rgb", "depth"))
+    base = torch.eye(4, dtype=torch.float64)
+    base[:3, :] = torch.from_numpy(np.asarray(rt, np.float64).reshape(3, 4))
+    T, _ = pose.refine_object(render, mask, [None] * len(views), rgbs, depths=depths, valids=valids, base=base,
+                              steps=steps, means=scene.means.float(), quats=scene.quats.float())
+    return T[:3, :].detach().cpu().numpy().astype(np.float32)
+
+
 def edit_checkpoint(ckpt: str, object_points: np.ndarray, matrix: ArrayLike, scale: float, pose_from: ArrayLike,
                     pose_to: ArrayLike, out: str, tol: float = 0.0, outlier_factor: float = 1.0,
-                    device: str = "cuda", rotate_sh: bool = False) -> int:
+                    device: str = "cuda", rotate_sh: bool = False, refine: Optional[dict] = None) -> int:
     """Load `ckpt`, move the Gaussians inside the object's hull, write `out` with `step` 0.  Only
     `pipeline["_model.means"]` and `pipeline["_model.quats"]` change — with rotate_sh also
     `pipeline["_model.colors_all"]`, the moved Gaussians' SH coefficients turned with them and written back in their
@@ -201,6 +288,18 @@ def edit_checkpoint(ckpt: str, object_points: np.ndarray, matrix: ArrayLike, sca
     means = m0.detach().to(device=device, dtype=torch.float32).contiguous()
     quats = q0.detach().to(device=device, dtype=torch.float32).contiguous()
     sh = pipe[keys[2]].detach().to(device=device, dtype=torch.float32).contiguous() if rotate_sh else None
+    if refine is not None:
+        # re-localise the object against the observed frames first (pose.refine_object); the move itself stays the
+        # exact path below.  refine: transforms (the frames' transforms.json), transform_json (the dataparser's file,
+        # for the cameras), depth_dir, steps
+        from ._cli import load_scene
+        sel, n_sel = select_and_move(means, None, planes, None, tol)
+        if int(n_sel.item()) == 0:
+            raise ValueError("no Gaussian lies inside the object's hull")
+        cams, rgbs, depths, valids = read_refine_frames(refine["transforms"], refine.get("transform_json"), scale,
+                                                        refine.get("depth_dir"))
+        rt = refine_scene_transform(load_scene(ckpt)[0], sel, rt, cams, rgbs, depths, valids,
+                                    steps=int(refine.get("steps") or 100))
     _, count = select_and_move(means, quats, planes, rt, tol, sh=sh)
     selected = int(count.item())
     if selected == 0:
@@ -233,12 +332,28 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--outlier-factor", type=float, default=1.0)
     ap.add_argument("--rotate-sh", action="store_true",
                     help="also rotate the moved Gaussians' SH colour coefficients (_model.colors_all)")
+    ap.add_argument("--refine-transforms", default=None, metavar="T.json",
+                    help="re-localise the object first: a transforms.json (OpenCV c2w, raw frame) of frames captured "
+                         "after the object was put down, images in images/<stem>.png next to it; the pose change is "
+                         "corrected by fitting the render to them with the Gaussians frozen (pose.refine_object)")
+    ap.add_argument("--refine-depth", default=None, metavar="DIR",
+                    help="with --refine-transforms: <stem>.npy depth maps of those frames, metres")
+    ap.add_argument("--refine-steps", type=int, default=None, metavar="K",
+                    help="with --refine-transforms: at most K evaluations of the loss (default 100)")
     a = ap.parse_args(argv)
+    if not a.refine_transforms and (a.refine_depth or a.refine_steps is not None):
+        ap.error("--refine-depth / --refine-steps need --refine-transforms")
+    if a.refine_steps is not None and a.refine_steps < 1:
+        ap.error(f"--refine-steps must be >= 1, got {a.refine_steps}")
     with open(a.transform_json) as f:
         tj = json.load(f)
+    refine = None
+    if a.refine_transforms:
+        refine = {"transforms": a.refine_transforms, "transform_json": a.transform_json, "depth_dir": a.refine_depth,
+                  "steps": a.refine_steps}
     try:
         n = edit_checkpoint(a.ckpt, load_object_points(a.object_points), *load_transform_json(tj), a.pose_from,
-                            a.pose_to, a.out, a.tol, a.outlier_factor, rotate_sh=a.rotate_sh)
+                            a.pose_to, a.out, a.tol, a.outlier_factor, rotate_sh=a.rotate_sh, refine=refine)
     except (KeyError, ValueError) as exc:
         raise SystemExit(f"error: {exc}") from exc
     print(f"selected {n} Gaussians; wrote {a.out}")

@@ -1345,3 +1345,89 @@ def quat_to_rotmat(quat: Tensor) -> Tensor:
     if quat.shape[-1] != 4:
         raise ValueError(f"quat must have dimensions (..., 4), got {tuple(quat.shape)}")
     return _QuatToRotmat.apply(quat)
+
+
+# ------------------------------------------------------------------------------------------------
+# RigidMove: a subset of the Gaussians moved by a pose that is itself a tensor
+# ------------------------------------------------------------------------------------------------
+def _quat_mul(a: Tensor, b: Tensor) -> Tensor:
+    """Hamilton product of wxyz quaternions, every component in the order of include/gg_raster.h"""
+    w1, x1, y1, z1 = a.unbind(-1)
+    w2, x2, y2, z2 = b.unbind(-1)
+    return torch.stack((w1 * w2 - x1 * x2 - y1 * y2 - z1 * z2, w1 * x2 + x1 * w2 + y1 * z2 - z1 * y2,
+                        w1 * y2 - x1 * z2 + y1 * w2 + z1 * x2, w1 * z2 + x1 * y2 - y1 * x2 + z1 * w2), -1)
+
+
+def rigid_move_torch(means: Tensor, quats: Tensor, mask: Optional[Tensor], rt: Tensor, qt: Tensor):
+    """gg_rigid_fwd's formulas as a torch composite on any device: fp64 inside, each output rounded once to the
+    input's dtype, rows not selected passed through.  What RigidMove runs on CPU tensors (the host tests and the
+    oracle-backed routes) and what tools/rigid_bench.py times the kernels against."""
+    rt64 = rt.reshape(3, 4).double()
+    m, q = means.double(), quats.double()
+    R, t = rt64[:, :3], rt64[:, 3]
+    moved = ((R[:, 0] * m[:, 0:1] + R[:, 1] * m[:, 1:2]) + R[:, 2] * m[:, 2:3]) + t
+    turned = _quat_mul(qt.reshape(1, 4).double(), q)
+    moved, turned = moved.to(means.dtype), turned.to(quats.dtype)
+    if mask is None:
+        return moved, turned
+    sel = (mask != 0)[:, None]
+    return torch.where(sel, moved, means), torch.where(sel, turned, quats)
+
+
+class RigidMoveFunction(Function):
+    """(means, quats, mask, rt, qt) -> (means', quats') on gg_rigid_fwd / gg_rigid_bwd.  The pose's gradient is the
+    kernels' ordered fp64 sum: the same inputs give the same bits."""
+
+    @staticmethod
+    def forward(ctx, means: Tensor, quats: Tensor, mask: Optional[Tensor], rt: Tensor, qt: Tensor):
+        dev = _require_hip(means, quats, rt, qt, *([mask] if mask is not None else []))
+        m, q = _f32(means), _f32(quats)
+        n = m.shape[0]
+        if m.ndim != 2 or m.shape[1] != 3 or q.shape != (n, 4):
+            raise ValueError(f"means must be (N, 3) and quats (N, 4), got {tuple(m.shape)} and {tuple(q.shape)}")
+        if rt.numel() != 12 or qt.numel() != 4:
+            raise ValueError(f"rt must hold 12 numbers and qt 4, got {tuple(rt.shape)} and {tuple(qt.shape)}")
+        if mask is not None:
+            if mask.shape != (n,) or mask.dtype not in (torch.uint8, torch.bool):
+                raise ValueError(f"mask must be a uint8 or bool (N,) tensor, got {mask.dtype} {tuple(mask.shape)}")
+            mask = mask.contiguous().view(torch.uint8)
+        rt_c, qt_c = _f32(rt.detach()).reshape(12), _f32(qt.detach()).reshape(4)
+        m_out, q_out = torch.empty_like(m), torch.empty_like(q)
+        _lib.check(_lib.load().gg_rigid_fwd(n, _ptr(m), _ptr(q), _ptr(mask), _ptr(rt_c), _ptr(qt_c), _ptr(m_out),
+                                            _ptr(q_out), _stream(dev)), "gg_rigid_fwd")
+        ctx.save_for_backward(m, q, mask, rt_c, qt_c)
+        ctx.shapes = (rt.shape, qt.shape, rt.dtype, qt.dtype, means.dtype, quats.dtype)
+        return m_out.to(means.dtype), q_out.to(quats.dtype)
+
+    @staticmethod
+    def backward(ctx, g_means, g_quats):
+        m, q, mask, rt_c, qt_c = ctx.saved_tensors
+        rt_shape, qt_shape, rt_dtype, qt_dtype, m_dtype, q_dtype = ctx.shapes
+        dev, n = m.device, m.shape[0]
+        lib = _lib.load()
+        rows = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]     # frozen Gaussians: the pose-only pass
+        g_m = None if g_means is None else _f32(g_means)
+        g_q = None if g_quats is None else _f32(g_quats)
+        v_m = torch.empty_like(m) if rows else None
+        v_q = torch.empty_like(q) if rows else None
+        v_pose = torch.empty(16, dtype=torch.float32, device=dev)
+        ws = _workspace(lib.gg_rigid_bwd_workspace(n), dev)
+        _lib.check(lib.gg_rigid_bwd(n, _ptr(m), _ptr(q), _ptr(mask), _ptr(rt_c), _ptr(qt_c), _ptr(g_m), _ptr(g_q),
+                                    _ptr(v_m), _ptr(v_q), _ptr(v_pose), C.c_void_p(v_pose.data_ptr() + 48), _ptr(ws),
+                                    ws.numel(), _stream(dev)), "gg_rigid_bwd")
+        return (v_m.to(m_dtype) if ctx.needs_input_grad[0] else None,
+                v_q.to(q_dtype) if ctx.needs_input_grad[1] else None, None,
+                v_pose[:12].reshape(rt_shape).to(rt_dtype) if ctx.needs_input_grad[3] else None,
+                v_pose[12:].reshape(qt_shape).to(qt_dtype) if ctx.needs_input_grad[4] else None)
+
+
+def RigidMove(means: Tensor, quats: Tensor, mask: Optional[Tensor], rt: Tensor, qt: Tensor) -> Tuple[Tensor, Tensor]:
+    """Move the rows of `means` (N, 3) and `quats` (N, 4, wxyz) that `mask` (N,) uint8 / bool selects (None: every
+    row) by the pose rt = [R | t] (12 numbers, row-major) and qt, the quaternion of R: means' = R x + t,
+    quats' = qt (x) q, not normalised; the other rows pass through.  Differentiable in means, quats, rt and qt.
+    On a HIP device one kernel each way (RigidMoveFunction); CPU tensors run the torch composite of the same formulas
+    (rigid_move_torch) — that route is for the host tests and the oracle-backed operators, not a fallback: a HIP
+    tensor never takes it."""
+    if means.device.type == "cpu":
+        return rigid_move_torch(means, quats, mask, rt, qt)
+    return RigidMoveFunction.apply(means, quats, mask, rt, qt)

@@ -297,6 +297,11 @@ def make_fused_model_class(base, ops=_ops, background_override=lambda: None, fus
         # "eager": on every call, in a plain dict, as the reference does; "off": feature_vis = first 3 channels
         feature_vis_mode = "lazy"
 
+        # None, or (mask (N,) uint8, rt (3, 4), qt (4,)): get_outputs renders the scene with the selected Gaussians moved
+        # by that pose (ops.RigidMove, differentiable in rt and qt; pose.refine_object sets it).  The parameters stay
+        # as they are.  None: not one launch more, the same bits
+        object_pose = None
+
         def get_outputs(self, camera) -> Dict[str, Union[torch.Tensor, List]]:
             if not hasattr(camera, "camera_to_worlds"):            # :633-635
                 print("Called get_outputs with not a camera")
@@ -386,7 +391,11 @@ def make_fused_model_class(base, ops=_ops, background_override=lambda: None, fus
             else:
                 _, full_proj, cam_pos = view_c
             n = min(self.step // self.config.sh_degree_interval, self.config.sh_degree)
-            out = fused_view(self, pick(self.means), pick(self.scales), pick(self.quats), pick(self.opacities),
+            means, quats = self.means, self.quats
+            if self.object_pose is not None:   # pose.refine_object: the selected rows moved by a pose that is a tensor
+                pose_mask, pose_rt, pose_qt = self.object_pose
+                means, quats = getattr(ops, "RigidMove", _ops.RigidMove)(means, quats, pose_mask, pose_rt, pose_qt)
+            out = fused_view(self, pick(means), pick(self.scales), pick(quats), pick(self.opacities),
                              pick(self.colors_all), pick(self.feature), viewmat, projmat, cam_pos, fx, fy, cx, cy,
                              H, W, tile_bounds, n, ops, full_proj=full_proj)
             if out is None:

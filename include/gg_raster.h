@@ -638,6 +638,38 @@ int gg_hull_edit(int num_points, float *means, float *quats, int num_planes, con
 int gg_sh_rotate(int num_points, int num_bases, float *coeffs, const uint8_t *mask, const float *bands,
                  gg_stream_t stream);
 
+/* ---- the rigid move as a differentiable operator (PARITY "Object pose refinement") ------------------
+ * gg_rigid_fwd moves the selected rows by a pose held on the DEVICE (it is an autograd tensor inside an optimiser
+ * loop: no host read-back); gg_rigid_bwd is its vector-Jacobian product, per row and for the pose.
+ *   rt:   12 floats, [R | t] row-major 3 x 4.   qt: 4 floats, wxyz, the quaternion of R (keeping it consistent with
+ *         R is the caller's job).
+ *   mask: (num_points) uint8, non-zero = selected (gg_hull_edit's mask as it is), or NULL: every row.
+ * Forward, a selected row, every fp32 input widened to fp64, no contraction:
+ *   m'_a = (float)(((R[a][0] x + R[a][1] y) + R[a][2] z) + t[a])
+ *   q'   = (float)(qt (x) q), the Hamilton product: each component four fp64 products added left to right in the
+ *          order of the usual expression, rounded once:
+ *            w = w1 w2 - x1 x2 - y1 y2 - z1 z2      x = w1 x2 + x1 w2 + y1 z2 - z1 y2
+ *            y = w1 y2 - x1 z2 + y1 w2 + z1 x2      z = w1 z2 + x1 y2 - y1 x2 + z1 w2
+ *   Nothing is normalised (the renderer normalises).  A row not selected is copied byte for byte.
+ * Backward, per row: selected  v_m[b] = (float)((R[0][b] g0 + R[1][b] g1) + R[2][b] g2),
+ *   v_q = (float)(conj(qt) (x) g_q); not selected: the cotangent's bytes.  g_means or g_quats NULL is read as zeros.
+ *   v_means and v_quats may each be NULL (both: the pose-only pass for frozen Gaussians, where a row not selected
+ *   costs its mask byte only).
+ * Backward, the pose: sixteen sums over the selected rows, v_rt[a][b] = sum g_a p_b (b < 3), v_rt[a][3] = sum g_a,
+ *   v_qt = sum g_q (x) conj(q) (the expression above with the second operand's x, y, z negated).  Every term is
+ *   fp64; one row of 16 per workgroup of 256 Gaussians by gg_block_row<16>, then one workgroup's
+ *   gg_chain_sum<16, GG_SUM_CHAINS> (csrc/ordered_sum.h).  The totals are rounded to fp32 and WRITTEN (not added).
+ *   No floating-point atomics: the same inputs give the same bytes, whatever ws held on entry.  num_points == 0
+ *   writes sixteen zeros and nothing else (ws is not looked at).
+ * Alignment: means*, g_means, v_means, rt, qt, v_rt, v_qt 4 bytes; quats*, g_quats, v_quats 16; mask 1; ws 256,
+ * gg_rigid_bwd_workspace(num_points) bytes (0 for num_points < 0).  The outputs must not overlap the inputs. */
+size_t gg_rigid_bwd_workspace(int num_points);
+int gg_rigid_fwd(int num_points, const float *means, const float *quats, const uint8_t *mask, const float *rt,
+                 const float *qt, float *means_out, float *quats_out, gg_stream_t stream);
+int gg_rigid_bwd(int num_points, const float *means, const float *quats, const uint8_t *mask, const float *rt,
+                 const float *qt, const float *g_means, const float *g_quats, float *v_means, float *v_quats,
+                 float *v_rt, float *v_qt, void *ws, size_t ws_bytes, gg_stream_t stream);
+
 /* ---- per-view masks of the moved object (reference scripts/project_hull.py :83-121; DESIGN 3.14, PARITY "Scene
  * update") -----------------------------------------------------------------------------------------------------------
  * For every view v and pose (0 = before, 1 = after) — a job — in fp64, no contraction:
