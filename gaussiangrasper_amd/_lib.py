@@ -152,6 +152,8 @@ SIGNATURES = {
     "gg_field_distance_workspace": (_SZ, [_P]),
     "gg_field_distance": (_I, [_P, _P, _I64, _P, _P, _SZ, _P]),
     "gg_field_paths": (_I, [_P, _P, _P, _I, _I, _P, _I, _P, _P, _I, _P, _P, _P]),
+    "gg_height_map": (_I, [_I, _P, _P, C.c_double, _I, _P, _P, _P, _P, _P, _P]),
+    "gg_place_search": (_I, [_P, _P, _I, _P, _P, C.c_int32, _P, _P, _P, _P]),
     "gg_prof_enable": (_I, [_I]),
     "gg_prof_reset": (_I, []),
     "gg_prof_get": (_I, [_I, C.POINTER(C.c_int), C.POINTER(C.c_double)]),

@@ -13,6 +13,7 @@
 // gg_field_paths      a thread per pose with the spheres in LDS, then a thread per path for first_hit.  No atomics.
 #include <math.h>
 
+#include "field_cell.h"
 #include "gg_common.h"
 
 #define FS_THREADS 256
@@ -20,24 +21,11 @@
 #define FD_THREADS 256
 #define FD_TILE 8                  // lines per workgroup of a distance pass
 #define FP_THREADS 256
-#define FIELD_CELL_CLAMP 1073741824.0   // 2^30: a cell index beyond it is outside every volume and every reach
 
 struct FieldGrid {
     int X, Y, Z;
     double lo[3], h;
 };
-
-// The cell along one axis of d = p - lo: floor(d / h), corrected by one so that c h <= d < (c + 1) h holds in fp64.
-// d finite.  Clamped to +-2^30 (outside every volume, and further from it than any reach).
-__device__ __forceinline__ int field_cell(double d, double h) {
-    double c = floor(d / h);
-    c = c < -FIELD_CELL_CLAMP ? -FIELD_CELL_CLAMP : (c > FIELD_CELL_CLAMP ? FIELD_CELL_CLAMP : c);
-    if (c * h > d)
-        c -= 1.0;
-    else if ((c + 1.0) * h <= d)
-        c += 1.0;
-    return (int)c;
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // splat

@@ -1216,6 +1216,51 @@ int gg_field_paths(const int32_t *dims, const double *grid, const int32_t *dist2
                    const float *poses, int num_spheres, const float *spheres, const int32_t *need2, int32_t outside,
                    int32_t *slack, int32_t *first_hit, gg_stream_t stream);
 
+/* ---- placement: height maps and the resting search (PARITY "Placement") ----------------------------
+ * A plane grid: dims (host, 2 ints) U, V cells, 1 <= each <= GG_PLACE_MAX_DIM; grid (host, 4 doubles) lo_u, lo_v, ONE
+ * square cell edge h > 0 and the level height hz > 0, all finite.  A map is int32 [U][V] (C order, v fastest) of
+ * integer height levels; a cell that holds nothing is GG_PLACE_EMPTY.
+ *
+ * gg_height_map: points to height levels, for F frames in one call.  points fp32 [N][3]; weights fp32 [N] or null;
+ * min_weight not NaN; frames fp64 [F][12] on the DEVICE, 8-byte aligned: the origin o, then the axes e0, e1, e2,
+ * taken as given (the host makes them orthonormal), 1 <= F <= GG_PLACE_MAX_YAWS; N <= GG_PLACE_MAX_POINTS.  A point
+ * takes part iff its three coordinates are finite and weights is null or min_weight < (double)w.  Per frame:
+ * d = (double)p - o, c_a = (d_0 e_a0 + d_1 e_a1) + d_2 e_a2 in fp64 with exactly this parenthesisation and no
+ * contraction.  When c_0 - lo_u, c_1 - lo_v and c_2 are all finite, the cell along u is the integer a with
+ * (double)a h <= c_0 - lo_u < (double)(a + 1) h (the distance field's rule: a division may propose, the comparisons
+ * decide), along v the same with c_1 - lo_v, and the level the integer z with (double)z hz <= c_2 < (double)(z + 1) hz,
+ * clamped to +-GG_PLACE_MAX_LEVEL.  A point whose cell is outside the grid, or for which one of the three is not
+ * finite, is dropped for that frame.  map int32 [F][U][V], in / out: map[f][a][b] = max(map[f][a][b], z) by integer
+ * atomic max; the caller fills it with GG_PLACE_EMPTY first, several calls accumulate, and the result is the same from
+ * run to run.  dropped int64 [F] (8-byte aligned) is WRITTEN: the points of this call that took no part or were
+ * dropped for that frame.  N == 0 writes only dropped.  One mode only: the UNDERSIDE of an object is its map in a
+ * frame with e2 = -n, under = max level(-c_2).  fp32 and int32 arrays 4-byte aligned.
+ *
+ * gg_place_search: the resting height of an object over every yaw and anchor.  top int32 [U][V]; foot (host, 2 ints)
+ * A, B in 1..GG_PLACE_MAX_FOOT with A <= U, B <= V; under int32 [K][A][B], K in 0..GG_PLACE_MAX_YAWS; tol in
+ * 0..GG_PLACE_MAX_LEVEL.  THE CALLER'S DUTY: every level that is not GG_PLACE_EMPTY lies within +-GG_PLACE_MAX_LEVEL,
+ * so that every sum below stays under 2^30.  With I = U - A + 1, J = V - B + 1, for yaw k and anchor (i, j) in
+ * [0, I) x [0, J), over the object cells (a, b) with under[k][a][b] != GG_PLACE_EMPTY:
+ *   s(a, b) = top[i + a][j + b] + under[k][a][b]
+ *   rest    int32 [K][I][J]    = max s
+ *   contact int32 [K][I][J]    = the number of object cells with s >= rest - tol
+ *   support int32 [K][I][J][6] = over those contact cells: sum a, sum b, min a, max a, min b, max b.
+ * The anchor is INVALID when map k has no object cell, or when top[i + a][j + b] is GG_PLACE_EMPTY for an object cell
+ * (a, b); it gets rest = GG_PLACE_EMPTY, contact = 0, support = {0, 0, -1, -1, -1, -1}.  Every output element is
+ * written; no atomics and no floating point.  K == 0 writes nothing.  Every array 4-byte aligned.
+ * Null, misaligned or out-of-range arguments: GG_ERR_INVALID_ARG naming the argument, before any launch. */
+#define GG_PLACE_EMPTY (-2147483647 - 1) /* INT32_MIN */
+#define GG_PLACE_MAX_LEVEL (1 << 28)
+#define GG_PLACE_MAX_DIM 4096
+#define GG_PLACE_MAX_FOOT 128
+#define GG_PLACE_MAX_YAWS 256
+#define GG_PLACE_MAX_POINTS (1 << 30)
+int gg_height_map(int num_points, const float *points, const float *weights, double min_weight, int num_frames,
+                  const double *frames, const double *grid, const int32_t *dims, int32_t *map, int64_t *dropped,
+                  gg_stream_t stream);
+int gg_place_search(const int32_t *dims, const int32_t *top, int num_yaws, const int32_t *foot, const int32_t *under,
+                    int32_t tol, int32_t *rest, int32_t *contact, int32_t *support, gg_stream_t stream);
+
 /* ---- in-library kernel timing (measurement only; off by default) --------------------------------
  * When enabled, every launch of the kernels below is bracketed by a hipEvent pair recorded on the
  * launch stream, so bench.py can report the average duration of exactly that kernel over its
