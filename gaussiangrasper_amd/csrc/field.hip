@@ -11,6 +11,14 @@
 //                     and every thread finds its cell's minimum by an outward search that ends at delta^2 >= best.
 //                     A pass reads and writes only its own lines, so y runs in place on the workspace.
 // gg_field_paths      a thread per pose with the spheres in LDS, then a thread per path for first_hit.  No atomics.
+// gg_field_route      the cost-to-go over the free cells.  The volume is cut into bricks of FR_BRICK^3
+//                     cells.  A round is one launch with a workgroup per brick; the workgroup of a brick that is
+//                     not flagged returns, an active one loads its costs and free bits with a one-cell halo into
+//                     LDS, relaxes the 26 moves there until nothing changes, writes back what fell and flags (for the
+//                     next round) the neighbours that read a changed outer cell.  No workgroup waits for another:
+//                     every dependency is a launch boundary, and the host reads one array of counters per FR_BATCH
+//                     rounds to see that a round flagged nothing.
+// gg_field_descend    a wave per path: lane m < 27 tests move m, a ballot's lowest set lane is the tie rule.
 #include <math.h>
 
 #include "field_cell.h"
@@ -21,6 +29,10 @@
 #define FD_THREADS 256
 #define FD_TILE 8                  // lines per workgroup of a distance pass
 #define FP_THREADS 256
+#define FR_BRICK 8                 // cells per brick edge
+#define FR_HALO 10                 // FR_BRICK + 2: the brick with its one-cell halo
+#define FR_THREADS 256             // two cells of a brick per thread; four paths (waves) per workgroup of the descent
+#define FR_BATCH 16                // rounds enqueued between two read-backs of the counters
 
 struct FieldGrid {
     int X, Y, Z;
@@ -272,6 +284,207 @@ __global__ __launch_bounds__(FP_THREADS) void field_first_hit_kernel(int P, int 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// route: the cost-to-go over the free cells, and the descent along it
+// ---------------------------------------------------------------------------------------------------------------
+// Move m = (dx + 1) 9 + (dy + 1) 3 + (dz + 1); m == 13 is no move.  Its weight is 3, 4 or 5 (the 3-4-5 chamfer).
+__device__ __forceinline__ constexpr int fr_dx(int m) { return m / 9 - 1; }
+__device__ __forceinline__ constexpr int fr_dy(int m) { return (m / 3) % 3 - 1; }
+__device__ __forceinline__ constexpr int fr_dz(int m) { return m % 3 - 1; }
+__device__ __forceinline__ constexpr int fr_weight(int m) {
+    return 2 + (fr_dx(m) != 0) + (fr_dy(m) != 0) + (fr_dz(m) != 0);
+}
+// The cells move m needs free, as bits numbered like the moves: every c + e with e_a in {0, d_a} (bit 13 is c).
+__device__ __forceinline__ constexpr unsigned fr_block_mask(int m) {
+    unsigned mask = 0u;
+    for (int a = 0; a <= (fr_dx(m) != 0); ++a)
+        for (int b = 0; b <= (fr_dy(m) != 0); ++b)
+            for (int c = 0; c <= (fr_dz(m) != 0); ++c)
+                mask |= 1u << ((a * fr_dx(m) + 1) * 9 + (b * fr_dy(m) + 1) * 3 + (c * fr_dz(m) + 1));
+    return mask;
+}
+
+// Reads and writes of `cost` that may meet another brick's within a round: relaxed, at the device's scope.
+__device__ __forceinline__ int fr_load(const int *p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void fr_store(int *p, int v) {
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// cost = FAR, the workspace (counters and both flag arrays) and `ignored` zero
+__global__ __launch_bounds__(FR_THREADS) void route_init_kernel(long long cells, int *__restrict__ cost,
+                                                                long long ws_words, unsigned *__restrict__ ws,
+                                                                unsigned long long *__restrict__ ignored) {
+    const long long i = (long long)blockIdx.x * FR_THREADS + threadIdx.x;
+    if (i < cells) cost[i] = GG_FIELD_FAR;
+    if (i < ws_words) ws[i] = 0u;
+    if (i == 0) *ignored = 0ull;
+}
+
+__global__ __launch_bounds__(FR_THREADS) void route_zero_kernel(unsigned *p, int n) {
+    if ((int)threadIdx.x < n) p[threadIdx.x] = 0u;
+}
+
+// A goal that is inside and free costs 0.  Its brick and the bricks around it start active: a goal in an outer
+// layer is read by them, and no round's write-back announces it.
+__global__ __launch_bounds__(FR_THREADS) void route_goals_kernel(int X, int Y, int Z, int bx, int by, int bz,
+                                                                 const int *__restrict__ dist2, int need, int G,
+                                                                 const int *__restrict__ goals, int *cost,
+                                                                 unsigned *flags,
+                                                                 unsigned long long *__restrict__ ignored) {
+    const int i = blockIdx.x * FR_THREADS + threadIdx.x;      // G <= GG_FIELD_MAX_GOALS
+    if (i >= G) return;
+    const int x = goals[(size_t)i * 3], y = goals[(size_t)i * 3 + 1], z = goals[(size_t)i * 3 + 2];
+    const bool in = x >= 0 && x < X && y >= 0 && y < Y && z >= 0 && z < Z;
+    const size_t at = in ? ((size_t)x * Y + y) * Z + z : 0;
+    if (!in || dist2[at] < need) {
+        atomicAdd(ignored, 1ull);
+        return;
+    }
+    fr_store(cost + at, 0);
+    const int ix = x / FR_BRICK, iy = y / FR_BRICK, iz = z / FR_BRICK;
+    for (int a = max(ix - 1, 0); a <= min(ix + 1, bx - 1); ++a)
+        for (int b = max(iy - 1, 0); b <= min(iy + 1, by - 1); ++b)
+            for (int c = max(iz - 1, 0); c <= min(iz + 1, bz - 1); ++c) flags[((size_t)a * by + b) * bz + c] = 1u;
+}
+
+// One round, one workgroup per brick.  `cur` holds this round's flags, `next` the next round's: a brick clears its
+// own flag in cur, other bricks only set flags in next, so cur is all zero when the round is over and serves as the
+// round after next's `next` without a fill.  *counter: the flags this round turned from 0 to 1.
+__global__ __launch_bounds__(FR_THREADS) void route_round_kernel(int X, int Y, int Z, int bx, int by, int bz,
+                                                                 const int *__restrict__ dist2, int need, int *cost,
+                                                                 unsigned *cur, unsigned *next, unsigned *counter) {
+    __shared__ int s_cost[FR_HALO * FR_HALO * FR_HALO];
+    __shared__ unsigned char s_free[FR_HALO * FR_HALO * FR_HALO];
+    __shared__ unsigned s_active, s_dirs;
+    const int tid = threadIdx.x;
+    const int brick = blockIdx.x;
+    if (tid == 0) {
+        s_active = cur[brick];
+        s_dirs = 0u;
+        if (s_active) cur[brick] = 0u;
+    }
+    __syncthreads();
+    if (!s_active) return;
+    const int iz = brick % bz, iy = (brick / bz) % by, ix = brick / (bz * by);
+    const int x0 = ix * FR_BRICK, y0 = iy * FR_BRICK, z0 = iz * FR_BRICK;
+    for (int i = tid; i < FR_HALO * FR_HALO * FR_HALO; i += FR_THREADS) {
+        const int x = x0 + i / (FR_HALO * FR_HALO) - 1, y = y0 + (i / FR_HALO) % FR_HALO - 1, z = z0 + i % FR_HALO - 1;
+        const bool in = x >= 0 && x < X && y >= 0 && y < Y && z >= 0 && z < Z;
+        const size_t at = in ? ((size_t)x * Y + y) * Z + z : 0;
+        const bool open = in && dist2[at] >= need;
+        s_free[i] = open ? 1 : 0;
+        s_cost[i] = open ? fr_load(cost + at) : GG_FIELD_FAR;
+    }
+    __syncthreads();
+    // two cells per thread: their place in LDS, the cost they were loaded with, and the moves they may make
+    int at[2], loaded[2], own[2];
+    unsigned allow[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int i = tid + k * FR_THREADS;
+        at[k] = (((i >> 6) + 1) * FR_HALO + ((i >> 3) & 7) + 1) * FR_HALO + (i & 7) + 1;
+        loaded[k] = own[k] = s_cost[at[k]];
+        unsigned open = 0u;
+#pragma unroll
+        for (int m = 0; m < 27; ++m)
+            open |= (unsigned)s_free[at[k] + (fr_dx(m) * FR_HALO + fr_dy(m)) * FR_HALO + fr_dz(m)] << m;
+        allow[k] = 0u;
+#pragma unroll
+        for (int m = 0; m < 27; ++m)
+            if (m != 13 && (open & fr_block_mask(m)) == fr_block_mask(m)) allow[k] |= 1u << m;
+    }
+    // Jacobi sweeps in LDS: all read, then all write.  Every sweep that goes on lowers a cell, costs are integers
+    // >= 0, so the loop ends; it waits for nothing outside this workgroup.
+    for (;;) {
+        int nv[2];
+        bool fell = false;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            nv[k] = own[k];
+#pragma unroll
+            for (int m = 0; m < 27; ++m)
+                if (m != 13 && (allow[k] >> m & 1u))
+                    nv[k] = min(nv[k], s_cost[at[k] + (fr_dx(m) * FR_HALO + fr_dy(m)) * FR_HALO + fr_dz(m)] + fr_weight(m));
+            fell = fell || nv[k] < own[k];
+        }
+        if (!__syncthreads_or(fell)) break;
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+            if (nv[k] < own[k]) s_cost[at[k]] = own[k] = nv[k];
+        __syncthreads();
+    }
+    // write back what fell; a changed cell of the outer layer is read by the bricks on its side(s)
+    unsigned dirs = 0u;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        if (own[k] >= loaded[k]) continue;
+        const int i = tid + k * FR_THREADS;
+        const int lx = i >> 6, ly = (i >> 3) & 7, lz = i & 7;
+        fr_store(cost + ((size_t)(x0 + lx) * Y + (y0 + ly)) * Z + (z0 + lz), own[k]);
+#pragma unroll
+        for (int m = 0; m < 27; ++m) {
+            const bool reads = (fr_dx(m) == 0 || lx == (fr_dx(m) < 0 ? 0 : FR_BRICK - 1)) &&
+                               (fr_dy(m) == 0 || ly == (fr_dy(m) < 0 ? 0 : FR_BRICK - 1)) &&
+                               (fr_dz(m) == 0 || lz == (fr_dz(m) < 0 ? 0 : FR_BRICK - 1));
+            if (m != 13 && reads) dirs |= 1u << m;
+        }
+    }
+    if (dirs) atomicOr(&s_dirs, dirs);
+    __syncthreads();
+    if (tid < 27 && (s_dirs >> tid & 1u)) {
+        const int a = ix + fr_dx(tid), b = iy + fr_dy(tid), c = iz + fr_dz(tid);
+        if (a >= 0 && a < bx && b >= 0 && b < by && c >= 0 && c < bz)
+            if (atomicExch(next + ((size_t)a * by + b) * bz + c, 1u) == 0u) atomicAdd(counter, 1u);
+    }
+}
+
+// One wave per path.  The walk ends by construction: every step lowers the cost by at least 3.
+__global__ __launch_bounds__(FR_THREADS) void route_descend_kernel(int X, int Y, int Z, const int *__restrict__ dist2,
+                                                                   int need, const int *__restrict__ cost, int P,
+                                                                   const int *__restrict__ starts, int max_cells,
+                                                                   int *__restrict__ cells, int *__restrict__ length) {
+    const int lane = threadIdx.x & 63;
+    const int p = blockIdx.x * (FR_THREADS / 64) + (threadIdx.x >> 6);      // P max_cells <= GG_FIELD_MAX_POSES
+    if (p >= P) return;                                                     // the same for the whole wave
+    auto open = [&](int x, int y, int z) {
+        return x >= 0 && x < X && y >= 0 && y < Y && z >= 0 && z < Z && dist2[((size_t)x * Y + y) * Z + z] >= need;
+    };
+    int c[3] = {starts[(size_t)p * 3], starts[(size_t)p * 3 + 1], starts[(size_t)p * 3 + 2]};
+    int *row = cells + (size_t)p * max_cells * 3;
+    int here = open(c[0], c[1], c[2]) ? cost[((size_t)c[0] * Y + c[1]) * Z + c[2]] : GG_FIELD_FAR;
+    int n = 0;
+    if (here < GG_FIELD_FAR) {
+        const int m = lane, dx = fr_dx(m), dy = fr_dy(m), dz = fr_dz(m), w = fr_weight(m);
+        const int bound = here / 3 + 1;
+        if (lane == 0) row[0] = c[0], row[1] = c[1], row[2] = c[2];
+        n = 1;
+        for (int step = 0; step < bound && here > 0; ++step) {
+            bool take = false;
+            if (m < 27 && m != 13) {
+                bool ok = true;
+                for (int a = 0; a <= (dx != 0); ++a)
+                    for (int b = 0; b <= (dy != 0); ++b)
+                        for (int e = 0; e <= (dz != 0); ++e)
+                            ok = ok && open(c[0] + a * dx, c[1] + b * dy, c[2] + e * dz);
+                take = ok && cost[((size_t)(c[0] + dx) * Y + (c[1] + dy)) * Z + (c[2] + dz)] + w == here;
+            }
+            const uint64_t found = __ballot(take);
+            if (found == 0ull) break;                      // `cost` is no fixed point of this dist2 and need
+            const int pick = (int)__builtin_ctzll(found);  // the lowest move number: the tie rule
+            c[0] += fr_dx(pick), c[1] += fr_dy(pick), c[2] += fr_dz(pick);
+            here -= fr_weight(pick);
+            if (lane == 0 && n < max_cells) row[3 * n] = c[0], row[3 * n + 1] = c[1], row[3 * n + 2] = c[2];
+            ++n;
+        }
+        if (here > 0) n = 0;
+    }
+    if (n == 0) c[0] = c[1] = c[2] = -1;
+    for (int r = n + lane; r < max_cells; r += 64) row[3 * r] = c[0], row[3 * r + 1] = c[1], row[3 * r + 2] = c[2];
+    if (lane == 0) length[p] = n;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------------------------
 static bool field_dims_ok(const int32_t *dims) {
@@ -392,6 +605,104 @@ extern "C" int gg_field_paths(const int32_t *dims, const double *grid, const int
                        s, g, dist2, total, poses, num_spheres, spheres, need2, outside, slack);
     hipLaunchKernelGGL(field_first_hit_kernel, dim3((unsigned)((num_paths + FP_THREADS - 1) / FP_THREADS)),
                        dim3(FP_THREADS), 0, s, num_paths, num_waypoints, slack, first_hit);
+    GG_CHECK_LAUNCH();
+    return GG_OK;
+}
+
+static void route_bricks(const int32_t *dims, int *b) {
+    for (int a = 0; a < 3; ++a) b[a] = (dims[a] + FR_BRICK - 1) / FR_BRICK;
+}
+
+// the counters of one batch of rounds, then the two flag arrays: one 32-bit word each
+static size_t route_ws_words(const int32_t *dims) {
+    int b[3];
+    route_bricks(dims, b);
+    return (size_t)FR_BATCH + 2 * ((size_t)b[0] * b[1] * b[2]);
+}
+
+extern "C" size_t gg_field_route_workspace(const int32_t *dims) {
+    if (!field_dims_ok(dims)) return 0;
+    return gg_align_up(route_ws_words(dims) * 4, 256);
+}
+
+extern "C" int gg_field_route(const int32_t *dims, const int32_t *dist2, int32_t need, int num_goals,
+                              const int32_t *goals, int32_t *cost, int64_t *ignored, int max_rounds, int *rounds_out,
+                              void *ws, size_t ws_bytes, gg_stream_t stream) {
+    GG_REQUIRE(field_dims_ok(dims), FIELD_DIMS_MSG);
+    GG_REQUIRE(need >= 0 && need <= GG_FIELD_FAR, "need must be in 0..GG_FIELD_FAR");
+    GG_REQUIRE(num_goals >= 0 && num_goals <= GG_FIELD_MAX_GOALS, "need 0 <= num_goals <= GG_FIELD_MAX_GOALS");
+    GG_REQUIRE(max_rounds >= 1, "max_rounds must be >= 1");
+    GG_REQUIRE(rounds_out, "null pointer: rounds_out (a host int)");
+    GG_REQUIRE(dist2 && cost && ignored, "null pointer: dist2 / cost / ignored");
+    GG_REQUIRE(num_goals == 0 || goals, "null pointer: goals");
+    GG_REQUIRE((((uintptr_t)dist2 | (uintptr_t)goals | (uintptr_t)cost) & 3) == 0 && ((uintptr_t)ignored & 7) == 0,
+               "dist2 / goals / cost / ignored misaligned");
+    GG_REQUIRE_WS(ws, ws_bytes, gg_field_route_workspace(dims));
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t cells = field_cells(dims);
+    const int64_t words = (int64_t)route_ws_words(dims);
+    int b[3];
+    route_bricks(dims, b);
+    const int64_t bricks = (int64_t)b[0] * b[1] * b[2];
+    unsigned *counters = (unsigned *)ws, *flags = counters + FR_BATCH;
+    *rounds_out = 0;
+    const int64_t span = cells > words ? cells : words;
+    hipLaunchKernelGGL(route_init_kernel, dim3((unsigned)((span + FR_THREADS - 1) / FR_THREADS)), dim3(FR_THREADS), 0,
+                       s, (long long)cells, cost, (long long)words, counters,
+                       reinterpret_cast<unsigned long long *>(ignored));
+    if (num_goals == 0) {
+        GG_CHECK_LAUNCH();
+        return GG_OK;
+    }
+    hipLaunchKernelGGL(route_goals_kernel, dim3((unsigned)((num_goals + FR_THREADS - 1) / FR_THREADS)),
+                       dim3(FR_THREADS), 0, s, dims[0], dims[1], dims[2], b[0], b[1], b[2], dist2, need, num_goals,
+                       goals, cost, flags, reinterpret_cast<unsigned long long *>(ignored));
+    GG_CHECK_LAUNCH();
+    // Rounds in batches; after each batch the counters come back.  Once a round has flagged nothing the rounds
+    // behind it find no active brick.  The loop is bounded by max_rounds, and no kernel in it can wait.
+    unsigned flagged[FR_BATCH];
+    for (int done = 0; done < max_rounds;) {
+        const int n = max_rounds - done < FR_BATCH ? max_rounds - done : FR_BATCH;
+        if (done > 0) hipLaunchKernelGGL(route_zero_kernel, dim3(1), dim3(FR_THREADS), 0, s, counters, FR_BATCH);
+        for (int r = 0; r < n; ++r) {
+            unsigned *cur = flags + (size_t)((done + r) & 1) * bricks, *next = flags + (size_t)((done + r + 1) & 1) * bricks;
+            hipLaunchKernelGGL(route_round_kernel, dim3((unsigned)bricks), dim3(FR_THREADS), 0, s, dims[0], dims[1],
+                               dims[2], b[0], b[1], b[2], dist2, need, cost, cur, next, counters + r);
+        }
+        GG_CHECK_LAUNCH();
+        hipError_t e = hipMemcpyAsync(flagged, counters, sizeof(unsigned) * n, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            gg_set_error("%s: reading the round counters back failed: %s", __func__, hipGetErrorString(e));
+            return GG_ERR_LAUNCH;
+        }
+        for (int r = 0; r < n; ++r)
+            if (flagged[r] == 0u) {
+                *rounds_out = done + r + 1;
+                return GG_OK;
+            }
+        done += n;
+    }
+    *rounds_out = max_rounds;
+    gg_set_error("%s: no convergence within max_rounds = %d rounds; cost holds upper bounds", __func__, max_rounds);
+    return GG_ERR_NOT_CONVERGED;
+}
+
+extern "C" int gg_field_descend(const int32_t *dims, const int32_t *dist2, int32_t need, const int32_t *cost,
+                                int num_paths, const int32_t *starts, int max_cells, int32_t *cells, int32_t *length,
+                                gg_stream_t stream) {
+    GG_REQUIRE(field_dims_ok(dims), FIELD_DIMS_MSG);
+    GG_REQUIRE(need >= 0 && need <= GG_FIELD_FAR, "need must be in 0..GG_FIELD_FAR");
+    GG_REQUIRE(num_paths >= 0 && max_cells >= 1, "need num_paths >= 0 and max_cells >= 1");
+    GG_REQUIRE((int64_t)num_paths * max_cells <= GG_FIELD_MAX_POSES, "num_paths max_cells > GG_FIELD_MAX_POSES");
+    if (num_paths == 0) return GG_OK;
+    GG_REQUIRE(dist2 && cost && starts && cells && length, "null pointer: dist2 / cost / starts / cells / length");
+    GG_REQUIRE((((uintptr_t)dist2 | (uintptr_t)cost | (uintptr_t)starts | (uintptr_t)cells | (uintptr_t)length) & 3) == 0,
+               "dist2 / cost / starts / cells / length misaligned");
+    const int per = FR_THREADS / 64;
+    hipLaunchKernelGGL(route_descend_kernel, dim3((unsigned)((num_paths + per - 1) / per)), dim3(FR_THREADS), 0,
+                       (hipStream_t)stream, dims[0], dims[1], dims[2], dist2, need, cost, num_paths, starts, max_cells,
+                       cells, length);
     GG_CHECK_LAUNCH();
     return GG_OK;
 }

@@ -9,7 +9,7 @@ PARITY.md "Distance field"; the design in DESIGN.md §3.25.
     gripper_spheres    a grasp gripper model (grasp.default_gripper, ...) at given sizes, covered by spheres
     grasp_poses        (M, 17) grasp rows as (M, 1, 12) poses
     approach_paths     the straight approach of every row from a standoff, as (M, steps, 12) poses
-    interpolate        slerp plus lerp between two poses, on the host
+    interpolate        slerp plus lerp between two poses, on the host (slerp_rotations: its slerp at given fractions)
     path_clear         slack per waypoint, first hit and clear per path
     python -m gaussiangrasper_amd.field --ckpt IN --bbox x0 y0 z0 x1 y1 z1 --voxel H --out field.npz [...]
 
@@ -180,21 +180,31 @@ def interpolate(pose_a: ArrayLike, pose_b: ArrayLike, steps: int) -> np.ndarray:
         raise ValueError("a pose is 12 finite numbers: R row-major, then t")
     if steps < 2:
         raise ValueError(f"steps must be >= 2, got {steps}")
-    qa, qb = _quat(a[:9].reshape(3, 3)), _quat(b[:9].reshape(3, 3))
+    frac = np.arange(steps) / (steps - 1.0)
+    out = np.empty((steps, 12))
+    out[:, :9] = slerp_rotations(a[:9], b[:9], frac)
+    for i, s in enumerate(frac):
+        out[i, 9:] = (1.0 - s) * a[9:] + s * b[9:]
+    out[0], out[-1] = a, b
+    return out.astype(np.float32)
+
+
+def slerp_rotations(rot_a: np.ndarray, rot_b: np.ndarray, fractions: Sequence[float]) -> np.ndarray:
+    """(n, 9) float64 rotations, row-major, at `fractions` (each in 0..1) of the shorter arc from rot_a to rot_b (9
+    numbers each): interpolate's slerp, for callers that bring their own fractions (transit.transit_poses)."""
+    qa, qb = _quat(np.asarray(rot_a, np.float64).reshape(3, 3)), _quat(np.asarray(rot_b, np.float64).reshape(3, 3))
     dot = float(qa @ qb)
     if dot < 0.0:
         qb, dot = -qb, -dot
     theta = math.acos(min(1.0, dot))
-    out = np.empty((steps, 12))
-    for i, s in enumerate(np.arange(steps) / (steps - 1.0)):
+    out = np.empty((len(fractions), 9))
+    for i, s in enumerate(fractions):
         if theta < 1e-9:
             q = (1.0 - s) * qa + s * qb
         else:
             q = (math.sin((1.0 - s) * theta) * qa + math.sin(s * theta) * qb) / math.sin(theta)
-        out[i, :9] = _rotmat(q / np.linalg.norm(q)).reshape(-1)
-        out[i, 9:] = (1.0 - s) * a[9:] + s * b[9:]
-    out[0], out[-1] = a, b
-    return out.astype(np.float32)
+        out[i] = _rotmat(q / np.linalg.norm(q)).reshape(-1)
+    return out
 
 
 # ------------------------------------------------------------------------------------------------

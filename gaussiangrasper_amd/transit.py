@@ -1,0 +1,362 @@
+"""Transit planning through the distance field: the exact cost-to-go over the free cells (`gg_field_route`) and the
+descent along it (`gg_field_descend`), csrc/field.hip, and the poses of a carried gripper along the path that comes
+out.  The contract is in include/gg_raster.h and PARITY.md "Transit planning"; the design, the convergence argument
+and the derivation of the planning pad in DESIGN.md §3.29.
+
+    cells_of           the header's cell rule on the host in fp64
+    route / descend_cells   the two calls as they are
+    cost_to_go         the cost field towards goal points, for a ball of `radius` kept `margin` away
+    descend            the paths from start points down a cost field, called again when a path was cut
+    bounding_radius    the ball about the gripper's origin that holds the gripper at every orientation
+    carried_spheres    spheres that cover the points of the carried object, gripper frame
+    polyline_points / transit_poses    a cell path as `steps` poses, by arc length, the orientation by slerp
+    plan_transit       cost field, descent, poses, and field.path_clear with the real spheres as the verdict
+    python -m gaussiangrasper_amd.transit --field field.npz --from POSES.npy --to POSE.npy --gripper default [...]
+
+Out of scope: smoothing or shortcutting of the chamfer polyline, orientation-aware planning (the bounding ball is the
+price of a search in three dimensions), and the kinematics of the arm."""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import math
+import sys
+from dataclasses import dataclass
+from typing import Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+from torch import Tensor
+
+from . import _lib
+from ._call import (ArrayLike, positive, ptr as _ptr, require_hip as _require_hip, sized_workspace,
+                    stream as _stream, to_device)
+from .field import (FAR, MAX_POSES, MAX_SPHERES, DistanceField, PathClearance, gripper_spheres, interpolate, need2,
+                    path_clear, slerp_rotations)
+
+MAX_GOALS = 1 << 24            # GG_FIELD_MAX_GOALS
+MAX_ROUNDS = 4096
+FIRST_CELLS = 256              # descend's first guess of the longest path, in cells
+CELL_CLAMP = 2.0 ** 30         # field_cell.h FIELD_CELL_CLAMP
+# DESIGN.md §3.29 "The planning pad": sqrt(3) h on the radius, and a hair for what float32 poses lose
+PAD_CELLS = math.sqrt(3.0)
+PAD_HAIR = 1e-6
+# UNVERIFIED default (PARITY.md "Transit planning"): this project's choice, not checked on a real checkpoint
+STEPS = 64
+
+
+@dataclass
+class CostToGo:
+    cost: Tensor           # int32 [X][Y][Z]: chamfer 3-4-5 cost to the nearest goal, FAR where there is none
+    need: int              # a cell is free iff dist2 >= need
+    goals: np.ndarray      # (G, 3) int32 goal cells
+    ignored: Tensor        # 0-dim int64: goals outside the volume or not free
+    rounds: int            # rounds of relaxation the call took
+    field: DistanceField   # whose dist2 the cost belongs to (stale after its next update())
+
+
+@dataclass
+class TransitPlan:
+    poses: Tensor              # (P, steps, 12) float32 on the field's device
+    clearance: PathClearance   # field.path_clear of `poses` with the real spheres: the verdict
+    cost: np.ndarray           # (P,) float64 path length in scene units, chamfer 3-4-5 (cost h / 3); inf: no path
+    best: int                  # the cheapest path that is planned and clear, -1 when there is none
+    planned: np.ndarray        # (P,) bool: a path was found (the others hold the straight field.interpolate path)
+    cells: Tensor              # (P, L, 3) int32 cell paths, `length` of each
+    length: Tensor             # (P,) int32
+    cost_to_go: CostToGo
+
+
+# ------------------------------------------------------------------------------------------------
+# host side
+# ------------------------------------------------------------------------------------------------
+def cells_of(field, points: ArrayLike) -> np.ndarray:
+    """(N, 3) int32 cells of (N, 3) points by the header's rule in fp64: per axis the c with c h <= d < (c + 1) h,
+    d = (double)p - lo (a division proposes and is clamped to +-2^30, the comparisons decide: field_cell.h step by
+    step); a cell outside the volume is returned as it is.  A point that is not finite gives the row -1, -1, -1."""
+    p = np.asarray(points.detach().cpu() if isinstance(points, Tensor) else points, np.float64).reshape(-1, 3)
+    grid = np.asarray(field.grid, np.float64)
+    h = float(grid[3])
+    fin = np.isfinite(p).all(1)
+    d = np.where(fin[:, None], p, 0.0) - grid[:3]
+    c = np.clip(np.floor(d / h), -CELL_CLAMP, CELL_CLAMP)
+    c = np.where(c * h > d, c - 1.0, np.where((c + 1.0) * h <= d, c + 1.0, c))
+    return np.where(fin[:, None], c, -1.0).astype(np.int32)
+
+
+def cell_centres(field, cells: ArrayLike) -> np.ndarray:
+    """lo + (c + 0.5) h, fp64"""
+    grid = np.asarray(field.grid, np.float64)
+    return grid[:3] + (np.asarray(cells, np.float64) + 0.5) * grid[3]
+
+
+def bounding_radius(spheres: ArrayLike, radius: Union[float, ArrayLike]) -> float:
+    """max_s |c_s| + r_s: the ball of that radius about the gripper's origin contains every sphere, and with them
+    whatever they cover, at every orientation of the gripper."""
+    c = np.asarray(spheres, np.float64).reshape(-1, 3)
+    r = np.broadcast_to(np.asarray(radius, np.float64), (len(c),))
+    if len(c) == 0 or not (np.isfinite(c).all() and np.isfinite(r).all() and (r >= 0).all()):
+        raise ValueError("bounding_radius needs at least one sphere, finite centres and finite radii >= 0")
+    return float((np.linalg.norm(c, axis=1) + r).max())
+
+
+def carried_spheres(points_in_gripper_frame: ArrayLike, radius: float) -> np.ndarray:
+    """(S, 3) float32 centres, gripper frame, whose balls of `radius` cover the points of the carried object: the
+    centres of the occupied voxels of edge 2 radius / sqrt(3) (half diagonal = radius; the edge is taken 1e-4
+    shorter, as field.gripper_spheres does, which is far more than the centres lose as float32).  Points that are
+    not finite are left out.  ValueError beyond GG_FIELD_MAX_SPHERES."""
+    p = np.asarray(points_in_gripper_frame.detach().cpu() if isinstance(points_in_gripper_frame, Tensor)
+                   else points_in_gripper_frame, np.float64).reshape(-1, 3)
+    p = p[np.isfinite(p).all(1)]
+    edge = 2.0 * positive("radius", radius) / math.sqrt(3.0) * (1.0 - 1e-4)
+    if len(p) == 0:
+        return np.zeros((0, 3), np.float32)
+    vox = np.unique(np.floor(p / edge).astype(np.int64), axis=0)
+    if len(vox) > MAX_SPHERES:
+        raise ValueError(f"{len(vox)} spheres of radius {radius} are more than {MAX_SPHERES}: use a larger radius")
+    return ((vox + 0.5) * edge).astype(np.float32)
+
+
+def planning_radius(spheres: ArrayLike, radius: Union[float, ArrayLike], h: float) -> float:
+    """(bounding_radius + sqrt(3) h) (1 + 1e-6): a cell whose dist2 meets need2 of THIS radius holds only origins at
+    which every sphere, at any orientation, meets its own need2 (DESIGN.md §3.29 "The planning pad")."""
+    return (bounding_radius(spheres, radius) + PAD_CELLS * positive("h", h)) * (1.0 + PAD_HAIR)
+
+
+def polyline_points(points: np.ndarray, steps: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(pts (steps, 3), seg (steps,), frac (steps,)): `steps` points at equal arc length along the polyline through
+    the (K, 3) `points`, the first and last exactly its ends; seg[i] is the segment (points[seg], points[seg + 1])
+    that holds pts[i], frac[i] its share of the whole length (i / (steps - 1) when the length is 0)."""
+    p = np.asarray(points, np.float64).reshape(-1, 3)
+    steps = int(steps)
+    if steps < 2 or len(p) < 2:
+        raise ValueError(f"need steps >= 2 and at least two points, got {steps} and {len(p)}")
+    seglen = np.linalg.norm(np.diff(p, axis=0), axis=1)
+    total = float(seglen.sum())
+    even = np.arange(steps) / (steps - 1.0)
+    if total <= 0.0:
+        return np.repeat(p[:1], steps, 0), np.zeros(steps, np.int64), even
+    s = even * total
+    keep = np.nonzero(seglen > 0.0)[0]                  # a point at a joint belongs to the segment that starts there,
+    cum = np.concatenate([[0.0], np.cumsum(seglen[keep])])      # never to a segment of no length
+    j = np.clip(np.searchsorted(cum, s, side="right") - 1, 0, len(keep) - 1)
+    seg = keep[j]
+    t = np.clip((s - cum[j]) / seglen[seg], 0.0, 1.0)
+    pts = (1.0 - t)[:, None] * p[seg] + t[:, None] * p[seg + 1]
+    pts[0], pts[-1] = p[0], p[-1]
+    return pts, seg.astype(np.int64), s / total
+
+
+def transit_poses(pose_from: ArrayLike, pose_to: ArrayLike, cells: ArrayLike, length: int, field,
+                  steps: int = STEPS) -> np.ndarray:
+    """(steps, 12) float32 poses along a cell path: the polyline from pose_from's position through the centres of the
+    first `length` rows of `cells` to pose_to's position, resampled at equal arc length; the rotation by
+    field.interpolate's slerp at the share of the arc passed.  The first and last pose are exactly the inputs."""
+    a, b = (np.asarray(p, np.float64).reshape(-1) for p in (pose_from, pose_to))
+    if a.shape != (12,) or b.shape != (12,) or not (np.isfinite(a).all() and np.isfinite(b).all()):
+        raise ValueError("a pose is 12 finite numbers: R row-major, then t")
+    c = np.asarray(cells.detach().cpu() if isinstance(cells, Tensor) else cells, np.int64).reshape(-1, 3)
+    length = int(length)
+    if not 1 <= length <= len(c):
+        raise ValueError(f"length must be in 1..{len(c)} (the rows of cells), got {length}")
+    line = np.concatenate([a[None, 9:], cell_centres(field, c[:length]), b[None, 9:]])
+    pts, _, frac = polyline_points(line, steps)
+    out = np.empty((len(pts), 12))
+    out[:, :9] = slerp_rotations(a[:9], b[:9], frac)
+    out[:, 9:] = pts
+    out[0], out[-1] = a, b
+    return out.astype(np.float32)
+
+
+# ------------------------------------------------------------------------------------------------
+# device side: the two calls
+# ------------------------------------------------------------------------------------------------
+def _dims(dims):
+    shape = tuple(int(v) for v in np.asarray(dims).reshape(-1))
+    if len(shape) != 3:
+        raise ValueError("dims is (3,) cells")
+    return (C.c_int32 * 3)(*shape), shape
+
+
+def _int32_volume(t: Tensor, name: str, shape) -> None:
+    if t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous int32 {shape} tensor, got {t.dtype} {tuple(t.shape)}")
+
+
+def _cells_arg(cells: ArrayLike, name: str, dev) -> Tensor:
+    t = to_device(cells, torch.int32, dev)
+    if t.ndim != 2 or t.shape[1] != 3:
+        if t.numel() == 0:
+            return t.reshape(0, 3)
+        raise ValueError(f"{name} must be (N, 3) cells, got {tuple(t.shape)}")
+    return t
+
+
+def route(dist2: Tensor, dims, need: int, goals: ArrayLike, max_rounds: int = MAX_ROUNDS,
+          out: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, int]:
+    """(cost int32 [X][Y][Z], ignored 0-dim int64, rounds) of one gg_field_route call.  dist2 int32 [X][Y][Z] on the
+    HIP device (no CPU path); goals (G, 3) int32 cells.  The call waits for the device (once per batch of rounds).
+    GGError when max_rounds run out; `out`, when given, then holds upper bounds."""
+    dev = _require_hip(dist2)
+    d, shape = _dims(dims)
+    _int32_volume(dist2, "dist2", shape)
+    if not 0 <= int(need) <= FAR:
+        raise ValueError(f"need must be in 0..{FAR}, got {need}")
+    if int(max_rounds) < 1:
+        raise ValueError(f"max_rounds must be >= 1, got {max_rounds}")
+    g = _cells_arg(goals, "goals", dev)
+    if g.shape[0] > MAX_GOALS:
+        raise ValueError(f"{g.shape[0]} goals are more than {MAX_GOALS}")
+    if out is None:
+        out = torch.empty(shape, dtype=torch.int32, device=dev)
+    else:
+        _int32_volume(out, "out", shape)
+        if out.device != dev:
+            raise ValueError(f"out must be on {dev}")
+    lib = _lib.load()
+    ws = sized_workspace(lib.gg_field_route_workspace(d), f"{shape} cells are beyond gg_field_route's limits", dev)
+    ignored = torch.zeros(1, dtype=torch.int64, device=dev)
+    rounds = C.c_int(0)
+    _lib.check(lib.gg_field_route(d, _ptr(dist2), int(need), g.shape[0], _ptr(g) if g.shape[0] else None, _ptr(out),
+                                  _ptr(ignored), int(max_rounds), C.byref(rounds), _ptr(ws), ws.numel(), _stream(dev)),
+               "gg_field_route")
+    return out, ignored[0], int(rounds.value)
+
+
+def descend_cells(dist2: Tensor, dims, need: int, cost: Tensor, starts: ArrayLike,
+                  max_cells: int) -> Tuple[Tensor, Tensor]:
+    """(cells (P, max_cells, 3) int32, length (P,) int32) of one gg_field_descend call; starts (P, 3) int32 cells."""
+    dev = _require_hip(dist2, cost)
+    d, shape = _dims(dims)
+    _int32_volume(dist2, "dist2", shape)
+    _int32_volume(cost, "cost", shape)
+    if not 0 <= int(need) <= FAR:
+        raise ValueError(f"need must be in 0..{FAR}, got {need}")
+    s = _cells_arg(starts, "starts", dev)
+    p, max_cells = s.shape[0], int(max_cells)
+    if max_cells < 1 or p * max_cells > MAX_POSES:
+        raise ValueError(f"need max_cells >= 1 and P max_cells <= {MAX_POSES}, got {p} x {max_cells}")
+    cells = torch.empty(p, max_cells, 3, dtype=torch.int32, device=dev)
+    length = torch.empty(p, dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().gg_field_descend(d, _ptr(dist2), int(need), _ptr(cost), p, _ptr(s) if p else None,
+                                            max_cells, _ptr(cells), _ptr(length), _stream(dev)), "gg_field_descend")
+    return cells, length
+
+
+def cost_to_go(field: DistanceField, goal_points: ArrayLike, radius: float, margin: float = 0.0,
+               max_rounds: int = MAX_ROUNDS) -> CostToGo:
+    """The cost field of `field` (update() first) towards the cells of (G, 3) goal points, for a ball of `radius`
+    kept `margin` away from every occupied cell: a cell is free iff dist2 >= field.need2(radius, margin, h)."""
+    need = int(need2(float(radius), margin, field.h))
+    goals = cells_of(field, goal_points)
+    cost, ignored, rounds = route(field.dist2, field.dims, need, goals, max_rounds)
+    return CostToGo(cost, need, goals, ignored, rounds, field)
+
+
+def descend(ctg: CostToGo, start_points: ArrayLike, max_cells: Optional[int] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    """(cells (P, L, 3) int32, length (P,) int32, cost_at_start (P,) int32) from (P, 3) start points down `ctg`.
+    L is max_cells (FIRST_CELLS when None), or the longest path when that is longer: the call is then made again
+    with that much room, so no path comes back cut.  cost_at_start is FAR for a start outside the volume."""
+    f = ctg.field
+    starts = cells_of(f, start_points)
+    dev = ctg.cost.device
+    room = FIRST_CELLS if max_cells is None else int(max_cells)
+    cells, length = descend_cells(f.dist2, f.dims, ctg.need, ctg.cost, starts, room)
+    longest = int(length.max()) if len(starts) else 0
+    if longest > room:
+        cells, length = descend_cells(f.dist2, f.dims, ctg.need, ctg.cost, starts, longest)
+    dims = np.asarray(f.dims, np.int64)
+    inside = ((starts >= 0) & (starts < dims)).all(1)
+    flat = (np.clip(starts, 0, dims - 1).astype(np.int64) * [dims[1] * dims[2], dims[2], 1]).sum(1)
+    at = ctg.cost.reshape(-1)[torch.from_numpy(flat).to(dev)]
+    at = torch.where(torch.from_numpy(inside).to(dev), at, torch.full_like(at, FAR))
+    return cells, length, at
+
+
+def plan_transit(field: DistanceField, poses_from: ArrayLike, pose_to: ArrayLike, spheres: ArrayLike,
+                 radius: Union[float, ArrayLike], margin: float = 0.0, steps: int = STEPS,
+                 max_rounds: int = MAX_ROUNDS) -> TransitPlan:
+    """Paths for the gripper (and what it carries: `spheres` (S, 3) of `radius`, gripper frame) from each of the
+    (P, 12) poses_from to pose_to through field (update() first): ONE cost field from pose_to's cell for the ball
+    of planning_radius, one descent for all P starts, transit_poses for each, and field.path_clear of those poses with
+    the real spheres as the verdict.  A start from which there is no path gets the straight field.interpolate poses,
+    planned False and cost inf."""
+    a = np.asarray(poses_from.detach().cpu() if isinstance(poses_from, Tensor) else poses_from, np.float64)
+    a = a.reshape(-1, 12)
+    b = np.asarray(pose_to.detach().cpu() if isinstance(pose_to, Tensor) else pose_to, np.float64).reshape(-1)
+    if b.shape != (12,) or not (np.isfinite(a).all() and np.isfinite(b).all()):
+        raise ValueError("poses_from is (P, 12) and pose_to (12,) finite numbers: R row-major, then t")
+    sp = np.asarray(spheres.detach().cpu() if isinstance(spheres, Tensor) else spheres, np.float32).reshape(-1, 3)
+    ctg = cost_to_go(field, b[None, 9:], planning_radius(sp, radius, field.h), margin, max_rounds)
+    cells, length, at = descend(ctg, a[:, 9:])
+    n, c, at = length.cpu().numpy(), cells.cpu().numpy(), at.cpu().numpy()
+    planned = n > 0
+    poses = np.stack([transit_poses(a[i], b, c[i], n[i], field, steps) if planned[i] else interpolate(a[i], b, steps)
+                      for i in range(len(a))]) if len(a) else np.zeros((0, int(steps), 12), np.float32)
+    clearance = path_clear(field, poses, sp, radius, margin)
+    cost = np.where(planned, at.astype(np.float64) * field.h / 3.0, np.inf)
+    ok = planned & clearance.clear.cpu().numpy()
+    best = int(np.argmin(np.where(ok, cost, np.inf))) if ok.any() else -1
+    return TransitPlan(to_device(poses, torch.float32, field.dist2.device), clearance, cost, best, planned, cells,
+                       length, ctg)
+
+
+# ------------------------------------------------------------------------------------------------
+# command line
+# ------------------------------------------------------------------------------------------------
+def main(argv: Optional[Sequence[str]] = None) -> int:
+    from .grasp import load_gripper_option
+    ap = argparse.ArgumentParser(prog="python -m gaussiangrasper_amd.transit",
+                                 description="Collision-free transit of the gripper through a saved distance field: "
+                                             "from each start pose to one goal pose.")
+    ap.add_argument("--field", required=True, help=".npz of python -m gaussiangrasper_amd.field (--out)")
+    ap.add_argument("--from", dest="start", required=True, help=".npy (P, 12) or (12,) start poses: R row-major, then t")
+    ap.add_argument("--to", required=True, help=".npy (12,) goal pose")
+    ap.add_argument("--gripper", required=True, metavar="{default,FILE.json}", help="the gripper model")
+    ap.add_argument("--width", type=float, default=0.08, help="the gripper's opening, scene units")
+    ap.add_argument("--depth", type=float, default=0.02, help="the fingers' depth")
+    ap.add_argument("--height", type=float, default=0.02, help="the fingers' height")
+    ap.add_argument("--radius", type=float, default=0.005, help="radius of the covering spheres")
+    ap.add_argument("--margin", type=float, default=0.0, help="clearance kept beyond the spheres")
+    ap.add_argument("--steps", type=int, default=STEPS, help="waypoints per path")
+    ap.add_argument("--carried", default=None, help=".npy (N, 3) points of the carried object, gripper frame")
+    ap.add_argument("--out", required=True, help="output .npy (P, steps, 12) poses")
+    ap.add_argument("--report", required=True, help="output .npz slack, first_hit, clear, cost, best, planned, spheres")
+    a = ap.parse_args(argv)
+    for n in ("radius", "width"):
+        if not (math.isfinite(getattr(a, n)) and getattr(a, n) > 0.0):
+            ap.error(f"--{n} must be finite and > 0, got {getattr(a, n)}")
+    for n in ("margin", "depth", "height"):
+        if not (math.isfinite(getattr(a, n)) and getattr(a, n) >= 0.0):
+            ap.error(f"--{n} must be finite and >= 0, got {getattr(a, n)}")
+    if a.steps < 2:
+        ap.error(f"--steps must be >= 2, got {a.steps}")
+    try:
+        spheres = gripper_spheres(load_gripper_option(a.gripper), a.width, a.depth, a.height, a.radius)
+        if a.carried:
+            spheres = np.concatenate([spheres, carried_spheres(np.load(a.carried), a.radius)])
+            if len(spheres) > MAX_SPHERES:
+                raise ValueError(f"{len(spheres)} spheres with the carried object are more than {MAX_SPHERES}: "
+                                 "use a larger --radius")
+        start = np.asarray(np.load(a.start), np.float64)
+        goal = np.asarray(np.load(a.to), np.float64).reshape(-1)
+        if start.ndim not in (1, 2) or start.shape[-1] != 12 or goal.shape != (12,):
+            raise ValueError(f"expected (P, 12) start poses and a (12,) goal pose, got {start.shape} and {goal.shape}")
+        field = DistanceField.load(a.field)
+        plan = plan_transit(field, start.reshape(-1, 12), goal, spheres, a.radius, a.margin, a.steps)
+        np.save(a.out, plan.poses.cpu().numpy())
+        clear = plan.clearance.clear.cpu().numpy()
+        np.savez(a.report, slack=plan.clearance.slack.cpu().numpy(), first_hit=plan.clearance.first_hit.cpu().numpy(),
+                 clear=clear, cost=plan.cost, best=np.int64(plan.best), planned=plan.planned, spheres=spheres,
+                 length=plan.length.cpu().numpy(), rounds=np.int64(plan.cost_to_go.rounds))
+    except (KeyError, ValueError, OSError, _lib.GGError) as exc:
+        raise SystemExit(f"error: {exc}") from exc
+    print(f"{int(plan.planned.sum())} of {len(plan.planned)} starts have a path, {int((plan.planned & clear).sum())} "
+          f"clear; best {plan.best}"
+          + (f" at {plan.cost[plan.best]:.4f} scene units" if plan.best >= 0 else "")
+          + f"; {plan.cost_to_go.rounds} rounds; wrote {a.out} and {a.report}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

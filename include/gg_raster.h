@@ -37,6 +37,7 @@ extern "C" {
 #define GG_ERR_LAUNCH (-2)
 #define GG_ERR_WORKSPACE (-3)
 #define GG_ERR_UNSUPPORTED (-4)
+#define GG_ERR_NOT_CONVERGED (-5) /* gg_field_route: max_rounds ran out; the output holds valid upper bounds */
 
 typedef void *gg_stream_t; /* hipStream_t */
 
@@ -1198,7 +1199,43 @@ int gg_tsdf_mesh_emit(const int32_t *dims, const float *grid, const float *tsdf,
  * not finite is outside), d = dist2[cell].  slack int32 [P][W] = min_s (d - need2[s]); GG_FIELD_FAR when S == 0;
  * INT32_MIN for a pose that is not finite.  first_hit int32 [P] = the smallest w with slack < 0, or W.  No atomics
  * and no floating-point decision beyond the cell rule.  P W <= GG_FIELD_MAX_POSES, S <= GG_FIELD_MAX_SPHERES; with
- * P == 0 or W == 0 nothing is written.  Every array 4-byte aligned. */
+ * P == 0 or W == 0 nothing is written.  Every array 4-byte aligned.
+ *
+ * Transit planning (PARITY "Transit planning"): shortest paths through the free cells, integers only.
+ * A cell is FREE iff it is inside the volume and dist2[cell] >= need, need in 0..GG_FIELD_FAR.  A MOVE is a
+ * d in {-1, 0, 1}^3 other than 0, numbered m = (dx + 1) 9 + (dy + 1) 3 + (dz + 1); its weight is 3, 4 or 5 for one,
+ * two or three components that are not 0 (the 3-4-5 chamfer).  The move d from cell c is ALLOWED iff every cell c + e
+ * with e_a in {0, d_a} is free (2, 4 or 8 cells): every point of the segment between the two centres then lies in a
+ * free cell under the half-open cell rule, and no path squeezes between two blocked cells that touch by an edge or a
+ * corner.
+ *
+ * gg_field_route: the cost-to-go.  goals int32 [G][3] cells, G in 0..GG_FIELD_MAX_GOALS; a goal outside the volume or
+ * not free takes no part and is counted in ignored (device, one int64, WRITTEN); duplicates take part.  cost int32
+ * [X][Y][Z] (written whole) = the smallest sum of weights over sequences of allowed moves from the cell to a goal
+ * that takes part: 0 on such a goal, exactly GG_FIELD_FAR on cells that are not free, on cells no sequence leads
+ * from, and everywhere when no goal takes part.  The largest finite cost is below 5 2^27 < 2^30: nothing saturates.
+ * The result does not depend on the schedule.  The call runs rounds of relaxation (one launch each, no kernel waits
+ * for another workgroup) until a round changes nothing that another brick reads; UNLIKE THE OTHER ENTRIES IT
+ * SYNCHRONISES `stream` once per batch of rounds to read that back, so it cannot be captured into a graph.
+ * max_rounds >= 1 bounds the loop; rounds_out (a HOST int, written) receives the rounds it took, the last of which
+ * changed nothing (0 when G == 0), a number that may differ by a few from run to run.  When max_rounds run out the
+ * call returns GG_ERR_NOT_CONVERGED and says so in gg_last_error(); cost then holds VALID UPPER BOUNDS: every value
+ * below FAR is the weight of a real sequence of allowed moves to a goal, but not yet the smallest.  ws:
+ * gg_field_route_workspace(dims) bytes (0 for dims out of range), 256-byte aligned, of any content.  dist2, goals
+ * and cost 4-byte aligned, ignored 8-byte.
+ *
+ * gg_field_descend: paths down a cost-to-go.  dist2, need: as given to gg_field_route; cost: its converged result.
+ * starts int32 [P][3]; max_cells >= 1, P max_cells <= GG_FIELD_MAX_POSES; cells int32 [P][max_cells][3]; length
+ * int32 [P].  From a start that is free and costs less than FAR: while the cost here is not 0, take the allowed move
+ * with cost[next] + weight == cost[here] that has the lowest number m.  length[p] = the cells of the whole path,
+ * start and goal included (1: the start is a goal); 0 when the start is outside, not free or costs FAR (and when
+ * `cost` is not route's fixed point for this dist2 and need, so that no move fits somewhere on the way).  The first
+ * min(length, max_cells) rows of cells[p] are the path's cells in order: with length > max_cells the path is cut
+ * and length still counts all of it (call again with more room); with 0 < length <= max_cells the rows from length
+ * on repeat the last cell, so that a consumer of a fixed number of waypoints can take the array as it is; with
+ * length 0 every row is -1, -1, -1.  A walk takes at most cost[start] / 3 + 1 steps.  P == 0 writes nothing.  Every
+ * array 4-byte aligned.
+ * Null, misaligned or out-of-range arguments: GG_ERR_INVALID_ARG naming the argument, before any launch. */
 #define GG_FIELD_MAX_DIM 1024
 #define GG_FIELD_MAX_CELLS (1 << 27)
 #define GG_FIELD_FAR (1 << 30)
@@ -1215,6 +1252,13 @@ int gg_field_distance(const int32_t *dims, const int64_t *mass, int64_t threshol
 int gg_field_paths(const int32_t *dims, const double *grid, const int32_t *dist2, int num_paths, int num_waypoints,
                    const float *poses, int num_spheres, const float *spheres, const int32_t *need2, int32_t outside,
                    int32_t *slack, int32_t *first_hit, gg_stream_t stream);
+#define GG_FIELD_MAX_GOALS (1 << 24)
+size_t gg_field_route_workspace(const int32_t *dims);
+int gg_field_route(const int32_t *dims, const int32_t *dist2, int32_t need, int num_goals, const int32_t *goals,
+                   int32_t *cost, int64_t *ignored, int max_rounds, int *rounds_out, void *ws, size_t ws_bytes,
+                   gg_stream_t stream);
+int gg_field_descend(const int32_t *dims, const int32_t *dist2, int32_t need, const int32_t *cost, int num_paths,
+                     const int32_t *starts, int max_cells, int32_t *cells, int32_t *length, gg_stream_t stream);
 
 /* ---- placement: height maps and the resting search (PARITY "Placement") ----------------------------
  * A plane grid: dims (host, 2 ints) U, V cells, 1 <= each <= GG_PLACE_MAX_DIM; grid (host, 4 doubles) lo_u, lo_v, ONE
