@@ -155,6 +155,8 @@ SIGNATURES = {
     "gg_field_route_workspace": (_SZ, [_P]),
     "gg_field_route": (_I, [_P, _P, C.c_int32, _I, _P, _P, _P, _I, C.POINTER(C.c_int), _P, _SZ, _P]),
     "gg_field_descend": (_I, [_P, _P, C.c_int32, _P, _I, _P, _I, _P, _P, _P]),
+    "gg_field_sight": (_I, [_P, _P, C.c_int32, _I, _P, _P, _P, _P, _P]),
+    "gg_field_shortcut": (_I, [_P, _P, C.c_int32, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
     "gg_height_map": (_I, [_I, _P, _P, C.c_double, _I, _P, _P, _P, _P, _P, _P]),
     "gg_place_search": (_I, [_P, _P, _I, _P, _P, C.c_int32, _P, _P, _P, _P]),
     "gg_prof_enable": (_I, [_I]),

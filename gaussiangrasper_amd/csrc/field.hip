@@ -19,6 +19,11 @@
 //                     every dependency is a launch boundary, and the host reads one array of counters per FR_BATCH
 //                     rounds to see that a round flagged nothing.
 // gg_field_descend    a wave per path: lane m < 27 tests move m, a ballot's lowest set lane is the tie rule.
+// gg_field_sight      a lane per segment: the integer boundary walk between two cell centres over its whole cover
+//                     (DESIGN.md §3.30); a tie of two or three crossings opens every cell that touches the point.
+// gg_field_shortcut   a workgroup per path: its 256 lanes walk 256 candidate segments from the anchor, each leaving
+//                     at its first cell that is not free; the highest set lane of each wave's ballot, and the largest
+//                     of the four in LDS, is the farthest clear candidate.
 #include <math.h>
 
 #include "field_cell.h"
@@ -31,7 +36,8 @@
 #define FP_THREADS 256
 #define FR_BRICK 8                 // cells per brick edge
 #define FR_HALO 10                 // FR_BRICK + 2: the brick with its one-cell halo
-#define FR_THREADS 256             // two cells of a brick per thread; four paths (waves) per workgroup of the descent
+#define FR_THREADS 256             // two cells of a brick per thread; four paths (waves) per workgroup of the descent;
+                                   // one path per workgroup of the shortcut
 #define FR_BATCH 16                // rounds enqueued between two read-backs of the counters
 
 struct FieldGrid {
@@ -485,6 +491,124 @@ __global__ __launch_bounds__(FR_THREADS) void route_descend_kernel(int X, int Y,
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// sight: the cover of a segment between two cell centres, and greedy string pulling on top of it
+// ---------------------------------------------------------------------------------------------------------------
+struct FrSight {
+    int cover, blocked;
+};
+
+// The boundary walk from cell a to cell b, both inside the volume.  With n_a = |b_a - a_a| the segment crosses the
+// k-th boundary of axis a at t_a = (2 k + 1) / (2 n_a); t_a < t_b iff (2 k_a + 1) n_b < (2 k_b + 1) n_a, products
+// below 2^22.  An axis with n_a == 0 compares as t = infinity; one whose crossings are used up has t > 1, past every
+// crossing still open.  A step takes every axis at the smallest t (the set `first`): the segment goes through a
+// face, an edge or a corner there, and the 1, 3 or 7 cells c + e s, e a subset of `first` other than 0, are the cells
+// that touch that point and have not been counted.  At most n_x + n_y + n_z steps, every cell inside the box of a, b.
+// FIRST: return at the first cell that is not free (cover is then the cells counted so far).
+template <bool FIRST>
+__device__ __forceinline__ FrSight fr_walk(int Y, int Z, const int *__restrict__ dist2, int need, int ax, int ay,
+                                           int az, int bx, int by, int bz) {
+    auto shut = [&](int x, int y, int z) { return dist2[((size_t)x * Y + y) * Z + z] < need ? 1 : 0; };
+    const int n0 = abs(bx - ax), n1 = abs(by - ay), n2 = abs(bz - az);
+    const int s0 = bx > ax ? 1 : -1, s1 = by > ay ? 1 : -1, s2 = bz > az ? 1 : -1;
+    int x = ax, y = ay, z = az, k0 = 0, k1 = 0, k2 = 0;
+    FrSight r{1, shut(x, y, z)};
+    if (FIRST && r.blocked) return r;
+    const int total = n0 + n1 + n2;
+    // the axis at the smallest t always has its flag set, so every step uses up a crossing; `step` bounds it anyway
+    for (int done = 0, step = 0; done < total && step < total; ++step) {
+        const int u0 = 2 * k0 + 1, u1 = 2 * k1 + 1, u2 = 2 * k2 + 1;
+        const bool f0 = u0 * n1 <= u1 * n0 && u0 * n2 <= u2 * n0;
+        const bool f1 = u1 * n0 <= u0 * n1 && u1 * n2 <= u2 * n1;
+        const bool f2 = u2 * n0 <= u0 * n2 && u2 * n1 <= u1 * n2;
+        const int first = (f0 ? 1 : 0) | (f1 ? 2 : 0) | (f2 ? 4 : 0);
+#pragma unroll
+        for (int e = 1; e < 8; ++e) {
+            if ((e & ~first) != 0) continue;
+            r.cover += 1;
+            r.blocked += shut(x + ((e & 1) ? s0 : 0), y + ((e & 2) ? s1 : 0), z + ((e & 4) ? s2 : 0));
+            if (FIRST && r.blocked) return r;
+        }
+        if (f0) x += s0, ++k0, ++done;
+        if (f1) y += s1, ++k1, ++done;
+        if (f2) z += s2, ++k2, ++done;
+    }
+    return r;
+}
+
+__device__ __forceinline__ bool fr_inside(int X, int Y, int Z, int x, int y, int z) {
+    return x >= 0 && x < X && y >= 0 && y < Y && z >= 0 && z < Z;
+}
+
+// One lane per segment, the whole cover.
+__global__ __launch_bounds__(FR_THREADS) void route_sight_kernel(int X, int Y, int Z, const int *__restrict__ dist2,
+                                                                 int need, int S, const int *__restrict__ a,
+                                                                 const int *__restrict__ b, int *__restrict__ cover,
+                                                                 int *__restrict__ blocked) {
+    const int i = blockIdx.x * FR_THREADS + threadIdx.x;      // S <= GG_FIELD_MAX_POSES
+    if (i >= S) return;
+    const int ax = a[(size_t)i * 3], ay = a[(size_t)i * 3 + 1], az = a[(size_t)i * 3 + 2];
+    const int bx = b[(size_t)i * 3], by = b[(size_t)i * 3 + 1], bz = b[(size_t)i * 3 + 2];
+    FrSight r{0, -1};
+    if (fr_inside(X, Y, Z, ax, ay, az) && fr_inside(X, Y, Z, bx, by, bz))
+        r = fr_walk<false>(Y, Z, dist2, need, ax, ay, az, bx, by, bz);
+    cover[i] = r.cover;
+    blocked[i] = r.blocked;
+}
+
+// One workgroup per path.  From anchor i the 256 lanes take 256 candidates j, chunk by chunk from the far end of the
+// window towards i; lane l of a chunk that ends at `top` has j = top - 255 + l.  Each wave's ballot gives its largest
+// clear j; the four meet in LDS (two buffers, used in turn, so one barrier per chunk is enough) and the largest of
+// them is the chunk's answer.  The first chunk with a clear lane ends the scan.  i, top and next are the same in
+// every lane of the workgroup, so every lane reaches every barrier.
+__global__ __launch_bounds__(FR_THREADS) void route_shortcut_kernel(int X, int Y, int Z,
+                                                                    const int *__restrict__ dist2, int need, int P,
+                                                                    int max_cells, const int *__restrict__ cells,
+                                                                    const int *__restrict__ length, int window,
+                                                                    int *__restrict__ keep, int *__restrict__ count,
+                                                                    int *__restrict__ blocked) {
+    __shared__ int s_best[2][FR_THREADS / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int p = blockIdx.x;                                               // P max_cells <= GG_FIELD_MAX_POSES
+    const int *row = cells + (size_t)p * max_cells * 3;
+    int *out = keep + (size_t)p * max_cells;
+    const int n = min(length[p], max_cells);
+    int kept = 0, bad = 0, pad = -1, turn = 0;
+    if (n > 0) {
+        if (tid == 0) out[0] = 0;
+        kept = 1;
+        pad = n - 1;
+        for (int i = 0; i < n - 1;) {
+            const int ax = row[3 * i], ay = row[3 * i + 1], az = row[3 * i + 2];
+            const bool from = fr_inside(X, Y, Z, ax, ay, az);
+            const int far = (int)min((long long)i + window, (long long)n - 1);
+            int next = -1;
+            for (int top = far; top > i && next < 0; top -= FR_THREADS) {
+                const int j = top - (FR_THREADS - 1) + tid;
+                bool clear = false;
+                if (j > i && from) {
+                    const int bx = row[3 * j], by = row[3 * j + 1], bz = row[3 * j + 2];
+                    clear = fr_inside(X, Y, Z, bx, by, bz) &&
+                            fr_walk<true>(Y, Z, dist2, need, ax, ay, az, bx, by, bz).blocked == 0;
+                }
+                const uint64_t seen = __ballot(clear);
+                if (lane == 0)
+                    s_best[turn][wave] = seen != 0ull ? top - (FR_THREADS - 1) + wave * 64 + 63 - __builtin_clzll(seen) : -1;
+                __syncthreads();
+#pragma unroll
+                for (int w = 0; w < FR_THREADS / 64; ++w) next = max(next, s_best[turn][w]);
+                turn ^= 1;
+            }
+            if (next < 0) next = i + 1, ++bad;                              // no candidate is clear, i + 1 among them
+            if (tid == 0) out[kept] = next;
+            ++kept;
+            i = next;
+        }
+    }
+    for (int r = kept + tid; r < max_cells; r += FR_THREADS) out[r] = pad;
+    if (tid == 0) count[p] = kept, blocked[p] = bad;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------------------------
 static bool field_dims_ok(const int32_t *dims) {
@@ -703,6 +827,45 @@ extern "C" int gg_field_descend(const int32_t *dims, const int32_t *dist2, int32
     hipLaunchKernelGGL(route_descend_kernel, dim3((unsigned)((num_paths + per - 1) / per)), dim3(FR_THREADS), 0,
                        (hipStream_t)stream, dims[0], dims[1], dims[2], dist2, need, cost, num_paths, starts, max_cells,
                        cells, length);
+    GG_CHECK_LAUNCH();
+    return GG_OK;
+}
+
+extern "C" int gg_field_sight(const int32_t *dims, const int32_t *dist2, int32_t need, int num_segments,
+                              const int32_t *a, const int32_t *b, int32_t *cover, int32_t *blocked,
+                              gg_stream_t stream) {
+    GG_REQUIRE(field_dims_ok(dims), FIELD_DIMS_MSG);
+    GG_REQUIRE(need >= 0 && need <= GG_FIELD_FAR, "need must be in 0..GG_FIELD_FAR");
+    GG_REQUIRE(num_segments >= 0 && num_segments <= GG_FIELD_MAX_POSES,
+               "need 0 <= num_segments <= GG_FIELD_MAX_POSES");
+    if (num_segments == 0) return GG_OK;
+    GG_REQUIRE(dist2 && a && b && cover && blocked, "null pointer: dist2 / a / b / cover / blocked");
+    GG_REQUIRE((((uintptr_t)dist2 | (uintptr_t)a | (uintptr_t)b | (uintptr_t)cover | (uintptr_t)blocked) & 3) == 0,
+               "dist2 / a / b / cover / blocked misaligned");
+    hipLaunchKernelGGL(route_sight_kernel, dim3((unsigned)((num_segments + FR_THREADS - 1) / FR_THREADS)),
+                       dim3(FR_THREADS), 0, (hipStream_t)stream, dims[0], dims[1], dims[2], dist2, need, num_segments,
+                       a, b, cover, blocked);
+    GG_CHECK_LAUNCH();
+    return GG_OK;
+}
+
+extern "C" int gg_field_shortcut(const int32_t *dims, const int32_t *dist2, int32_t need, int num_paths,
+                                 int max_cells, const int32_t *cells, const int32_t *length, int window,
+                                 int32_t *keep, int32_t *count, int32_t *blocked, gg_stream_t stream) {
+    GG_REQUIRE(field_dims_ok(dims), FIELD_DIMS_MSG);
+    GG_REQUIRE(need >= 0 && need <= GG_FIELD_FAR, "need must be in 0..GG_FIELD_FAR");
+    GG_REQUIRE(num_paths >= 0 && max_cells >= 1, "need num_paths >= 0 and max_cells >= 1");
+    GG_REQUIRE((int64_t)num_paths * max_cells <= GG_FIELD_MAX_POSES, "num_paths max_cells > GG_FIELD_MAX_POSES");
+    GG_REQUIRE(window >= 1, "window must be >= 1");
+    if (num_paths == 0) return GG_OK;
+    GG_REQUIRE(dist2 && cells && length && keep && count && blocked,
+               "null pointer: dist2 / cells / length / keep / count / blocked");
+    GG_REQUIRE((((uintptr_t)dist2 | (uintptr_t)cells | (uintptr_t)length | (uintptr_t)keep | (uintptr_t)count |
+                 (uintptr_t)blocked) & 3) == 0,
+               "dist2 / cells / length / keep / count / blocked misaligned");
+    hipLaunchKernelGGL(route_shortcut_kernel, dim3((unsigned)num_paths), dim3(FR_THREADS), 0,
+                       (hipStream_t)stream, dims[0], dims[1], dims[2], dist2, need, num_paths, max_cells, cells,
+                       length, window, keep, count, blocked);
     GG_CHECK_LAUNCH();
     return GG_OK;
 }

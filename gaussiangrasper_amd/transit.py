@@ -1,20 +1,25 @@
-"""Transit planning through the distance field: the exact cost-to-go over the free cells (`gg_field_route`) and the
-descent along it (`gg_field_descend`), csrc/field.hip, and the poses of a carried gripper along the path that comes
-out.  The contract is in include/gg_raster.h and PARITY.md "Transit planning"; the design, the convergence argument
-and the derivation of the planning pad in DESIGN.md §3.29.
+"""Transit planning through the distance field: the exact cost-to-go over the free cells (`gg_field_route`), the
+descent along it (`gg_field_descend`), the exact line of sight through the free cells (`gg_field_sight`) and greedy
+string pulling of a descended path on top of it (`gg_field_shortcut`), csrc/field.hip, and the poses of a carried
+gripper along the path that comes out.  The contract is in include/gg_raster.h and PARITY.md "Transit planning"; the
+design, the convergence argument and the derivation of the planning pad in DESIGN.md §3.29, the line of sight and
+why a pulled path is as safe as a descended one in §3.30.
 
     cells_of           the header's cell rule on the host in fp64
-    route / descend_cells   the two calls as they are
+    route / descend_cells / sight / shortcut_cells   the four calls as they are
     cost_to_go         the cost field towards goal points, for a ball of `radius` kept `margin` away
     descend            the paths from start points down a cost field, called again when a path was cut
+    line_of_sight      is the straight segment between the cells of two scene points clear for a ball of `radius`
+    shortcut           a descended path pulled taut: the kept rows, and the kept cells padded as descend pads
     bounding_radius    the ball about the gripper's origin that holds the gripper at every orientation
     carried_spheres    spheres that cover the points of the carried object, gripper frame
     polyline_points / transit_poses    a cell path as `steps` poses, by arc length, the orientation by slerp
-    plan_transit       cost field, descent, poses, and field.path_clear with the real spheres as the verdict
-    python -m gaussiangrasper_amd.transit --field field.npz --from POSES.npy --to POSE.npy --gripper default [...]
+    plan_transit       cost field, descent, (shortcut,) poses, and field.path_clear with the real spheres as the verdict
+    python -m gaussiangrasper_amd.transit --field field.npz --from POSES.npy --to POSE.npy --gripper default
+                                          [--shortcut [--window W]] [...]
 
-Out of scope: smoothing or shortcutting of the chamfer polyline, orientation-aware planning (the bounding ball is the
-price of a search in three dimensions), and the kinematics of the arm."""
+Out of scope: spline smoothing of the polyline (the pulled path still turns at its kept cells), orientation-aware
+planning (the bounding ball is the price of a search in three dimensions), and the kinematics of the arm."""
 from __future__ import annotations
 
 import argparse
@@ -65,6 +70,18 @@ class TransitPlan:
     cells: Tensor              # (P, L, 3) int32 cell paths, `length` of each
     length: Tensor             # (P,) int32
     cost_to_go: CostToGo
+    keep: Optional[Tensor] = None       # (P, L) int32 rows of `cells` the poses run through (shortcut=True only)
+    count: Optional[Tensor] = None      # (P,) int32 how many of them (shortcut=True only)
+    euclid: Optional[np.ndarray] = None     # (P,) float64 length of the polyline the poses follow: the start, the
+    #                                         centres of the cells they run through, the goal; inf: no path
+
+
+@dataclass
+class Shortcut:
+    keep: Tensor               # (P, L) int32 kept rows of the path, ascending; from `count` on the last one repeats
+    count: Tensor              # (P,) int32 kept rows; 0 for a path of no cells (its keep rows are -1)
+    blocked: Tensor            # (P,) int32 kept segments that are not clear: 0 for every path a descent produced
+    cells: Tensor              # (P, L, 3) int32 the kept cells, padded as descend pads (-1 rows for no path)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -168,8 +185,30 @@ def transit_poses(pose_from: ArrayLike, pose_to: ArrayLike, cells: ArrayLike, le
     return out.astype(np.float32)
 
 
+def polyline_lengths(field, starts: ArrayLike, goal: ArrayLike, cells: ArrayLike, length: ArrayLike) -> np.ndarray:
+    """(P,) float64: the length, scene units, of the polyline from starts[p] through the centres of the first
+    length[p] rows of cells[p] to `goal`, the line transit_poses resamples; inf where length[p] is 0."""
+    s = np.asarray(starts, np.float64).reshape(-1, 3)
+    g = np.asarray(goal, np.float64).reshape(1, 3)
+    if len(s) == 0:
+        return np.zeros(0)
+    c = np.asarray(cells.detach().cpu() if isinstance(cells, Tensor) else cells, np.int64).reshape(len(s), -1, 3)
+    n = np.asarray(length.detach().cpu() if isinstance(length, Tensor) else length, np.int64).reshape(-1)
+    out = np.full(len(s), np.inf)
+    for p in np.nonzero(n > 0)[0]:
+        line = np.concatenate([s[p:p + 1], cell_centres(field, c[p, :n[p]]), g])
+        out[p] = np.linalg.norm(np.diff(line, axis=0), axis=1).sum()
+    return out
+
+
+def best_path(planned: ArrayLike, clear: ArrayLike, rank: ArrayLike) -> int:
+    """the planned and clear path of the smallest `rank` (the first of equals), -1 when there is none"""
+    ok = np.asarray(planned, bool) & np.asarray(clear, bool)
+    return int(np.argmin(np.where(ok, np.asarray(rank, np.float64), np.inf))) if ok.any() else -1
+
+
 # ------------------------------------------------------------------------------------------------
-# device side: the two calls
+# device side: the calls as they are
 # ------------------------------------------------------------------------------------------------
 def _dims(dims):
     shape = tuple(int(v) for v in np.asarray(dims).reshape(-1))
@@ -243,6 +282,80 @@ def descend_cells(dist2: Tensor, dims, need: int, cost: Tensor, starts: ArrayLik
     return cells, length
 
 
+def sight(dist2: Tensor, dims, need: int, a: ArrayLike, b: ArrayLike) -> Tuple[Tensor, Tensor]:
+    """(cover (S,) int32, blocked (S,) int32) of one gg_field_sight call; a, b (S, 3) int32 cells.  blocked 0: the
+    segment between the two centres is clear; -1 (and cover 0): an end is outside the volume."""
+    dev = _require_hip(dist2)
+    d, shape = _dims(dims)
+    _int32_volume(dist2, "dist2", shape)
+    if not 0 <= int(need) <= FAR:
+        raise ValueError(f"need must be in 0..{FAR}, got {need}")
+    ca, cb = _cells_arg(a, "a", dev), _cells_arg(b, "b", dev)
+    s = ca.shape[0]
+    if cb.shape[0] != s or s > MAX_POSES:
+        raise ValueError(f"a and b must hold the same number of cells, at most {MAX_POSES}: got {s} and {cb.shape[0]}")
+    cover = torch.empty(s, dtype=torch.int32, device=dev)
+    blocked = torch.empty(s, dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().gg_field_sight(d, _ptr(dist2), int(need), s, _ptr(ca) if s else None,
+                                          _ptr(cb) if s else None, _ptr(cover), _ptr(blocked), _stream(dev)),
+               "gg_field_sight")
+    return cover, blocked
+
+
+def line_of_sight(field: DistanceField, points_a: ArrayLike, points_b: ArrayLike, radius: float,
+                  margin: float = 0.0) -> Tensor:
+    """(S,) bool on the field's device: the straight segment between the CENTRES of the cells of points_a[s] and
+    points_b[s] (scene points, (S, 3)) is clear for a ball of `radius` kept `margin` away: every cell its cover
+    holds is inside the volume and has dist2 >= field.need2(radius, margin, h).  False for a point outside."""
+    need = int(need2(float(radius), margin, field.h))
+    _, blocked = sight(field.dist2, field.dims, need, cells_of(field, points_a), cells_of(field, points_b))
+    return blocked == 0
+
+
+def shortcut_cells(dist2: Tensor, dims, need: int, cells: Tensor, length: Tensor,
+                   window: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """(keep (P, max_cells) int32, count (P,) int32, blocked (P,) int32) of one gg_field_shortcut call; cells
+    (P, max_cells, 3) int32 and length (P,) int32 as descend_cells returns them."""
+    dev = _require_hip(dist2)
+    d, shape = _dims(dims)
+    _int32_volume(dist2, "dist2", shape)
+    if not 0 <= int(need) <= FAR:
+        raise ValueError(f"need must be in 0..{FAR}, got {need}")
+    c = to_device(cells, torch.int32, dev)
+    n = to_device(length, torch.int32, dev).reshape(-1)
+    if c.ndim != 3 or c.shape[2] != 3 or c.shape[0] != n.shape[0]:
+        raise ValueError(f"cells must be (P, max_cells, 3) and length (P,), got {tuple(c.shape)} and {tuple(n.shape)}")
+    p, max_cells = c.shape[0], c.shape[1]
+    if max_cells < 1 or p * max_cells > MAX_POSES:
+        raise ValueError(f"need max_cells >= 1 and P max_cells <= {MAX_POSES}, got {p} x {max_cells}")
+    if int(window) < 1:
+        raise ValueError(f"window must be >= 1, got {window}")
+    c = c.contiguous()
+    keep = torch.empty(p, max_cells, dtype=torch.int32, device=dev)
+    count = torch.empty(p, dtype=torch.int32, device=dev)
+    blocked = torch.empty(p, dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().gg_field_shortcut(d, _ptr(dist2), int(need), p, max_cells, _ptr(c) if p else None,
+                                             _ptr(n) if p else None, min(int(window), MAX_POSES), _ptr(keep),
+                                             _ptr(count), _ptr(blocked), _stream(dev)), "gg_field_shortcut")
+    return keep, count, blocked
+
+
+def shortcut(ctg: CostToGo, cells: Tensor, length: Tensor, window: Optional[int] = None) -> Shortcut:
+    """Greedy string pulling of the paths `descend` returned, against the free cells `ctg` was made for: from each
+    kept cell the farthest cell within `window` rows (None: the whole path) whose segment is clear is kept next.
+    Every point of the polyline through the kept centres then lies in a free cell of `ctg`."""
+    f = ctg.field
+    if window is None:
+        window = max(int(cells.shape[1]), 1)
+    keep, count, blocked = shortcut_cells(f.dist2, f.dims, ctg.need, cells, length, window)
+    kept = torch.gather(to_device(cells, torch.int32, keep.device), 1,
+                        keep.clamp(min=0).long()[:, :, None].expand(-1, -1, 3))
+    return Shortcut(keep, count, blocked, torch.where(keep[:, :, None] >= 0, kept, torch.full_like(kept, -1)))
+
+
+_shortcut = shortcut           # plan_transit's argument of the same name hides the function there
+
+
 def cost_to_go(field: DistanceField, goal_points: ArrayLike, radius: float, margin: float = 0.0,
                max_rounds: int = MAX_ROUNDS) -> CostToGo:
     """The cost field of `field` (update() first) towards the cells of (G, 3) goal points, for a ball of `radius`
@@ -275,12 +388,17 @@ def descend(ctg: CostToGo, start_points: ArrayLike, max_cells: Optional[int] = N
 
 def plan_transit(field: DistanceField, poses_from: ArrayLike, pose_to: ArrayLike, spheres: ArrayLike,
                  radius: Union[float, ArrayLike], margin: float = 0.0, steps: int = STEPS,
-                 max_rounds: int = MAX_ROUNDS) -> TransitPlan:
+                 max_rounds: int = MAX_ROUNDS, shortcut: bool = False, window: Optional[int] = None) -> TransitPlan:
     """Paths for the gripper (and what it carries: `spheres` (S, 3) of `radius`, gripper frame) from each of the
     (P, 12) poses_from to pose_to through field (update() first): ONE cost field from pose_to's cell for the ball
     of planning_radius, one descent for all P starts, transit_poses for each, and field.path_clear of those poses with
     the real spheres as the verdict.  A start from which there is no path gets the straight field.interpolate poses,
-    planned False and cost inf."""
+    planned False and cost inf.
+
+    shortcut=True pulls every path taut first (`shortcut`, within `window` rows; None: the whole path): the poses
+    then run through the kept cells only, `keep` and `count` say which, and `best` is the planned and clear path of
+    the smallest `euclid` rather than of the smallest chamfer `cost` (which keeps its meaning).  `euclid` is filled
+    either way."""
     a = np.asarray(poses_from.detach().cpu() if isinstance(poses_from, Tensor) else poses_from, np.float64)
     a = a.reshape(-1, 12)
     b = np.asarray(pose_to.detach().cpu() if isinstance(pose_to, Tensor) else pose_to, np.float64).reshape(-1)
@@ -291,14 +409,21 @@ def plan_transit(field: DistanceField, poses_from: ArrayLike, pose_to: ArrayLike
     cells, length, at = descend(ctg, a[:, 9:])
     n, c, at = length.cpu().numpy(), cells.cpu().numpy(), at.cpu().numpy()
     planned = n > 0
+    keep = count = None
+    if shortcut:
+        if window is not None and int(window) < 1:
+            raise ValueError(f"window must be >= 1, got {window}")
+        pulled = _shortcut(ctg, cells, length, window)
+        keep, count = pulled.keep, pulled.count
+        n, c = count.cpu().numpy(), pulled.cells.cpu().numpy()
     poses = np.stack([transit_poses(a[i], b, c[i], n[i], field, steps) if planned[i] else interpolate(a[i], b, steps)
                       for i in range(len(a))]) if len(a) else np.zeros((0, int(steps), 12), np.float32)
     clearance = path_clear(field, poses, sp, radius, margin)
     cost = np.where(planned, at.astype(np.float64) * field.h / 3.0, np.inf)
-    ok = planned & clearance.clear.cpu().numpy()
-    best = int(np.argmin(np.where(ok, cost, np.inf))) if ok.any() else -1
+    euclid = polyline_lengths(field, a[:, 9:], b[9:], c, n)
+    best = best_path(planned, clearance.clear.cpu().numpy(), euclid if shortcut else cost)
     return TransitPlan(to_device(poses, torch.float32, field.dist2.device), clearance, cost, best, planned, cells,
-                       length, ctg)
+                       length, ctg, keep, count, euclid)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -320,9 +445,16 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--margin", type=float, default=0.0, help="clearance kept beyond the spheres")
     ap.add_argument("--steps", type=int, default=STEPS, help="waypoints per path")
     ap.add_argument("--carried", default=None, help=".npy (N, 3) points of the carried object, gripper frame")
+    ap.add_argument("--shortcut", action="store_true", help="pull the paths taut: poses through the kept cells only")
+    ap.add_argument("--window", type=int, default=None, help="with --shortcut: rows looked ahead (default: the path)")
     ap.add_argument("--out", required=True, help="output .npy (P, steps, 12) poses")
-    ap.add_argument("--report", required=True, help="output .npz slack, first_hit, clear, cost, best, planned, spheres")
+    ap.add_argument("--report", required=True, help="output .npz slack, first_hit, clear, cost, euclid, best, planned, "
+                                                    "spheres; with --shortcut keep and count too")
     a = ap.parse_args(argv)
+    if a.window is not None and not a.shortcut:
+        ap.error("--window needs --shortcut")
+    if a.window is not None and a.window < 1:
+        ap.error(f"--window must be >= 1, got {a.window}")
     for n in ("radius", "width"):
         if not (math.isfinite(getattr(a, n)) and getattr(a, n) > 0.0):
             ap.error(f"--{n} must be finite and > 0, got {getattr(a, n)}")
@@ -343,17 +475,22 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         if start.ndim not in (1, 2) or start.shape[-1] != 12 or goal.shape != (12,):
             raise ValueError(f"expected (P, 12) start poses and a (12,) goal pose, got {start.shape} and {goal.shape}")
         field = DistanceField.load(a.field)
-        plan = plan_transit(field, start.reshape(-1, 12), goal, spheres, a.radius, a.margin, a.steps)
+        plan = plan_transit(field, start.reshape(-1, 12), goal, spheres, a.radius, a.margin, a.steps,
+                            shortcut=a.shortcut, window=a.window)
         np.save(a.out, plan.poses.cpu().numpy())
         clear = plan.clearance.clear.cpu().numpy()
+        pulled = {"keep": plan.keep.cpu().numpy(), "count": plan.count.cpu().numpy()} if a.shortcut else {}
         np.savez(a.report, slack=plan.clearance.slack.cpu().numpy(), first_hit=plan.clearance.first_hit.cpu().numpy(),
                  clear=clear, cost=plan.cost, best=np.int64(plan.best), planned=plan.planned, spheres=spheres,
-                 length=plan.length.cpu().numpy(), rounds=np.int64(plan.cost_to_go.rounds))
+                 length=plan.length.cpu().numpy(), rounds=np.int64(plan.cost_to_go.rounds), euclid=plan.euclid,
+                 **pulled)
     except (KeyError, ValueError, OSError, _lib.GGError) as exc:
         raise SystemExit(f"error: {exc}") from exc
     print(f"{int(plan.planned.sum())} of {len(plan.planned)} starts have a path, {int((plan.planned & clear).sum())} "
           f"clear; best {plan.best}"
           + (f" at {plan.cost[plan.best]:.4f} scene units" if plan.best >= 0 else "")
+          + (f" ({plan.euclid[plan.best]:.4f} along {int(plan.count[plan.best])} kept cells)"
+             if a.shortcut and plan.best >= 0 else "")
           + f"; {plan.cost_to_go.rounds} rounds; wrote {a.out} and {a.report}")
     return 0
 

@@ -1235,6 +1235,34 @@ int gg_tsdf_mesh_emit(const int32_t *dims, const float *grid, const float *tsdf,
  * on repeat the last cell, so that a consumer of a fixed number of waypoints can take the array as it is; with
  * length 0 every row is -1, -1, -1.  A walk takes at most cost[start] / 3 + 1 steps.  P == 0 writes nothing.  Every
  * array 4-byte aligned.
+ *
+ * Line of sight: the block rule at any length.  For cells a and b inside the volume, COVER(a, b) is the
+ * set of cells c whose CLOSED cube [c, c + 1]^3 (cell units) meets the closed segment between the centres a + 1/2 and
+ * b + 1/2.  The segment is CLEAR iff every cell of its cover is inside the volume and free.  Where the segment goes
+ * exactly through a face edge or a corner, all 4 or 8 cells that touch there belong to the cover; for b - a a move
+ * the cover is exactly the 2, 4 or 8 cells of the block rule, so every move a descent made is clear.  Every decision
+ * is an integer comparison: with n_a = |b_a - a_a| the segment crosses the k-th boundary of axis a at
+ * t = (2 k + 1) / (2 n_a), and two crossings are ordered by (2 k + 1) n_b against (2 k' + 1) n_a, products below 2^22
+ * with GG_FIELD_MAX_DIM 1024; equality is a tie, and a tie opens every cell it touches.  Every point of a clear
+ * segment then lies in a free cell under the half-open cell rule, and no segment squeezes between two blocked cells
+ * that touch by an edge or a corner.
+ *
+ * gg_field_sight: a, b int32 [S][3] cells, S in 0..GG_FIELD_MAX_POSES; cover int32 [S] = the number of cells of the
+ * cover, blocked int32 [S] = how many of them are not free (0: clear).  An endpoint outside the volume gives cover 0
+ * and blocked -1, with no walk; a == b gives cover 1.  The whole cover is walked, at most n_x + n_y + n_z steps.  No
+ * atomics, a pure function of the inputs, symmetric in a and b.  S == 0 writes nothing.
+ *
+ * gg_field_shortcut: greedy string pulling of cell paths.  cells int32 [P][max_cells][3] and length int32 [P] as
+ * gg_field_descend writes them (any cell sequence is accepted); n = min(length, max_cells), so a cut path is
+ * shortened as far as it goes.  window >= 1; max_cells >= 1, P max_cells <= GG_FIELD_MAX_POSES.  From the anchor
+ * i = 0 the next anchor is the LARGEST j in (i, min(i + window, n - 1)] whose segment cells[i] -> cells[j] is clear
+ * (sight is not monotone in j); when there is none it is j = i + 1, clear or not; repeated until i = n - 1.  A cell
+ * outside the volume ends no segment that is clear.  keep int32 [P][max_cells]: the anchors, ascending, the first 0,
+ * the last n - 1; the rows from count on repeat n - 1.  count int32 [P]: the number of anchors (1 for n == 1, at most
+ * n).  blocked int32 [P]: the kept segments that are not clear: 0 for every path a descent produced with this dist2
+ * and need, the caller's to look at for any other.  length <= 0: count 0, blocked 0 and every keep row -1.
+ * window == 1 returns the path itself.  No atomics, a pure function of the inputs.  P == 0 writes nothing.  Every
+ * array 4-byte aligned.
  * Null, misaligned or out-of-range arguments: GG_ERR_INVALID_ARG naming the argument, before any launch. */
 #define GG_FIELD_MAX_DIM 1024
 #define GG_FIELD_MAX_CELLS (1 << 27)
@@ -1259,6 +1287,11 @@ int gg_field_route(const int32_t *dims, const int32_t *dist2, int32_t need, int 
                    gg_stream_t stream);
 int gg_field_descend(const int32_t *dims, const int32_t *dist2, int32_t need, const int32_t *cost, int num_paths,
                      const int32_t *starts, int max_cells, int32_t *cells, int32_t *length, gg_stream_t stream);
+int gg_field_sight(const int32_t *dims, const int32_t *dist2, int32_t need, int num_segments, const int32_t *a,
+                   const int32_t *b, int32_t *cover, int32_t *blocked, gg_stream_t stream);
+int gg_field_shortcut(const int32_t *dims, const int32_t *dist2, int32_t need, int num_paths, int max_cells,
+                      const int32_t *cells, const int32_t *length, int window, int32_t *keep, int32_t *count,
+                      int32_t *blocked, gg_stream_t stream);
 
 /* ---- placement: height maps and the resting search (PARITY "Placement") ----------------------------
  * A plane grid: dims (host, 2 ints) U, V cells, 1 <= each <= GG_PLACE_MAX_DIM; grid (host, 4 doubles) lo_u, lo_v, ONE
