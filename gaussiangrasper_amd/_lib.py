@@ -159,6 +159,9 @@ SIGNATURES = {
     "gg_field_shortcut": (_I, [_P, _P, C.c_int32, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
     "gg_height_map": (_I, [_I, _P, _P, C.c_double, _I, _P, _P, _P, _P, _P, _P]),
     "gg_place_search": (_I, [_P, _P, _I, _P, _P, C.c_int32, _P, _P, _P, _P]),
+    "gg_arm_fk": (_I, [_I, _P, _I, _P, _P, _P]),
+    "gg_arm_follow": (_I, [_I, _P, _I, _I, _P, _I, _P] + [C.c_double] * 6 + [_I] + [_P] * 4 + [_P]),
+    "gg_arm_clear": (_I, [_I, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, C.c_int32, _P, _P, _P]),
     "gg_prof_enable": (_I, [_I]),
     "gg_prof_reset": (_I, []),
     "gg_prof_get": (_I, [_I, C.POINTER(C.c_int), C.POINTER(C.c_double)]),

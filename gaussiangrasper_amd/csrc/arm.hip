@@ -1,0 +1,617 @@
+// arm.hip — the arm behind the gripper: forward kinematics of a serial chain, inverse kinematics along gripper pose
+// paths by damped least squares, and the whole arm's link spheres against the scene's distance field.  The contract is
+// in include/gg_raster.h (gg_arm_*) and PARITY.md "Arm reachability"; the design in DESIGN.md §3.31.
+//
+// gg_arm_fk       a thread per configuration.
+// gg_arm_follow   a thread per (path, seed): the waypoints of a path in order, each from the solution of the one
+//                 before.  The chain is a kernel argument (scalar loads with constant offsets once the joint loops are
+//                 unrolled); per joint the thread keeps the world axis and origin (6 doubles), forms the Jacobian's
+//                 columns from them when it needs them, and accumulates J J^T column by column, so that no array is
+//                 indexed by a value the compiler does not know.  No thread waits for another, no atomics; the loops
+//                 are bounded by num_waypoints and max_iter.
+// The three kernels are templates on the joint count J, so every `j < J` is decided when they are compiled, and the
+// joint's kind enters by factors of 1 and 0, not by a branch: no condition that is the same for every lane is kept
+// across the iteration loop (DESIGN.md §3.31 has the reason).
+// gg_arm_clear    a one-wave workgroup per configuration: every lane runs the chain (the same values in all of them),
+//                 lane 0 leaves the J + 2 frames in LDS, the lanes stride over the spheres, and a butterfly over
+//                 (slack, index) leaves the minimum and the lowest sphere that attains it in every lane.
+//
+// All arithmetic is fp64 and the file is built with -ffp-contract=off: a composed entry is (a0 b0 + a1 b1) + a2 b2,
+// plus t, exactly as the header says.
+#include <math.h>
+
+#include <type_traits>
+
+#include "field_cell.h"
+#include "gg_common.h"
+
+#define ARM_THREADS 64
+#define ARM_FRAMES (GG_ARM_MAX_JOINTS + 2)
+
+struct ArmChain {
+    int J;
+    double rev[GG_ARM_MAX_JOINTS], pri[GG_ARM_MAX_JOINTS];       // 1, 0 for a revolute joint; 0, 1 for a prismatic one
+    double base[12];
+    double fixed[GG_ARM_MAX_JOINTS][12];          // A_j, j < J
+    double tip[12];                              // A_J: the last link to the gripper frame
+    double axis[GG_ARM_MAX_JOINTS][3];
+    double lo[GG_ARM_MAX_JOINTS], hi[GG_ARM_MAX_JOINTS];
+};
+
+struct ArmGrid {
+    int X, Y, Z;
+    double lo[3], h;
+};
+
+struct ArmLaw {
+    double tol_p, tol_r, L, k, lambda_min, max_step;
+    int max_iter;
+};
+
+// ---------------------------------------------------------------------------------------------------------------
+// the chain
+// ---------------------------------------------------------------------------------------------------------------
+// T <- T B: R = R_T R_B, t = R_T t_B + t_T; each entry a sum of three products added left to right (plus t).
+__device__ __forceinline__ void arm_compose(double *T, const double *B) {
+    double o[12];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[3 * r + c] = (T[3 * r] * B[c] + T[3 * r + 1] * B[3 + c]) + T[3 * r + 2] * B[6 + c];
+        o[9 + r] = ((T[3 * r] * B[9] + T[3 * r + 1] * B[10]) + T[3 * r + 2] * B[11]) + T[9 + r];
+    }
+#pragma unroll
+    for (int i = 0; i < 12; ++i) T[i] = o[i];
+}
+
+// M_j(q): Rodrigues' rotation about the unit axis a, (I c + (1 - c) a a^T) + s [a]x, or the translation q a.  No
+// branch on the joint's kind: with (rev, pri) = (1, 0) or (0, 1) the angle is rev q and the slide pri q, and a factor of
+// exactly 1 or 0 changes no bit of a finite value: a prismatic joint gets the rotation of angle 0, which is I, and a
+// revolute one the translation 0.  (A kind is the same for every lane; a branch on it, kept across the iteration loop
+// while lanes leave it, is the form the compiler was seen to get wrong: DESIGN.md 3.31.)
+__device__ __forceinline__ void arm_motion(double rev, double pri, const double *a, double q, double *M) {
+    const double ang = rev * q, slide = pri * q;
+    const double c = cos(ang), s = sin(ang), v = 1.0 - c;
+    M[0] = (c + v * (a[0] * a[0]));
+    M[1] = (v * (a[0] * a[1])) + s * (-a[2]);
+    M[2] = (v * (a[0] * a[2])) + s * a[1];
+    M[3] = (v * (a[1] * a[0])) + s * a[2];
+    M[4] = (c + v * (a[1] * a[1]));
+    M[5] = (v * (a[1] * a[2])) + s * (-a[0]);
+    M[6] = (v * (a[2] * a[0])) + s * (-a[1]);
+    M[7] = (v * (a[2] * a[1])) + s * a[0];
+    M[8] = (c + v * (a[2] * a[2]));
+    M[9] = slide * a[0];
+    M[10] = slide * a[1];
+    M[11] = slide * a[2];
+}
+
+template <int J>
+__device__ __forceinline__ bool arm_finite_q(const double *q) {
+    bool fin = true;
+#pragma unroll
+    for (int j = 0; j < J; ++j) fin = fin && isfinite(q[j]);
+    return fin;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// fk
+// ---------------------------------------------------------------------------------------------------------------
+template <int J>
+__global__ __launch_bounds__(ARM_THREADS) void arm_fk_kernel(ArmChain arm, int M, const double *__restrict__ q_in,
+                                                             double *__restrict__ frames) {
+    const int m = blockIdx.x * ARM_THREADS + threadIdx.x;        // M <= 2^26 and the grid covers M: no overflow
+    if (m >= M) return;
+    double q[GG_ARM_MAX_JOINTS];
+#pragma unroll
+    for (int j = 0; j < GG_ARM_MAX_JOINTS; ++j) q[j] = j < J ? q_in[(size_t)m * J + j] : 0.0;
+    double *out = frames + (size_t)m * (J + 2) * 12;
+    if (!arm_finite_q<J>(q)) {
+        for (int i = 0; i < (J + 2) * 12; ++i) out[i] = __builtin_nan("");
+        return;
+    }
+    double T[12], Mj[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) out[i] = T[i] = arm.base[i];
+#pragma unroll
+    for (int j = 0; j < GG_ARM_MAX_JOINTS; ++j) {
+        if (j < J) {
+            arm_compose(T, arm.fixed[j]);
+            arm_motion(arm.rev[j], arm.pri[j], arm.axis[j], q[j], Mj);
+            arm_compose(T, Mj);
+#pragma unroll
+            for (int i = 0; i < 12; ++i) out[(j + 1) * 12 + i] = T[i];
+        }
+    }
+    arm_compose(T, arm.tip);
+#pragma unroll
+    for (int i = 0; i < 12; ++i) out[(J + 1) * 12 + i] = T[i];
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// follow
+// ---------------------------------------------------------------------------------------------------------------
+// The rotation vector of a rotation matrix through its quaternion (Shepperd: the largest of trace, R00, R11, R22 is
+// the pivot, the first of equals), w >= 0.
+__device__ __forceinline__ void arm_rotvec(const double *R, double *e) {
+    const double t = (R[0] + R[4]) + R[8];
+    double w, x, y, z;
+    if (t >= R[0] && t >= R[4] && t >= R[8]) {
+        w = 1.0 + t;
+        x = R[7] - R[5];
+        y = R[2] - R[6];
+        z = R[3] - R[1];
+    } else if (R[0] >= R[4] && R[0] >= R[8]) {
+        w = R[7] - R[5];
+        x = ((1.0 + R[0]) - R[4]) - R[8];
+        y = R[3] + R[1];
+        z = R[6] + R[2];
+    } else if (R[4] >= R[8]) {
+        w = R[2] - R[6];
+        x = R[3] + R[1];
+        y = ((1.0 + R[4]) - R[8]) - R[0];
+        z = R[7] + R[5];
+    } else {
+        w = R[3] - R[1];
+        x = R[6] + R[2];
+        y = R[7] + R[5];
+        z = ((1.0 + R[8]) - R[0]) - R[4];
+    }
+    const double n = sqrt(((w * w + x * x) + y * y) + z * z);
+    w = w / n;
+    x = x / n;
+    y = y / n;
+    z = z / n;
+    if (w < 0.0) {
+        w = -w;
+        x = -x;
+        y = -y;
+        z = -z;
+    }
+    const double nv = sqrt((x * x + y * y) + z * z);
+    if (nv < 1e-12) {
+        e[0] = 2.0 * x;
+        e[1] = 2.0 * y;
+        e[2] = 2.0 * z;
+    } else {
+        const double ang = 2.0 * atan2(nv, w);
+        e[0] = ang * (x / nv);
+        e[1] = ang * (y / nv);
+        e[2] = ang * (z / nv);
+    }
+}
+
+// Column j of the geometric Jacobian with its rotational rows scaled by L, from the joint's world axis z and origin o
+// and the gripper's position p: [z x (p - o); L z] for a revolute joint, [z; 0] for a prismatic one, by factors of 1 and 0.
+__device__ __forceinline__ void arm_column(double rev, double pri, const double *z, const double *o, const double *p,
+                                           double L, double *c) {
+    const double d0 = p[0] - o[0], d1 = p[1] - o[1], d2 = p[2] - o[2];
+    c[0] = rev * (z[1] * d2 - z[2] * d1) + pri * z[0];
+    c[1] = rev * (z[2] * d0 - z[0] * d2) + pri * z[1];
+    c[2] = rev * (z[0] * d1 - z[1] * d0) + pri * z[2];
+    c[3] = rev * (L * z[0]);
+    c[4] = rev * (L * z[1]);
+    c[5] = rev * (L * z[2]);
+}
+
+template <int J>
+__global__ __launch_bounds__(ARM_THREADS) void arm_follow_kernel(ArmChain arm, ArmLaw law, int P, int W, int S,
+                                                                 const float *__restrict__ poses,
+                                                                 const double *__restrict__ seeds,
+                                                                 double *__restrict__ q_out, int *__restrict__ iters,
+                                                                 double *__restrict__ resid,
+                                                                 int *__restrict__ first_fail) {
+    const int i = blockIdx.x * ARM_THREADS + threadIdx.x;        // P S <= 2^26
+    if (i >= P * S) return;
+    const int path = i / S;
+    double q[GG_ARM_MAX_JOINTS];
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < GG_ARM_MAX_JOINTS; ++j) {
+        q[j] = 0.0;
+        if (j < J) {
+            const double v = seeds[(size_t)i * J + j];
+            ok = ok && isfinite(v);
+            q[j] = fmin(fmax(v, arm.lo[j]), arm.hi[j]);
+        }
+    }
+    int w = 0;
+    for (; w < W && ok; ++w) {
+        double Rt[9], pt[3];                                     // the target
+        const float *pose = poses + ((size_t)path * W + w) * 12;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            const float v = pose[k];
+            ok = ok && isfinite(v);
+            Rt[k] = (double)v;
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float v = pose[9 + k];
+            ok = ok && isfinite(v);
+            pt[k] = (double)v;
+        }
+        if (!ok) break;
+        int it = 0;
+        double np_ = 0.0, nr_ = 0.0;
+        for (;;) {
+            // FK, keeping every joint's world axis and origin
+            double T[12], Mj[12], zs[GG_ARM_MAX_JOINTS][3], os[GG_ARM_MAX_JOINTS][3];
+#pragma unroll
+            for (int k = 0; k < 12; ++k) T[k] = arm.base[k];
+#pragma unroll
+            for (int j = 0; j < GG_ARM_MAX_JOINTS; ++j) {
+                if (j < J) {
+                    arm_compose(T, arm.fixed[j]);
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        zs[j][k] = (T[3 * k] * arm.axis[j][0] + T[3 * k + 1] * arm.axis[j][1]) + T[3 * k + 2] * arm.axis[j][2];
+                        os[j][k] = T[9 + k];
+                    }
+                    arm_motion(arm.rev[j], arm.pri[j], arm.axis[j], q[j], Mj);
+                    arm_compose(T, Mj);
+                }
+            }
+            arm_compose(T, arm.tip);
+            // the error
+            double e[6], Re[9], er[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) e[k] = pt[k] - T[9 + k];
+#pragma unroll
+            for (int a = 0; a < 3; ++a)
+#pragma unroll
+                for (int b = 0; b < 3; ++b)
+                    Re[3 * a + b] = (Rt[3 * a] * T[3 * b] + Rt[3 * a + 1] * T[3 * b + 1]) + Rt[3 * a + 2] * T[3 * b + 2];
+            arm_rotvec(Re, er);
+            np_ = sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
+            nr_ = sqrt((er[0] * er[0] + er[1] * er[1]) + er[2] * er[2]);
+            if (!(isfinite(np_) && isfinite(nr_))) {
+                ok = false;
+                break;
+            }
+            if (np_ <= law.tol_p && nr_ <= law.tol_r) break;     // converged
+            if (it == law.max_iter) {
+                ok = false;
+                break;
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) e[3 + k] = law.L * er[k];
+            double ee = e[0] * e[0];
+#pragma unroll
+            for (int k = 1; k < 6; ++k) ee = ee + e[k] * e[k];
+            const double lambda2 = law.k * ee + law.lambda_min * law.lambda_min;
+            // A = J J^T + lambda2 I (lower triangle), a column at a time
+            double A[6][6];
+#pragma unroll
+            for (int a = 0; a < 6; ++a)
+#pragma unroll
+                for (int b = 0; b <= a; ++b) A[a][b] = 0.0;
+#pragma unroll
+            for (int j = 0; j < GG_ARM_MAX_JOINTS; ++j) {
+                if (j < J) {
+                    double c[6];
+                    arm_column(arm.rev[j], arm.pri[j], zs[j], os[j], T + 9, law.L, c);
+#pragma unroll
+                    for (int a = 0; a < 6; ++a)
+#pragma unroll
+                        for (int b = 0; b <= a; ++b) A[a][b] = A[a][b] + c[a] * c[b];
+                }
+            }
+#pragma unroll
+            for (int a = 0; a < 6; ++a) A[a][a] = A[a][a] + lambda2;
+            // Cholesky in place, then the two triangular solves
+            bool pd = true;
+#pragma unroll
+            for (int a = 0; a < 6; ++a) {
+#pragma unroll
+                for (int b = 0; b <= a; ++b) {
+                    double s = A[a][b];
+#pragma unroll
+                    for (int k = 0; k < b; ++k) s = s - A[a][k] * A[b][k];
+                    if (a == b) {
+                        pd = pd && s > 0.0;
+                        A[a][a] = sqrt(s);
+                    } else {
+                        A[a][b] = s / A[b][b];
+                    }
+                }
+            }
+            if (!pd) {
+                ok = false;
+                break;
+            }
+            double y[6];
+#pragma unroll
+            for (int a = 0; a < 6; ++a) {
+                double s = e[a];
+#pragma unroll
+                for (int k = 0; k < a; ++k) s = s - A[a][k] * y[k];
+                y[a] = s / A[a][a];
+            }
+#pragma unroll
+            for (int a = 5; a >= 0; --a) {
+                double s = y[a];
+#pragma unroll
+                for (int k = a + 1; k < 6; ++k) s = s - A[k][a] * y[k];
+                y[a] = s / A[a][a];
+            }
+            // dq = J^T y, limited to max_step
+            double dq[GG_ARM_MAX_JOINTS], big = 0.0;
+            bool fin = true;
+#pragma unroll
+            for (int j = 0; j < GG_ARM_MAX_JOINTS; ++j) {
+                dq[j] = 0.0;
+                if (j < J) {
+                    double c[6];
+                    arm_column(arm.rev[j], arm.pri[j], zs[j], os[j], T + 9, law.L, c);
+                    double s = c[0] * y[0];
+#pragma unroll
+                    for (int k = 1; k < 6; ++k) s = s + c[k] * y[k];
+                    dq[j] = s;
+                    fin = fin && isfinite(s);
+                    big = fmax(big, fabs(s));
+                }
+            }
+            if (!fin) {
+                ok = false;
+                break;
+            }
+            const double scale = big > law.max_step ? law.max_step / big : 1.0;
+#pragma unroll
+            for (int j = 0; j < GG_ARM_MAX_JOINTS; ++j)
+                if (j < J) {
+                    const double step = big > law.max_step ? dq[j] * scale : dq[j];
+                    q[j] = fmin(fmax(q[j] + step, arm.lo[j]), arm.hi[j]);
+                }
+            ++it;
+        }
+        if (!ok) break;
+        const size_t at = (size_t)i * W + w;
+#pragma unroll
+        for (int j = 0; j < GG_ARM_MAX_JOINTS; ++j)
+            if (j < J) q_out[at * J + j] = q[j];
+        iters[at] = it;
+        resid[at * 2] = np_;
+        resid[at * 2 + 1] = nr_;
+    }
+    // w: the failed waypoint, or W
+    first_fail[i] = w;
+    for (int v = w; v < W; ++v) {
+        const size_t at = (size_t)i * W + v;
+        for (int j = 0; j < J; ++j) q_out[at * J + j] = __builtin_nan("");
+        iters[at] = -1;
+        resid[at * 2] = __builtin_nan("");
+        resid[at * 2 + 1] = __builtin_nan("");
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// clear
+// ---------------------------------------------------------------------------------------------------------------
+template <int J>
+__global__ __launch_bounds__(GG_WAVE) void arm_clear_kernel(ArmChain arm, ArmGrid g, const int *__restrict__ dist2,
+                                                            int M, const double *__restrict__ q_in, int S,
+                                                            const float *__restrict__ spheres,
+                                                            const int *__restrict__ frame,
+                                                            const int *__restrict__ need2, int outside,
+                                                            int *__restrict__ slack, int *__restrict__ worst) {
+    __shared__ double s_frames[ARM_FRAMES * 12];
+    const int m = blockIdx.x;                                    // one wave, one configuration; the grid is M
+    const int lane = threadIdx.x;
+    double q[GG_ARM_MAX_JOINTS];
+#pragma unroll
+    for (int j = 0; j < GG_ARM_MAX_JOINTS; ++j) q[j] = j < J ? q_in[(size_t)m * J + j] : 0.0;
+    if (!arm_finite_q<J>(q)) {                                 // the same in every lane of the wave
+        if (lane == 0) {
+            slack[m] = INT32_MIN;
+            worst[m] = -1;
+        }
+        return;
+    }
+    {
+        double T[12], Mj[12];
+#pragma unroll
+        for (int i = 0; i < 12; ++i) T[i] = arm.base[i];
+        if (lane == 0)
+#pragma unroll
+            for (int i = 0; i < 12; ++i) s_frames[i] = T[i];
+#pragma unroll
+        for (int j = 0; j < GG_ARM_MAX_JOINTS; ++j) {
+            if (j < J) {
+                arm_compose(T, arm.fixed[j]);
+                arm_motion(arm.rev[j], arm.pri[j], arm.axis[j], q[j], Mj);
+                arm_compose(T, Mj);
+                if (lane == 0)
+#pragma unroll
+                    for (int i = 0; i < 12; ++i) s_frames[(j + 1) * 12 + i] = T[i];
+            }
+        }
+        arm_compose(T, arm.tip);
+        if (lane == 0)
+#pragma unroll
+            for (int i = 0; i < 12; ++i) s_frames[(J + 1) * 12 + i] = T[i];
+    }
+    __syncthreads();                                             // a one-wave workgroup: the LDS writes are done
+    const int dim[3] = {g.X, g.Y, g.Z};
+    int best = GG_FIELD_FAR, who = INT32_MAX;
+    for (int s = lane; s < S; s += GG_WAVE) {
+        const double x = (double)spheres[3 * s], y = (double)spheres[3 * s + 1], z = (double)spheres[3 * s + 2];
+        const int f = min(max(frame[s], 0), J + 1);              // the caller keeps it in 0..J+1; no read leaves LDS
+        const double *T = s_frames + f * 12;
+        int cell[3];
+        bool in = true;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const double c = ((T[3 * a] * x + T[3 * a + 1] * y) + T[3 * a + 2] * z) + T[9 + a];
+            const bool fin = isfinite(c);                        // a centre that is not finite is outside
+            cell[a] = fin ? field_cell(c - g.lo[a], g.h) : -1;
+            in = in && cell[a] >= 0 && cell[a] < dim[a];
+        }
+        const int d = in ? dist2[((size_t)cell[0] * g.Y + cell[1]) * g.Z + cell[2]] : outside;
+        const int sl = d - need2[s];
+        if (sl < best || (sl == best && s < who)) best = sl, who = s;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const int ob = __shfl_xor(best, off, GG_WAVE), ow = __shfl_xor(who, off, GG_WAVE);
+        if (ob < best || (ob == best && ow < who)) best = ob, who = ow;
+    }
+    if (lane == 0) {
+        slack[m] = best;
+        worst[m] = who == INT32_MAX ? -1 : who;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// C ABI
+// ---------------------------------------------------------------------------------------------------------------
+static bool arm_rotation_ok(const double *T) {
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) {
+            const double d = (T[a] * T[b] + T[3 + a] * T[3 + b]) + T[6 + a] * T[6 + b];
+            if (!(fabs(d - (a == b ? 1.0 : 0.0)) <= 1e-9)) return false;
+        }
+    return true;
+}
+
+#define ARM_REFUSE(...)                   \
+    do {                                  \
+        gg_set_error(__VA_ARGS__);        \
+        return false;                     \
+    } while (0)
+
+// The host array `arm` as the kernels' argument; false (and the error set) for an arm the header refuses.
+static bool arm_chain(const char *who, int num_joints, const double *arm, ArmChain *c) {
+    if (num_joints < 1 || num_joints > GG_ARM_MAX_JOINTS)
+        ARM_REFUSE("%s: num_joints must be in 1..GG_ARM_MAX_JOINTS", who);
+    if (!arm) ARM_REFUSE("%s: null pointer: arm (a host array of GG_ARM_DOUBLES(num_joints) doubles)", who);
+    const int J = num_joints;
+    for (int i = 0; i < GG_ARM_DOUBLES(J); ++i)
+        if (!isfinite(arm[i])) ARM_REFUSE("%s: arm: entry %d is not finite", who, i);
+    *c = ArmChain{};
+    c->J = J;
+    for (int i = 0; i < 12; ++i) c->base[i] = arm[i];
+    if (!arm_rotation_ok(c->base)) ARM_REFUSE("%s: arm: base: |R^T R - I|max > 1e-9", who);
+    for (int j = 0; j <= J; ++j) {
+        double *A = j < J ? c->fixed[j] : c->tip;
+        for (int i = 0; i < 12; ++i) A[i] = arm[12 + 12 * j + i];
+        if (!arm_rotation_ok(A)) ARM_REFUSE("%s: arm: fixed[%d]: |R^T R - I|max > 1e-9", who, j);
+    }
+    const double *joints = arm + 12 * (J + 2);
+    for (int j = 0; j < J; ++j) {
+        const double *r = joints + 6 * j;
+        const double n2 = (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2];
+        if (!(fabs(n2 - 1.0) <= 1e-9)) ARM_REFUSE("%s: arm: axis[%d]: the squared length is off 1 by more than 1e-9", who, j);
+        if (r[3] > r[4]) ARM_REFUSE("%s: arm: joint %d: lo > hi", who, j);
+        if (r[5] != 0.0 && r[5] != 1.0) ARM_REFUSE("%s: arm: kind[%d] must be 0 (revolute) or 1 (prismatic)", who, j);
+        for (int k = 0; k < 3; ++k) c->axis[j][k] = r[k];
+        c->lo[j] = r[3];
+        c->hi[j] = r[4];
+        c->rev[j] = r[5] == 0.0 ? 1.0 : 0.0;
+        c->pri[j] = r[5] == 0.0 ? 0.0 : 1.0;
+    }
+    return true;
+}
+
+// The kernels are templates on the joint count: every `j < J` is decided when they are compiled.
+template <typename F>
+static void arm_dispatch(int J, F &&launch) {
+    switch (J) {
+        case 1: launch(std::integral_constant<int, 1>{}); break;
+        case 2: launch(std::integral_constant<int, 2>{}); break;
+        case 3: launch(std::integral_constant<int, 3>{}); break;
+        case 4: launch(std::integral_constant<int, 4>{}); break;
+        case 5: launch(std::integral_constant<int, 5>{}); break;
+        case 6: launch(std::integral_constant<int, 6>{}); break;
+        case 7: launch(std::integral_constant<int, 7>{}); break;
+        default: launch(std::integral_constant<int, 8>{}); break;
+    }
+}
+
+extern "C" int gg_arm_fk(int num_joints, const double *arm, int num_rows, const double *q, double *frames,
+                         gg_stream_t stream) {
+    ArmChain c;
+    if (!arm_chain(__func__, num_joints, arm, &c)) return GG_ERR_INVALID_ARG;
+    GG_REQUIRE(num_rows >= 0 && num_rows <= GG_FIELD_MAX_POSES, "need 0 <= num_rows <= GG_FIELD_MAX_POSES");
+    if (num_rows == 0) return GG_OK;
+    GG_REQUIRE(q && frames, "null pointer: q / frames");
+    GG_REQUIRE((((uintptr_t)q | (uintptr_t)frames) & 7) == 0, "q / frames misaligned");
+    arm_dispatch(num_joints, [&](auto joints) {
+        hipLaunchKernelGGL((arm_fk_kernel<decltype(joints)::value>),
+                           dim3((unsigned)((num_rows + ARM_THREADS - 1) / ARM_THREADS)), dim3(ARM_THREADS), 0,
+                           (hipStream_t)stream, c, num_rows, q, frames);
+    });
+    GG_CHECK_LAUNCH();
+    return GG_OK;
+}
+
+extern "C" int gg_arm_follow(int num_joints, const double *arm, int num_paths, int num_waypoints, const float *poses,
+                             int num_seeds, const double *seeds, double tol_p, double tol_r, double rot_length,
+                             double gain, double lambda_min, double max_step, int max_iter, double *q_out,
+                             int32_t *iters, double *resid, int32_t *first_fail, gg_stream_t stream) {
+    ArmChain c;
+    if (!arm_chain(__func__, num_joints, arm, &c)) return GG_ERR_INVALID_ARG;
+    GG_REQUIRE(num_paths >= 0 && num_waypoints >= 0 && num_seeds >= 0, "num_paths / num_waypoints / num_seeds < 0");
+    GG_REQUIRE((int64_t)num_paths * num_seeds <= GG_FIELD_MAX_POSES &&
+                   (int64_t)num_paths * num_seeds * (int64_t)(num_waypoints > 0 ? num_waypoints : 1) <= GG_FIELD_MAX_POSES,
+               "num_paths num_seeds num_waypoints > GG_FIELD_MAX_POSES");
+    GG_REQUIRE(isfinite(tol_p) && tol_p >= 0.0, "tol_p must be finite and >= 0");
+    GG_REQUIRE(isfinite(tol_r) && tol_r >= 0.0, "tol_r must be finite and >= 0");
+    GG_REQUIRE(isfinite(rot_length) && rot_length > 0.0, "rot_length must be finite and > 0");
+    GG_REQUIRE(isfinite(gain) && gain >= 0.0, "gain must be finite and >= 0");
+    GG_REQUIRE(isfinite(lambda_min) && lambda_min > 0.0, "lambda_min must be finite and > 0");
+    GG_REQUIRE(isfinite(max_step) && max_step > 0.0, "max_step must be finite and > 0");
+    GG_REQUIRE(max_iter >= 0 && max_iter <= GG_ARM_MAX_ITER, "max_iter must be in 0..GG_ARM_MAX_ITER");
+    if (num_paths == 0 || num_seeds == 0) return GG_OK;
+    GG_REQUIRE(seeds && first_fail, "null pointer: seeds / first_fail");
+    GG_REQUIRE(num_waypoints == 0 || (poses && q_out && iters && resid), "null pointer: poses / q_out / iters / resid");
+    GG_REQUIRE((((uintptr_t)seeds | (uintptr_t)q_out | (uintptr_t)resid) & 7) == 0 &&
+                   (((uintptr_t)poses | (uintptr_t)iters | (uintptr_t)first_fail) & 3) == 0,
+               "poses / seeds / q_out / iters / resid / first_fail misaligned");
+    const ArmLaw law{tol_p, tol_r, rot_length, gain, lambda_min, max_step, max_iter};
+    const int total = num_paths * num_seeds;
+    arm_dispatch(num_joints, [&](auto joints) {
+        hipLaunchKernelGGL((arm_follow_kernel<decltype(joints)::value>),
+                           dim3((unsigned)((total + ARM_THREADS - 1) / ARM_THREADS)), dim3(ARM_THREADS), 0,
+                           (hipStream_t)stream, c, law, num_paths, num_waypoints, num_seeds, poses, seeds, q_out, iters,
+                           resid, first_fail);
+    });
+    GG_CHECK_LAUNCH();
+    return GG_OK;
+}
+
+extern "C" int gg_arm_clear(int num_joints, const double *arm, const int32_t *dims, const double *grid,
+                            const int32_t *dist2, int num_rows, const double *q, int num_spheres, const float *spheres,
+                            const int32_t *frame, const int32_t *need2, int32_t outside, int32_t *slack,
+                            int32_t *worst, gg_stream_t stream) {
+    ArmChain c;
+    if (!arm_chain(__func__, num_joints, arm, &c)) return GG_ERR_INVALID_ARG;
+    GG_REQUIRE(dims, "null pointer: dims (a host array of 3 ints)");
+    int64_t cells = 1;
+    for (int a = 0; a < 3; ++a) {
+        GG_REQUIRE(dims[a] >= 1 && dims[a] <= GG_FIELD_MAX_DIM, "need 1 <= dims[a] <= GG_FIELD_MAX_DIM");
+        cells *= dims[a];
+    }
+    GG_REQUIRE(cells <= GG_FIELD_MAX_CELLS, "dims[0] dims[1] dims[2] > GG_FIELD_MAX_CELLS");
+    GG_REQUIRE(grid, "null pointer: grid (a host array of 4 doubles)");
+    GG_REQUIRE(isfinite(grid[0]) && isfinite(grid[1]) && isfinite(grid[2]) && isfinite(grid[3]) && grid[3] > 0.0,
+               "grid: the corner must be finite and the cell edge h finite and > 0");
+    GG_REQUIRE(num_rows >= 0 && num_rows <= GG_FIELD_MAX_POSES, "need 0 <= num_rows <= GG_FIELD_MAX_POSES");
+    GG_REQUIRE(num_spheres >= 0 && num_spheres <= GG_FIELD_MAX_SPHERES,
+               "num_spheres must be in 0..GG_FIELD_MAX_SPHERES");
+    GG_REQUIRE(outside >= 0 && outside <= GG_FIELD_FAR, "outside must be in 0..GG_FIELD_FAR");
+    if (num_rows == 0) return GG_OK;
+    GG_REQUIRE(dist2 && q && slack && worst, "null pointer: dist2 / q / slack / worst");
+    GG_REQUIRE(num_spheres == 0 || (spheres && frame && need2), "null pointer: spheres / frame / need2");
+    GG_REQUIRE(((uintptr_t)q & 7) == 0 && (((uintptr_t)dist2 | (uintptr_t)spheres | (uintptr_t)frame |
+                                            (uintptr_t)need2 | (uintptr_t)slack | (uintptr_t)worst) & 3) == 0,
+               "dist2 / q / spheres / frame / need2 / slack / worst misaligned");
+    const ArmGrid g{dims[0], dims[1], dims[2], {grid[0], grid[1], grid[2]}, grid[3]};
+    arm_dispatch(num_joints, [&](auto joints) {
+        hipLaunchKernelGGL((arm_clear_kernel<decltype(joints)::value>), dim3((unsigned)num_rows), dim3(GG_WAVE), 0,
+                           (hipStream_t)stream, c, g, dist2, num_rows, q, num_spheres, spheres, frame, need2, outside,
+                           slack, worst);
+    });
+    GG_CHECK_LAUNCH();
+    return GG_OK;
+}

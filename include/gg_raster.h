@@ -1338,6 +1338,66 @@ int gg_height_map(int num_points, const float *points, const float *weights, dou
 int gg_place_search(const int32_t *dims, const int32_t *top, int num_yaws, const int32_t *foot, const int32_t *under,
                     int32_t tol, int32_t *rest, int32_t *contact, int32_t *support, gg_stream_t stream);
 
+/* ---- arm reachability: kinematics of a serial chain against the distance field (PARITY "Arm
+ * reachability") -------------------------------------------------------------------------------------------------
+ * The arm: J = num_joints in 1..GG_ARM_MAX_JOINTS and `arm`, a HOST array of GG_ARM_DOUBLES(J) doubles:
+ *   base[12]          world from arm base: R row-major (9), then t (3), the pose layout of gg_field_paths
+ *   fixed[J + 1][12]  A_j, j < J: link j to joint j at q_j = 0; A_J: the last link to the GRIPPER frame, the frame of
+ *                     the grasp rows (the columns of R are approach, closing and height)
+ *   joint[J][6]       axis[3] (a unit vector in the joint frame), lo, hi, kind (0.0 revolute, 1.0 prismatic)
+ * Frames: F_0 = base, F_{j+1} = (F_j A_j) M_j(q_j), F_{J+1} = F_J A_J the gripper pose.  M_j is Rodrigues' rotation
+ * (I c + (1 - c) a a^T) + s [a]x with c = cos q, s = sin q, or the translation by q a for a prismatic joint.  All
+ * fp64; a product X Y has R[r][c] = (X[r][0] Y[0][c] + X[r][1] Y[1][c]) + X[r][2] Y[2][c] and t[r] = ((X[r][0] t_0 +
+ * X[r][1] t_1) + X[r][2] t_2) + tX[r], no contraction.  An arm is refused (GG_ERR_INVALID_ARG naming what is wrong,
+ * before any launch) for an entry that is not finite, a rotation block of base or fixed with |R^T R - I|max > 1e-9,
+ * an axis whose squared length is off 1 by more than 1e-9, lo > hi, or a kind that is neither 0 nor 1.
+ *
+ * gg_arm_fk: q fp64 [M][J] -> frames fp64 [M][J + 2][12], F_0 .. F_{J+1}.  A row with a q that is not finite gives
+ * NaN in all of its frames.  Limits are not applied.  M <= GG_FIELD_MAX_POSES; M == 0 writes nothing.  Arrays 8-byte
+ * aligned.
+ *
+ * gg_arm_follow: inverse kinematics along pose paths.  poses fp32 [P][W][12] gripper poses (what gg_field_paths
+ * takes), seeds fp64 [P][S][J]; q_out fp64 [P][S][W][J], iters int32 [P][S][W], resid fp64 [P][S][W][2], first_fail
+ * int32 [P][S].  Every (path, seed) is independent: waypoint 0 starts from the seed clamped into the limits, waypoint
+ * w > 0 from the solution of w - 1.  Per waypoint, for it = 0, 1, ..., all in fp64:
+ *   1. FK.  e_p = p* - p; R_e = R* R^T; e_r = the rotation vector of R_e through its quaternion (Shepperd's branches:
+ *      the largest of trace, R00, R11, R22 is the pivot; normalised; w >= 0): 2 atan2(|v|, w) v / |v|, and 2 v when
+ *      |v| < 1e-12.
+ *   2. CONVERGED iff |e_p| <= tol_p and |e_r| <= tol_r: q_out = q, iters = it, resid = (|e_p|, |e_r|).
+ *   3. Otherwise, it == max_iter FAILS the waypoint.
+ *   4. Otherwise the geometric Jacobian: column j is [z_j x (p - o_j); L z_j] for a revolute and [z_j; 0] for a
+ *      prismatic joint, z_j and o_j the joint's axis and origin in the world (of F_j A_j); e = [e_p; L e_r];
+ *      lambda2 = gain (e . e) + lambda_min^2; dq = J^T (J J^T + lambda2 I)^-1 e by a 6 x 6 Cholesky solve; when
+ *      max|dq| > max_step, dq is scaled by max_step / max|dq|; q <- min(max(q + dq, lo), hi).  A pivot that is not
+ *      positive, or an error norm or a dq that is not finite, FAILS the waypoint.
+ * A pose or a seed with an entry that is not finite fails its waypoint (the seed: waypoint 0) at once.  first_fail =
+ * the failed waypoint, or W.  From the failed waypoint on: q_out NaN, iters -1, resid NaN.  No thread waits for
+ * another, no atomics, max_iter in 0..GG_ARM_MAX_ITER bounds every loop, and the same inputs give the same bytes.
+ * tol_p, tol_r, gain finite and >= 0; L (rot_length), lambda_min, max_step finite and > 0.  P S max(W, 1) <=
+ * GG_FIELD_MAX_POSES; P == 0 or S == 0 writes nothing.  fp64 arrays 8-byte aligned, the others 4-byte.
+ *
+ * gg_arm_clear: the whole arm against the distance field.  dims, grid, dist2, need2, outside: as gg_field_paths takes
+ * them.  q fp64 [M][J]; spheres fp32 [S][3] centres, each in the frame F_f with f = frame[s] (int32 [S], THE CALLER'S
+ * DUTY: in 0..J + 1; the kernel clamps it into that range, so no read goes astray); J + 1 is the gripper frame, so the
+ * sphere sets of gg_field_paths go in unchanged.  Per sphere c_k = ((R[k][0] x + R[k][1] y) + R[k][2] z) + t_k with
+ * R, t of F_f, its cell by the distance field's rule (a centre that is not finite is outside), d = dist2[cell] or
+ * `outside`.  slack int32 [M] = min_s (d - need2[s]): GG_FIELD_FAR when S == 0, INT32_MIN for a row with a q that is
+ * not finite.  worst int32 [M] = the lowest s that attains the minimum, -1 when S == 0 or the row is not finite.  No
+ * atomics.  S <= GG_FIELD_MAX_SPHERES, M <= GG_FIELD_MAX_POSES; M == 0 writes nothing.  q 8-byte aligned, the other
+ * arrays 4-byte.
+ * Null, misaligned or out-of-range arguments: GG_ERR_INVALID_ARG naming the argument, before any launch. */
+#define GG_ARM_MAX_JOINTS 8
+#define GG_ARM_MAX_ITER 1024
+#define GG_ARM_DOUBLES(J) (12 * ((J) + 2) + 6 * (J))
+int gg_arm_fk(int num_joints, const double *arm, int num_rows, const double *q, double *frames, gg_stream_t stream);
+int gg_arm_follow(int num_joints, const double *arm, int num_paths, int num_waypoints, const float *poses,
+                  int num_seeds, const double *seeds, double tol_p, double tol_r, double rot_length, double gain,
+                  double lambda_min, double max_step, int max_iter, double *q_out, int32_t *iters, double *resid,
+                  int32_t *first_fail, gg_stream_t stream);
+int gg_arm_clear(int num_joints, const double *arm, const int32_t *dims, const double *grid, const int32_t *dist2,
+                 int num_rows, const double *q, int num_spheres, const float *spheres, const int32_t *frame,
+                 const int32_t *need2, int32_t outside, int32_t *slack, int32_t *worst, gg_stream_t stream);
+
 /* ---- in-library kernel timing (measurement only; off by default) --------------------------------
  * When enabled, every launch of the kernels below is bracketed by a hipEvent pair recorded on the
  * launch stream, so bench.py can report the average duration of exactly that kernel over its
