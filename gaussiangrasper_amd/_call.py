@@ -44,6 +44,11 @@ def to_device(x: ArrayLike, dtype: torch.dtype, dev: torch.device) -> Tensor:
     return t.to(device=dev, dtype=dtype).contiguous()
 
 
+def host_array(x: ArrayLike, dtype=None) -> np.ndarray:
+    """A tensor (detached, brought to the host), array or sequence as a numpy array of `dtype` (None: as it is)."""
+    return np.asarray(x.detach().cpu().numpy() if isinstance(x, Tensor) else x, dtype)
+
+
 def f32(t: Tensor) -> Tensor:
     return t.contiguous() if t.dtype == torch.float32 else t.float().contiguous()
 
@@ -106,3 +111,13 @@ def positive(name: str, v: float) -> float:
     if not (math.isfinite(v) and v > 0.0):
         raise ValueError(f"{name} must be finite and > 0, got {v}")
     return v
+
+
+def check_finite_options(ap, a, positive=(), nonneg=()) -> None:
+    """ap.error unless the parsed options named in `positive` are finite and > 0, those in `nonneg` finite and >= 0."""
+    for n in positive:
+        if not (math.isfinite(getattr(a, n)) and getattr(a, n) > 0.0):
+            ap.error(f"--{n} must be finite and > 0, got {getattr(a, n)}")
+    for n in nonneg:
+        if not (math.isfinite(getattr(a, n)) and getattr(a, n) >= 0.0):
+            ap.error(f"--{n} must be finite and >= 0, got {getattr(a, n)}")

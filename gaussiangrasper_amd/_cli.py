@@ -25,6 +25,18 @@ def load_scene(ckpt: str):
     return scene.to("cuda"), mlp_state
 
 
+def add_gripper_sphere_options(ap, prefix: str = "") -> None:
+    """--gripper, --width, --depth, --height, --radius, --margin: a gripper model covered by spheres
+    (field.gripper_spheres).  `prefix` starts every help string; without one --gripper is required."""
+    ap.add_argument("--gripper", default=None, required=not prefix, metavar="{default,FILE.json}",
+                    help=prefix + "the gripper model")
+    ap.add_argument("--width", type=float, default=0.08, help=prefix + "the gripper's opening, scene units")
+    ap.add_argument("--depth", type=float, default=0.02, help=prefix + "the fingers' depth")
+    ap.add_argument("--height", type=float, default=0.02, help=prefix + "the fingers' height")
+    ap.add_argument("--radius", type=float, default=0.005, help=prefix + "radius of the covering spheres")
+    ap.add_argument("--margin", type=float, default=0.0, help=prefix + "clearance kept beyond the spheres")
+
+
 def add_grasp_options(ap) -> None:
     """What the grasp and grasp_propose command lines share: --mu, --min-opacity, --max-collision (grasp.contacts);
     --gripper, --approach, --max-body-collision, --max-sweep-collision (grasp.clearance); --nms-translation,

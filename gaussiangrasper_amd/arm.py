@@ -30,14 +30,14 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._call import (ArrayLike, default_device, grid_args, host_ptr, nonneg, positive, ptr as _ptr,
-                    require_hip as _require_hip, stream as _stream, to_device)
+from ._call import (ArrayLike, check_finite_options, default_device, host_array, host_ptr, nonneg, positive,
+                    ptr as _ptr, require_hip as _require_hip, stream as _stream, to_device)
+# GG_FIELD_FAR, GG_FIELD_MAX_SPHERES, GG_FIELD_MAX_POSES, and the argument checks of the calls on the volume
+from .field import (FAR, MAX_POSES, MAX_SPHERES, DistanceField, approach_paths, cell_count, gripper_spheres, need2,
+                    pose_paths, sphere_table, volume_args, volume_tensor)
 
 MAX_JOINTS = 8                 # GG_ARM_MAX_JOINTS
 MAX_ITER = 1024                # GG_ARM_MAX_ITER
-FAR = 1 << 30                  # GG_FIELD_FAR
-MAX_SPHERES = 1024             # GG_FIELD_MAX_SPHERES
-MAX_POSES = 1 << 26            # GG_FIELD_MAX_POSES
 ORTHO_TOL = 1e-9
 # This project's choices (PARITY.md "Arm reachability"); none has been measured on a robot
 IK_DEFAULTS = dict(tol_p=1e-4, tol_r=1e-3, L=0.1, k=1.0, lambda_min=1e-4, max_step=0.2, max_iter=100)
@@ -291,8 +291,7 @@ def follow(arm: Arm, poses: Tensor, seeds: Tensor, tol_p: float = IK_DEFAULTS["t
     (no CPU path).  Every (path, seed) follows its path on its own, each waypoint from the solution of the one before."""
     dev = _require_hip(poses, seeds)
     J, a = _arm_args(arm)
-    if poses.dtype != torch.float32 or poses.ndim != 3 or poses.shape[2] != 12:
-        raise ValueError(f"poses must be a float32 (P, W, 12) tensor, got {poses.dtype} {tuple(poses.shape)}")
+    poses = pose_paths(poses)
     p, w = poses.shape[:2]
     if seeds.dtype != torch.float64 or seeds.ndim != 3 or seeds.shape[0] != p or seeds.shape[2] != J:
         raise ValueError(f"seeds must be a float64 ({p}, S, {J}) tensor, got {seeds.dtype} {tuple(seeds.shape)}")
@@ -301,7 +300,7 @@ def follow(arm: Arm, poses: Tensor, seeds: Tensor, tol_p: float = IK_DEFAULTS["t
         raise ValueError(f"{p} paths x {s} seeds x {w} waypoints are more than {MAX_POSES}")
     if not 0 <= int(max_iter) <= MAX_ITER:
         raise ValueError(f"max_iter must be in 0..{MAX_ITER}, got {max_iter}")
-    poses, seeds = poses.contiguous(), seeds.contiguous()
+    seeds = seeds.contiguous()
     q = torch.empty(p, s, w, J, dtype=torch.float64, device=dev)
     iters = torch.empty(p, s, w, dtype=torch.int32, device=dev)
     resid = torch.empty(p, s, w, 2, dtype=torch.float64, device=dev)
@@ -321,27 +320,18 @@ def clear(arm: Arm, dist2: Tensor, grid, dims, q: Tensor, spheres: Tensor, frame
     HIP device (no CPU path)."""
     dev = _require_hip(dist2, q, spheres, frame, need)
     J, a = _arm_args(arm)
-    g, d = grid_args((np.asarray(grid, np.float64).reshape(-1), np.asarray(dims, np.int64).reshape(-1)))
-    shape = tuple(int(v) for v in np.asarray(dims).reshape(-1))
-    if dist2.dtype != torch.int32 or tuple(dist2.shape) != shape or not dist2.is_contiguous():
-        raise ValueError(f"dist2 must be a contiguous int32 {shape} tensor, got {dist2.dtype} {tuple(dist2.shape)}")
+    d, g, shape = volume_args(dims, grid)
+    volume_tensor(dist2, "dist2", torch.int32, shape)
     q = _q_rows(q, J)
-    if spheres.dtype != torch.float32 or spheres.ndim != 2 or spheres.shape[1] != 3:
-        raise ValueError(f"spheres must be a float32 (S, 3) tensor, got {spheres.dtype} {tuple(spheres.shape)}")
-    s, m = spheres.shape[0], q.shape[0]
-    for name, t in (("frame", frame), ("need", need)):
-        if t.dtype != torch.int32 or tuple(t.shape) != (s,):
-            raise ValueError(f"{name} must be an int32 ({s},) tensor, got {t.dtype} {tuple(t.shape)}")
-    if m > MAX_POSES or s > MAX_SPHERES:
-        raise ValueError(f"{m} rows and {s} spheres: at most {MAX_POSES} rows and {MAX_SPHERES} spheres")
-    if not 0 <= int(outside) <= FAR:
-        raise ValueError(f"outside must be in 0..{FAR}, got {outside}")
-    spheres, frame, need = spheres.contiguous(), frame.contiguous(), need.contiguous()
+    spheres, frame, need = sphere_table(spheres, frame=frame, need=need)
+    m = q.shape[0]
+    if m > MAX_POSES:
+        raise ValueError(f"{m} rows are more than {MAX_POSES}")
     slack = torch.empty(m, dtype=torch.int32, device=dev)
     worst = torch.empty(m, dtype=torch.int32, device=dev)
-    _lib.check(_lib.load().gg_arm_clear(J, host_ptr(a), d, g, _ptr(dist2), m, _ptr(q), s, _ptr(spheres), _ptr(frame),
-                                        _ptr(need), int(outside), _ptr(slack), _ptr(worst), _stream(dev)),
-               "gg_arm_clear")
+    _lib.check(_lib.load().gg_arm_clear(J, host_ptr(a), d, g, _ptr(dist2), m, _ptr(q), spheres.shape[0], _ptr(spheres),
+                                        _ptr(frame), _ptr(need), cell_count("outside", outside), _ptr(slack),
+                                        _ptr(worst), _stream(dev)), "gg_arm_clear")
     return slack, worst
 
 
@@ -382,10 +372,9 @@ def select(first_fail: ArrayLike, num_waypoints: int, clear_ok: ArrayLike, jump:
 
 def _sphere_set(arm: Arm, spheres, radius, margin: float, h: float):
     """centres, frames and need2 of the arm's link spheres followed by the gripper-frame `spheres` of `radius`"""
-    from .field import need2
     c, f, r = arm.link_spheres()
     if spheres is not None:
-        sp = np.asarray(spheres.detach().cpu() if isinstance(spheres, Tensor) else spheres, np.float32).reshape(-1, 3)
+        sp = host_array(spheres, np.float32).reshape(-1, 3)
         c = np.concatenate([c, sp])
         f = np.concatenate([f, np.full(len(sp), arm.num_joints + 1, np.int32)])
         r = np.concatenate([r, np.broadcast_to(np.asarray(radius, np.float64), (len(sp),))])
@@ -459,8 +448,7 @@ def reach_grasps(arm: Arm, rows: ArrayLike, standoff: float, steps: int, field=N
     `gripper` model (grasp.default_gripper, ...) its spheres of `radius` ride on the gripper frame at each row's
     width, depth and height; leave it None when the field holds the object to be grasped, which the fingers touch at
     the last waypoint (field.py's note on the grasp pose)."""
-    from .field import approach_paths, gripper_spheres
-    g = np.asarray(rows.detach().cpu() if isinstance(rows, Tensor) else rows, np.float64)
+    g = host_array(rows, np.float64)
     poses = approach_paths(g, standoff, steps)
     dev = default_device("arm") if field is None else field.dist2.device
     if gripper is None or field is None:
@@ -478,7 +466,6 @@ def reach_grasps(arm: Arm, rows: ArrayLike, standoff: float, steps: int, field=N
 # command line
 # ------------------------------------------------------------------------------------------------
 def main(argv: Optional[Sequence[str]] = None) -> int:
-    from .field import DistanceField
     from .grasp import load_grasps
     ap = argparse.ArgumentParser(prog="python -m gaussiangrasper_amd.arm",
                                  description="Which gripper poses an arm reaches, in which joint configurations, and "
@@ -508,10 +495,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         ap.error("--standoff and --steps go with --grasps")
     if a.spheres and not a.field:
         ap.error("--spheres needs --field")
-    if not (math.isfinite(a.radius) and a.radius > 0.0):
-        ap.error(f"--radius must be finite and > 0, got {a.radius}")
-    if not (math.isfinite(a.margin) and a.margin >= 0.0):
-        ap.error(f"--margin must be finite and >= 0, got {a.margin}")
+    check_finite_options(ap, a, positive=("radius",), nonneg=("margin",))
     if a.seeds < 1:
         ap.error(f"--seeds must be >= 1, got {a.seeds}")
     if not 0 <= a.max_iter <= MAX_ITER:
@@ -525,8 +509,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         field = DistanceField.load(a.field) if a.field else None
         kw = dict(field=field, radius=a.radius, margin=a.margin, num_seeds=a.seeds, seed=a.seed, max_iter=a.max_iter)
         if a.grasps:
-            from .field import approach_paths
-            poses = approach_paths(load_grasps(a.grasps), a.standoff, a.steps)
+            poses =approach_paths(load_grasps(a.grasps), a.standoff, a.steps)
         else:
             poses = np.asarray(np.load(a.poses), np.float32)
             if poses.ndim != 3 or poses.shape[2] != 12:

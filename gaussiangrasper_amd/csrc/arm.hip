@@ -22,8 +22,7 @@
 
 #include <type_traits>
 
-#include "field_cell.h"
-#include "gg_common.h"
+#include "field_volume.h"
 
 #define ARM_THREADS 64
 #define ARM_FRAMES (GG_ARM_MAX_JOINTS + 2)
@@ -36,11 +35,6 @@ struct ArmChain {
     double tip[12];                              // A_J: the last link to the gripper frame
     double axis[GG_ARM_MAX_JOINTS][3];
     double lo[GG_ARM_MAX_JOINTS], hi[GG_ARM_MAX_JOINTS];
-};
-
-struct ArmGrid {
-    int X, Y, Z;
-    double lo[3], h;
 };
 
 struct ArmLaw {
@@ -389,7 +383,7 @@ __global__ __launch_bounds__(ARM_THREADS) void arm_follow_kernel(ArmChain arm, A
 // clear
 // ---------------------------------------------------------------------------------------------------------------
 template <int J>
-__global__ __launch_bounds__(GG_WAVE) void arm_clear_kernel(ArmChain arm, ArmGrid g, const int *__restrict__ dist2,
+__global__ __launch_bounds__(GG_WAVE) void arm_clear_kernel(ArmChain arm, FieldGrid g, const int *__restrict__ dist2,
                                                             int M, const double *__restrict__ q_in, int S,
                                                             const float *__restrict__ spheres,
                                                             const int *__restrict__ frame,
@@ -432,22 +426,11 @@ __global__ __launch_bounds__(GG_WAVE) void arm_clear_kernel(ArmChain arm, ArmGri
             for (int i = 0; i < 12; ++i) s_frames[(J + 1) * 12 + i] = T[i];
     }
     __syncthreads();                                             // a one-wave workgroup: the LDS writes are done
-    const int dim[3] = {g.X, g.Y, g.Z};
     int best = GG_FIELD_FAR, who = INT32_MAX;
     for (int s = lane; s < S; s += GG_WAVE) {
-        const double x = (double)spheres[3 * s], y = (double)spheres[3 * s + 1], z = (double)spheres[3 * s + 2];
         const int f = min(max(frame[s], 0), J + 1);              // the caller keeps it in 0..J+1; no read leaves LDS
-        const double *T = s_frames + f * 12;
-        int cell[3];
-        bool in = true;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const double c = ((T[3 * a] * x + T[3 * a + 1] * y) + T[3 * a + 2] * z) + T[9 + a];
-            const bool fin = isfinite(c);                        // a centre that is not finite is outside
-            cell[a] = fin ? field_cell(c - g.lo[a], g.h) : -1;
-            in = in && cell[a] >= 0 && cell[a] < dim[a];
-        }
-        const int d = in ? dist2[((size_t)cell[0] * g.Y + cell[1]) * g.Z + cell[2]] : outside;
+        const int d = field_probe(g, dist2, s_frames + f * 12, (double)spheres[3 * s], (double)spheres[3 * s + 1],
+                                  (double)spheres[3 * s + 2], outside);
         const int sl = d - need2[s];
         if (sl < best || (sl == best && s < who)) best = sl, who = s;
     }
@@ -586,16 +569,10 @@ extern "C" int gg_arm_clear(int num_joints, const double *arm, const int32_t *di
                             int32_t *worst, gg_stream_t stream) {
     ArmChain c;
     if (!arm_chain(__func__, num_joints, arm, &c)) return GG_ERR_INVALID_ARG;
-    GG_REQUIRE(dims, "null pointer: dims (a host array of 3 ints)");
-    int64_t cells = 1;
-    for (int a = 0; a < 3; ++a) {
-        GG_REQUIRE(dims[a] >= 1 && dims[a] <= GG_FIELD_MAX_DIM, "need 1 <= dims[a] <= GG_FIELD_MAX_DIM");
-        cells *= dims[a];
-    }
-    GG_REQUIRE(cells <= GG_FIELD_MAX_CELLS, "dims[0] dims[1] dims[2] > GG_FIELD_MAX_CELLS");
+    GG_REQUIRE(field_dims_ok(dims), FIELD_DIMS_MSG);
     GG_REQUIRE(grid, "null pointer: grid (a host array of 4 doubles)");
-    GG_REQUIRE(isfinite(grid[0]) && isfinite(grid[1]) && isfinite(grid[2]) && isfinite(grid[3]) && grid[3] > 0.0,
-               "grid: the corner must be finite and the cell edge h finite and > 0");
+    FieldGrid g;
+    GG_REQUIRE(field_grid(dims, grid, &g), FIELD_GRID_MSG);
     GG_REQUIRE(num_rows >= 0 && num_rows <= GG_FIELD_MAX_POSES, "need 0 <= num_rows <= GG_FIELD_MAX_POSES");
     GG_REQUIRE(num_spheres >= 0 && num_spheres <= GG_FIELD_MAX_SPHERES,
                "num_spheres must be in 0..GG_FIELD_MAX_SPHERES");
@@ -606,7 +583,6 @@ extern "C" int gg_arm_clear(int num_joints, const double *arm, const int32_t *di
     GG_REQUIRE(((uintptr_t)q & 7) == 0 && (((uintptr_t)dist2 | (uintptr_t)spheres | (uintptr_t)frame |
                                             (uintptr_t)need2 | (uintptr_t)slack | (uintptr_t)worst) & 3) == 0,
                "dist2 / q / spheres / frame / need2 / slack / worst misaligned");
-    const ArmGrid g{dims[0], dims[1], dims[2], {grid[0], grid[1], grid[2]}, grid[3]};
     arm_dispatch(num_joints, [&](auto joints) {
         hipLaunchKernelGGL((arm_clear_kernel<decltype(joints)::value>), dim3((unsigned)num_rows), dim3(GG_WAVE), 0,
                            (hipStream_t)stream, c, g, dist2, num_rows, q, num_spheres, spheres, frame, need2, outside,

@@ -26,8 +26,7 @@
 //                     of the four in LDS, is the farthest clear candidate.
 #include <math.h>
 
-#include "field_cell.h"
-#include "gg_common.h"
+#include "field_volume.h"
 
 #define FS_THREADS 256
 #define FS_THREAD_REACH 2          // rows that reach further are walked by their whole wave
@@ -39,11 +38,6 @@
 #define FR_THREADS 256             // two cells of a brick per thread; four paths (waves) per workgroup of the descent;
                                    // one path per workgroup of the shortcut
 #define FR_BATCH 16                // rounds enqueued between two read-backs of the counters
-
-struct FieldGrid {
-    int X, Y, Z;
-    double lo[3], h;
-};
 
 // ---------------------------------------------------------------------------------------------------------------
 // splat
@@ -118,7 +112,7 @@ __device__ __forceinline__ void fs_cell(const FieldGrid &g, const FsRow &r, int 
             ((u0 * u0) * (r.A[1] * r.A[2]) + (u1 * u1) * (r.A[0] * r.A[2])) + (u2 * u2) * (r.A[0] * r.A[1]);
         hit = lhs <= r.rhs;
     }
-    if (hit) atomicAdd(mass + ((size_t)x * g.Y + y) * g.Z + z, vote);
+    if (hit) atomicAdd(mass + g.at(x, y, z), vote);
 }
 
 // The row's box cut to the volume: lo[a] <= hi[a] on every axis, or false.  c is within +-2^30 and reach <= 64.
@@ -261,20 +255,9 @@ __global__ __launch_bounds__(FP_THREADS) void field_paths_kernel(FieldGrid g, co
         slack[i] = INT32_MIN;
         return;
     }
-    const int dim[3] = {g.X, g.Y, g.Z};
     int m = GG_FIELD_FAR;
     for (int s = 0; s < S; ++s) {
-        const double x = (double)s_c[3 * s], y = (double)s_c[3 * s + 1], z = (double)s_c[3 * s + 2];
-        int cell[3];
-        bool in = true;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const double c = ((T[3 * a] * x + T[3 * a + 1] * y) + T[3 * a + 2] * z) + T[9 + a];
-            const bool ok = isfinite(c);          // a centre that is not finite is outside
-            cell[a] = ok ? field_cell(c - g.lo[a], g.h) : -1;
-            in = in && cell[a] >= 0 && cell[a] < dim[a];
-        }
-        const int d = in ? dist2[((size_t)cell[0] * g.Y + cell[1]) * g.Z + cell[2]] : outside;
+        const int d = field_probe(g, dist2, T, (double)s_c[3 * s], (double)s_c[3 * s + 1], (double)s_c[3 * s + 2], outside);
         m = min(m, d - s_need[s]);
     }
     slack[i] = m;
@@ -333,21 +316,18 @@ __global__ __launch_bounds__(FR_THREADS) void route_zero_kernel(unsigned *p, int
 
 // A goal that is inside and free costs 0.  Its brick and the bricks around it start active: a goal in an outer
 // layer is read by them, and no round's write-back announces it.
-__global__ __launch_bounds__(FR_THREADS) void route_goals_kernel(int X, int Y, int Z, int bx, int by, int bz,
-                                                                 const int *__restrict__ dist2, int need, int G,
+__global__ __launch_bounds__(FR_THREADS) void route_goals_kernel(FieldFree v, int bx, int by, int bz, int G,
                                                                  const int *__restrict__ goals, int *cost,
                                                                  unsigned *flags,
                                                                  unsigned long long *__restrict__ ignored) {
     const int i = blockIdx.x * FR_THREADS + threadIdx.x;      // G <= GG_FIELD_MAX_GOALS
     if (i >= G) return;
     const int x = goals[(size_t)i * 3], y = goals[(size_t)i * 3 + 1], z = goals[(size_t)i * 3 + 2];
-    const bool in = x >= 0 && x < X && y >= 0 && y < Y && z >= 0 && z < Z;
-    const size_t at = in ? ((size_t)x * Y + y) * Z + z : 0;
-    if (!in || dist2[at] < need) {
+    if (!v.open(x, y, z)) {
         atomicAdd(ignored, 1ull);
         return;
     }
-    fr_store(cost + at, 0);
+    fr_store(cost + v.at(x, y, z), 0);
     const int ix = x / FR_BRICK, iy = y / FR_BRICK, iz = z / FR_BRICK;
     for (int a = max(ix - 1, 0); a <= min(ix + 1, bx - 1); ++a)
         for (int b = max(iy - 1, 0); b <= min(iy + 1, by - 1); ++b)
@@ -357,8 +337,7 @@ __global__ __launch_bounds__(FR_THREADS) void route_goals_kernel(int X, int Y, i
 // One round, one workgroup per brick.  `cur` holds this round's flags, `next` the next round's: a brick clears its
 // own flag in cur, other bricks only set flags in next, so cur is all zero when the round is over and serves as the
 // round after next's `next` without a fill.  *counter: the flags this round turned from 0 to 1.
-__global__ __launch_bounds__(FR_THREADS) void route_round_kernel(int X, int Y, int Z, int bx, int by, int bz,
-                                                                 const int *__restrict__ dist2, int need, int *cost,
+__global__ __launch_bounds__(FR_THREADS) void route_round_kernel(FieldFree v, int bx, int by, int bz, int *cost,
                                                                  unsigned *cur, unsigned *next, unsigned *counter) {
     __shared__ int s_cost[FR_HALO * FR_HALO * FR_HALO];
     __shared__ unsigned char s_free[FR_HALO * FR_HALO * FR_HALO];
@@ -376,11 +355,9 @@ __global__ __launch_bounds__(FR_THREADS) void route_round_kernel(int X, int Y, i
     const int x0 = ix * FR_BRICK, y0 = iy * FR_BRICK, z0 = iz * FR_BRICK;
     for (int i = tid; i < FR_HALO * FR_HALO * FR_HALO; i += FR_THREADS) {
         const int x = x0 + i / (FR_HALO * FR_HALO) - 1, y = y0 + (i / FR_HALO) % FR_HALO - 1, z = z0 + i % FR_HALO - 1;
-        const bool in = x >= 0 && x < X && y >= 0 && y < Y && z >= 0 && z < Z;
-        const size_t at = in ? ((size_t)x * Y + y) * Z + z : 0;
-        const bool open = in && dist2[at] >= need;
+        const bool open = v.open(x, y, z);
         s_free[i] = open ? 1 : 0;
-        s_cost[i] = open ? fr_load(cost + at) : GG_FIELD_FAR;
+        s_cost[i] = open ? fr_load(cost + v.at(x, y, z)) : GG_FIELD_FAR;
     }
     __syncthreads();
     // two cells per thread: their place in LDS, the cost they were loaded with, and the moves they may make
@@ -427,7 +404,7 @@ __global__ __launch_bounds__(FR_THREADS) void route_round_kernel(int X, int Y, i
         if (own[k] >= loaded[k]) continue;
         const int i = tid + k * FR_THREADS;
         const int lx = i >> 6, ly = (i >> 3) & 7, lz = i & 7;
-        fr_store(cost + ((size_t)(x0 + lx) * Y + (y0 + ly)) * Z + (z0 + lz), own[k]);
+        fr_store(cost + v.at(x0 + lx, y0 + ly, z0 + lz), own[k]);
 #pragma unroll
         for (int m = 0; m < 27; ++m) {
             const bool reads = (fr_dx(m) == 0 || lx == (fr_dx(m) < 0 ? 0 : FR_BRICK - 1)) &&
@@ -446,19 +423,15 @@ __global__ __launch_bounds__(FR_THREADS) void route_round_kernel(int X, int Y, i
 }
 
 // One wave per path.  The walk ends by construction: every step lowers the cost by at least 3.
-__global__ __launch_bounds__(FR_THREADS) void route_descend_kernel(int X, int Y, int Z, const int *__restrict__ dist2,
-                                                                   int need, const int *__restrict__ cost, int P,
+__global__ __launch_bounds__(FR_THREADS) void route_descend_kernel(FieldFree v, const int *__restrict__ cost, int P,
                                                                    const int *__restrict__ starts, int max_cells,
                                                                    int *__restrict__ cells, int *__restrict__ length) {
     const int lane = threadIdx.x & 63;
     const int p = blockIdx.x * (FR_THREADS / 64) + (threadIdx.x >> 6);      // P max_cells <= GG_FIELD_MAX_POSES
     if (p >= P) return;                                                     // the same for the whole wave
-    auto open = [&](int x, int y, int z) {
-        return x >= 0 && x < X && y >= 0 && y < Y && z >= 0 && z < Z && dist2[((size_t)x * Y + y) * Z + z] >= need;
-    };
     int c[3] = {starts[(size_t)p * 3], starts[(size_t)p * 3 + 1], starts[(size_t)p * 3 + 2]};
     int *row = cells + (size_t)p * max_cells * 3;
-    int here = open(c[0], c[1], c[2]) ? cost[((size_t)c[0] * Y + c[1]) * Z + c[2]] : GG_FIELD_FAR;
+    int here = v.open(c[0], c[1], c[2]) ? cost[v.at(c[0], c[1], c[2])] : GG_FIELD_FAR;
     int n = 0;
     if (here < GG_FIELD_FAR) {
         const int m = lane, dx = fr_dx(m), dy = fr_dy(m), dz = fr_dz(m), w = fr_weight(m);
@@ -472,8 +445,8 @@ __global__ __launch_bounds__(FR_THREADS) void route_descend_kernel(int X, int Y,
                 for (int a = 0; a <= (dx != 0); ++a)
                     for (int b = 0; b <= (dy != 0); ++b)
                         for (int e = 0; e <= (dz != 0); ++e)
-                            ok = ok && open(c[0] + a * dx, c[1] + b * dy, c[2] + e * dz);
-                take = ok && cost[((size_t)(c[0] + dx) * Y + (c[1] + dy)) * Z + (c[2] + dz)] + w == here;
+                            ok = ok && v.open(c[0] + a * dx, c[1] + b * dy, c[2] + e * dz);
+                take = ok && cost[v.at(c[0] + dx, c[1] + dy, c[2] + dz)] + w == here;
             }
             const uint64_t found = __ballot(take);
             if (found == 0ull) break;                      // `cost` is no fixed point of this dist2 and need
@@ -505,9 +478,8 @@ struct FrSight {
 // that touch that point and have not been counted.  At most n_x + n_y + n_z steps, every cell inside the box of a, b.
 // FIRST: return at the first cell that is not free (cover is then the cells counted so far).
 template <bool FIRST>
-__device__ __forceinline__ FrSight fr_walk(int Y, int Z, const int *__restrict__ dist2, int need, int ax, int ay,
-                                           int az, int bx, int by, int bz) {
-    auto shut = [&](int x, int y, int z) { return dist2[((size_t)x * Y + y) * Z + z] < need ? 1 : 0; };
+__device__ __forceinline__ FrSight fr_walk(const FieldFree &v, int ax, int ay, int az, int bx, int by, int bz) {
+    auto shut = [&](int x, int y, int z) { return v.dist2[v.at(x, y, z)] < v.need ? 1 : 0; };
     const int n0 = abs(bx - ax), n1 = abs(by - ay), n2 = abs(bz - az);
     const int s0 = bx > ax ? 1 : -1, s1 = by > ay ? 1 : -1, s2 = bz > az ? 1 : -1;
     int x = ax, y = ay, z = az, k0 = 0, k1 = 0, k2 = 0;
@@ -535,13 +507,8 @@ __device__ __forceinline__ FrSight fr_walk(int Y, int Z, const int *__restrict__
     return r;
 }
 
-__device__ __forceinline__ bool fr_inside(int X, int Y, int Z, int x, int y, int z) {
-    return x >= 0 && x < X && y >= 0 && y < Y && z >= 0 && z < Z;
-}
-
 // One lane per segment, the whole cover.
-__global__ __launch_bounds__(FR_THREADS) void route_sight_kernel(int X, int Y, int Z, const int *__restrict__ dist2,
-                                                                 int need, int S, const int *__restrict__ a,
+__global__ __launch_bounds__(FR_THREADS) void route_sight_kernel(FieldFree v, int S, const int *__restrict__ a,
                                                                  const int *__restrict__ b, int *__restrict__ cover,
                                                                  int *__restrict__ blocked) {
     const int i = blockIdx.x * FR_THREADS + threadIdx.x;      // S <= GG_FIELD_MAX_POSES
@@ -549,8 +516,7 @@ __global__ __launch_bounds__(FR_THREADS) void route_sight_kernel(int X, int Y, i
     const int ax = a[(size_t)i * 3], ay = a[(size_t)i * 3 + 1], az = a[(size_t)i * 3 + 2];
     const int bx = b[(size_t)i * 3], by = b[(size_t)i * 3 + 1], bz = b[(size_t)i * 3 + 2];
     FrSight r{0, -1};
-    if (fr_inside(X, Y, Z, ax, ay, az) && fr_inside(X, Y, Z, bx, by, bz))
-        r = fr_walk<false>(Y, Z, dist2, need, ax, ay, az, bx, by, bz);
+    if (v.inside(ax, ay, az) && v.inside(bx, by, bz)) r = fr_walk<false>(v, ax, ay, az, bx, by, bz);
     cover[i] = r.cover;
     blocked[i] = r.blocked;
 }
@@ -560,9 +526,8 @@ __global__ __launch_bounds__(FR_THREADS) void route_sight_kernel(int X, int Y, i
 // clear j; the four meet in LDS (two buffers, used in turn, so one barrier per chunk is enough) and the largest of
 // them is the chunk's answer.  The first chunk with a clear lane ends the scan.  i, top and next are the same in
 // every lane of the workgroup, so every lane reaches every barrier.
-__global__ __launch_bounds__(FR_THREADS) void route_shortcut_kernel(int X, int Y, int Z,
-                                                                    const int *__restrict__ dist2, int need, int P,
-                                                                    int max_cells, const int *__restrict__ cells,
+__global__ __launch_bounds__(FR_THREADS) void route_shortcut_kernel(FieldFree v, int P, int max_cells,
+                                                                    const int *__restrict__ cells,
                                                                     const int *__restrict__ length, int window,
                                                                     int *__restrict__ keep, int *__restrict__ count,
                                                                     int *__restrict__ blocked) {
@@ -579,7 +544,7 @@ __global__ __launch_bounds__(FR_THREADS) void route_shortcut_kernel(int X, int Y
         pad = n - 1;
         for (int i = 0; i < n - 1;) {
             const int ax = row[3 * i], ay = row[3 * i + 1], az = row[3 * i + 2];
-            const bool from = fr_inside(X, Y, Z, ax, ay, az);
+            const bool from = v.inside(ax, ay, az);
             const int far = (int)min((long long)i + window, (long long)n - 1);
             int next = -1;
             for (int top = far; top > i && next < 0; top -= FR_THREADS) {
@@ -587,8 +552,7 @@ __global__ __launch_bounds__(FR_THREADS) void route_shortcut_kernel(int X, int Y
                 bool clear = false;
                 if (j > i && from) {
                     const int bx = row[3 * j], by = row[3 * j + 1], bz = row[3 * j + 2];
-                    clear = fr_inside(X, Y, Z, bx, by, bz) &&
-                            fr_walk<true>(Y, Z, dist2, need, ax, ay, az, bx, by, bz).blocked == 0;
+                    clear = v.inside(bx, by, bz) && fr_walk<true>(v, ax, ay, az, bx, by, bz).blocked == 0;
                 }
                 const uint64_t seen = __ballot(clear);
                 if (lane == 0)
@@ -611,28 +575,14 @@ __global__ __launch_bounds__(FR_THREADS) void route_shortcut_kernel(int X, int Y
 // ---------------------------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------------------------
-static bool field_dims_ok(const int32_t *dims) {
-    if (!dims) return false;
-    int64_t cells = 1;
-    for (int a = 0; a < 3; ++a) {
-        if (dims[a] < 1 || dims[a] > GG_FIELD_MAX_DIM) return false;
-        cells *= dims[a];
-    }
-    return cells <= GG_FIELD_MAX_CELLS;
+// num_paths rows of max_cells cells each, as gg_field_descend writes and gg_field_shortcut reads them
+#define GG_REQUIRE_FIELD_PATHS(num_paths, max_cells)                                                              \
+    GG_REQUIRE((num_paths) >= 0 && (max_cells) >= 1 && (int64_t)(num_paths) * (max_cells) <= GG_FIELD_MAX_POSES, \
+               "need num_paths >= 0, max_cells >= 1 and num_paths max_cells <= GG_FIELD_MAX_POSES")
+
+static FieldFree field_free(const int32_t *dims, const int32_t *dist2, int32_t need) {
+    return FieldFree{{dims[0], dims[1], dims[2]}, dist2, need};
 }
-
-static bool field_grid(const int32_t *dims, const double *grid, FieldGrid *g) {
-    for (int a = 0; a < 4; ++a)
-        if (!isfinite(grid[a])) return false;
-    if (!(grid[3] > 0.0)) return false;
-    *g = FieldGrid{dims[0], dims[1], dims[2], {grid[0], grid[1], grid[2]}, grid[3]};
-    return true;
-}
-
-static int64_t field_cells(const int32_t *dims) { return (int64_t)dims[0] * dims[1] * dims[2]; }
-
-#define FIELD_DIMS_MSG "need 1 <= dims[a] <= GG_FIELD_MAX_DIM and dims[0] dims[1] dims[2] <= GG_FIELD_MAX_CELLS"
-#define FIELD_GRID_MSG "grid: the corner must be finite and the cell edge h finite and > 0"
 
 extern "C" int gg_field_splat(const int32_t *dims, const double *grid, int num_rows, const float *means,
                               const float *rot, const float *scales, const float *weights, double extent,
@@ -753,7 +703,7 @@ extern "C" int gg_field_route(const int32_t *dims, const int32_t *dist2, int32_t
                               const int32_t *goals, int32_t *cost, int64_t *ignored, int max_rounds, int *rounds_out,
                               void *ws, size_t ws_bytes, gg_stream_t stream) {
     GG_REQUIRE(field_dims_ok(dims), FIELD_DIMS_MSG);
-    GG_REQUIRE(need >= 0 && need <= GG_FIELD_FAR, "need must be in 0..GG_FIELD_FAR");
+    GG_REQUIRE_FIELD_NEED(need);
     GG_REQUIRE(num_goals >= 0 && num_goals <= GG_FIELD_MAX_GOALS, "need 0 <= num_goals <= GG_FIELD_MAX_GOALS");
     GG_REQUIRE(max_rounds >= 1, "max_rounds must be >= 1");
     GG_REQUIRE(rounds_out, "null pointer: rounds_out (a host int)");
@@ -768,6 +718,7 @@ extern "C" int gg_field_route(const int32_t *dims, const int32_t *dist2, int32_t
     int b[3];
     route_bricks(dims, b);
     const int64_t bricks = (int64_t)b[0] * b[1] * b[2];
+    const FieldFree v = field_free(dims, dist2, need);
     unsigned *counters = (unsigned *)ws, *flags = counters + FR_BATCH;
     *rounds_out = 0;
     const int64_t span = cells > words ? cells : words;
@@ -779,8 +730,8 @@ extern "C" int gg_field_route(const int32_t *dims, const int32_t *dist2, int32_t
         return GG_OK;
     }
     hipLaunchKernelGGL(route_goals_kernel, dim3((unsigned)((num_goals + FR_THREADS - 1) / FR_THREADS)),
-                       dim3(FR_THREADS), 0, s, dims[0], dims[1], dims[2], b[0], b[1], b[2], dist2, need, num_goals,
-                       goals, cost, flags, reinterpret_cast<unsigned long long *>(ignored));
+                       dim3(FR_THREADS), 0, s, v, b[0], b[1], b[2], num_goals, goals, cost, flags,
+                       reinterpret_cast<unsigned long long *>(ignored));
     GG_CHECK_LAUNCH();
     // Rounds in batches; after each batch the counters come back.  Once a round has flagged nothing the rounds
     // behind it find no active brick.  The loop is bounded by max_rounds, and no kernel in it can wait.
@@ -790,8 +741,8 @@ extern "C" int gg_field_route(const int32_t *dims, const int32_t *dist2, int32_t
         if (done > 0) hipLaunchKernelGGL(route_zero_kernel, dim3(1), dim3(FR_THREADS), 0, s, counters, FR_BATCH);
         for (int r = 0; r < n; ++r) {
             unsigned *cur = flags + (size_t)((done + r) & 1) * bricks, *next = flags + (size_t)((done + r + 1) & 1) * bricks;
-            hipLaunchKernelGGL(route_round_kernel, dim3((unsigned)bricks), dim3(FR_THREADS), 0, s, dims[0], dims[1],
-                               dims[2], b[0], b[1], b[2], dist2, need, cost, cur, next, counters + r);
+            hipLaunchKernelGGL(route_round_kernel, dim3((unsigned)bricks), dim3(FR_THREADS), 0, s, v, b[0], b[1],
+                               b[2], cost, cur, next, counters + r);
         }
         GG_CHECK_LAUNCH();
         hipError_t e = hipMemcpyAsync(flagged, counters, sizeof(unsigned) * n, hipMemcpyDeviceToHost, s);
@@ -816,17 +767,16 @@ extern "C" int gg_field_descend(const int32_t *dims, const int32_t *dist2, int32
                                 int num_paths, const int32_t *starts, int max_cells, int32_t *cells, int32_t *length,
                                 gg_stream_t stream) {
     GG_REQUIRE(field_dims_ok(dims), FIELD_DIMS_MSG);
-    GG_REQUIRE(need >= 0 && need <= GG_FIELD_FAR, "need must be in 0..GG_FIELD_FAR");
-    GG_REQUIRE(num_paths >= 0 && max_cells >= 1, "need num_paths >= 0 and max_cells >= 1");
-    GG_REQUIRE((int64_t)num_paths * max_cells <= GG_FIELD_MAX_POSES, "num_paths max_cells > GG_FIELD_MAX_POSES");
+    GG_REQUIRE_FIELD_NEED(need);
+    GG_REQUIRE_FIELD_PATHS(num_paths, max_cells);
     if (num_paths == 0) return GG_OK;
     GG_REQUIRE(dist2 && cost && starts && cells && length, "null pointer: dist2 / cost / starts / cells / length");
     GG_REQUIRE((((uintptr_t)dist2 | (uintptr_t)cost | (uintptr_t)starts | (uintptr_t)cells | (uintptr_t)length) & 3) == 0,
                "dist2 / cost / starts / cells / length misaligned");
     const int per = FR_THREADS / 64;
     hipLaunchKernelGGL(route_descend_kernel, dim3((unsigned)((num_paths + per - 1) / per)), dim3(FR_THREADS), 0,
-                       (hipStream_t)stream, dims[0], dims[1], dims[2], dist2, need, cost, num_paths, starts, max_cells,
-                       cells, length);
+                       (hipStream_t)stream, field_free(dims, dist2, need), cost, num_paths, starts, max_cells, cells,
+                       length);
     GG_CHECK_LAUNCH();
     return GG_OK;
 }
@@ -835,7 +785,7 @@ extern "C" int gg_field_sight(const int32_t *dims, const int32_t *dist2, int32_t
                               const int32_t *a, const int32_t *b, int32_t *cover, int32_t *blocked,
                               gg_stream_t stream) {
     GG_REQUIRE(field_dims_ok(dims), FIELD_DIMS_MSG);
-    GG_REQUIRE(need >= 0 && need <= GG_FIELD_FAR, "need must be in 0..GG_FIELD_FAR");
+    GG_REQUIRE_FIELD_NEED(need);
     GG_REQUIRE(num_segments >= 0 && num_segments <= GG_FIELD_MAX_POSES,
                "need 0 <= num_segments <= GG_FIELD_MAX_POSES");
     if (num_segments == 0) return GG_OK;
@@ -843,8 +793,8 @@ extern "C" int gg_field_sight(const int32_t *dims, const int32_t *dist2, int32_t
     GG_REQUIRE((((uintptr_t)dist2 | (uintptr_t)a | (uintptr_t)b | (uintptr_t)cover | (uintptr_t)blocked) & 3) == 0,
                "dist2 / a / b / cover / blocked misaligned");
     hipLaunchKernelGGL(route_sight_kernel, dim3((unsigned)((num_segments + FR_THREADS - 1) / FR_THREADS)),
-                       dim3(FR_THREADS), 0, (hipStream_t)stream, dims[0], dims[1], dims[2], dist2, need, num_segments,
-                       a, b, cover, blocked);
+                       dim3(FR_THREADS), 0, (hipStream_t)stream, field_free(dims, dist2, need), num_segments, a, b,
+                       cover, blocked);
     GG_CHECK_LAUNCH();
     return GG_OK;
 }
@@ -853,9 +803,8 @@ extern "C" int gg_field_shortcut(const int32_t *dims, const int32_t *dist2, int3
                                  int max_cells, const int32_t *cells, const int32_t *length, int window,
                                  int32_t *keep, int32_t *count, int32_t *blocked, gg_stream_t stream) {
     GG_REQUIRE(field_dims_ok(dims), FIELD_DIMS_MSG);
-    GG_REQUIRE(need >= 0 && need <= GG_FIELD_FAR, "need must be in 0..GG_FIELD_FAR");
-    GG_REQUIRE(num_paths >= 0 && max_cells >= 1, "need num_paths >= 0 and max_cells >= 1");
-    GG_REQUIRE((int64_t)num_paths * max_cells <= GG_FIELD_MAX_POSES, "num_paths max_cells > GG_FIELD_MAX_POSES");
+    GG_REQUIRE_FIELD_NEED(need);
+    GG_REQUIRE_FIELD_PATHS(num_paths, max_cells);
     GG_REQUIRE(window >= 1, "window must be >= 1");
     if (num_paths == 0) return GG_OK;
     GG_REQUIRE(dist2 && cells && length && keep && count && blocked,
@@ -864,8 +813,8 @@ extern "C" int gg_field_shortcut(const int32_t *dims, const int32_t *dist2, int3
                  (uintptr_t)blocked) & 3) == 0,
                "dist2 / cells / length / keep / count / blocked misaligned");
     hipLaunchKernelGGL(route_shortcut_kernel, dim3((unsigned)num_paths), dim3(FR_THREADS), 0,
-                       (hipStream_t)stream, dims[0], dims[1], dims[2], dist2, need, num_paths, max_cells, cells,
-                       length, window, keep, count, blocked);
+                       (hipStream_t)stream, field_free(dims, dist2, need), num_paths, max_cells, cells, length, window,
+                       keep, count, blocked);
     GG_CHECK_LAUNCH();
     return GG_OK;
 }

@@ -29,8 +29,8 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._call import (ArrayLike, default_device, f32_rows, grid_args, nonneg, positive, ptr as _ptr,
-                    require_hip as _require_hip, sized_workspace, stream as _stream, to_device)
+from ._call import (ArrayLike, check_finite_options, default_device, f32_rows, host_array, nonneg, positive,
+                    ptr as _ptr, require_hip as _require_hip, sized_workspace, stream as _stream, to_device)
 from .grasp import MIN_WEIGHT, check_gripper
 
 FAR = 1 << 30                  # GG_FIELD_FAR
@@ -128,7 +128,7 @@ def gripper_spheres(parts: ArrayLike, width: float, depth: float, height: float,
 
 def grasp_poses(rows: ArrayLike) -> np.ndarray:
     """(M, 17) grasp rows (grasp.load_grasps) as (M, 1, 12) float32 poses: R row-major, then t."""
-    g = np.asarray(rows.cpu() if isinstance(rows, Tensor) else rows, np.float32)
+    g = host_array(rows, np.float32)
     if g.ndim != 2 or g.shape[1] != 17:
         raise ValueError(f"grasp rows are (M, 17), got {g.shape}")
     return np.ascontiguousarray(g[:, None, 4:16])
@@ -210,12 +210,49 @@ def slerp_rotations(rot_a: np.ndarray, rot_b: np.ndarray, fractions: Sequence[fl
 # ------------------------------------------------------------------------------------------------
 # device side: the three calls
 # ------------------------------------------------------------------------------------------------
-def _volume(grid, dims):
-    g = np.asarray(grid, np.float64).reshape(-1)
-    d = np.asarray(dims, np.int64).reshape(-1)
-    if g.shape != (4,) or d.shape != (3,):
-        raise ValueError("grid is (4,) lower corner and cell edge, dims (3,) cells")
-    return grid_args((g, d)), tuple(int(v) for v in d)
+def volume_args(dims, grid=None):
+    """(c_int32[3] dims, c_double[4] grid or None, shape tuple) for the C ABI; transit.py and arm.py use these too."""
+    d = host_array(dims, np.int64).reshape(-1)
+    g = None if grid is None else host_array(grid, np.float64).reshape(-1)
+    if d.shape != (3,) or (g is not None and g.shape != (4,)):
+        raise ValueError("dims is (3,) cells" + ("" if g is None else ", grid (4,) lower corner and cell edge"))
+    shape = tuple(int(v) for v in d)
+    return (C.c_int32 * 3)(*shape), None if g is None else (C.c_double * 4)(*g.tolist()), shape
+
+
+def volume_tensor(t: Tensor, name: str, dtype: torch.dtype, shape, dev: Optional[torch.device] = None) -> Tensor:
+    """`t` after checking that it is a contiguous `dtype` tensor of `shape` (and on `dev`, when given)."""
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {dtype} {tuple(shape)} tensor, got {t.dtype} {tuple(t.shape)}")
+    if dev is not None and t.device != dev:
+        raise ValueError(f"{name} must be on {dev}, got {t.device}")
+    return t
+
+
+def cell_count(name: str, v: int) -> int:
+    """A squared cell distance (`need`, `outside`) as an int in 0..FAR."""
+    if not 0 <= int(v) <= FAR:
+        raise ValueError(f"{name} must be in 0..{FAR}, got {v}")
+    return int(v)
+
+
+def pose_paths(poses: Tensor) -> Tensor:
+    """`poses` contiguous, after checking that it is float32 (P, W, 12)."""
+    if poses.dtype != torch.float32 or poses.ndim != 3 or poses.shape[2] != 12:
+        raise ValueError(f"poses must be a float32 (P, W, 12) tensor, got {poses.dtype} {tuple(poses.shape)}")
+    return poses.contiguous()
+
+
+def sphere_table(spheres: Tensor, **int32_columns: Tensor):
+    """(spheres, *columns) contiguous: spheres float32 (S, 3), S <= MAX_SPHERES, every named column int32 (S,)."""
+    spheres = f32_rows(spheres, "spheres", 3)
+    s = spheres.shape[0]
+    if s > MAX_SPHERES:
+        raise ValueError(f"{s} spheres are more than {MAX_SPHERES}")
+    for name, t in int32_columns.items():
+        if t.dtype != torch.int32 or tuple(t.shape) != (s,):
+            raise ValueError(f"{name} must be an int32 ({s},) tensor, got {t.dtype} {tuple(t.shape)}")
+    return (spheres, *(t.contiguous() for t in int32_columns.values()))
 
 
 def splat(mass: Tensor, grid, dims, means: Tensor, rot: Tensor, scales: Tensor, weights: Tensor,
@@ -225,9 +262,8 @@ def splat(mass: Tensor, grid, dims, means: Tensor, rot: Tensor, scales: Tensor, 
     place).  means (N, 3), rot (N, 9) or (N, 3, 3), scales (N, 3) activated, weights (N,): float32 on the same device
     (no CPU path).  Nothing waits on the host."""
     dev = _require_hip(mass, means, rot, scales, weights)
-    (g, d), shape = _volume(grid, dims)
-    if mass.dtype != torch.int64 or tuple(mass.shape) != shape or not mass.is_contiguous():
-        raise ValueError(f"mass must be a contiguous int64 {shape} tensor, got {mass.dtype} {tuple(mass.shape)}")
+    d, g, shape = volume_args(dims, grid)
+    volume_tensor(mass, "mass", torch.int64, shape)
     means = f32_rows(means, "means", 3)
     n = means.shape[0]
     rot = f32_rows(rot.reshape(rot.shape[0], 9) if rot.ndim == 3 else rot, "rot", 9)
@@ -254,17 +290,14 @@ def distance(mass: Tensor, dims, threshold: int = THRESHOLD, out: Optional[Tenso
     """dist2 int32 [X][Y][Z] of `mass` (gg_field_distance): the squared distance, in cells, to the nearest cell with
     mass >= threshold; FAR everywhere when there is none."""
     dev = _require_hip(mass)
-    shape = tuple(int(v) for v in np.asarray(dims).reshape(-1))
-    if mass.dtype != torch.int64 or tuple(mass.shape) != shape or not mass.is_contiguous():
-        raise ValueError(f"mass must be a contiguous int64 {shape} tensor, got {mass.dtype} {tuple(mass.shape)}")
+    d, _, shape = volume_args(dims)
+    volume_tensor(mass, "mass", torch.int64, shape)
     if int(threshold) < 1:
         raise ValueError(f"threshold must be >= 1, got {threshold}")
-    d = (C.c_int32 * 3)(*shape)
     lib = _lib.load()
     if out is None:
         out = torch.empty(shape, dtype=torch.int32, device=dev)
-    elif out.dtype != torch.int32 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != dev:
-        raise ValueError(f"out must be a contiguous int32 {shape} tensor on {dev}")
+    volume_tensor(out, "out", torch.int32, shape, dev)
     ws = sized_workspace(lib.gg_field_distance_workspace(d), f"{shape} cells are beyond gg_field_distance's limits",
                          dev)
     _lib.check(lib.gg_field_distance(d, _ptr(mass), int(threshold), _ptr(out), _ptr(ws), ws.numel(), _stream(dev)),
@@ -277,25 +310,18 @@ def paths(dist2: Tensor, grid, dims, poses: Tensor, spheres: Tensor, need: Tenso
     """(slack (P, W) int32, first_hit (P,) int32) of one gg_field_paths call.  poses (P, W, 12) and spheres (S, 3)
     float32, need (S,) int32 in 0..FAR, dist2 int32 [X][Y][Z]: on the HIP device (no CPU path)."""
     dev = _require_hip(dist2, poses, spheres, need)
-    (g, d), shape = _volume(grid, dims)
-    if dist2.dtype != torch.int32 or tuple(dist2.shape) != shape or not dist2.is_contiguous():
-        raise ValueError(f"dist2 must be a contiguous int32 {shape} tensor, got {dist2.dtype} {tuple(dist2.shape)}")
-    if poses.dtype != torch.float32 or poses.ndim != 3 or poses.shape[2] != 12:
-        raise ValueError(f"poses must be a float32 (P, W, 12) tensor, got {poses.dtype} {tuple(poses.shape)}")
-    spheres = f32_rows(spheres, "spheres", 3)
-    s = spheres.shape[0]
-    if need.dtype != torch.int32 or tuple(need.shape) != (s,):
-        raise ValueError(f"need must be an int32 ({s},) tensor, got {need.dtype} {tuple(need.shape)}")
+    d, g, shape = volume_args(dims, grid)
+    volume_tensor(dist2, "dist2", torch.int32, shape)
+    poses = pose_paths(poses)
+    spheres, need = sphere_table(spheres, need=need)
     p, w = poses.shape[:2]
-    if p * w > MAX_POSES or s > MAX_SPHERES:
-        raise ValueError(f"{p} x {w} poses and {s} spheres: at most {MAX_POSES} poses and {MAX_SPHERES} spheres")
-    if not 0 <= int(outside) <= FAR:
-        raise ValueError(f"outside must be in 0..{FAR}, got {outside}")
-    poses, need = poses.contiguous(), need.contiguous()
+    if p * w > MAX_POSES:
+        raise ValueError(f"{p} x {w} poses are more than {MAX_POSES}")
     slack = torch.empty(p, w, dtype=torch.int32, device=dev)
     first = torch.empty(p, dtype=torch.int32, device=dev)
-    _lib.check(_lib.load().gg_field_paths(d, g, _ptr(dist2), p, w, _ptr(poses), s, _ptr(spheres), _ptr(need),
-                                          int(outside), _ptr(slack), _ptr(first), _stream(dev)), "gg_field_paths")
+    _lib.check(_lib.load().gg_field_paths(d, g, _ptr(dist2), p, w, _ptr(poses), spheres.shape[0], _ptr(spheres),
+                                          _ptr(need), cell_count("outside", outside), _ptr(slack), _ptr(first),
+                                          _stream(dev)), "gg_field_paths")
     return slack, first
 
 
@@ -405,7 +431,8 @@ def path_clear(field: DistanceField, poses: ArrayLike, spheres: ArrayLike, radiu
 # command line
 # ------------------------------------------------------------------------------------------------
 def main(argv: Optional[Sequence[str]] = None) -> int:
-    from ._cli import add_object_options, check_object_options, load_scene, object_mask
+    from ._cli import (add_gripper_sphere_options, add_object_options, check_object_options, load_scene,
+                       object_mask)
     from .frames import load_transform_json
     from .grasp import load_gripper_option
     ap = argparse.ArgumentParser(prog="python -m gaussiangrasper_amd.field",
@@ -425,12 +452,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                        "selects the Gaussians that are left out of the field (the object being carried)")
     ap.add_argument("--out", required=True, help="output .npz: mass, dist2, grid, dims, threshold")
     ap.add_argument("--paths", default=None, help=".npy (P, W, 12) gripper poses, scene frame: R row-major, then t")
-    ap.add_argument("--gripper", default=None, metavar="{default,FILE.json}", help="with --paths: the gripper model")
-    ap.add_argument("--width", type=float, default=0.08, help="with --paths: the gripper's opening, scene units")
-    ap.add_argument("--depth", type=float, default=0.02, help="with --paths: the fingers' depth")
-    ap.add_argument("--height", type=float, default=0.02, help="with --paths: the fingers' height")
-    ap.add_argument("--radius", type=float, default=0.005, help="with --paths: radius of the covering spheres")
-    ap.add_argument("--margin", type=float, default=0.0, help="with --paths: clearance kept beyond the spheres")
+    add_gripper_sphere_options(ap, "with --paths: ")
     ap.add_argument("--outside", choices=("free", "blocked"), default="free",
                     help="with --paths: what space outside the box counts as")
     ap.add_argument("--report", default=None, help="with --paths: output .npz slack, first_hit, clear, spheres")
@@ -438,12 +460,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     check_object_options(ap, a, "optional")
     if bool(a.paths) != bool(a.gripper) or bool(a.paths) != bool(a.report):
         ap.error("--paths, --gripper and --report go together")
-    for n in ("voxel", "radius", "width"):
-        if not (math.isfinite(getattr(a, n)) and getattr(a, n) > 0.0):
-            ap.error(f"--{n} must be finite and > 0, got {getattr(a, n)}")
-    for n in ("extent", "margin", "depth", "height"):
-        if not (math.isfinite(getattr(a, n)) and getattr(a, n) >= 0.0):
-            ap.error(f"--{n} must be finite and >= 0, got {getattr(a, n)}")
+    check_finite_options(ap, a, positive=("voxel", "radius", "width"), nonneg=("extent", "margin", "depth", "height"))
     if not 0 <= a.max_reach <= MAX_REACH_LIMIT:
         ap.error(f"--max-reach must be in 0..{MAX_REACH_LIMIT}, got {a.max_reach}")
     if math.isnan(a.min_opacity):

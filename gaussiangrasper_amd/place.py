@@ -39,8 +39,8 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._call import (ArrayLike, default_device, f32_rows, nonneg, positive, ptr as _ptr, require_hip as _require_hip,
-                    stream as _stream, to_device)
+from ._call import (ArrayLike, check_finite_options, default_device, f32_rows, host_array, nonneg, positive,
+                    ptr as _ptr, require_hip as _require_hip, stream as _stream, to_device)
 
 EMPTY = -(1 << 31)             # GG_PLACE_EMPTY
 MAX_LEVEL = 1 << 28            # GG_PLACE_MAX_LEVEL
@@ -99,10 +99,6 @@ class Placements:
 # ------------------------------------------------------------------------------------------------
 # host side (numpy, fp64)
 # ------------------------------------------------------------------------------------------------
-def _np(x) -> np.ndarray:
-    return x.detach().cpu().numpy() if isinstance(x, Tensor) else np.asarray(x)
-
-
 def _plane(plane) -> Tuple[np.ndarray, float]:
     """(n, offset) of a support.SupportPlane or of a pair (normal, offset), n brought to unit length."""
     n, d = (plane.normal, plane.offset) if hasattr(plane, "normal") else plane
@@ -227,8 +223,8 @@ def propose(found: PlaceSearch, under: ArrayLike, frame: PlaneFrame, grid: Array
     ordered by the distance of the landed pivot from `target` (a 3-D point) when given, else by descending contact
     fraction; ties by (k, i, j) ascending.  The gates are integer comparisons (contact cells[k]' >= min_contact cells[k]
     is one product in fp64); only the order by target uses the transforms.  top_k: the first so many."""
-    rest, contact, support = (_np(x).astype(np.int64) for x in (found.rest, found.contact, found.support))
-    und = _np(under).astype(np.int64)
+    rest, contact, support = (host_array(x, np.int64) for x in (found.rest, found.contact, found.support))
+    und = host_array(under, np.int64)
     K, A, B = und.shape
     if rest.shape[:1] != (K,) or contact.shape != rest.shape or support.shape != rest.shape + (6,):
         raise ValueError(f"rest {rest.shape}, contact {contact.shape}, support {support.shape} do not belong to "
@@ -266,7 +262,7 @@ def release_paths(placements: Placements, grasp_row: ArrayLike, lift: float, ste
     `grasp_row` ((17,), grasp.load_grasps: R at 4..12, t at 13..15) carried along with the object, T_place . grasp
     pose, descending against the plane's normal from `lift` scene units above at waypoint 0 to the placement itself at
     the last one, orientation fixed."""
-    g = np.asarray(grasp_row.cpu() if isinstance(grasp_row, Tensor) else grasp_row, np.float64).reshape(-1)
+    g = host_array(grasp_row, np.float64).reshape(-1)
     if g.shape != (17,):
         raise ValueError(f"a grasp row is (17,), got {g.shape}")
     steps, up = int(steps), nonneg("lift", lift)
@@ -305,7 +301,7 @@ def height_map(points: Tensor, weights: Optional[Tensor], frames: ArrayLike, gri
         weights = f32_rows(weights, "weights", None)
         if weights.shape[0] != points.shape[0]:
             raise ValueError(f"points has {points.shape[0]} rows, weights {weights.shape[0]}")
-    fr = np.ascontiguousarray(np.asarray(_np(frames), np.float64).reshape(-1, 12))
+    fr = np.ascontiguousarray(host_array(frames, np.float64).reshape(-1, 12))
     F = fr.shape[0]
     if not 1 <= F <= MAX_YAWS:
         raise ValueError(f"need 1..{MAX_YAWS} frames, got {F}")
@@ -366,7 +362,7 @@ def top_map(points, weights, frame: PlaneFrame, grid, dims, min_weight: float = 
     opacities with the object's set to 0, which leaves it out) per cell of the plane's grid.  Cells that no point fell
     in are given `floor`, the plane's own level, unless floor is None: a table is never sampled densely enough for
     every cell."""
-    top = _np(maps(points, weights, frame.rows()[None], grid, dims, min_weight)[0])[0].astype(np.int32)
+    top = host_array(maps(points, weights, frame.rows()[None], grid, dims, min_weight)[0])[0].astype(np.int32)
     if floor is not None:
         if not -MAX_LEVEL <= int(floor) <= MAX_LEVEL:
             raise ValueError(f"floor must be within +-{MAX_LEVEL}, got {floor}")
@@ -399,7 +395,7 @@ def under_maps(points, weights, frame: PlaneFrame, pivot: ArrayLike, radius: flo
     A = footprint_cells(radius, cell, dilate)
     frames = yaw_frames(frame, pivot, yaws, A, A, cell)
     und, dropped = maps(points, weights, underside(frames), np.array([0.0, 0.0, cell, level]), (A, A), min_weight)
-    return dilate_maps(_np(und), dilate), frames, _np(dropped)
+    return dilate_maps(host_array(und), dilate), frames, host_array(dropped)
 
 
 def object_pivot(points, object_weights, normal: ArrayLike, min_weight: float = 0.0) -> Tuple[np.ndarray, float]:
@@ -407,7 +403,7 @@ def object_pivot(points, object_weights, normal: ArrayLike, min_weight: float = 
     (the object's points are read back for it, the others are not), and the largest distance of one of them from the
     line through the pivot along `normal`."""
     n = np.asarray(normal, np.float64).reshape(3)
-    ow = _np(object_weights).astype(np.float64).reshape(-1)
+    ow = host_array(object_weights, np.float64).reshape(-1)
     sel = np.nonzero(ow > float(min_weight))[0]
     if isinstance(points, Tensor):
         obj = points[torch.from_numpy(sel).to(points.device)].detach().cpu().numpy().astype(np.float64)
@@ -551,9 +547,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     a = ap.parse_args(argv)
     check_object_options(ap, a, "required")
     check_support_options(ap, a, grasp=False)
-    for n in ("cell", "level", "region"):
-        if not (math.isfinite(getattr(a, n)) and getattr(a, n) > 0.0):
-            ap.error(f"--{n} must be finite and > 0, got {getattr(a, n)}")
+    check_finite_options(ap, a, positive=("cell", "level", "region"))
     if not 1 <= a.yaws <= MAX_YAWS:
         ap.error(f"--yaws must be in 1..{MAX_YAWS}, got {a.yaws}")
     if not 0 <= a.tol <= MAX_LEVEL or a.dilate < 0 or a.stability_margin < 0:
@@ -577,7 +571,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     np.savez(a.out, transform=p.transform, yaw=p.yaw, anchor=p.anchor, rest=p.rest, lift=p.lift,
              contact_frac=p.contact_frac, score=p.score, yaw_angles=yaw_angles(a.yaws), normal=plan.frame.e2,
              pivot=plan.pivot)
-    valid = int((_np(plan.found.rest) != EMPTY).sum())
+    valid = int((host_array(plan.found.rest) != EMPTY).sum())
     print(f"{tuple(int(d) for d in plan.dims)} cells, footprint {plan.under.shape[1]} x {plan.under.shape[2]} x "
           f"{plan.under.shape[0]} yaws: {valid} valid anchors, {len(p.yaw)} placements; wrote {a.out}")
     return 0

@@ -34,10 +34,10 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._call import (ArrayLike, positive, ptr as _ptr, require_hip as _require_hip, sized_workspace,
-                    stream as _stream, to_device)
-from .field import (FAR, MAX_POSES, MAX_SPHERES, DistanceField, PathClearance, gripper_spheres, interpolate, need2,
-                    path_clear, slerp_rotations)
+from ._call import (ArrayLike, check_finite_options, host_array, positive, ptr as _ptr, require_hip as _require_hip,
+                    sized_workspace, stream as _stream, to_device)
+from .field import (FAR, MAX_POSES, MAX_SPHERES, DistanceField, PathClearance, cell_count, gripper_spheres,
+                    interpolate, need2, path_clear, slerp_rotations, volume_args, volume_tensor)
 
 MAX_GOALS = 1 << 24            # GG_FIELD_MAX_GOALS
 MAX_ROUNDS = 4096
@@ -91,7 +91,7 @@ def cells_of(field, points: ArrayLike) -> np.ndarray:
     """(N, 3) int32 cells of (N, 3) points by the header's rule in fp64: per axis the c with c h <= d < (c + 1) h,
     d = (double)p - lo (a division proposes and is clamped to +-2^30, the comparisons decide: field_cell.h step by
     step); a cell outside the volume is returned as it is.  A point that is not finite gives the row -1, -1, -1."""
-    p = np.asarray(points.detach().cpu() if isinstance(points, Tensor) else points, np.float64).reshape(-1, 3)
+    p = host_array(points, np.float64).reshape(-1, 3)
     grid = np.asarray(field.grid, np.float64)
     h = float(grid[3])
     fin = np.isfinite(p).all(1)
@@ -122,8 +122,7 @@ def carried_spheres(points_in_gripper_frame: ArrayLike, radius: float) -> np.nda
     centres of the occupied voxels of edge 2 radius / sqrt(3) (half diagonal = radius; the edge is taken 1e-4
     shorter, as field.gripper_spheres does, which is far more than the centres lose as float32).  Points that are
     not finite are left out.  ValueError beyond GG_FIELD_MAX_SPHERES."""
-    p = np.asarray(points_in_gripper_frame.detach().cpu() if isinstance(points_in_gripper_frame, Tensor)
-                   else points_in_gripper_frame, np.float64).reshape(-1, 3)
+    p = host_array(points_in_gripper_frame, np.float64).reshape(-1, 3)
     p = p[np.isfinite(p).all(1)]
     edge = 2.0 * positive("radius", radius) / math.sqrt(3.0) * (1.0 - 1e-4)
     if len(p) == 0:
@@ -172,7 +171,7 @@ def transit_poses(pose_from: ArrayLike, pose_to: ArrayLike, cells: ArrayLike, le
     a, b = (np.asarray(p, np.float64).reshape(-1) for p in (pose_from, pose_to))
     if a.shape != (12,) or b.shape != (12,) or not (np.isfinite(a).all() and np.isfinite(b).all()):
         raise ValueError("a pose is 12 finite numbers: R row-major, then t")
-    c = np.asarray(cells.detach().cpu() if isinstance(cells, Tensor) else cells, np.int64).reshape(-1, 3)
+    c = host_array(cells, np.int64).reshape(-1, 3)
     length = int(length)
     if not 1 <= length <= len(c):
         raise ValueError(f"length must be in 1..{len(c)} (the rows of cells), got {length}")
@@ -192,8 +191,8 @@ def polyline_lengths(field, starts: ArrayLike, goal: ArrayLike, cells: ArrayLike
     g = np.asarray(goal, np.float64).reshape(1, 3)
     if len(s) == 0:
         return np.zeros(0)
-    c = np.asarray(cells.detach().cpu() if isinstance(cells, Tensor) else cells, np.int64).reshape(len(s), -1, 3)
-    n = np.asarray(length.detach().cpu() if isinstance(length, Tensor) else length, np.int64).reshape(-1)
+    c = host_array(cells, np.int64).reshape(len(s), -1, 3)
+    n = host_array(length, np.int64).reshape(-1)
     out = np.full(len(s), np.inf)
     for p in np.nonzero(n > 0)[0]:
         line = np.concatenate([s[p:p + 1], cell_centres(field, c[p, :n[p]]), g])
@@ -210,18 +209,6 @@ def best_path(planned: ArrayLike, clear: ArrayLike, rank: ArrayLike) -> int:
 # ------------------------------------------------------------------------------------------------
 # device side: the calls as they are
 # ------------------------------------------------------------------------------------------------
-def _dims(dims):
-    shape = tuple(int(v) for v in np.asarray(dims).reshape(-1))
-    if len(shape) != 3:
-        raise ValueError("dims is (3,) cells")
-    return (C.c_int32 * 3)(*shape), shape
-
-
-def _int32_volume(t: Tensor, name: str, shape) -> None:
-    if t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous():
-        raise ValueError(f"{name} must be a contiguous int32 {shape} tensor, got {t.dtype} {tuple(t.shape)}")
-
-
 def _cells_arg(cells: ArrayLike, name: str, dev) -> Tensor:
     t = to_device(cells, torch.int32, dev)
     if t.ndim != 2 or t.shape[1] != 3:
@@ -237,10 +224,9 @@ def route(dist2: Tensor, dims, need: int, goals: ArrayLike, max_rounds: int = MA
     HIP device (no CPU path); goals (G, 3) int32 cells.  The call waits for the device (once per batch of rounds).
     GGError when max_rounds run out; `out`, when given, then holds upper bounds."""
     dev = _require_hip(dist2)
-    d, shape = _dims(dims)
-    _int32_volume(dist2, "dist2", shape)
-    if not 0 <= int(need) <= FAR:
-        raise ValueError(f"need must be in 0..{FAR}, got {need}")
+    d, _, shape = volume_args(dims)
+    volume_tensor(dist2, "dist2", torch.int32, shape)
+    need = cell_count("need", need)
     if int(max_rounds) < 1:
         raise ValueError(f"max_rounds must be >= 1, got {max_rounds}")
     g = _cells_arg(goals, "goals", dev)
@@ -248,15 +234,12 @@ def route(dist2: Tensor, dims, need: int, goals: ArrayLike, max_rounds: int = MA
         raise ValueError(f"{g.shape[0]} goals are more than {MAX_GOALS}")
     if out is None:
         out = torch.empty(shape, dtype=torch.int32, device=dev)
-    else:
-        _int32_volume(out, "out", shape)
-        if out.device != dev:
-            raise ValueError(f"out must be on {dev}")
+    volume_tensor(out, "out", torch.int32, shape, dev)
     lib = _lib.load()
     ws = sized_workspace(lib.gg_field_route_workspace(d), f"{shape} cells are beyond gg_field_route's limits", dev)
     ignored = torch.zeros(1, dtype=torch.int64, device=dev)
     rounds = C.c_int(0)
-    _lib.check(lib.gg_field_route(d, _ptr(dist2), int(need), g.shape[0], _ptr(g) if g.shape[0] else None, _ptr(out),
+    _lib.check(lib.gg_field_route(d, _ptr(dist2), need, g.shape[0], _ptr(g) if g.shape[0] else None, _ptr(out),
                                   _ptr(ignored), int(max_rounds), C.byref(rounds), _ptr(ws), ws.numel(), _stream(dev)),
                "gg_field_route")
     return out, ignored[0], int(rounds.value)
@@ -266,18 +249,17 @@ def descend_cells(dist2: Tensor, dims, need: int, cost: Tensor, starts: ArrayLik
                   max_cells: int) -> Tuple[Tensor, Tensor]:
     """(cells (P, max_cells, 3) int32, length (P,) int32) of one gg_field_descend call; starts (P, 3) int32 cells."""
     dev = _require_hip(dist2, cost)
-    d, shape = _dims(dims)
-    _int32_volume(dist2, "dist2", shape)
-    _int32_volume(cost, "cost", shape)
-    if not 0 <= int(need) <= FAR:
-        raise ValueError(f"need must be in 0..{FAR}, got {need}")
+    d, _, shape = volume_args(dims)
+    volume_tensor(dist2, "dist2", torch.int32, shape)
+    volume_tensor(cost, "cost", torch.int32, shape)
+    need = cell_count("need", need)
     s = _cells_arg(starts, "starts", dev)
     p, max_cells = s.shape[0], int(max_cells)
     if max_cells < 1 or p * max_cells > MAX_POSES:
         raise ValueError(f"need max_cells >= 1 and P max_cells <= {MAX_POSES}, got {p} x {max_cells}")
     cells = torch.empty(p, max_cells, 3, dtype=torch.int32, device=dev)
     length = torch.empty(p, dtype=torch.int32, device=dev)
-    _lib.check(_lib.load().gg_field_descend(d, _ptr(dist2), int(need), _ptr(cost), p, _ptr(s) if p else None,
+    _lib.check(_lib.load().gg_field_descend(d, _ptr(dist2), need, _ptr(cost), p, _ptr(s) if p else None,
                                             max_cells, _ptr(cells), _ptr(length), _stream(dev)), "gg_field_descend")
     return cells, length
 
@@ -286,17 +268,16 @@ def sight(dist2: Tensor, dims, need: int, a: ArrayLike, b: ArrayLike) -> Tuple[T
     """(cover (S,) int32, blocked (S,) int32) of one gg_field_sight call; a, b (S, 3) int32 cells.  blocked 0: the
     segment between the two centres is clear; -1 (and cover 0): an end is outside the volume."""
     dev = _require_hip(dist2)
-    d, shape = _dims(dims)
-    _int32_volume(dist2, "dist2", shape)
-    if not 0 <= int(need) <= FAR:
-        raise ValueError(f"need must be in 0..{FAR}, got {need}")
+    d, _, shape = volume_args(dims)
+    volume_tensor(dist2, "dist2", torch.int32, shape)
+    need = cell_count("need", need)
     ca, cb = _cells_arg(a, "a", dev), _cells_arg(b, "b", dev)
     s = ca.shape[0]
     if cb.shape[0] != s or s > MAX_POSES:
         raise ValueError(f"a and b must hold the same number of cells, at most {MAX_POSES}: got {s} and {cb.shape[0]}")
     cover = torch.empty(s, dtype=torch.int32, device=dev)
     blocked = torch.empty(s, dtype=torch.int32, device=dev)
-    _lib.check(_lib.load().gg_field_sight(d, _ptr(dist2), int(need), s, _ptr(ca) if s else None,
+    _lib.check(_lib.load().gg_field_sight(d, _ptr(dist2), need, s, _ptr(ca) if s else None,
                                           _ptr(cb) if s else None, _ptr(cover), _ptr(blocked), _stream(dev)),
                "gg_field_sight")
     return cover, blocked
@@ -317,10 +298,9 @@ def shortcut_cells(dist2: Tensor, dims, need: int, cells: Tensor, length: Tensor
     """(keep (P, max_cells) int32, count (P,) int32, blocked (P,) int32) of one gg_field_shortcut call; cells
     (P, max_cells, 3) int32 and length (P,) int32 as descend_cells returns them."""
     dev = _require_hip(dist2)
-    d, shape = _dims(dims)
-    _int32_volume(dist2, "dist2", shape)
-    if not 0 <= int(need) <= FAR:
-        raise ValueError(f"need must be in 0..{FAR}, got {need}")
+    d, _, shape = volume_args(dims)
+    volume_tensor(dist2, "dist2", torch.int32, shape)
+    need = cell_count("need", need)
     c = to_device(cells, torch.int32, dev)
     n = to_device(length, torch.int32, dev).reshape(-1)
     if c.ndim != 3 or c.shape[2] != 3 or c.shape[0] != n.shape[0]:
@@ -334,7 +314,7 @@ def shortcut_cells(dist2: Tensor, dims, need: int, cells: Tensor, length: Tensor
     keep = torch.empty(p, max_cells, dtype=torch.int32, device=dev)
     count = torch.empty(p, dtype=torch.int32, device=dev)
     blocked = torch.empty(p, dtype=torch.int32, device=dev)
-    _lib.check(_lib.load().gg_field_shortcut(d, _ptr(dist2), int(need), p, max_cells, _ptr(c) if p else None,
+    _lib.check(_lib.load().gg_field_shortcut(d, _ptr(dist2), need, p, max_cells, _ptr(c) if p else None,
                                              _ptr(n) if p else None, min(int(window), MAX_POSES), _ptr(keep),
                                              _ptr(count), _ptr(blocked), _stream(dev)), "gg_field_shortcut")
     return keep, count, blocked
@@ -399,12 +379,10 @@ def plan_transit(field: DistanceField, poses_from: ArrayLike, pose_to: ArrayLike
     then run through the kept cells only, `keep` and `count` say which, and `best` is the planned and clear path of
     the smallest `euclid` rather than of the smallest chamfer `cost` (which keeps its meaning).  `euclid` is filled
     either way."""
-    a = np.asarray(poses_from.detach().cpu() if isinstance(poses_from, Tensor) else poses_from, np.float64)
-    a = a.reshape(-1, 12)
-    b = np.asarray(pose_to.detach().cpu() if isinstance(pose_to, Tensor) else pose_to, np.float64).reshape(-1)
+    a, b = host_array(poses_from, np.float64).reshape(-1, 12), host_array(pose_to, np.float64).reshape(-1)
     if b.shape != (12,) or not (np.isfinite(a).all() and np.isfinite(b).all()):
         raise ValueError("poses_from is (P, 12) and pose_to (12,) finite numbers: R row-major, then t")
-    sp = np.asarray(spheres.detach().cpu() if isinstance(spheres, Tensor) else spheres, np.float32).reshape(-1, 3)
+    sp = host_array(spheres, np.float32).reshape(-1, 3)
     ctg = cost_to_go(field, b[None, 9:], planning_radius(sp, radius, field.h), margin, max_rounds)
     cells, length, at = descend(ctg, a[:, 9:])
     n, c, at = length.cpu().numpy(), cells.cpu().numpy(), at.cpu().numpy()
@@ -430,6 +408,7 @@ def plan_transit(field: DistanceField, poses_from: ArrayLike, pose_to: ArrayLike
 # command line
 # ------------------------------------------------------------------------------------------------
 def main(argv: Optional[Sequence[str]] = None) -> int:
+    from ._cli import add_gripper_sphere_options
     from .grasp import load_gripper_option
     ap = argparse.ArgumentParser(prog="python -m gaussiangrasper_amd.transit",
                                  description="Collision-free transit of the gripper through a saved distance field: "
@@ -437,12 +416,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--field", required=True, help=".npz of python -m gaussiangrasper_amd.field (--out)")
     ap.add_argument("--from", dest="start", required=True, help=".npy (P, 12) or (12,) start poses: R row-major, then t")
     ap.add_argument("--to", required=True, help=".npy (12,) goal pose")
-    ap.add_argument("--gripper", required=True, metavar="{default,FILE.json}", help="the gripper model")
-    ap.add_argument("--width", type=float, default=0.08, help="the gripper's opening, scene units")
-    ap.add_argument("--depth", type=float, default=0.02, help="the fingers' depth")
-    ap.add_argument("--height", type=float, default=0.02, help="the fingers' height")
-    ap.add_argument("--radius", type=float, default=0.005, help="radius of the covering spheres")
-    ap.add_argument("--margin", type=float, default=0.0, help="clearance kept beyond the spheres")
+    add_gripper_sphere_options(ap)
     ap.add_argument("--steps", type=int, default=STEPS, help="waypoints per path")
     ap.add_argument("--carried", default=None, help=".npy (N, 3) points of the carried object, gripper frame")
     ap.add_argument("--shortcut", action="store_true", help="pull the paths taut: poses through the kept cells only")
@@ -455,12 +429,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         ap.error("--window needs --shortcut")
     if a.window is not None and a.window < 1:
         ap.error(f"--window must be >= 1, got {a.window}")
-    for n in ("radius", "width"):
-        if not (math.isfinite(getattr(a, n)) and getattr(a, n) > 0.0):
-            ap.error(f"--{n} must be finite and > 0, got {getattr(a, n)}")
-    for n in ("margin", "depth", "height"):
-        if not (math.isfinite(getattr(a, n)) and getattr(a, n) >= 0.0):
-            ap.error(f"--{n} must be finite and >= 0, got {getattr(a, n)}")
+    check_finite_options(ap, a, positive=("radius", "width"), nonneg=("margin", "depth", "height"))
     if a.steps < 2:
         ap.error(f"--steps must be >= 2, got {a.steps}")
     try:
