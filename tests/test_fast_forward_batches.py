@@ -17,28 +17,10 @@ import numpy as np
 import pytest
 import torch
 
+from backward_cases import CONIC, QUADS, _np_inputs, _quadrant_lists, _reach      # noqa: F401 (shared constructions)
 from test_fast_forward import DEV, Pair, _close, _np, _t
 
 pytestmark = pytest.mark.gpu
-
-CONIC = 1.5625        # sigma = 0.8 pixels
-QUADS = ((0, 0), (8, 0), (0, 8), (8, 8))      # (x0, y0) of the four quadrants of tile 0
-
-
-def _np_inputs(xys, conics, radii, opac, col, bg, h, w):
-    """the oracle's argument tuple; list order = index order, tile counts from the radius box as the projection does"""
-    n = len(xys)
-    xys, conics = np.ascontiguousarray(xys, np.float32), np.ascontiguousarray(conics, np.float32)
-    radii = np.ascontiguousarray(radii, np.int32)
-    depths = np.linspace(1.0, 2.0, n).astype(np.float32)
-    tiles_x, tiles_y = (w + 15) // 16, (h + 15) // 16
-    x0 = np.clip(np.floor((xys[:, 0] - radii) / 16.0), 0, tiles_x)
-    x1 = np.clip(np.floor((xys[:, 0] + radii) / 16.0) + 1, 0, tiles_x)
-    y0 = np.clip(np.floor((xys[:, 1] - radii) / 16.0), 0, tiles_y)
-    y1 = np.clip(np.floor((xys[:, 1] + radii) / 16.0) + 1, 0, tiles_y)
-    nth = ((x1 - x0) * (y1 - y0)).astype(np.int32)
-    opac = np.ascontiguousarray(opac, np.float32).reshape(n, 1)
-    return xys, depths, radii, conics, nth, np.ascontiguousarray(col, np.float32), opac, np.ascontiguousarray(bg, np.float32)
 
 
 class Built(Pair):
@@ -57,23 +39,6 @@ class Built(Pair):
         b = P.bin_and_sort_gaussians(self.xys, _t(depths), _t(radii), _t(nth), h, w)
         self.ids, self.tile_bins = b.gaussian_ids_sorted, b.tile_bins
         self.ws = torch.empty(self.lib.gg_blend_workspace(self.n), dtype=torch.uint8, device=DEV)
-
-
-def _reach(opac, conic=CONIC):
-    return np.sqrt(2.0 * np.log(255.0 * np.asarray(opac, np.float64)) / conic)
-
-
-def _quadrant_lists(order, rng):
-    """small Gaussians, one per entry of `order` (quadrant numbers in list order), centred inside their quadrant"""
-    n = len(order)
-    opac = rng.uniform(0.02, 0.3, n)
-    assert _reach(opac).max() < 2.9           # centres keep 3 pixels from the neighbouring quadrants' pixel centres
-    q = np.asarray(order)
-    x0 = np.array([QUADS[k][0] for k in q], np.float64)
-    y0 = np.array([QUADS[k][1] for k in q], np.float64)
-    xys = np.stack([x0 + rng.uniform(2.0, 5.0, n), y0 + rng.uniform(2.0, 5.0, n)], axis=1)
-    conics = np.tile(np.float32([CONIC, 0.0, CONIC]), (n, 1))
-    return xys, conics, np.full(n, 3, np.int32), opac
 
 
 def _check(pc, oracle, tol_images=True):
