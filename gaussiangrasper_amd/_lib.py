@@ -162,6 +162,9 @@ SIGNATURES = {
     "gg_arm_fk": (_I, [_I, _P, _I, _P, _P, _P]),
     "gg_arm_follow": (_I, [_I, _P, _I, _I, _P, _I, _P] + [C.c_double] * 6 + [_I] + [_P] * 4 + [_P]),
     "gg_arm_clear": (_I, [_I, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, C.c_int32, _P, _P, _P]),
+    "gg_arm_self": (_I, [_I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "gg_arm_motion": (_I, [_I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P, C.c_int32, _P, _P, _P, C.c_double, _I]
+                      + [_P] * 7 + [_P]),
     "gg_prof_enable": (_I, [_I]),
     "gg_prof_reset": (_I, []),
     "gg_prof_get": (_I, [_I, C.POINTER(C.c_int), C.POINTER(C.c_double)]),

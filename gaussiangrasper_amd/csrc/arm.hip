@@ -15,6 +15,12 @@
 // gg_arm_clear    a one-wave workgroup per configuration: every lane runs the chain (the same values in all of them),
 //                 lane 0 leaves the J + 2 frames in LDS, the lanes stride over the spheres, and a butterfly over
 //                 (slack, index) leaves the minimum and the lowest sphere that attains it in every lane.
+// gg_arm_self     a one-wave workgroup per configuration: the frames as in clear, then the sphere centres in LDS, the
+//                 lanes stride over the pairs s < t in lexicographic order, and a butterfly over (gap, s S + t).
+// gg_arm_motion   a one-wave workgroup per edge: the sweep bound B by a butterfly maximum, the sample count n from it
+//                 (the same in every lane, read back through readfirstlane so that the sample loop is a scalar loop),
+//                 then per sample what clear and self do, and a running (minimum, first sample, index).  Whether
+//                 the field and the pairs are tested are template arguments, not conditions kept across the loops.
 //
 // All arithmetic is fp64 and the file is built with -ffp-contract=off: a composed entry is (a0 b0 + a1 b1) + a2 b2,
 // plus t, exactly as the header says.
@@ -446,6 +452,272 @@ __global__ __launch_bounds__(GG_WAVE) void arm_clear_kernel(ArmChain arm, FieldG
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// self and motion
+// ---------------------------------------------------------------------------------------------------------------
+// Which frame pairs are tested, as bits: bit f (J_MAX + 2) + g of the 100.  A kernel argument that lanes index with
+// their own f and g; two words and a shift need no array.
+struct ArmPairs {
+    unsigned long long lo, hi;
+    __device__ __forceinline__ bool on(int f, int g) const {
+        const int b = f * ARM_FRAMES + g;
+        return ((b < 64 ? lo >> b : hi >> (b - 64)) & 1ull) != 0;
+    }
+};
+
+// The dynamic LDS of one workgroup: the J + 2 frames, then per sphere the world centre (3 doubles) and the radius, then
+// the spheres' frames as bytes.
+struct ArmLds {
+    double *frames, *centre, *radius;
+    unsigned char *frame_of;
+};
+
+__device__ __forceinline__ ArmLds arm_lds(double *base, int S) {
+    ArmLds l;
+    l.frames = base;
+    l.centre = base + ARM_FRAMES * 12;
+    l.radius = l.centre + 3 * (size_t)S;
+    l.frame_of = (unsigned char *)(l.radius + S);
+    return l;
+}
+
+static size_t arm_lds_bytes(int S) { return (size_t)(ARM_FRAMES * 12 + 4 * S) * sizeof(double) + (size_t)S; }
+
+// What a workgroup reads of the sphere table once: the frame of every sphere, clamped into 0..J + 1 as clear clamps it,
+// and the radii when the pairs are tested.
+template <int J, bool SELF>
+__device__ __forceinline__ void arm_stage_spheres(const ArmLds &l, int lane, int S, const int *__restrict__ frame,
+                                                  const double *__restrict__ radius) {
+    for (int s = lane; s < S; s += GG_WAVE) {
+        l.frame_of[s] = (unsigned char)min(max(frame[s], 0), J + 1);
+        if (SELF) l.radius[s] = radius[s];
+    }
+}
+
+// Every lane runs the chain of q (the same values in all of them); lane 0 leaves F_0 .. F_{J+1} in LDS.
+template <int J>
+__device__ __forceinline__ void arm_frames_to_lds(const ArmChain &arm, const double *q, int lane, double *s_frames) {
+    double T[12], Mj[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) T[i] = arm.base[i];
+    if (lane == 0)
+#pragma unroll
+        for (int i = 0; i < 12; ++i) s_frames[i] = T[i];
+#pragma unroll
+    for (int j = 0; j < GG_ARM_MAX_JOINTS; ++j) {
+        if (j < J) {
+            arm_compose(T, arm.fixed[j]);
+            arm_motion(arm.rev[j], arm.pri[j], arm.axis[j], q[j], Mj);
+            arm_compose(T, Mj);
+            if (lane == 0)
+#pragma unroll
+                for (int i = 0; i < 12; ++i) s_frames[(j + 1) * 12 + i] = T[i];
+        }
+    }
+    arm_compose(T, arm.tip);
+    if (lane == 0)
+#pragma unroll
+        for (int i = 0; i < 12; ++i) s_frames[(J + 1) * 12 + i] = T[i];
+}
+
+// One configuration whose frames are in LDS: the lanes stride over the spheres; with FIELD the probe of clear and the
+// butterfly over (slack, sphere); with SELF the world centres go to LDS, in the probe's own operation order.
+template <bool FIELD, bool SELF>
+__device__ __forceinline__ void arm_sphere_pass(const ArmLds &l, const FieldGrid &g, const int *__restrict__ dist2,
+                                                int lane, int S, const float *__restrict__ spheres,
+                                                const int *__restrict__ need2, int outside, int *slack, int *worst) {
+    int best = GG_FIELD_FAR, who = INT32_MAX;
+    for (int s = lane; s < S; s += GG_WAVE) {
+        const double *T = l.frames + (int)l.frame_of[s] * 12;
+        const double x = (double)spheres[3 * s], y = (double)spheres[3 * s + 1], z = (double)spheres[3 * s + 2];
+        if (FIELD) {
+            const int sl = field_probe(g, dist2, T, x, y, z, outside) - need2[s];
+            if (sl < best || (sl == best && s < who)) best = sl, who = s;
+        }
+        if (SELF) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) l.centre[3 * s + a] = ((T[3 * a] * x + T[3 * a + 1] * y) + T[3 * a + 2] * z) + T[9 + a];
+        }
+    }
+    if (FIELD) {
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const int ob = __shfl_xor(best, off, GG_WAVE), ow = __shfl_xor(who, off, GG_WAVE);
+            if (ob < best || (ob == best && ow < who)) best = ob, who = ow;
+        }
+    }
+    *slack = best;
+    *worst = who == INT32_MAX ? -1 : who;
+}
+
+// The centres are in LDS: lane l takes the pairs l, l + 64, ... of the lexicographic order of (s, t), s < t, walking
+// (s, t) forward row by row; the butterfly over (gap, s S + t) leaves the minimum and the lowest pair that attains it
+// in every lane.  key INT32_MAX: no tested pair.
+__device__ __forceinline__ void arm_pair_pass(const ArmLds &l, const ArmPairs &pairs, int lane, int S, double *gap,
+                                              int *key) {
+    double best = __builtin_inf();
+    int who = INT32_MAX;
+    int s = 0, t = 1 + lane;
+    for (;;) {
+        while (t >= S && s < S - 1) {                            // past the end of row s: on into row s + 1
+            t -= S;
+            ++s;
+            t += s + 1;
+        }
+        if (s >= S - 1) break;
+        if (pairs.on((int)l.frame_of[s], (int)l.frame_of[t])) {
+            const double dx = l.centre[3 * s] - l.centre[3 * t], dy = l.centre[3 * s + 1] - l.centre[3 * t + 1],
+                         dz = l.centre[3 * s + 2] - l.centre[3 * t + 2];
+            const double d2 = (dx * dx + dy * dy) + dz * dz;
+            const double gp = sqrt(d2) - (l.radius[s] + l.radius[t]);
+            const int k = s * S + t;
+            if (gp < best || (gp == best && k < who)) best = gp, who = k;
+        }
+        t += GG_WAVE;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double ob = __shfl_xor(best, off, GG_WAVE);
+        const int ow = __shfl_xor(who, off, GG_WAVE);
+        if (ob < best || (ob == best && ow < who)) best = ob, who = ow;
+    }
+    *gap = best;
+    *key = who;
+}
+
+template <int J>
+__global__ __launch_bounds__(GG_WAVE) void arm_self_kernel(ArmChain arm, ArmPairs pairs, int M,
+                                                           const double *__restrict__ q_in, int S,
+                                                           const float *__restrict__ spheres,
+                                                           const int *__restrict__ frame,
+                                                           const double *__restrict__ radius, double *__restrict__ gap,
+                                                           int *__restrict__ pair) {
+    extern __shared__ double arm_dyn[];
+    const ArmLds l = arm_lds(arm_dyn, S);
+    const int m = blockIdx.x;                                    // one wave, one configuration; the grid is M
+    const int lane = threadIdx.x;
+    double q[GG_ARM_MAX_JOINTS];
+#pragma unroll
+    for (int j = 0; j < GG_ARM_MAX_JOINTS; ++j) q[j] = j < J ? q_in[(size_t)m * J + j] : 0.0;
+    if (!arm_finite_q<J>(q)) {                                 // the same in every lane of the wave
+        if (lane == 0) {
+            gap[m] = __builtin_nan("");
+            pair[2 * (size_t)m] = -1;
+            pair[2 * (size_t)m + 1] = -1;
+        }
+        return;
+    }
+    arm_stage_spheres<J, true>(l, lane, S, frame, radius);
+    arm_frames_to_lds<J>(arm, q, lane, l.frames);
+    __syncthreads();                                             // a one-wave workgroup: the LDS writes are done
+    int unused_slack, unused_worst;
+    arm_sphere_pass<false, true>(l, FieldGrid{}, nullptr, lane, S, spheres, nullptr, 0, &unused_slack, &unused_worst);
+    __syncthreads();
+    double gp;
+    int key;
+    arm_pair_pass(l, pairs, lane, S, &gp, &key);
+    if (lane == 0) {
+        gap[m] = gp;
+        pair[2 * (size_t)m] = key == INT32_MAX ? -1 : key / S;
+        pair[2 * (size_t)m + 1] = key == INT32_MAX ? -1 : key % S;
+    }
+}
+
+struct ArmMotionOut {
+    int *samples, *slack, *slack_at, *worst;
+    double *gap;
+    int *gap_at, *pair;
+};
+
+template <int J, bool FIELD, bool SELF>
+__global__ __launch_bounds__(GG_WAVE) void arm_motion_kernel(ArmChain arm, ArmPairs pairs, FieldGrid g,
+                                                             const int *__restrict__ dist2, int E,
+                                                             const double *__restrict__ q_a,
+                                                             const double *__restrict__ q_b, int S,
+                                                             const float *__restrict__ spheres,
+                                                             const int *__restrict__ frame,
+                                                             const int *__restrict__ need2, int outside,
+                                                             const double *__restrict__ radius,
+                                                             const double *__restrict__ reach, double res,
+                                                             int max_samples, ArmMotionOut out) {
+    extern __shared__ double arm_dyn[];
+    const ArmLds l = arm_lds(arm_dyn, S);
+    const int e = blockIdx.x;                                    // one wave, one edge; the grid is E
+    const int lane = threadIdx.x;
+    double qa[GG_ARM_MAX_JOINTS], dq[GG_ARM_MAX_JOINTS], qb[GG_ARM_MAX_JOINTS];
+#pragma unroll
+    for (int j = 0; j < GG_ARM_MAX_JOINTS; ++j) {
+        qa[j] = j < J ? q_a[(size_t)e * J + j] : 0.0;
+        qb[j] = j < J ? q_b[(size_t)e * J + j] : 0.0;
+    }
+    // the sweep bound: b_s with j ascending from 0.0, B their maximum (exact, so the butterfly's order does not matter)
+    double B = 0.0;
+    int n = 0;
+#pragma unroll
+    for (int j = 0; j < GG_ARM_MAX_JOINTS; ++j) dq[j] = qb[j] - qa[j];
+    // the same in every lane of the wave, and a scalar: no lane mask of it lives across the loops below
+    if (__builtin_amdgcn_readfirstlane((int)(arm_finite_q<J>(qa) && arm_finite_q<J>(qb)))) {
+        for (int s = lane; s < S; s += GG_WAVE) {
+            double b = 0.0;
+#pragma unroll
+            for (int j = 0; j < GG_ARM_MAX_JOINTS; ++j)
+                if (j < J) b = b + fabs(dq[j]) * reach[(size_t)j * S + s];
+            B = fmax(B, b);
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) B = fmax(B, __shfl_xor(B, off, GG_WAVE));
+        if (!(B > (double)max_samples * res)) {
+            // the smallest n >= 1 with n res >= B: the division proposes, the comparisons decide
+            const double guess = ceil(B / res);
+            n = guess >= 1.0 ? (guess <= (double)max_samples ? (int)guess : max_samples) : 1;
+            while (n < max_samples && (double)n * res < B) ++n;
+            while (n > 1 && (double)(n - 1) * res >= B) --n;
+        }
+    }
+    n = __builtin_amdgcn_readfirstlane(n);                       // a scalar: the sample loop is the same for the wave
+    if (n == 0) {                                                // not finite, or not resolved by max_samples
+        if (lane == 0) {
+            out.samples[e] = 0;
+            out.slack[e] = INT32_MIN;
+            out.slack_at[e] = out.worst[e] = out.gap_at[e] = -1;
+            out.gap[e] = __builtin_nan("");
+            out.pair[2 * (size_t)e] = out.pair[2 * (size_t)e + 1] = -1;
+        }
+        return;
+    }
+    arm_stage_spheres<J, SELF>(l, lane, S, frame, radius);
+    int slack = INT32_MAX, slack_at = 0, worst = -1, gap_at = 0, gap_key = INT32_MAX;
+    double gap = __builtin_inf();
+    for (int i = 0; i <= n; ++i) {
+        double q[GG_ARM_MAX_JOINTS];
+        const double f = (double)i / (double)n;
+#pragma unroll
+        for (int j = 0; j < GG_ARM_MAX_JOINTS; ++j) q[j] = i == n ? qb[j] : qa[j] + f * dq[j];
+        arm_frames_to_lds<J>(arm, q, lane, l.frames);
+        __syncthreads();                                         // frames (and, at i == 0, the sphere table) are in LDS
+        int sl, wo;
+        arm_sphere_pass<FIELD, SELF>(l, g, dist2, lane, S, spheres, need2, outside, &sl, &wo);
+        if (FIELD && sl < slack) slack = sl, slack_at = i, worst = wo;
+        __syncthreads();                                         // the centres are in LDS; the frames may be rewritten
+        if (SELF) {
+            double gp;
+            int key;
+            arm_pair_pass(l, pairs, lane, S, &gp, &key);
+            if (gp < gap) gap = gp, gap_at = i, gap_key = key;
+        }
+    }
+    if (lane == 0) {
+        out.samples[e] = n;
+        out.slack[e] = FIELD ? slack : GG_FIELD_FAR;
+        out.slack_at[e] = FIELD ? slack_at : -1;
+        out.worst[e] = FIELD ? worst : -1;
+        out.gap[e] = gap;
+        out.gap_at[e] = SELF ? gap_at : -1;
+        out.pair[2 * (size_t)e] = gap_key == INT32_MAX ? -1 : gap_key / S;
+        out.pair[2 * (size_t)e + 1] = gap_key == INT32_MAX ? -1 : gap_key % S;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------------------------
 static bool arm_rotation_ok(const double *T) {
@@ -587,6 +859,95 @@ extern "C" int gg_arm_clear(int num_joints, const double *arm, const int32_t *di
         hipLaunchKernelGGL((arm_clear_kernel<decltype(joints)::value>), dim3((unsigned)num_rows), dim3(GG_WAVE), 0,
                            (hipStream_t)stream, c, g, dist2, num_rows, q, num_spheres, spheres, frame, need2, outside,
                            slack, worst);
+    });
+    GG_CHECK_LAUNCH();
+    return GG_OK;
+}
+
+// The host table `pairs` [(J + 2)][(J + 2)] as the kernels' bits; null: nothing is tested.
+static ArmPairs arm_pairs(int J, const uint8_t *pairs) {
+    ArmPairs p{0ull, 0ull};
+    if (!pairs) return p;
+    for (int f = 0; f < J + 2; ++f)
+        for (int g = 0; g < J + 2; ++g)
+            if (pairs[f * (J + 2) + g]) {
+                const int b = f * ARM_FRAMES + g;
+                (b < 64 ? p.lo : p.hi) |= 1ull << (b & 63);
+            }
+    return p;
+}
+
+extern "C" int gg_arm_self(int num_joints, const double *arm, int num_rows, const double *q, int num_spheres,
+                           const float *spheres, const int32_t *frame, const double *radius, const uint8_t *pairs,
+                           double *gap, int32_t *pair, gg_stream_t stream) {
+    ArmChain c;
+    if (!arm_chain(__func__, num_joints, arm, &c)) return GG_ERR_INVALID_ARG;
+    GG_REQUIRE(num_rows >= 0 && num_rows <= GG_FIELD_MAX_POSES, "need 0 <= num_rows <= GG_FIELD_MAX_POSES");
+    GG_REQUIRE(num_spheres >= 0 && num_spheres <= GG_ARM_MAX_SELF_SPHERES,
+               "num_spheres must be in 0..GG_ARM_MAX_SELF_SPHERES");
+    GG_REQUIRE(pairs, "null pointer: pairs (a host array of (num_joints + 2)^2 bytes)");
+    if (num_rows == 0) return GG_OK;
+    GG_REQUIRE(q && gap && pair, "null pointer: q / gap / pair");
+    GG_REQUIRE(num_spheres == 0 || (spheres && frame && radius), "null pointer: spheres / frame / radius");
+    GG_REQUIRE((((uintptr_t)q | (uintptr_t)radius | (uintptr_t)gap) & 7) == 0 &&
+                   (((uintptr_t)spheres | (uintptr_t)frame | (uintptr_t)pair) & 3) == 0,
+               "q / radius / gap / spheres / frame / pair misaligned");
+    const ArmPairs p = arm_pairs(num_joints, pairs);
+    arm_dispatch(num_joints, [&](auto joints) {
+        hipLaunchKernelGGL((arm_self_kernel<decltype(joints)::value>), dim3((unsigned)num_rows), dim3(GG_WAVE),
+                           arm_lds_bytes(num_spheres), (hipStream_t)stream, c, p, num_rows, q, num_spheres, spheres,
+                           frame, radius, gap, pair);
+    });
+    GG_CHECK_LAUNCH();
+    return GG_OK;
+}
+
+extern "C" int gg_arm_motion(int num_joints, const double *arm, const int32_t *dims, const double *grid,
+                             const int32_t *dist2, int num_edges, const double *q_a, const double *q_b,
+                             int num_spheres, const float *spheres, const int32_t *frame, const int32_t *need2,
+                             int32_t outside, const double *radius, const uint8_t *pairs, const double *reach,
+                             double res, int max_samples, int32_t *samples, int32_t *slack, int32_t *slack_at,
+                             int32_t *worst, double *gap, int32_t *gap_at, int32_t *pair, gg_stream_t stream) {
+    ArmChain c;
+    if (!arm_chain(__func__, num_joints, arm, &c)) return GG_ERR_INVALID_ARG;
+    FieldGrid g{};
+    if (dist2) {
+        GG_REQUIRE(field_dims_ok(dims), FIELD_DIMS_MSG);
+        GG_REQUIRE(grid, "null pointer: grid (a host array of 4 doubles)");
+        GG_REQUIRE(field_grid(dims, grid, &g), FIELD_GRID_MSG);
+        GG_REQUIRE(outside >= 0 && outside <= GG_FIELD_FAR, "outside must be in 0..GG_FIELD_FAR");
+    }
+    GG_REQUIRE(num_edges >= 0 && num_edges <= GG_FIELD_MAX_POSES, "need 0 <= num_edges <= GG_FIELD_MAX_POSES");
+    GG_REQUIRE(num_spheres >= 0 && num_spheres <= GG_ARM_MAX_SELF_SPHERES,
+               "num_spheres must be in 0..GG_ARM_MAX_SELF_SPHERES");
+    GG_REQUIRE(isfinite(res) && res > 0.0, "res must be finite and > 0");
+    GG_REQUIRE(max_samples >= 1 && max_samples <= GG_ARM_MAX_SAMPLES, "max_samples must be in 1..GG_ARM_MAX_SAMPLES");
+    if (num_edges == 0) return GG_OK;
+    GG_REQUIRE(q_a && q_b, "null pointer: q_a / q_b");
+    GG_REQUIRE(samples && slack && slack_at && worst && gap && gap_at && pair,
+               "null pointer: samples / slack / slack_at / worst / gap / gap_at / pair");
+    GG_REQUIRE(num_spheres == 0 || (spheres && frame && reach), "null pointer: spheres / frame / reach");
+    GG_REQUIRE(num_spheres == 0 || !dist2 || need2, "null pointer: need2");
+    GG_REQUIRE(num_spheres == 0 || !pairs || radius, "null pointer: radius");
+    GG_REQUIRE((((uintptr_t)q_a | (uintptr_t)q_b | (uintptr_t)radius | (uintptr_t)reach | (uintptr_t)gap) & 7) == 0,
+               "q_a / q_b / radius / reach / gap misaligned");
+    GG_REQUIRE((((uintptr_t)dist2 | (uintptr_t)spheres | (uintptr_t)frame | (uintptr_t)need2 | (uintptr_t)samples |
+                 (uintptr_t)slack | (uintptr_t)slack_at | (uintptr_t)worst | (uintptr_t)gap_at | (uintptr_t)pair) & 3) == 0,
+               "dist2 / spheres / frame / need2 / samples / slack / slack_at / worst / gap_at / pair misaligned");
+    const ArmPairs p = arm_pairs(num_joints, pairs);
+    const ArmMotionOut out{samples, slack, slack_at, worst, gap, gap_at, pair};
+    const bool with_field = dist2 != nullptr, with_self = pairs != nullptr;
+    arm_dispatch(num_joints, [&](auto joints) {
+        constexpr int J = decltype(joints)::value;
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)num_edges), dim3(GG_WAVE), arm_lds_bytes(num_spheres),
+                               (hipStream_t)stream, c, p, g, dist2, num_edges, q_a, q_b, num_spheres, spheres, frame,
+                               need2, outside, radius, reach, res, max_samples, out);
+        };
+        if (with_field && with_self) launch(arm_motion_kernel<J, true, true>);
+        else if (with_field) launch(arm_motion_kernel<J, true, false>);
+        else if (with_self) launch(arm_motion_kernel<J, false, true>);
+        else launch(arm_motion_kernel<J, false, false>);
     });
     GG_CHECK_LAUNCH();
     return GG_OK;

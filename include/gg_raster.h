@@ -1385,9 +1385,51 @@ int gg_place_search(const int32_t *dims, const int32_t *top, int num_yaws, const
  * not finite.  worst int32 [M] = the lowest s that attains the minimum, -1 when S == 0 or the row is not finite.  No
  * atomics.  S <= GG_FIELD_MAX_SPHERES, M <= GG_FIELD_MAX_POSES; M == 0 writes nothing.  q 8-byte aligned, the other
  * arrays 4-byte.
+ *
+ * gg_arm_self and gg_arm_motion: the arm against itself, and a straight joint-space move against the field and
+ * against itself.  The arm, frames, sphere centres c, cell rule, need2 and outside: exactly as gg_arm_clear states
+ * them.  New inputs: radius fp64 [S] (metres; THE CALLER'S DUTY: finite, >= 0); pairs, a HOST array of
+ * (J + 2) x (J + 2) bytes: the sphere pair s < t is TESTED iff pairs[frame[s]][frame[t]] != 0 (frame clamped as in
+ * gg_arm_clear; the caller passes it symmetric); reach fp64 [J][S] (THE CALLER'S DUTY: finite, >= 0; below).
+ * S <= GG_ARM_MAX_SELF_SPHERES for both entries.
+ *
+ * gg_arm_self: q fp64 [M][J].  For every tested pair d2 = (dx dx + dy dy) + dz dz with d = c_s - c_t, g = sqrt(d2) -
+ * (r_s + r_t), all fp64, no contraction.  gap fp64 [M] = the minimum g; pair int32 [M][2] = the lexicographically
+ * lowest (s, t) that attains it.  With no tested pair: +inf and (-1, -1).  For a q that is not finite: NaN and
+ * (-1, -1).  M <= GG_FIELD_MAX_POSES; M == 0 writes nothing.  pairs must not be null here.
+ *
+ * gg_arm_motion: edges q_a, q_b fp64 [E][J]; res finite and > 0; 1 <= max_samples <= GG_ARM_MAX_SAMPLES; E <=
+ * GG_FIELD_MAX_POSES.  Per edge:
+ *   1. The sweep bound: b_s = sum_j |q_b[j] - q_a[j]| reach[j][s], added for j ascending onto 0.0; B = max_s b_s, 0
+ *      when S == 0.
+ *   2. If B > (double)max_samples res the edge is UNRESOLVED: samples = 0, slack = INT32_MIN, slack_at = worst =
+ *      gap_at = -1, gap = NaN, pair = (-1, -1).  An edge with an entry of q_a or q_b that is not finite gets the same
+ *      outputs.
+ *   3. Otherwise n = the smallest integer >= 1 with (double)n res >= B (a division may propose it; these comparisons
+ *      decide it), and samples i = 0 .. n at q_i[j] = q_a[j] + ((double)i / (double)n) (q_b[j] - q_a[j]), the product
+ *      rounded, then the sum; sample n is q_b itself.
+ *   4. Per sample gg_arm_clear's (slack, worst) and gg_arm_self's (gap, pair).  samples int32 [E] = n; slack int32 [E]
+ *      = the minimum over the samples, slack_at int32 [E] = the lowest i that attains it, worst int32 [E] = the worst
+ *      sphere of that sample; gap fp64 [E], gap_at int32 [E], pair int32 [E][2] likewise (with no tested pair at all:
+ *      +inf, 0, (-1, -1); with S == 0: slack GG_FIELD_FAR, slack_at 0, worst -1).
+ * dist2 null: no field test (dims, grid, need2 and outside are not read): slack = GG_FIELD_FAR, slack_at = worst = -1.
+ * pairs null: no self test (radius is not read): gap = +inf, gap_at = -1, pair = (-1, -1).  No atomics; the same
+ * inputs give the same bytes; E == 0 writes nothing.
+ * WHAT THE OUTPUTS PROVE.  Assume reach[j][s] bounds the speed of sphere s's centre per unit of q_j wherever the
+ * joints are within their limits (for a revolute joint: the largest distance of the centre from the joint's axis;
+ * for a prismatic one: 1).  PRISMATIC JOINTS MUST BE INSIDE THEIR LIMITS ALONG THE EDGE FOR THE BOUND TO HOLD: THE
+ * CALLER'S DUTY.  Along the joint-linear motion q(t) = q_a + t (q_b - q_a) every centre then moves by at most b_s <= B
+ * in all, so by at most B / n <= res between consecutive samples, and every point of the motion is within res / 2 of
+ * a sampled position of the same sphere.  Hence: slack >= 0 with need2 = the distance field's need2(radius + res / 2,
+ * margin, h) proves that the balls of radius + margin about the centres meet no occupied cell at any time of the
+ * motion; gap >= self_margin + res proves that no tested pair comes closer than self_margin at any time (from the nearer
+ * of the two neighbouring samples the two centres have moved by at most res together).  DESIGN 3.33 has the proof.
+ * fp64 arrays 8-byte aligned, the others 4-byte.
  * Null, misaligned or out-of-range arguments: GG_ERR_INVALID_ARG naming the argument, before any launch. */
 #define GG_ARM_MAX_JOINTS 8
 #define GG_ARM_MAX_ITER 1024
+#define GG_ARM_MAX_SELF_SPHERES 256
+#define GG_ARM_MAX_SAMPLES 4096
 #define GG_ARM_DOUBLES(J) (12 * ((J) + 2) + 6 * (J))
 int gg_arm_fk(int num_joints, const double *arm, int num_rows, const double *q, double *frames, gg_stream_t stream);
 int gg_arm_follow(int num_joints, const double *arm, int num_paths, int num_waypoints, const float *poses,
@@ -1397,6 +1439,15 @@ int gg_arm_follow(int num_joints, const double *arm, int num_paths, int num_wayp
 int gg_arm_clear(int num_joints, const double *arm, const int32_t *dims, const double *grid, const int32_t *dist2,
                  int num_rows, const double *q, int num_spheres, const float *spheres, const int32_t *frame,
                  const int32_t *need2, int32_t outside, int32_t *slack, int32_t *worst, gg_stream_t stream);
+int gg_arm_self(int num_joints, const double *arm, int num_rows, const double *q, int num_spheres,
+                const float *spheres, const int32_t *frame, const double *radius, const uint8_t *pairs, double *gap,
+                int32_t *pair, gg_stream_t stream);
+int gg_arm_motion(int num_joints, const double *arm, const int32_t *dims, const double *grid, const int32_t *dist2,
+                  int num_edges, const double *q_a, const double *q_b, int num_spheres, const float *spheres,
+                  const int32_t *frame, const int32_t *need2, int32_t outside, const double *radius,
+                  const uint8_t *pairs, const double *reach, double res, int max_samples, int32_t *samples,
+                  int32_t *slack, int32_t *slack_at, int32_t *worst, double *gap, int32_t *gap_at, int32_t *pair,
+                  gg_stream_t stream);
 
 /* ---- in-library kernel timing (measurement only; off by default) --------------------------------
  * When enabled, every launch of the kernels below is bracketed by a hipEvent pair recorded on the
