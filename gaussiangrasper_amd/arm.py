@@ -20,10 +20,10 @@ in DESIGN.md §3.31 and §3.33.
     python -m gaussiangrasper_amd.arm --arm {default,FILE.json} (--grasps G.npy --standoff D --steps N | --poses P.npy)
                                       [--field field.npz --radius R --margin M] --out q.npy --report r.npz
                                       [--check-motion --motion-res R --self-margin M --max-samples N]
-                                      [--connect-from Q.npy]
+                                      [--connect-from Q.npy [--connect-roadmap {N,FILE.npz}]]
 
-Out of scope: a sampling planner (RRT, PRM) between configurations, velocity and torque limits.  The spheres cover the
-link models they are given and nothing more."""
+Routes through more than one intermediate configuration are roadmap.py's (a probabilistic roadmap over `motion`).  Out of
+scope: velocity and torque limits.  The spheres cover the link models they are given and nothing more."""
 from __future__ import annotations
 
 import argparse
@@ -838,6 +838,10 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--connect-from", default=None, metavar="Q.npy",
                     help=".npy (A, J) or (J,) configurations: a clear move (direct, or through one via configuration) "
                          "from each to the first configuration of every path")
+    ap.add_argument("--connect-roadmap", default=None, metavar="{N,FILE.npz}",
+                    help="with --connect-from: plan through a roadmap (gaussiangrasper_amd.roadmap) of N sampled "
+                         "configurations, or through a saved one, in place of the one-via search; the report then has "
+                         "roadmap_cost, roadmap_hops and roadmap_waypoints")
     ap.add_argument("--out", required=True, help="output .npy (P, W, J) joint configurations (NaN: not reachable)")
     ap.add_argument("--report", required=True, help="output .npz reachable, clear, seed, slack, worst, jump, "
                                                     "first_fail, iters; with --check-motion also motion_ok, samples, "
@@ -859,6 +863,14 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         ap.error("--check-motion and --connect-from need --field or --motion-res")
     if not 1 <= a.max_samples <= MAX_SAMPLES:
         ap.error(f"--max-samples must be in 1..{MAX_SAMPLES}, got {a.max_samples}")
+    if a.connect_roadmap is not None:
+        if not a.connect_from:
+            ap.error("--connect-roadmap goes with --connect-from")
+        if not a.connect_roadmap.endswith(".npz"):
+            from .roadmap import MAX_NODES
+            if not (a.connect_roadmap.isdigit() and 1 <= int(a.connect_roadmap) <= MAX_NODES):
+                ap.error(f"--connect-roadmap must be a number of nodes in 1..{MAX_NODES} or a .npz file, got "
+                         f"{a.connect_roadmap}")
     if a.seeds < 1:
         ap.error(f"--seeds must be >= 1, got {a.seeds}")
     if not 0 <= a.max_iter <= MAX_ITER:
@@ -899,6 +911,22 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             start = start.reshape(-1, J)
             q0 = res.q[:, 0].cpu().numpy() if poses.shape[1] else np.zeros((0, J))
             have = np.nonzero(np.isfinite(q0).all(1))[0]
+        if a.connect_from and a.connect_roadmap is not None:
+            from . import roadmap as _roadmap
+            mkw = dict(spheres=spheres, radius=a.radius, margin=a.margin, self_margin=a.self_margin, res=a.motion_res,
+                       max_samples=a.max_samples)
+            if a.connect_roadmap.endswith(".npz"):
+                pl = _roadmap.plan(arm, start, q0[have], field,
+                                   roadmap=_roadmap.Roadmap.load(a.connect_roadmap).attach(arm, field))
+            else:
+                pl = _roadmap.plan(arm, start, q0[have], field, num_nodes=int(a.connect_roadmap), seed=a.seed, **mkw)
+            rep = _roadmap.plan_report(pl)
+            cost = np.full((len(start), len(q0)), -1, np.int64)
+            hops = np.full((len(start), len(q0)), -1, np.int64)
+            way = np.full((len(start), len(q0)) + rep["waypoints"].shape[2:], np.nan)
+            cost[:, have], hops[:, have], way[:, have] = rep["cost"], rep["hops"], rep["waypoints"]
+            report.update(roadmap_cost=cost, roadmap_hops=hops, roadmap_waypoints=way)
+        elif a.connect_from:
             con = connect(arm, start, q0[have], field, seed=a.seed, spheres=spheres, radius=a.radius, margin=a.margin,
                           self_margin=a.self_margin, res=a.motion_res, max_samples=a.max_samples)
             via = np.full((len(start), len(q0)), -2, np.int64)
@@ -916,7 +944,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     print(f"{int(res.reachable.sum())} of {poses.shape[0]} paths reachable, {int(res.clear.sum())} clear"
           + ("" if field is not None else " (no field: clearance not tested)")
           + (f", {int(res.motion_ok.sum())} with every move between waypoints clear" if a.check_motion else "")
-          + (f", {int((report['connect_via'] != -2).sum())} of {report['connect_via'].size} connections found"
+          + (f", {int((report['roadmap_hops'] >= 0).sum())} of {report['roadmap_hops'].size} connections found through "
+             "the roadmap" if a.connect_from and a.connect_roadmap is not None else
+             f", {int((report['connect_via'] != -2).sum())} of {report['connect_via'].size} connections found"
              if a.connect_from else "") + f"; wrote {a.out} and {a.report}")
     return 0
 

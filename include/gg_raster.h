@@ -1449,6 +1449,72 @@ int gg_arm_motion(int num_joints, const double *arm, const int32_t *dims, const 
                   int32_t *slack, int32_t *slack_at, int32_t *worst, double *gap, int32_t *gap_at, int32_t *pair,
                   gg_stream_t stream);
 
+/* ---- arm roadmap: joint-space neighbours and exact shortest routes over a checked graph (csrc/roadmap.hip) --------
+ * Source of the contract: none in the reference; the probabilistic roadmap is textbook (Kavraki et al. 1996), every
+ * constant is this project's choice (PARITY.md "Arm roadmap").  All three entries are pure functions of their inputs:
+ * integer or fixed-order fp64 decisions, the same inputs give the same bytes.
+ *
+ * gg_roadmap_neighbours: the k nearest nodes of every query in a weighted joint metric.  J = num_joints in
+ * 1..GG_ARM_MAX_JOINTS; nodes fp64 [N][J], N <= GG_ROADMAP_MAX_NODES; queries fp64 [M][J], M <= GG_FIELD_MAX_POSES;
+ * metric, a HOST array of J doubles, each finite and >= 0; skip int32 [M]: a node index the query must not return, or
+ * -1 (null: none); valid uint8 [N], any address (null: every node is valid); k in 1..GG_ROADMAP_MAX_K.
+ *   d2(m, i) = ((e_0 e_0 + e_1 e_1) + ...) + e_{J-1} e_{J-1},  e_j = metric[j] (queries[m][j] - nodes[i][j]),
+ * all fp64, every operation rounded (no contraction), j ascending.  Node i TAKES PART for query m iff valid[i] != 0,
+ * every entry of the node is finite, i != skip[m] and d2 < +inf.  idx int32 [M][k] and d2 fp64 [M][k]: the k nodes
+ * that take part of smallest (d2, i), lexicographic, ascending; with fewer than k of them the remaining slots hold -1
+ * and +inf.  A query with an entry that is not finite: every slot -1 and NaN.  A node equal to the query under
+ * another index is a neighbour at distance 0.  No atomics.  M == 0 writes nothing; N == 0 writes the empty rows.
+ * nodes, queries, d2 8-byte aligned; skip, idx 4-byte.
+ *
+ * THE GRAPH of gg_roadmap_route and gg_roadmap_descend, in CSR: offsets int32 [N + 1], targets and weights int32 [E]
+ * with E = num_edges <= 2^27; the edges of node i are offsets[i] .. offsets[i + 1] - 1.  THE CALLER'S DUTY: offsets
+ * does not decrease, offsets[0] == 0, offsets[N] <= E (the kernels cut every row to 0..E, so a broken table reads
+ * nothing outside the arrays, and computes nothing of use).  max_weight >= 1 and (int64) N max_weight < 2^30, checked
+ * on the host: with it no cost of a walk without repeated nodes reaches GG_FIELD_FAR.  Edge e of node i is USABLE iff
+ * 0 <= targets[e] < N and 1 <= weights[e] <= max_weight; other edges take no part.  Self loops and parallel edges
+ * are allowed.  The graph is directed: an undirected one stores both directions.
+ *
+ * gg_roadmap_route: cost-to-go for Q = num_queries goal sets.  goal_offsets, a HOST array of Q + 1 ints (checked:
+ * starts at 0, does not decrease, at most 2^27 goals); goals int32 [G], G = goal_offsets[Q]: the goals of query q are
+ * goals[goal_offsets[q] .. goal_offsets[q + 1] - 1]; a goal outside 0..N-1 takes no part, duplicates take part.
+ * cost int32 [Q][N], Q N <= 2^27, written whole: the smallest sum of weights over the walks of usable edges from the
+ * node to a goal of the query; 0 on a goal; exactly GG_FIELD_FAR where no walk exists, and everywhere for a query
+ * without a goal that takes part.  ignored int64 (device, written): the edges of the rows that are not usable,
+ * counted once per call.  The values are integers and relaxation only lowers them, so the result, the greatest fixed
+ * point below GG_FIELD_FAR, does not depend on the schedule.  Rounds of pull relaxation, one launch each: every (query,
+ * node) takes the minimum over its own row of weights[e] + cost[targets[e]], in place.  No kernel waits for another
+ * workgroup.  A changed flag per round is read back once per batch of rounds: THE CALL SYNCHRONISES `stream` AND
+ * CANNOT BE CAPTURED INTO A GRAPH.  max_rounds >= 1; rounds_out, a HOST int: the rounds run, the last of which
+ * changed nothing.  When max_rounds run out before that the call returns GG_ERR_NOT_CONVERGED; cost then holds VALID
+ * UPPER BOUNDS: every value below GG_FIELD_FAR is the weight of a real walk to a goal.  ws: gg_roadmap_route_workspace(N,
+ * Q) bytes (0: out of range), 256-byte aligned.  Arrays 4-byte aligned, ignored 8-byte.
+ *
+ * gg_roadmap_descend: walks down a cost-to-go.  cost int32 [Q][N] as gg_roadmap_route wrote it; query int32 [P] and
+ * starts int32 [P]; max_nodes >= 1, P max_nodes <= GG_FIELD_MAX_POSES; path int32 [P][max_nodes], length int32 [P].
+ * From a start with cost < GG_FIELD_FAR: while the cost here is not 0, take the usable edge with cost[target] +
+ * weight == cost[here] of the LOWEST POSITION IN THE ROW.  Weights are >= 1, so the cost falls strictly and the walk
+ * visits no node twice.  length = the nodes of the whole path, start and goal included; 0 for a query or a start out
+ * of range, a start at GG_FIELD_FAR, or a cost that is not route's fixed point (no edge fits).  With length >
+ * max_nodes the path is cut and length still counts all of it; rows from length on repeat the last node; with
+ * length 0 every row is -1: gg_field_descend's behaviour.  No atomics.  P == 0 writes nothing.  Arrays 4-byte aligned.
+ *
+ * Null, misaligned or out-of-range arguments: GG_ERR_INVALID_ARG naming the argument, before any launch. */
+#define GG_ROADMAP_MAX_K 32
+#define GG_ROADMAP_MAX_NODES 65536
+#define GG_ROADMAP_TILE 256 /* nodes staged per tile by gg_roadmap_neighbours: not part of the result, the tests' edge */
+int gg_roadmap_neighbours(int num_joints, int num_nodes, const double *nodes, int num_queries, const double *queries,
+                          const double *metric, const int32_t *skip, const uint8_t *valid, int k, int32_t *idx,
+                          double *d2, gg_stream_t stream);
+size_t gg_roadmap_route_workspace(int num_nodes, int num_queries);
+int gg_roadmap_route(int num_nodes, int num_edges, const int32_t *offsets, const int32_t *targets,
+                     const int32_t *weights, int32_t max_weight, int num_queries, const int32_t *goal_offsets,
+                     const int32_t *goals, int32_t *cost, int64_t *ignored, int max_rounds, int *rounds_out, void *ws,
+                     size_t ws_bytes, gg_stream_t stream);
+int gg_roadmap_descend(int num_nodes, int num_edges, const int32_t *offsets, const int32_t *targets,
+                       const int32_t *weights, int32_t max_weight, int num_queries, const int32_t *cost,
+                       int num_paths, const int32_t *query, const int32_t *starts, int max_nodes, int32_t *path,
+                       int32_t *length, gg_stream_t stream);
+
 /* ---- in-library kernel timing (measurement only; off by default) --------------------------------
  * When enabled, every launch of the kernels below is bracketed by a hipEvent pair recorded on the
  * launch stream, so bench.py can report the average duration of exactly that kernel over its
