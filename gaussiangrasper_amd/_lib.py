@@ -169,6 +169,8 @@ SIGNATURES = {
     "gg_roadmap_route_workspace": (_SZ, [_I, _I]),
     "gg_roadmap_route": (_I, [_I, _I, _P, _P, _P, C.c_int32, _I, _P, _P, _P, _P, _I, C.POINTER(C.c_int), _P, _SZ, _P]),
     "gg_roadmap_descend": (_I, [_I, _I, _P, _P, _P, C.c_int32, _I, _P, _I, _P, _P, _I, _P, _P, _P]),
+    "gg_traj_time": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _I] + [_P] * 9 + [_P]),
+    "gg_traj_sample": (_I, [_I, _I, _I, _P, _P, _P, _I] + [_P] * 6 + [C.c_double, _I] + [_P] * 4 + [_P]),
     "gg_prof_enable": (_I, [_I]),
     "gg_prof_reset": (_I, []),
     "gg_prof_get": (_I, [_I, C.POINTER(C.c_int), C.POINTER(C.c_double)]),

@@ -22,8 +22,9 @@ in DESIGN.md §3.31 and §3.33.
                                       [--check-motion --motion-res R --self-margin M --max-samples N]
                                       [--connect-from Q.npy [--connect-roadmap {N,FILE.npz}]]
 
-Routes through more than one intermediate configuration are roadmap.py's (a probabilistic roadmap over `motion`).  Out of
-scope: velocity and torque limits.  The spheres cover the link models they are given and nothing more."""
+Routes through more than one intermediate configuration are roadmap.py's (a probabilistic roadmap over `motion`); when
+the arm is where along them, inside joint velocity and acceleration limits, is trajectory.py's.  Out of scope: torque
+limits and jerk.  The spheres cover the link models they are given and nothing more."""
 from __future__ import annotations
 
 import argparse

@@ -17,8 +17,10 @@ PARITY.md "Arm roadmap"; the design in DESIGN.md §3.34.
     plan               from every q_from to every q_to through the roadmap -> Plan
     python -m gaussiangrasper_amd.roadmap build --arm {default,FILE.json} --field field.npz --out roadmap.npz ...
     python -m gaussiangrasper_amd.roadmap plan  --arm ... --field ... --from A.npy --to B.npy --out way.npz ...
+                                                [--time-limits {default,FILE.json}]
 
-Out of scope: lazy edge evaluation, roadmap repair after the scene changes, velocity and torque limits."""
+When the arm is where along a route, inside joint velocity and acceleration limits, is trajectory.py's.  Out of scope:
+lazy edge evaluation, roadmap repair after the scene changes, torque limits and jerk."""
 from __future__ import annotations
 
 import argparse
@@ -689,6 +691,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     pp.add_argument("--to", dest="q_to", required=True, help=".npy (B, J) or (J,) goal configurations")
     pp.add_argument("--shortcut", type=int, default=0, help="string-pull the routes over this window (0: not)")
     pp.add_argument("--out", required=True, help="output .npz cost, length, hops, waypoints (A, B, W, J; NaN padded)")
+    pp.add_argument("--time-limits", default=None, metavar="{default,FILE.json}",
+                    help="joint velocity and acceleration limits: adds duration (A, B), seconds, to the report "
+                         "(python -m gaussiangrasper_amd.trajectory)")
     a = ap.parse_args(argv)
     sp = bp if a.command == "build" else pp
     _check_options(sp, a)
@@ -715,7 +720,11 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         else:
             p = plan(arm, ends[0], ends[1], field, shortcut_window=a.shortcut, num_nodes=a.nodes, k=a.k, seed=a.seed,
                      unit=a.unit, **kw)
-        np.savez(a.out, **plan_report(p))
+        report = plan_report(p)
+        if a.time_limits:
+            from . import trajectory as _traj
+            report["duration"] = _traj.time_plan(p, _traj.load_limits_option(a.time_limits), arm=arm).duration
+        np.savez(a.out, **report)
     except (KeyError, ValueError, OSError, _lib.GGError) as exc:
         raise SystemExit(f"error: {exc}") from exc
     print(f"{int((p.hops >= 0).sum())} of {p.hops.size} routes found; wrote {a.out}")

@@ -1515,6 +1515,88 @@ int gg_roadmap_descend(int num_nodes, int num_edges, const int32_t *offsets, con
                        int num_paths, const int32_t *query, const int32_t *starts, int max_nodes, int32_t *path,
                        int32_t *length, gg_stream_t stream);
 
+/* ---- arm trajectories: blended corners and the time law under joint limits (csrc/trajectory.hip) -------
+ * Source of the contract: none in the reference.  Parabolic corner blends and time parameterisation by reachability
+ * over a path grid are textbook (Kunz & Stilman 2012; Pham & Pham 2018), RECALLED, NOT READ; every constant is this
+ * project's choice (PARITY.md "Arm trajectories").  Both entries are pure functions of their inputs: fp64 throughout,
+ * only + - * / sqrt min max, every operation rounded (no contraction), no atomics, the same inputs give the same bytes.
+ *
+ * THE PATH.  J = num_joints in 1..GG_ARM_MAX_JOINTS; way fp64 [P][W][J], W = num_waypoints in
+ * 1..GG_TRAJ_MAX_WAYPOINTS; length int32 [P]: path p has n = length[p] waypoints, clamped into 1..W; blend fp64
+ * [P][W]: f_k = min(max(blend[p][k], 0), 1/2), NaN taken as 0, and f_0 = f_{n-1} = 0 whatever the array holds.
+ * d_k = w_{k+1} - w_k.  The parameter s runs over [0, n - 1]; segment k is w_k + (s - k) d_k.  About an interior
+ * waypoint with f_k > 0 the corner is replaced on s in [k - f_k, k + f_k] by the quadratic Bezier curve with control
+ * points w_k - f_k d_{k-1}, w_k, w_k + f_k d_k: q' runs linearly from d_{k-1} to d_k, q'' = (d_k - d_{k-1}) / (2 f_k)
+ * is constant, and q' is continuous along the whole path.  An interior waypoint with f_k = 0 is a STOP, as are both
+ * ends.  PIECES, in path order: for k = 0 .. n - 2, the blend about waypoint k (k >= 1 and f_k > 0), then the line of
+ * segment k of parameter length L = (1 - f_k) - f_{k+1}, skipped when L <= 0 (f_k = f_{k+1} = 1/2).  Every piece is cut
+ * into m = steps equal intervals of Delta = L / m (the blend: L = 2 f_k), 2 <= m <= GG_TRAJ_MAX_STEPS.  The grid has
+ * G = m (pieces) <= GG_TRAJ_GRID(W, m) = Gmax intervals and G + 1 points.  With tau = (double)a / (double)m at
+ * interval a of its piece, joint by joint:
+ *   line   q' = d_k at both ends, q'' = 0; q at the interval's start = w_k + (f_k + tau L) d_k
+ *   blend  e = d_k - d_{k-1}; q' = d_{k-1} + tau e at the start, d_{k-1} + ((double)(a + 1) / (double)m) e at the end
+ *          and d_k itself when a + 1 == m; q'' = e / L; q at the start = ((w_k - f_k d_{k-1}) + tau (L d_{k-1})) +
+ *          (tau tau) (f_k e).
+ *
+ * gg_traj_time: one launch for P paths.  v_max, a_max: HOST arrays of J doubles, finite and > 0.  Unknowns: x_i = (ds /
+ * dt)^2 at grid point i and u_i = d2s / dt2, constant on interval i, so x_{i+1} = x_i + 2 Delta u_i.  On interval i,
+ * with two = 2 Delta:
+ *   vcap   = min_j (v_j / max(|q'_j| at the start, |q'_j| at the end))^2; a joint with q' = 0 at both ends gives none.
+ *   next   = min(xbar_{i+1}, vcap).
+ *   rows   per joint and per end, A = q''_j and B = q'_j at the start, or B = two q''_j + q'_j(end) at the far end:
+ *          |A x + B u| <= a_j.  B != 0: the upper line u <= c + d x and the lower line u >= -c + d x with c = a_j / |B|,
+ *          d = -(A / B).  B == 0 and A != 0: the cap x <= a_j / |A|.  B == 0 and A == 0: no row.
+ *          One more row, 0 <= x + two u <= next: upper c = next / two, lower c = 0, both d = -(1 / two).
+ *   BACKWARDS from xbar_G = 0: xbar_i = 0 when grid point i is a stop; otherwise max(0, the minimum of vcap, of the caps
+ *          and of (c_hi - c_lo) / (d_lo - d_hi) over every (lower, upper) pair of rows with d_lo - d_hi > 0).  At most
+ *          (2 J + 1)^2 pairs; a minimum does not depend on its order.  (x, u) = (0, 0) meets every row and the rows are
+ *          linear, so the x for which some u meets them form an interval from 0, and xbar_i is its upper end.
+ *   FORWARDS from x_0 = 0, t_0 = 0: u_i = min over the upper lines of c + d x_i; x_{i+1} = min(max(x_i + two u_i, 0),
+ *          next); t_{i+1} = t_i + two / (sqrt(x_i) + sqrt(x_{i+1})), added in grid order.  infeasible = the largest of
+ *          (max over the lower lines of c + d x_i) - u_i over the intervals, and 0: 0 in exact arithmetic.
+ * Outputs: count int32 [P] = G; xbar, x, t fp64 [P][Gmax + 1]; u fp64 [P][Gmax]; q_grid fp64 [P][Gmax + 1][J], q at
+ * every grid point (the last: w_{n-1} itself), null: not written; duration fp64 [P] = t_G; infeasible fp64 [P]; status
+ * int32 [P]: GG_TRAJ_OK; GG_TRAJ_NOT_FINITE: a waypoint of the path is not finite; GG_TRAJ_ZERO_SEGMENT: a d_k is all
+ * zeros (checked when every waypoint is finite); GG_TRAJ_NO_DURATION: t_G is not finite.  Entries past the path's own
+ * (xbar, x, t, q_grid past point G; u from interval G on) are NaN.  A status that is not OK gives count 0 and NaN in
+ * every row, in duration and in infeasible.  A path of one waypoint: count 0, duration 0, xbar_0 = x_0 = t_0 = 0,
+ * q_grid row 0 = w_0.  Neighbouring paths do not see each other.  P (Gmax + 1) <= GG_FIELD_MAX_POSES; P == 0 writes
+ * nothing.  THE CALLER'S DUTY: |w| small enough that no d_k overflows.
+ *
+ * gg_traj_sample: way, length, blend, steps as above; count, x, u, t, duration, status as gg_traj_time wrote them (THE
+ * CALLER'S DUTY; a count that is not the path's own gives NaN rows, never a read outside the arrays).  dt finite and
+ * > 0, K = num_samples >= 1, P K <= GG_FIELD_MAX_POSES.  num int32 [P] = one more than the smallest k with (double)k dt
+ * >= duration (a division may propose it; these comparisons decide it), at most 2^30; 0 for a status that is not OK.
+ * Sample k < num is taken at tt = min((double)k dt, duration): interval i is the last with t_i <= tt, at most G - 1;
+ * tau = tt - t_i; r = sqrt(x_i); sd = r + u_i tau; ds = min(max((r + (0.5 u_i) tau) tau, 0), Delta_i); per joint, with
+ * q, q', q'' of interval i's start: qp = q' + ds q''; q = (q + ds q') + ((0.5 ds) ds) q''; qd = qp sd; qdd = q'' (sd sd)
+ * + qp u_i.  Outputs q, qd, qdd fp64 [P][K][J]; rows k >= num are NaN.  A path of one waypoint: w_0, 0, 0.
+ *
+ * WHAT THE OUTPUTS PROVE.  On an interval q'_j is linear in s, so |q'_j| takes its maximum at an end: x_i, x_{i+1} <=
+ * vcap and x linear in s between them give |dq_j/dt| <= v_j at every instant.  The joint acceleration q''_j x + q'_j u
+ * is linear in s as well (x and q' are, u and q'' are constant), so the rows at the two ends bound it at every instant:
+ * |d2q_j/dt2| <= a_j.  Both hold up to the rounding that `infeasible` and the clamp of x_{i+1} measure.  The law is
+ * the quickest ON ITS GRID; it says nothing about torque, jerk or Cartesian speed.  With f_k <= min(1/2, 2 delta /
+ * B_{k-1}, 2 delta / B_k), B_k gg_arm_motion's sweep bound of segment k, no sphere centre leaves the polyline's sweep
+ * by more than delta: a route whose edges passed gg_arm_motion with margin >= delta and self_margin >=
+ * 2 delta stays proven clear after blending.  fp64 arrays 8-byte aligned, the others 4-byte.
+ * Null, misaligned or out-of-range arguments: GG_ERR_INVALID_ARG naming the argument, before any launch. */
+#define GG_TRAJ_MAX_WAYPOINTS 64
+#define GG_TRAJ_MAX_STEPS 64
+#define GG_TRAJ_GRID(W, m) ((W) >= 2 ? (m) * (2 * (W) - 3) : 0)
+#define GG_TRAJ_OK 0
+#define GG_TRAJ_NOT_FINITE 1
+#define GG_TRAJ_ZERO_SEGMENT 2
+#define GG_TRAJ_NO_DURATION 3
+int gg_traj_time(int num_joints, int num_paths, int num_waypoints, const double *way, const int32_t *length,
+                 const double *blend, const double *v_max, const double *a_max, int steps, int32_t *count, double *xbar,
+                 double *x, double *u, double *t, double *q_grid, double *duration, double *infeasible, int32_t *status,
+                 gg_stream_t stream);
+int gg_traj_sample(int num_joints, int num_paths, int num_waypoints, const double *way, const int32_t *length,
+                   const double *blend, int steps, const int32_t *count, const double *x, const double *u,
+                   const double *t, const double *duration, const int32_t *status, double dt, int num_samples, double *q,
+                   double *qd, double *qdd, int32_t *num, gg_stream_t stream);
+
 /* ---- in-library kernel timing (measurement only; off by default) --------------------------------
  * When enabled, every launch of the kernels below is bracketed by a hipEvent pair recorded on the
  * launch stream, so bench.py can report the average duration of exactly that kernel over its
