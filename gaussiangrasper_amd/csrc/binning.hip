@@ -994,6 +994,8 @@ static int bin_sort_impl(int N, int64_t I, const int64_t *I_dev, const float *xy
         gg_set_error("gg_bin_sort: workspace too small (%zu < %zu)", ws_bytes, w.bytes);
         return GG_ERR_WORKSPACE;
     }
+    // the pieces are 256-byte multiples from `ws`; two of them hold uint4 records, one 64-bit pairs
+    GG_REQUIRE(((uintptr_t)ws & 15) == 0, "ws must be 16-byte aligned");
     gg_prof_begin(GG_K_BIN_SORT, s);
     // 1. depth order of the Gaussians, 2. their offsets in that order: by buckets (db_* above)
     const int nbk = db_buckets(N);

@@ -106,6 +106,8 @@ static int blend_begin(const char *entry, const BlendCall &c, bool backward, boo
         gg_set_error("%s: workspace too small", entry);
         return GG_ERR_WORKSPACE;
     }
+    // the kernels read a packed record as two float4 (blend2.hip, votes.hip, hits.hip)
+    BLEND_REQUIRE((reinterpret_cast<uintptr_t>(c.ws) & 15) == 0, "ws must be 16-byte aligned");
     w.s = (hipStream_t)c.stream;
     if (c.N > 0 && !records_ready) {
         gg_prof_begin(GG_K_BLEND_PREP, w.s);
@@ -118,7 +120,7 @@ static int blend_begin(const char *entry, const BlendCall &c, bool backward, boo
     w.tiles_x = (c.img_w + GG_BLOCK - 1) / GG_BLOCK;
     w.ntiles = w.tiles_x * ((c.img_h + GG_BLOCK - 1) / GG_BLOCK);
     w.ids = c.ids;
-    w.bins = (const int2 *)c.tile_bins;
+    w.bins = c.tile_bins;
     w.rec = (const GRec *)c.ws;
     return GG_OK;
 }

@@ -140,7 +140,7 @@ __global__ __launch_bounds__(64 * GG_WPB_OTHER)
 __attribute__((amdgpu_waves_per_eu((WIDE && EX && NCB == 1) ? GG_FWD_WAVES : (NCB == 2 ? (EX ? 4 : 3) : (NCB > 2 ? 2 : 1)))))
 void blend2_fwd_kernel(
     int C, int ch_off, int nch, int img_h, int img_w, int tiles_x, int ntiles,
-    const int32_t *__restrict__ ids, const int2 *__restrict__ bins, const GRec *__restrict__ rec,
+    const int32_t *__restrict__ ids, const int32_t *__restrict__ bins, const GRec *__restrict__ rec,
     const float *__restrict__ colors, const float *__restrict__ background,
     float *__restrict__ out_img, float *__restrict__ final_T, int32_t *__restrict__ final_idx,
     int write_final, Seg2 seg2 = Seg2()) {
@@ -161,7 +161,7 @@ void blend2_fwd_kernel(
     const bool inside = (i < img_h) && (j < img_w);
     const float px = (float)j, py = (float)i;
     const float xlo = (float)qx0, xhi = (float)(qx0 + 7), ylo = (float)qy0, yhi = (float)(qy0 + 7);
-    const int2 range = bins[tile];
+    const int2 range = gg_tile_range(bins, tile);
 
     STAMP_DECL;
     float T = 1.0f;
@@ -430,7 +430,7 @@ struct __attribute__((aligned(16))) FwdQueue {
 
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GG_FB_WAVES))) void blend2_fwd_batch_kernel(
     int C, int img_h, int img_w, int tiles_x, int ntiles, const int32_t *__restrict__ ids,
-    const int2 *__restrict__ bins, const GRec *__restrict__ rec, const float *__restrict__ colors,
+    const int32_t *__restrict__ bins, const GRec *__restrict__ rec, const float *__restrict__ colors,
     const float *__restrict__ background, float *__restrict__ out_img, float *__restrict__ final_T,
     int32_t *__restrict__ final_idx, Seg2 seg2, unsigned bytes1, unsigned bytes2) {
     __shared__ FwdQueue s_q;
@@ -450,7 +450,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GG_FB_WAVES)
     const int j = qx0 + (lane & 7), i = qy0 + (lane >> 3);
     const bool inside = (i < img_h) && (j < img_w);
     const float px = (float)j, py = (float)i;
-    const int2 range = bins[tile];
+    const int2 range = gg_tile_range(bins, tile);
     const int sl = lane & 15, q4 = lane >> 4;
 
     // The walk carries Ts = 2^15 T instead of T: a multiplication by a power of two commutes with every rounding of the
@@ -706,7 +706,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GG_FB_WAVES)
 template <int CH, int ABL = 0, bool DET = false>
 __global__ __launch_bounds__(64 * GG_WPB_OTHER) void blend2_bwd_narrow_kernel(
     int C, int ch_off, int nch, int img_h, int img_w, int tiles_x, int ntiles,
-    const int32_t *__restrict__ ids, const int2 *__restrict__ bins, const GRec *__restrict__ rec,
+    const int32_t *__restrict__ ids, const int32_t *__restrict__ bins, const GRec *__restrict__ rec,
     const float *__restrict__ colors, const float *__restrict__ background,
     const float *__restrict__ final_T, const int32_t *__restrict__ final_idx,
     const float *__restrict__ v_out, float *__restrict__ v_xy, float *__restrict__ v_conic,
@@ -731,7 +731,7 @@ __global__ __launch_bounds__(64 * GG_WPB_OTHER) void blend2_bwd_narrow_kernel(
     const bool inside = (i < img_h) && (j < img_w);
     const float px = (float)j, py = (float)i;
     const float xlo = (float)qx0, xhi = (float)(qx0 + 7), ylo = (float)qy0, yhi = (float)(qy0 + 7);
-    const int2 range = bins[tile];
+    const int2 range = gg_tile_range(bins, tile);
     const size_t p = inside ? ((size_t)i * img_w + j) : 0;
 
     const float T_final = inside ? final_T[p] : 1.0f;
@@ -962,7 +962,7 @@ struct Seg2B {
 template <bool FULL, int ABL = 0, int CHD = 32, bool DET = false, bool EX = false, bool S16 = false, bool MG = false>
 __global__ __launch_bounds__(64 * GG_WPB_WIDE_BWD) __attribute__((amdgpu_waves_per_eu(S16 ? GG_S16_WAVES : 3))) void blend2_bwd_wide_kernel(
     int C, int ch_off, int nch, int img_h, int img_w, int tiles_x, int ntiles,
-    const int32_t *__restrict__ ids, const int2 *__restrict__ bins, const GRec *__restrict__ rec,
+    const int32_t *__restrict__ ids, const int32_t *__restrict__ bins, const GRec *__restrict__ rec,
     const float *__restrict__ colors, const float *__restrict__ background,
     const float *__restrict__ final_T, const int32_t *__restrict__ final_idx,
     const float *__restrict__ v_out, float *__restrict__ v_xy, float *__restrict__ v_conic,
@@ -1004,7 +1004,7 @@ __global__ __launch_bounds__(64 * GG_WPB_WIDE_BWD) __attribute__((amdgpu_waves_p
     const int j = qx0 + (lane & 7), i = qy0 + (lane >> 3);
     const bool inside = (i < img_h) && (j < img_w);
     const float px = (float)j, py = (float)i;
-    const int2 range = bins[tile];
+    const int2 range = gg_tile_range(bins, tile);
     const size_t p = inside ? ((size_t)i * img_w + j) : 0;
 
     STAMP_DECL;

@@ -34,6 +34,12 @@ __device__ __forceinline__ void grec_pack(float x, float y, float opac, float ca
     d4[1] = make_float4(ca, cb, cc, 0.0f);
 }
 
+// [start, end) of a tile's list.  tile_bins is the caller's (tiles, 2) int32 array, which the header holds to 4 bytes:
+// the two ends are two int loads, never one 8-byte load
+__device__ __forceinline__ int2 gg_tile_range(const int32_t *__restrict__ bins, int tile) {
+    return make_int2(bins[2 * (size_t)tile], bins[2 * (size_t)tile + 1]);
+}
+
 // Tile of a workgroup.  Workgroups are dealt round-robin to the 8 XCDs (workgroup b runs on XCD
 // b & 7), each with its own L2.  XCD x takes the strips s = x, x+8, x+16, ... of GG_STRIP consecutive
 // tiles of a tile row: the tiles of a strip share most of their Gaussians (L2 hits), and the strips

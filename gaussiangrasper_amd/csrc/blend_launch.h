@@ -7,7 +7,7 @@
 struct BlendWalk {
     int img_h, img_w, tiles_x, ntiles;
     const int32_t *ids;
-    const int2 *bins;
+    const int32_t *bins;   // the caller's (tiles, 2) int32 array, 4-byte aligned: read through gg_tile_range
     const GRec *rec;
     hipStream_t s;
 };

@@ -106,7 +106,7 @@ __device__ __forceinline__ HitOut hit_walk(HitList &Lst, const int lane, const i
 template <bool FULL>
 __global__ __launch_bounds__(64 * GG_WPB_OTHER) void blend_hits_kernel(
     int N, int img_h, int img_w, int tiles_x, int ntiles, const int32_t *__restrict__ ids,
-    const int2 *__restrict__ bins, const GRec *__restrict__ rec, float t_hit, int32_t *__restrict__ hit_idx,
+    const int32_t *__restrict__ bins, const GRec *__restrict__ rec, float t_hit, int32_t *__restrict__ hit_idx,
     int32_t *__restrict__ top_idx, float *__restrict__ top_vis, int32_t *__restrict__ count) {
     __shared__ HitList lists[GG_WPB_OTHER];
     int wave;
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(64 * GG_WPB_OTHER) void blend_hits_kernel(
     const float px = (float)j, py = (float)i;
     const float xlo = (float)qx0, xhi = (float)(qx0 + 7), ylo = (float)qy0, yhi = (float)(qy0 + 7);
     // num_points == 0: the lists are not looked at, every pixel gets the defaults
-    const int2 range = N > 0 ? bins[tile] : make_int2(0, 0);
+    const int2 range = N > 0 ? gg_tile_range(bins, tile) : make_int2(0, 0);
     const HitOut o = hit_walk<FULL>(Lst, lane, range, px, py, xlo, xhi, ylo, yhi, inside, t_hit, ids, rec);
     if (inside) {
         const size_t p = (size_t)i * (size_t)img_w + (size_t)j;

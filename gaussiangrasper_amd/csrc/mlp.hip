@@ -570,7 +570,8 @@ extern "C" int gg_mlp_fwd_fast(int64_t num_rows, int in_dim, int hidden_dim, int
                "out_dim must be a multiple of 16, at most 3968 (two weight slices and the biases share 160 KB of LDS)");
     if (num_rows == 0) return GG_OK;
     GG_REQUIRE(x && w1 && b1 && w2 && b2 && y, "null pointer");
-    GG_REQUIRE((((uintptr_t)x | (uintptr_t)y) & 15) == 0, "x and y must be 16-byte aligned");
+    GG_REQUIRE(((uintptr_t)x & 15) == 0, "x must be 16-byte aligned");
+    GG_REQUIRE(((uintptr_t)y & 15) == 0, "y must be 16-byte aligned");
     if (ws == nullptr || ws_bytes < gg_mlp_fwd_fast_workspace(in_dim, hidden_dim, out_dim) || ((uintptr_t)ws & 15)) {
         gg_set_error("gg_mlp_fwd_fast: workspace of gg_mlp_fwd_fast_workspace() bytes, 16-byte aligned, expected");
         return GG_ERR_WORKSPACE;
@@ -622,7 +623,11 @@ extern "C" int gg_mlp_fwd(int64_t num_rows, int in_dim, int hidden_dim, int out_
     GG_REQUIRE(out_dim > 0 && out_dim % 32 == 0, "out_dim must be a positive multiple of 32");
     if (num_rows == 0) return GG_OK;
     GG_REQUIRE(x && w1 && b1 && w2 && b2 && y, "null pointer");
-    GG_REQUIRE((((uintptr_t)x | (uintptr_t)y) & 15) == 0, "x and y must be 16-byte aligned");
+    GG_REQUIRE(((uintptr_t)x & 15) == 0, "x must be 16-byte aligned");
+    GG_REQUIRE(((uintptr_t)y & 15) == 0, "y must be 16-byte aligned");
+    // the kernels stage W2 (and, for in_dim 128, W1) four floats per load; gg_mlp_fwd_fast packs them float by float
+    GG_REQUIRE(((uintptr_t)w1 & 15) == 0, "w1 must be 16-byte aligned");
+    GG_REQUIRE(((uintptr_t)w2 & 15) == 0, "w2 must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     const size_t lds_bytes = sizeof(float) * ((size_t)MLP_SLICE_NB * MLP_STEPS * 64 + MLP_HID + 32 * MLP_SLICE_NB);
     int dev = 0, cus = 256;

@@ -734,6 +734,7 @@ extern "C" int gg_project_fwd(int N, const float *means3d, const float *scales, 
     GG_REQUIRE(means3d && scales && quats && viewmat && projmat && cov3d && xys && depths &&
                    radii && conics && num_tiles_hit,
                "null pointer");
+    GG_REQUIRE(((uintptr_t)quats & 15) == 0, "quats must be 16-byte aligned");
     gg_prof_begin(GG_K_PROJECT_FWD, (hipStream_t)stream);
     hipLaunchKernelGGL(project_fwd_kernel, dim3((N + 255) / 256), dim3(256), 0,
                        (hipStream_t)stream, N, means3d, scales, glob_scale, quats, viewmat,
@@ -768,6 +769,7 @@ extern "C" int gg_project_fwd_count(int N, const float *means3d, const float *sc
     GG_REQUIRE(means3d && scales && quats && viewmat && projmat && cov3d && xys && depths &&
                    radii && conics && num_tiles_hit,
                "null pointer");
+    GG_REQUIRE(((uintptr_t)quats & 15) == 0, "quats must be 16-byte aligned");
     if (count_ws == nullptr || count_ws_bytes < gg_project_count_workspace(N) || ((uintptr_t)count_ws & 3)) {
         gg_set_error("gg_project_fwd_count: count workspace of gg_project_count_workspace() bytes expected");
         return GG_ERR_WORKSPACE;
@@ -819,6 +821,8 @@ extern "C" int gg_project_bwd_ex(int N, const float *means3d, const float *scale
     GG_REQUIRE(means3d && scales && quats && viewmat && projmat && radii && conics && v_xy &&
                    v_depth && v_conic && v_mean3d && v_scale && v_quat,
                "null pointer");
+    GG_REQUIRE(((uintptr_t)quats & 15) == 0, "quats must be 16-byte aligned");
+    GG_REQUIRE(((uintptr_t)v_quat & 15) == 0, "v_quat must be 16-byte aligned");
     gg_prof_begin(GG_K_PROJECT_BWD, (hipStream_t)stream);
     hipLaunchKernelGGL(project_bwd_kernel, dim3((N + 255) / 256), dim3(256), 0,
                        (hipStream_t)stream, N, means3d, scales, glob_scale, quats, viewmat,
@@ -1330,7 +1334,8 @@ extern "C" int gg_view_fwd(int N, const float *means, const float *log_scales, c
     }
     GG_REQUIRE(means && log_scales && quats && opacities && cam_pos && viewmat && projmat && scales && quats_n && opac &&
                    viewdirs && normals && axis && xys && depths && radii && conics && num_tiles_hit, "null pointer");
-    GG_REQUIRE((((uintptr_t)quats | (uintptr_t)quats_n) & 15) == 0, "quats / quats_n must be 16-byte aligned");
+    GG_REQUIRE(((uintptr_t)quats & 15) == 0, "quats must be 16-byte aligned");
+    GG_REQUIRE(((uintptr_t)quats_n & 15) == 0, "quats_n must be 16-byte aligned");
     if (parts == nullptr || parts_bytes < gg_view_fwd_workspace(N) || ((uintptr_t)parts & 3)) {
         gg_set_error("gg_view_fwd: partial-result array of gg_view_fwd_workspace() bytes expected");
         return GG_ERR_WORKSPACE;
@@ -1499,9 +1504,10 @@ static int view_bwd_check(int N, const float *rec, int rec_stride, const uint8_t
                           float *v_opacities) {
     GG_REQUIRE(rec && clamp_mask && means && scales && quats_raw && quats_n && opac && axis && viewmat && projmat && radii &&
                    conics && v_rgb && v_means && v_log_scales && v_quats && v_opacities, "null pointer");
-    GG_REQUIRE((((uintptr_t)quats_raw | (uintptr_t)quats_n | (uintptr_t)v_quats) & 15) == 0,
-               "quaternion arrays must be 16-byte aligned");
-    GG_REQUIRE((rec_stride & 3) != 0 || ((uintptr_t)rec & 15) == 0, "records of a multiple of 4 floats must be 16-byte aligned");
+    GG_REQUIRE(((uintptr_t)quats_raw & 15) == 0, "quats_raw must be 16-byte aligned");
+    GG_REQUIRE(((uintptr_t)quats_n & 15) == 0, "quats_n must be 16-byte aligned");
+    GG_REQUIRE(((uintptr_t)v_quats & 15) == 0, "v_quats must be 16-byte aligned");
+    GG_REQUIRE((rec_stride & 3) != 0 || ((uintptr_t)rec & 15) == 0, "rec: records of a multiple of 4 floats must be 16-byte aligned");
     return GG_OK;
 }
 extern "C" int gg_view_bwd(int N, const float *rec, int rec_stride, const uint8_t *clamp_mask, const float *means,

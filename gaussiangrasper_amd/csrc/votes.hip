@@ -168,7 +168,7 @@ __device__ __forceinline__ void vote_walk(VoteList &Lst, const int lane, const i
 
 __global__ __launch_bounds__(64 * GG_WPB_OTHER) void blend_votes_kernel(
     int L, int N, int img_h, int img_w, int tiles_x, int ntiles, const int32_t *__restrict__ ids,
-    const int2 *__restrict__ bins, const GRec *__restrict__ rec, const uint8_t *__restrict__ labels,
+    const int32_t *__restrict__ bins, const GRec *__restrict__ rec, const uint8_t *__restrict__ labels,
     unsigned long long *__restrict__ votes) {
     __shared__ VoteList lists[GG_WPB_OTHER];
     int wave;
@@ -182,7 +182,7 @@ __global__ __launch_bounds__(64 * GG_WPB_OTHER) void blend_votes_kernel(
     const bool inside = (i < img_h) && (j < img_w);
     const float px = (float)j, py = (float)i;
     const float xlo = (float)qx0, xhi = (float)(qx0 + 7), ylo = (float)qy0, yhi = (float)(qy0 + 7);
-    const int2 range = bins[tile];
+    const int2 range = gg_tile_range(bins, tile);
     if (range.y <= range.x) return;
 
     // A pixel outside the image or with a label >= L votes for nobody: its T need not be followed, so it counts as

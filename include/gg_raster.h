@@ -50,7 +50,9 @@ const char *gg_last_error(void);
  * Replaces gsplat `_C.project_gaussians_forward` (ProjectGaussians.forward; reference call
  * gaussian_splatting.py:699-713).  viewmat: >=12 floats row-major (the caller's viewmat[:3,:]);
  * projmat: 16 floats (projmat @ viewmat).  All six outputs are fully written (zeros for culled
- * Gaussians as the oracle documents), so they may be uninitialised on entry. */
+ * Gaussians as the oracle documents), so they may be uninitialised on entry.  quats (N, 4) is read one row per load:
+ * 16-byte aligned, here and in gg_project_fwd_count (as gg_activate_*, gg_view_* and gg_quat_to_rotmat_* require of the
+ * same array); a misaligned quats is refused with GG_ERR_INVALID_ARG before any launch. */
 int gg_project_fwd(int num_points, const float *means3d, const float *scales, float glob_scale,
                    const float *quats, const float *viewmat, const float *projmat, float fx,
                    float fy, float cx, float cy, int img_height, int img_width, int tiles_x,
@@ -71,7 +73,9 @@ int gg_project_fwd_count(int num_points, const float *means3d, const float *scal
 
 /* Replaces gsplat `_C.project_gaussians_backward` (ProjectGaussians.backward).  v_conic uses
  * gsplat's symmetric-matrix convention (v_conic[:,1] is half of dL/d conic.y).  Outputs fully
- * written (zeros where radii<=0). */
+ * written (zeros where radii<=0).  quats and v_quat (N, 4) are read / written one row per access: both 16-byte aligned,
+ * here and in gg_project_bwd_ex; a misaligned one is refused with GG_ERR_INVALID_ARG, its name in gg_last_error(),
+ * before any launch. */
 int gg_project_bwd(int num_points, const float *means3d, const float *scales, float glob_scale,
                    const float *quats, const float *viewmat, const float *projmat, float fx,
                    float fy, float cx, float cy, int img_height, int img_width,
@@ -246,7 +250,8 @@ int gg_count_intersects(int num_points, const int32_t *num_tiles_hit,
  *   isect_tile_sorted (I,) optional (may be NULL) — the tile id of every sorted entry.
  * Tile grids up to 1023 x 1023 (images up to 16 368 pixels a side): a Gaussian's tile box travels through the depth
  * sort in one 32-bit word (round 4); larger grids are rejected with GG_ERR_INVALID_ARG.  Workspace: ~44 bytes per Gaussian
- * + 12 bytes per list entry. */
+ * + 12 bytes per list entry, 16-byte aligned (it holds 16-byte records and 64-bit pairs) in gg_bin_sort, gg_bin_sort_dev
+ * and gg_bin_sort_dev_ex; a misaligned ws is refused with GG_ERR_INVALID_ARG before any launch. */
 size_t gg_bin_sort_workspace(int num_points, int64_t num_intersects);
 int gg_bin_sort(int num_points, int64_t num_intersects, const float *xys, const float *depths,
                 const int32_t *radii, const int32_t *num_tiles_hit, int tiles_x, int tiles_y,
@@ -281,7 +286,12 @@ int gg_bin_sort_dev_ex(int num_points, int64_t capacity, const int64_t *num_inte
 /* ---- alpha blending ----------------------------------------------------------------------
  * gg_blend_fwd replaces gsplat `_C.rasterize_forward` (C=3) and `_C.nd_rasterize_forward`
  * (any C >= 1).  colors (N,C), opacity (N,) or (N,1), background (C,), out_img (H,W,C),
- * final_Ts (H,W), final_idx (H,W).  ws: gg_blend_workspace(num_points) bytes. */
+ * final_Ts (H,W), final_idx (H,W).  tile_bins (tiles, 2) int32, 4-byte aligned like every int32 array here (a range's two
+ * ends are read as two ints).  ws: gg_blend_workspace(num_points) bytes, 16-byte aligned (the walks read a
+ * Gaussian's packed 32-byte record as two 16-byte loads) — for every entry that takes it: gg_blend_fwd, gg_blend_fwd_pair,
+ * gg_blend_fwd_pair_fast, gg_blend_fwd_pair_packed, gg_blend_bwd, gg_blend_bwd_pair, gg_blend_bwd_deterministic,
+ * gg_blend_votes and gg_blend_hits.  A misaligned ws is refused with GG_ERR_INVALID_ARG ("ws" in gg_last_error())
+ * before any launch. */
 size_t gg_blend_workspace(int num_points);
 int gg_blend_fwd(int channels, int num_points, int img_height, int img_width,
                  const int32_t *gaussian_ids_sorted, const int32_t *tile_bins, const float *xys,
@@ -338,7 +348,14 @@ int gg_blend_fwd_pair_packed(int channels, int channels2, int num_points, int im
  * Gaussian, {xy.x, xy.y, conic a, b, c, opacity[, colours]}: v_conic = v_xy + 2, v_opacity =
  * v_xy + 5 (and v_colors = v_xy + 6 with color_stride = geom_stride when the colours are part of
  * it).  The kernels add with float atomics; an interleaved record puts all of a Gaussian's
- * atomics of one instruction on one cache line instead of four. */
+ * atomics of one instruction on one cache line instead of four.
+ * Who owns the padding: with a stride the call owns num_points * stride floats starting at the row pointer — v_xy for
+ * geom_stride, v_colors for color_stride (v_colors2 for color_stride2 in gg_blend_bwd_pair) — and, unless the matching
+ * GG_BWD_ACCUMULATE_* flag is set, CLEARS ALL of them before it adds, the stride - width floats of padding behind every
+ * row included, the last row's too.  A row pointer that is not the start of such a span (a column slice of a wider
+ * array that starts at a non-zero column: the last row's padding would lie past the array's end) is the caller's
+ * error.  A v_colors / v_colors2 inside the interleaved record (v_xy + 6, stride geom_stride) is part of the
+ * record's span and is cleared with it. */
 int gg_blend_bwd(int channels, int num_points, int img_height, int img_width,
                  const int32_t *gaussian_ids_sorted, const int32_t *tile_bins, const float *xys,
                  const float *conics, const float *colors, const float *opacity,
@@ -355,7 +372,8 @@ int gg_blend_bwd(int channels, int num_points, int img_height, int img_width,
  * array together (alpha, T and the geometry gradients are those of all channels at once; D = <colour, v_out>
  * over 40 channels and both colour-gradient products run on the matrix pipe).  v_xy, v_conic, v_opacity hold
  * the geometry gradients of BOTH arrays (what autograd would sum over two gg_blend_bwd calls); v_colors /
- * v_colors2 the colour gradients, rows color_stride / color_stride2 floats apart (0 = dense).  geom_stride as
+ * v_colors2 the colour gradients, rows color_stride / color_stride2 floats apart (0 = dense; the padding is the call's,
+ * as gg_blend_bwd's paragraph on strides says).  geom_stride as
  * in gg_blend_bwd; v_colors2 = v_xy + 6 with color_stride2 = geom_stride puts the second array's gradients
  * into the interleaved record.  The second cotangent (H, W, channels2) is handed over as num_parts (1..3) images
  * of v_out_img2_channels[k] consecutive channels each (host arrays) — the caller's rgb | depth | normal cotangents
@@ -446,7 +464,9 @@ int gg_blend_hits(int num_points, int img_height, int img_width, const int32_t *
  * rendered feature image at nerfstudio/pipelines/base_pipeline.py:408):
  *     y = relu(x @ w1^T + b1) @ w2^T + b2,  x (num_rows, in_dim), w1 (128, in_dim), b1 (128),
  *     w2 (out_dim, 128), b2 (out_dim), y (num_rows, out_dim), all fp32 row-major (torch Linear
- *     layout).  hidden_dim must be 128, in_dim 8/16/32/64, out_dim a multiple of 32. */
+ *     layout).  hidden_dim must be 128, in_dim 8/16/32/64/128, out_dim a multiple of 32.  x, y, w1 and w2 are
+ *     16-byte aligned (rows of x, y and of the weights are read and written four floats at a time), b1 and b2
+ *     4-byte; a misaligned one is refused with GG_ERR_INVALID_ARG, its name in gg_last_error(), before any launch. */
 int gg_mlp_fwd(int64_t num_rows, int in_dim, int hidden_dim, int out_dim, const float *x,
                const float *w1, const float *b1, const float *w2, const float *b2, float *y,
                gg_stream_t stream);
@@ -461,7 +481,8 @@ int gg_debug_set_fwd_blocks(int pair_blocks, int chunk_blocks);
  * (tools/check_f16split.hip), but not gg_mlp_fwd's summation order: the two agree to ~1e-6 of the largest output
  * (tests/test_gpu_parity.py), not bit for bit.  in_dim 32 / 64 / 128, out_dim a multiple of 16 (<= 3968: LDS); `ws`:
  * gg_mlp_fwd_fast_workspace(in_dim, 128, out_dim) bytes, 16-byte aligned, rewritten by every call (the packed
- * weights: 0.3 MB at out_dim 512).  What the reference runs here is cuBLAS behind nn.Linear
+ * weights: 0.3 MB at out_dim 512).  x and y 16-byte aligned; w1, w2, b1, b2 4-byte (unlike gg_mlp_fwd: the packing
+ * pass reads the weights float by float).  What the reference runs here is cuBLAS behind nn.Linear
  * (gaussian_splatting.py:198-213): no summation order to match on that side. */
 size_t gg_mlp_fwd_fast_workspace(int in_dim, int hidden_dim, int out_dim);
 int gg_mlp_fwd_fast(int64_t num_rows, int in_dim, int hidden_dim, int out_dim, const float *x,

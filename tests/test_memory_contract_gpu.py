@@ -1,5 +1,8 @@
-"""The memory contract of the C entry points that predate the sentinel habit, one test per family, every call through
-ctypes on a sentinel arena (tests/arena.py):
+"""The memory contract of the geometry and task entry points that predate the sentinel habit (grasp, kNN, prepare,
+cluster, ICP, TSDF, object masks, hull edit, clip query, image and geometry losses), one test per family, every call
+through ctypes on a sentinel arena (tests/arena.py).  The training path's entries (view chain, projection, binning,
+blend, MLP, cosine loss) are held the same way by tests/test_memory_contract_core_gpu.py, which imports this file's
+helpers.
 
   * every device array at exactly the smallest alignment include/gg_raster.h and the entry point's GG_REQUIRE allow
     (byte arrays at odd addresses), followed by a guard;
