@@ -151,6 +151,10 @@ SIGNATURES = {
     "gg_field_splat": (_I, [_P, _P, _I, _P, _P, _P, _P, C.c_double, _I, C.c_double, _I, _P, _P, _P, _P]),
     "gg_field_distance_workspace": (_SZ, [_P]),
     "gg_field_distance": (_I, [_P, _P, _I64, _P, _P, _SZ, _P]),
+    "gg_field_distance_known": (_I, [_P, _P, _I64, _P, _I, _P, _P, _SZ, _P]),
+    "gg_depth_min_pyramid_size": (_I64, [_I, _I]),
+    "gg_depth_min_pyramid": (_I, [_I, _I, _I, _P, _P, _P]),
+    "gg_field_observe": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, C.c_double, C.c_double, C.c_double, _P, _P, _P]),
     "gg_field_paths": (_I, [_P, _P, _P, _I, _I, _P, _I, _P, _P, _I, _P, _P, _P]),
     "gg_field_route_workspace": (_SZ, [_P]),
     "gg_field_route": (_I, [_P, _P, C.c_int32, _I, _P, _P, _P, _I, C.POINTER(C.c_int), _P, _SZ, _P]),

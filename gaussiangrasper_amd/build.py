@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libgg_raster.so")
 SOURCES = ["project.hip", "binning.hip", "blend.hip", "blend2.hip", "votes.hip", "hits.hip", "mlp.hip", "losses.hip", "imgloss.hip", "densify.hip", "edit.hip", "sh_rotate.hip",
            "rigid.hip", "query.hip", "grasp.hip", "grasp_propose.hip", "grasp_clear.hip", "grasp_nms.hip", "support_plane.hip", "prepare.hip", "knn.hip", "cluster.hip", "objmask.hip",
-           "tsdf.hip", "register.hip", "field.hip", "place.hip", "arm.hip", "roadmap.hip", "trajectory.hip",
+           "tsdf.hip", "register.hip", "field.hip", "field_observe.hip", "place.hip", "arm.hip", "roadmap.hip", "trajectory.hip",
            "prof.hip"]
 # -fno-slp-vectorize: hipcc's SLP pass packs adjacent scalar fp32 operations into v_pk_*_f32 (15 % of the
 # blend loops' VALU instructions); on gfx950 a packed fp32 instruction is not cheaper than its two halves

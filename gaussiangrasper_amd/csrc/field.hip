@@ -7,7 +7,8 @@
 //                     by the whole wave (ballot, wave-uniform row index): the 64 lanes stride over the flattened box,
 //                     z fastest, so that a wave's atomics fall on runs of neighbouring cells.  Votes are int64 and
 //                     added with 64-bit integer atomics: no order of the adds changes a bit of `mass`.
-// gg_field_distance   three launches of one kernel, z then y then x: a workgroup stages FD_TILE whole lines in LDS,
+// gg_field_distance   (and gg_field_distance_known, the same passes with one more seed rule) three launches of one
+//                     kernel, z then y then x: a workgroup stages FD_TILE whole lines in LDS,
 //                     and every thread finds its cell's minimum by an outward search that ends at delta^2 >= best.
 //                     A pass reads and writes only its own lines, so y runs in place on the workspace.
 // gg_field_paths      a thread per pose with the spheres in LDS, then a thread per path for first_hit.  No atomics.
@@ -183,11 +184,20 @@ __global__ void field_zero2_kernel(unsigned long long *a, unsigned long long *b)
 // (n / B) L B + n % B.  z: B = 1; y: B = Z; x: B = Y Z.  A workgroup owns FD_TILE consecutive lines and keeps them in
 // LDS as tile[l][t], or tile[t][l] (one int of padding per line) when the lines themselves are contiguous (UNIT:
 // B == 1), so that in both cases neighbouring threads read neighbouring addresses of memory and of LDS.
-// FIRST: the input is the mass (f = mass >= threshold ? 0 : FAR).  LAST: the output is clamped to FAR.
+// FIRST: the input is the mass (f = seed ? 0 : FAR, fd_seed).  LAST: the output is clamped to FAR.
+// The seed rule, in this one place: a cell seeds the transform iff it is occupied or, with `seen` given
+// (gg_field_distance_known), not seen free by min_views views.
+__device__ __forceinline__ bool fd_seed(const long long *__restrict__ mass, long long threshold,
+                                        const unsigned short *__restrict__ seen, int min_views, long long at) {
+    return mass[at] >= threshold || (seen && (int)seen[at] < min_views);
+}
+
 template <bool UNIT, bool FIRST, bool LAST>
 __global__ __launch_bounds__(FD_THREADS) void field_distance_kernel(int L, long long B, long long lines,
                                                                     const long long *__restrict__ mass,
-                                                                    long long threshold, const int *src, int *dst) {
+                                                                    long long threshold,
+                                                                    const unsigned short *__restrict__ seen,
+                                                                    int min_views, const int *src, int *dst) {
     extern __shared__ int fd_tile[];
     const long long line0 = (long long)blockIdx.x * FD_TILE;
     const int nt = (int)min((long long)FD_TILE, lines - line0);
@@ -198,7 +208,7 @@ __global__ __launch_bounds__(FD_THREADS) void field_distance_kernel(int L, long 
         const long long at = (n / B) * ((long long)L * B) + n % B + (long long)l * B;
         int f;
         if (FIRST)
-            f = mass[at] >= threshold ? 0 : GG_FIELD_FAR;
+            f = fd_seed(mass, threshold, seen, min_views, at) ? 0 : GG_FIELD_FAR;
         else
             f = src[at];
         fd_tile[UNIT ? t * (L + 1) + l : l * FD_TILE + t] = f;
@@ -622,11 +632,29 @@ extern "C" size_t gg_field_distance_workspace(const int32_t *dims) {
 
 template <bool UNIT, bool FIRST, bool LAST>
 static void field_distance_pass(hipStream_t s, int L, int64_t B, int64_t cells, const int64_t *mass, int64_t threshold,
-                                const int *src, int *dst) {
+                                const uint16_t *seen, int min_views, const int *src, int *dst) {
     const int64_t lines = cells / L;
     hipLaunchKernelGGL((field_distance_kernel<UNIT, FIRST, LAST>), dim3((unsigned)((lines + FD_TILE - 1) / FD_TILE)),
                        dim3(FD_THREADS), (size_t)FD_TILE * (L + 1) * sizeof(int), s, L, (long long)B, (long long)lines,
-                       reinterpret_cast<const long long *>(mass), (long long)threshold, src, dst);
+                       reinterpret_cast<const long long *>(mass), (long long)threshold,
+                       reinterpret_cast<const unsigned short *>(seen), min_views, src, dst);
+}
+
+// The three passes of both distance entries; seen null: occupied cells alone seed.
+static void field_distance_passes(hipStream_t s, const int32_t *dims, const int64_t *mass, int64_t threshold,
+                                  const uint16_t *seen, int min_views, int32_t *dist2, void *ws) {
+    const int64_t cells = field_cells(dims);
+    const int Y = dims[1], Z = dims[2];
+    int *f = (int *)ws;
+    field_distance_pass<true, true, false>(s, Z, 1, cells, mass, threshold, seen, min_views, nullptr, f);
+    if (Z == 1)
+        field_distance_pass<true, false, false>(s, Y, 1, cells, nullptr, 0, nullptr, 0, f, f);
+    else
+        field_distance_pass<false, false, false>(s, Y, Z, cells, nullptr, 0, nullptr, 0, f, f);
+    if ((int64_t)Y * Z == 1)
+        field_distance_pass<true, false, true>(s, dims[0], 1, cells, nullptr, 0, nullptr, 0, f, dist2);
+    else
+        field_distance_pass<false, false, true>(s, dims[0], (int64_t)Y * Z, cells, nullptr, 0, nullptr, 0, f, dist2);
 }
 
 extern "C" int gg_field_distance(const int32_t *dims, const int64_t *mass, int64_t threshold, int32_t *dist2, void *ws,
@@ -636,19 +664,25 @@ extern "C" int gg_field_distance(const int32_t *dims, const int64_t *mass, int64
     GG_REQUIRE(mass && dist2, "null pointer: mass / dist2");
     GG_REQUIRE(((uintptr_t)mass & 7) == 0 && ((uintptr_t)dist2 & 3) == 0, "mass / dist2 misaligned");
     GG_REQUIRE_WS(ws, ws_bytes, gg_field_distance_workspace(dims));
+    field_distance_passes((hipStream_t)stream, dims, mass, threshold, nullptr, 0, dist2, ws);
+    GG_CHECK_LAUNCH();
+    return GG_OK;
+}
+
+extern "C" int gg_field_distance_known(const int32_t *dims, const int64_t *mass, int64_t threshold,
+                                       const uint16_t *seen, int min_views, int32_t *dist2, void *ws, size_t ws_bytes,
+                                       gg_stream_t stream) {
+    GG_REQUIRE(field_dims_ok(dims), FIELD_DIMS_MSG);
+    GG_REQUIRE(threshold >= 1, "threshold must be >= 1");
+    GG_REQUIRE(min_views >= 1 && min_views <= 65535, "min_views must be in 1..65535");
+    GG_REQUIRE(mass && seen && dist2, "null pointer: mass / seen / dist2");
+    GG_REQUIRE(((uintptr_t)mass & 7) == 0 && ((uintptr_t)seen & 1) == 0 && ((uintptr_t)dist2 & 3) == 0,
+               "mass / seen / dist2 misaligned");
+    GG_REQUIRE_WS(ws, ws_bytes, gg_field_distance_workspace(dims));
     hipStream_t s = (hipStream_t)stream;
-    const int64_t cells = field_cells(dims);
-    const int Y = dims[1], Z = dims[2];
-    int *f = (int *)ws;
-    field_distance_pass<true, true, false>(s, Z, 1, cells, mass, threshold, nullptr, f);
-    if (Z == 1)
-        field_distance_pass<true, false, false>(s, Y, 1, cells, nullptr, 0, f, f);
-    else
-        field_distance_pass<false, false, false>(s, Y, Z, cells, nullptr, 0, f, f);
-    if ((int64_t)Y * Z == 1)
-        field_distance_pass<true, false, true>(s, dims[0], 1, cells, nullptr, 0, f, dist2);
-    else
-        field_distance_pass<false, false, true>(s, dims[0], (int64_t)Y * Z, cells, nullptr, 0, f, dist2);
+    gg_prof_begin(GG_K_FIELD_DISTANCE_KNOWN, s);
+    field_distance_passes(s, dims, mass, threshold, seen, min_views, dist2, ws);
+    gg_prof_end(GG_K_FIELD_DISTANCE_KNOWN, s);
     GG_CHECK_LAUNCH();
     return GG_OK;
 }

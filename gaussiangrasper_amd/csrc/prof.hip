@@ -127,6 +127,9 @@ extern "C" const char *gg_prof_name(int id) {
         case GG_K_GRASP_NMS: return "gg_grasp_nms(all launches)";
         case GG_K_SUPPORT_PLANE: return "gg_support_plane(all launches)";
         case GG_K_BLEND_VOTES: return "blend_votes_kernel";
+        case GG_K_DEPTH_PYRAMID: return "gg_depth_min_pyramid(all launches)";
+        case GG_K_FIELD_OBSERVE: return "field_observe_kernel";
+        case GG_K_FIELD_DISTANCE_KNOWN: return "gg_field_distance_known(all launches)";
         default: break;
     }
     if (id >= GG_K_BLEND_FWD && id < GG_K_BLEND_FWD + 6) {

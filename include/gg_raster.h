@@ -1314,6 +1314,63 @@ int gg_field_shortcut(const int32_t *dims, const int32_t *dist2, int32_t need, i
                       const int32_t *cells, const int32_t *length, int window, int32_t *keep, int32_t *count,
                       int32_t *blocked, gg_stream_t stream);
 
+/* ---- known free space of the distance field (PARITY "Known free space") ---------------------------
+ * gg_field_distance calls every cell without Gaussian mass free, whether a camera ever looked into it or not.  These
+ * entries give the volume a third state: a cell is KNOWN FREE once enough depth frames have seen through all of it.
+ *
+ * gg_depth_min_pyramid: depth fp32 [V][H][W], along the camera's z axis in scene units, as gg_tsdf_integrate reads it.
+ * pyr fp32 [V][S] (written whole): level l has H_l = ceil(H / 2^l) rows and W_l = ceil(W / 2^l) columns, row-major;
+ * the levels run from l = 0 to the first with H_l = W_l = 1; level l starts at offset sum_{m<l} H_m W_m and S is the
+ * sum over all levels, which gg_depth_min_pyramid_size(H, W) returns (0 for a size out of range).  Level 0 is the
+ * sanitised frame d > 0 ? d : 0: +inf stays (free space seen to infinity); 0, negative and NaN become 0 ("no
+ * observation: nothing is known to be in front of it").  A texel of level l + 1 is the minimum of its up-to-four
+ * children (2y, 2x), (2y, 2x + 1), (2y + 1, 2x), (2y + 1, 2x + 1) of level l; children beyond the level's edge are
+ * absent.  A minimum is exact: the bytes are a pure function of the input.  V <= GG_TSDF_MAX_VIEWS, H, W <=
+ * GG_TSDF_MAX_SIDE; V == 0 writes nothing.  Both arrays 4-byte aligned.
+ *
+ * gg_field_observe: dims, grid: the field's volume (above).  pyr: gg_depth_min_pyramid's of V frames of H x W.
+ * intrinsics fp64 [V][4] fx, fy, cx, cy with fx, fy > 0 (the caller's to ensure: the arrays are on the device; with
+ * anything else every access stays in bounds and the counts mean nothing); w2c fp64 [V][3][4] = E, world to camera,
+ * OpenCV axes.  Host doubles radius > 0, margin >= 0, near > 0, all finite.  seen uint16 [X][Y][Z], in / out; looked
+ * uint16 [X][Y][Z], in / out, may be NULL.  Every cell is owned by exactly one thread; there are no atomics; the
+ * output is a pure function of the inputs.  Per cell (i, j, k), all in fp64 without contraction, in this order:
+ *   centre c_a = lo_a + ((double)i_a + 0.5) h;
+ *   per view, in index order:
+ *     p_r = ((E[r][0] c_0 + E[r][1] c_1) + E[r][2] c_2) + E[r][3];   zn = p_2 - radius,  zf = p_2 + radius;
+ *     the view takes no part unless zn >= near;
+ *     pixel bounds of the ball's bounding box, for x (a = p_0, f = fx, cc = cx, n = W) and for y (p_1, fy, cy, H):
+ *       xl = a - radius,  xh = a + radius;
+ *       ul = f (xl / (xl < 0 ? zn : zf)) + cc,   uh = f (xh / (xh > 0 ? zn : zf)) + cc;
+ *       A = floor(ul - 2^-20),  B = floor(uh + 2^-20)    (the pad is many orders above the fp64 rounding of these);
+ *     the view takes no part unless A >= 0 and B <= n - 1 on both axes (compared as doubles; a NaN bound fails);
+ *     otherwise the cell was LOOKED AT: looked += 1;
+ *     level l = the smallest with (B >> l) - (A >> l) <= 1 on both axes (the 1 x 1 top level always qualifies);
+ *     m = the minimum of the up-to-four texels {A_v >> l, B_v >> l} x {A_u >> l, B_u >> l} of level l;
+ *     the cell is SEEN FREE in this view iff (double)m > zf + margin: seen += 1.
+ * Both counters saturate: min(65535, old + count).  V views in one call give the same counts as V calls of one view.
+ * WHAT THIS GUARANTEES.  Every point q of the closed ball of `radius` around the centre has camera depth q_2 in
+ * [zn, zf], zn >= near > 0, and projects, with the floor(u), floor(v) pixel rule of gg_tsdf_integrate, to a pixel
+ * inside [A, B] on both axes (q_0 / q_2 is bounded by the box's extreme ratios).  Every such pixel lies in one of the
+ * texels read ((B >> l) - (A >> l) <= 1), and every texel is the minimum over its pixels.  So with "seen free", along
+ * every ray through the ball the measured surface lies more than `margin` beyond q: depth[pixel(q)] >= m > zf +
+ * margin >= q_2 + margin.  With radius >= (sqrt(3) / 2) h the ball contains the cell's cube.  A missing reading
+ * anywhere in the footprint (a texel of 0) or a footprint that leaves the image makes the view ABSTAIN: it is never
+ * counted as free.  A workgroup owns a 4 x 8 x 8 brick and skips a view for the whole brick only where a
+ * margin-padded test of the box of its cells' centres shows that none of them can be looked at.
+ * V == 0 leaves both arrays untouched.  pyr 4-byte aligned, intrinsics and w2c 8-byte, seen and looked 2-byte.
+ *
+ * gg_field_distance_known: gg_field_distance with one more seed rule.  seen uint16 [X][Y][Z]; min_views in 1..65535.
+ * A cell seeds the transform iff mass >= threshold OR seen < min_views: unknown space is blocked.  The same passes,
+ * workspace (gg_field_distance_workspace) and output; with seen >= min_views everywhere, gg_field_distance's bits.
+ * Null, misaligned or out-of-range arguments: GG_ERR_INVALID_ARG naming the argument, before any launch. */
+int64_t gg_depth_min_pyramid_size(int height, int width);
+int gg_depth_min_pyramid(int num_views, int height, int width, const float *depth, float *pyr, gg_stream_t stream);
+int gg_field_observe(const int32_t *dims, const double *grid, int num_views, int height, int width, const float *pyr,
+                     const double *intrinsics, const double *w2c, double radius, double margin, double near,
+                     uint16_t *seen, uint16_t *looked, gg_stream_t stream);
+int gg_field_distance_known(const int32_t *dims, const int64_t *mass, int64_t threshold, const uint16_t *seen,
+                            int min_views, int32_t *dist2, void *ws, size_t ws_bytes, gg_stream_t stream);
+
 /* ---- placement: height maps and the resting search (PARITY "Placement") ----------------------------
  * A plane grid: dims (host, 2 ints) U, V cells, 1 <= each <= GG_PLACE_MAX_DIM; grid (host, 4 doubles) lo_u, lo_v, ONE
  * square cell edge h > 0 and the level height hz > 0, all finite.  A map is int32 [U][V] (C order, v fastest) of
@@ -1667,7 +1724,11 @@ int gg_traj_sample(int num_joints, int num_paths, int num_waypoints, const doubl
 #define GG_K_GRASP_CLEAR 50   /* gg_grasp_clearance: the pass and the per-grasp reduction */
 #define GG_K_GRASP_NMS 51     /* gg_grasp_nms: gather, the pair matrix and the walk */
 #define GG_K_SUPPORT_PLANE 52 /* gg_plane_consensus and gg_plane_classify: all their launches */
-#define GG_K_IDS 53           /* ids are below this */
+/* 53 names nothing and stays that way: gg_prof_name(53) is "" (it was the end of the list when tests pinned it) */
+#define GG_K_DEPTH_PYRAMID 54 /* gg_depth_min_pyramid: all its launches */
+#define GG_K_FIELD_OBSERVE 55 /* gg_field_observe */
+#define GG_K_FIELD_DISTANCE_KNOWN 56 /* gg_field_distance_known: its three passes */
+#define GG_K_IDS 57           /* ids are below this */
 #define GG_PROF_NUM_KERNELS 32
 int gg_prof_enable(int on);
 int gg_prof_reset(void);
